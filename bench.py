@@ -1,6 +1,11 @@
 """bench.py -- headline metric of BASELINE.json on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR also writes what the last timed
+step returned (DIR/<name>.npy, float64).  --full adds everything else the bench measures: the 160-step windows, the
+roofline (a profiled repeat of the K steps), the no-skipping / dense-world variants, the CPU baselines and the solver,
+loop-closure, enumeration, occupancy, replay and latency legs, and writes the full record (--details).
 
 metric  : scan-matches/sec (BASELINE.json "scan-matches/sec + loop-closure solve ms, 10k-node graph")
 workload: BASELINE config[1] = single-scan CorrelateScan, 1081 beams, 0.3 m x 0.3 m x +-20 deg search @
@@ -119,6 +124,15 @@ def pmc_traffic(batch):
         return per_match * batch
     except (OSError, KeyError, ValueError):
         return None
+
+
+def dump_outputs(dirname, result, suffix=""):
+    """What the caller of the timed path receives from one step (kh_matcher_correlate_batch through CorrelateScanBatch): response,
+    mean pose, covariance and status of every match of the batch, each as DIR/<name><suffix>.npy in float64."""
+    resp, means, covs, status = result
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in (("response", resp), ("mean", means), ("covariance", covs), ("status", status)):
+        np.save(os.path.join(dirname, name + suffix + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 class _StdoutToStderr:
@@ -1054,15 +1068,23 @@ def main():
     ap.add_argument("--streams", type=int, default=1,
                     help="matcher handles (each its own HIP stream and host thread) a rank drives concurrently; "
                          "a step is still ONE batch of --batch matches on one of them")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (response, mean, covariance, status of every match) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline (windows, roofline, variants, CPU baselines, the other legs); "
+                         "the --no-* options below trim a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-solver", action="store_true")
     ap.add_argument("--no-loop", action="store_true")
     ap.add_argument("--no-replay-50k", action="store_true", help="skip config[4] at its stated size (50 000 scans: ~25 s with the queue's making)")
     ap.add_argument("--no-variants", action="store_true", help="skip the no-skipping / dense-world variants of the headline")
-    ap.add_argument("--details", default=os.path.join(ROOT, "profiles", "bench_details_latest.json"),
-                    help="where the full record (every key, notes, workload texts) is written; '' = nowhere")
+    ap.add_argument("--details", default=None,
+                    help="where the full record (every key, notes, workload texts) is written; '' = nowhere "
+                         "(default: profiles/bench_details_latest.json with --full, nowhere without)")
     ap.add_argument("--verbose", action="store_true", help="print the full record on the line instead of the compact one")
     args = ap.parse_args()
+    if args.details is None:
+        args.details = os.path.join(ROOT, "profiles", "bench_details_latest.json") if args.full else ""
 
     # --gpus is honoured: N > 1 without a launcher around us -> start the N ranks; a launcher whose world size differs -> refuse
     env_world = os.environ.get("WORLD_SIZE")
@@ -1114,13 +1136,20 @@ def main():
     corr = ((0.15, 0.15), (0.005, 0.005), math.radians(20.0), math.radians(0.5))
 
     def make_pairs(n_distinct, **scenario_kw):
-        """(queries, centers, bases) of B pairs; n_distinct < B tiles the distinct ones"""
-        qs, cs, bs = [], [], []
-        for b in range(n_distinct):
+        """(queries, centers, bases) of B pairs; n_distinct < B tiles the distinct ones.  The scenarios are built on a few host
+        threads (numpy's ray casting releases the GIL); each has its own seeded generator, so the pairs do not depend on the order."""
+        from concurrent.futures import ThreadPoolExecutor
+
+        def one(b):
             sc = Scenario(seed=1000 * rank + b, start=(37 * (rank * B + b)) % 380,
                           perturb=(0.04 * math.sin(b), -0.03 * math.cos(b), 0.01 * (b % 5 - 2)), **scenario_kw)
             q, base = sc.hip_scans()
-            qs.append(q); bs.append(base); cs.append(sc.query_pose)
+            return q, sc.query_pose, base
+        with ThreadPoolExecutor(max_workers=max(1, min(8, len(os.sched_getaffinity(0))))) as pool:
+            made = list(pool.map(one, range(n_distinct)))
+        qs = [q for q, _, _ in made]
+        cs = [c for _, c, _ in made]
+        bs = [b for _, _, b in made]
         idx = [b % n_distinct for b in range(B)]
         return [qs[i] for i in idx], np.asarray([cs[i] for i in idx]), [bs[i] for i in idx]
 
@@ -1139,9 +1168,12 @@ def main():
     def step(h, c=centers, a=arr):
         return h.CorrelateScanBatch(None, c, *corr, True, False, scan_array=a)
 
+    last_step = {}
+
     def timed(hs, n_steps, c=centers, a=arr):
         """n_steps steps dealt round-robin to the handles `hs` (one host thread each); returns (seconds, per-step seconds of the
-        first handle's thread, last result).  Barrier + synchronize on both sides; max over ranks."""
+        first handle's thread) and keeps the result of the last step in last_step["result"].  Barrier + synchronize on both
+        sides; max over ranks."""
         import threading
         results = [None] * len(hs)
         per_step = []
@@ -1172,6 +1204,7 @@ def main():
                 resp, means, covs, status = out
                 # (KH_BENCH_NO_CHECK: measurement builds whose kernels skip work on purpose, tools/build_variant.sh)
                 assert os.environ.get("KH_BENCH_NO_CHECK") or ((status == 0).all() and (resp > 0.1).all()), "matches failed"
+        last_step["result"] = results[(n_steps - 1) % len(hs)]
         return (shard.max_over_ranks(dt, device="cuda") if world > 1 else dt), per_step
 
     # (untimed setup in front of the W warm-up steps: half a second of steps, so that the device's clocks and the host pool's threads
@@ -1188,24 +1221,27 @@ def main():
     # THE timed region: exactly K steps, nothing but the work in it.  (Through round 4 the library's profiling events were on
     # during it: two records per chunk around the scoring kernel cost 10 % of the step -- 74 k with them, 87 k without, same box.)
     dt, per_step = timed(handles, args.steps)
-    # `value` is the K steps asked for; beside it a region of at least 160 steps (half a second) in five windows, so that the
-    # headline can be read against the box-to-box spread (a 20-step region is 0.07 s)
-    long_steps = max(args.steps, 160)
-    dt_long, per_step_long = (dt, per_step) if long_steps == args.steps else timed(handles, long_steps)
-    # the roofline's kernel durations: the same K steps once more with HIP events on the library's streams around the table,
-    # scoring and tie kernels of every launch (kh_matcher_profile / kh_matcher_profile_side)
-    for h in handles:
-        h.profile(True)
-    dt_profiled, _ = timed(handles, args.steps)
-    wave_loads = sum(h.score_loads() for h in handles)
-    sides = [h.profile_side() for h in handles]
-    profs = [h.profile(False) for h in handles]
-    prof = {k: sum(p[k] for p in profs) for k in profs[0]}
-    side = {k: sum(p[k] for p in sides) for k in sides[0]}
+    if args.dump_outputs and last_step.get("result") is not None:
+        dump_outputs(args.dump_outputs, last_step["result"], f"_rank{rank}" if world > 1 else "")
+    if args.full:
+        # `value` is the K steps asked for; beside it a region of at least 160 steps (half a second) in five windows, so that the
+        # headline can be read against the box-to-box spread (a 20-step region is 0.07 s)
+        long_steps = max(args.steps, 160)
+        dt_long, per_step_long = (dt, per_step) if long_steps == args.steps else timed(handles, long_steps)
+        # the roofline's kernel durations: the same K steps once more with HIP events on the library's streams around the table,
+        # scoring and tie kernels of every launch (kh_matcher_profile / kh_matcher_profile_side)
+        for h in handles:
+            h.profile(True)
+        dt_profiled, _ = timed(handles, args.steps)
+        wave_loads = sum(h.score_loads() for h in handles)
+        sides = [h.profile_side() for h in handles]
+        profs = [h.profile(False) for h in handles]
+        prof = {k: sum(p[k] for p in profs) for k in profs[0]}
+        side = {k: sum(p[k] for p in sides) for k in sides[0]}
 
     full = {}          # every key of the record; the line is cut from it
     variants = {}
-    if not args.no_variants and S == 1:
+    if args.full and not args.no_variants and S == 1:
         # (a) the same batch with empty-window skipping switched off (kh_matcher_set_debug bit 2): every one of the 81 x 1081 windows
         # of a match is scored whatever the grid holds -- the strict worst case, what a world without free space would cost
         n_var = max(5, args.steps // 4)
@@ -1247,7 +1283,7 @@ def main():
             variants["dense_world_error"] = repr(exc)[:200]
 
     solver_out = None
-    if not args.no_solver:
+    if args.full and not args.no_solver:
         # the sharded solve is a collective: every rank takes part, rank 0 reports
         if world > 1:
             dist.barrier()
@@ -1257,7 +1293,7 @@ def main():
             except Exception as exc:      # the headline line must survive a failure of the extra leg
                 solver_out = {"solver_leg_error": repr(exc)[:200]}
     strong_out = None
-    if not args.no_loop:
+    if args.full and not args.no_loop:
         if world > 1:
             dist.barrier()
         try:
@@ -1290,24 +1326,6 @@ def main():
         if world > 1:
             dist.barrier()
     if rank == 0:
-        k3_ms = prof["score_ms"] / max(1, prof["score_launches"])
-        # a step's batch is scored in sub-batches (pipelined with the host half): matches per scoring launch
-        per_launch = B * args.steps / max(1, prof["score_launches"])
-        alg = ALG_BYTES_C2 * per_launch
-        alg_gbs = alg / (k3_ms * 1e-3) / 1e9
-        # LDS side, measured live: K2' tallies on the device the wave-level ds_read_b32 (256 B each) K3' issues for the windows it keeps
-        loads_per_launch = wave_loads / max(1, prof["score_launches"])
-        lds_gbs = loads_per_launch * 256.0 / (k3_ms * 1e-3) / 1e9
-        traffic = pmc_traffic(per_launch)
-        chunk = max(1, len(per_step_long) // 5)
-        windows = [per_step_long[i * chunk:(i + 1) * chunk] for i in range(5)] if len(per_step_long) >= 5 else [per_step_long]
-        rates = sorted(world * B * len(w) / sum(w) for w in windows if w)
-        # reference lookups per CU clock (one figure that does not change its denominator from round to round):
-        # every lookup of the reference's access stream (nX * nY * nA * P per match) over the scoring kernel's time, and the part
-        # of them the kernel really reads (windows it keeps: 64 x 64 bytes each, of which 61 x 61 are poses)
-        cu_clocks = 256 * 2.4e9 * (k3_ms * 1e-3)
-        lookups_all = C2["nx"] * C2["ny"] * C2["na"] * P_BEAMS * per_launch
-        lookups_read = loads_per_launch / 16.0 * C2["nx"] * C2["ny"]
         full.update({
             "metric": "scan-matches/sec", "value": world * B * args.steps / dt, "unit": "scan-matches/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
@@ -1318,41 +1336,62 @@ def main():
                        "untimed_preroll_s": preroll_s},
             "config_workload": "BASELINE config[1]: single-scan CorrelateScan, 1081 beams, 0.3m x 0.3m x +-20deg @ 5mm/0.5deg "
                                "(61x61x81 poses), 8087^2 grid",
-            # per-step wall times of the timed region, dealt into five interleaved windows: spread of the headline
-            "value_windows": {"n": len(rates), "median": float(np.median(rates)) if rates else None, "min": rates[0] if rates else None,
-                              "max": rates[-1] if rates else None, "steps_per_window": len(windows[0]) if windows else 0,
-                              "steps": long_steps, "seconds": dt_long, "value": world * B * long_steps / dt_long},
-            # the dominant kernel reads LDS-resident window unions: the resource it leans on is the LDS read port (ds_read_b32:
-            # 128 B / clk / CU), not HBM.  `frac` is the live LDS->register byte rate against that port; the HBM side (recorded
-            # PMC) and the reference's algorithmic access stream are kept beside it, each labelled.
-            "roofline": {"bound": "lds", "kernel": SCORE_KERNEL, "achieved": lds_gbs, "peak": LDS_B32_PEAK_GBS,
-                         "unit": "GB/s", "frac": lds_gbs / LDS_B32_PEAK_GBS,
-                         "window_reads_per_launch": loads_per_launch, "avg_launch_ms": k3_ms, "matches_per_launch": per_launch,
-                         "ms_per_step_with_events": dt_profiled / args.steps * 1e3,
-                         "lookups_per_cu_clk": lookups_all / cu_clocks, "lookups_per_cu_clk_read": lookups_read / cu_clocks,
-                         "lookups_per_cu_clk_peak_b32": 128.0 * C2["nx"] * C2["ny"] / 4096.0, "lds_array_frac": lds_gbs / (2.0 * LDS_B32_PEAK_GBS),
-                         "side_kernels_ms_per_launch": {"k_offsets_lds": side["offsets_ms"] / max(1, prof["score_launches"]),
-                                                        "k_ties": side["ties_ms"] / max(1, prof["score_launches"])},
-                         "traffic": traffic, "hbm_frac": (traffic / (k3_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
-                         "algorithmic_bytes_per_launch": alg, "algorithmic_gbs": alg_gbs, "algorithmic_ratio": alg_gbs / HBM_PEAK_GBS,
-                         "traffic_source": "recorded: " + os.path.relpath(PMC_FILE, ROOT) + " (rocprofv3 PMC passes of this command; "
-                                           "(2*FETCH_SIZE + WRITE_SIZE)*1024, scaled to this run's matches per launch)",
-                         "note": "bound = the LDS read port.  A window (one beam at one angle: 64 bytes x 64 rows) is read from a staged LDS region "
-                                 "with sixteen wave-level ds_read_b32 of 256 B; `achieved` = windows kept x 4 KB over the launch time, `peak` = 128 B/clk/CU "
-                                 "x 256 CUs x 2.4 GHz (MI355X_MICROARCH.md, LDS table); the byte sums run on the matrix cores (v_mfma_i32_16x16x64_i8, "
-                                 "one per KB read).  algorithmic_ratio = the reference's own access stream (5 B per lookup, every lookup) over the "
-                                 "launch time against 8 TB/s: it exceeds 1 because the kernel reads LDS-resident windows, 4 lookups per dword, and "
-                                 "skips windows that hold only zeros -- it is not a fraction of a hardware limit"},
         })
+        if args.full:
+            k3_ms = prof["score_ms"] / max(1, prof["score_launches"])
+            # a step's batch is scored in sub-batches (pipelined with the host half): matches per scoring launch
+            per_launch = B * args.steps / max(1, prof["score_launches"])
+            alg = ALG_BYTES_C2 * per_launch
+            alg_gbs = alg / (k3_ms * 1e-3) / 1e9
+            # LDS side, measured live: K2' tallies on the device the wave-level ds_read_b32 (256 B each) K3' issues for the windows it keeps
+            loads_per_launch = wave_loads / max(1, prof["score_launches"])
+            lds_gbs = loads_per_launch * 256.0 / (k3_ms * 1e-3) / 1e9
+            traffic = pmc_traffic(per_launch)
+            chunk = max(1, len(per_step_long) // 5)
+            windows = [per_step_long[i * chunk:(i + 1) * chunk] for i in range(5)] if len(per_step_long) >= 5 else [per_step_long]
+            rates = sorted(world * B * len(w) / sum(w) for w in windows if w)
+            # reference lookups per CU clock (one figure that does not change its denominator from round to round):
+            # every lookup of the reference's access stream (nX * nY * nA * P per match) over the scoring kernel's time, and the part
+            # of them the kernel really reads (windows it keeps: 64 x 64 bytes each, of which 61 x 61 are poses)
+            cu_clocks = 256 * 2.4e9 * (k3_ms * 1e-3)
+            lookups_all = C2["nx"] * C2["ny"] * C2["na"] * P_BEAMS * per_launch
+            lookups_read = loads_per_launch / 16.0 * C2["nx"] * C2["ny"]
+            full.update({
+                # per-step wall times of the timed region, dealt into five interleaved windows: spread of the headline
+                "value_windows": {"n": len(rates), "median": float(np.median(rates)) if rates else None, "min": rates[0] if rates else None,
+                                  "max": rates[-1] if rates else None, "steps_per_window": len(windows[0]) if windows else 0,
+                                  "steps": long_steps, "seconds": dt_long, "value": world * B * long_steps / dt_long},
+                # the dominant kernel reads LDS-resident window unions: the resource it leans on is the LDS read port (ds_read_b32:
+                # 128 B / clk / CU), not HBM.  `frac` is the live LDS->register byte rate against that port; the HBM side (recorded
+                # PMC) and the reference's algorithmic access stream are kept beside it, each labelled.
+                "roofline": {"bound": "lds", "kernel": SCORE_KERNEL, "achieved": lds_gbs, "peak": LDS_B32_PEAK_GBS,
+                             "unit": "GB/s", "frac": lds_gbs / LDS_B32_PEAK_GBS,
+                             "window_reads_per_launch": loads_per_launch, "avg_launch_ms": k3_ms, "matches_per_launch": per_launch,
+                             "ms_per_step_with_events": dt_profiled / args.steps * 1e3,
+                             "lookups_per_cu_clk": lookups_all / cu_clocks, "lookups_per_cu_clk_read": lookups_read / cu_clocks,
+                             "lookups_per_cu_clk_peak_b32": 128.0 * C2["nx"] * C2["ny"] / 4096.0, "lds_array_frac": lds_gbs / (2.0 * LDS_B32_PEAK_GBS),
+                             "side_kernels_ms_per_launch": {"k_offsets_lds": side["offsets_ms"] / max(1, prof["score_launches"]),
+                                                            "k_ties": side["ties_ms"] / max(1, prof["score_launches"])},
+                             "traffic": traffic, "hbm_frac": (traffic / (k3_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
+                             "algorithmic_bytes_per_launch": alg, "algorithmic_gbs": alg_gbs, "algorithmic_ratio": alg_gbs / HBM_PEAK_GBS,
+                             "traffic_source": "recorded: " + os.path.relpath(PMC_FILE, ROOT) + " (rocprofv3 PMC passes of this command; "
+                                               "(2*FETCH_SIZE + WRITE_SIZE)*1024, scaled to this run's matches per launch)",
+                             "note": "bound = the LDS read port.  A window (one beam at one angle: 64 bytes x 64 rows) is read from a staged LDS region "
+                                     "with sixteen wave-level ds_read_b32 of 256 B; `achieved` = windows kept x 4 KB over the launch time, `peak` = 128 B/clk/CU "
+                                     "x 256 CUs x 2.4 GHz (the MI355X's LDS read rate); the byte sums run on the matrix cores (v_mfma_i32_16x16x64_i8, "
+                                     "one per KB read).  algorithmic_ratio = the reference's own access stream (5 B per lookup, every lookup) over the "
+                                     "launch time against 8 TB/s: it exceeds 1 because the kernel reads LDS-resident windows, 4 lookups per dword, and "
+                                     "skips windows that hold only zeros -- it is not a fraction of a hardware limit"},
+            })
         full.update(variants)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             with _StdoutToStderr():
                 full["cpu_baseline"] = cpu_baseline()
         if solver_out:
             full.update(solver_out)
         if strong_out:
             full.update(strong_out)
-        if world == 1 and not args.no_loop:
+        if args.full and world == 1 and not args.no_loop:
             full.update(loop_leg(local_rank, cpu=not args.no_cpu_baseline))
             full.update(enumeration_leg(local_rank))
             full.update(occupancy_leg(local_rank))

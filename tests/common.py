@@ -116,3 +116,22 @@ class Golden:
     def correlate_args(self):
         a = self.d["correlate_args"]
         return (a[0], a[1]), (a[2], a[3]), float(a[4]), float(a[5]), bool(a[6]), bool(a[7])
+
+
+# ---------------------------------------------------------------- recorded reference results (tests/golden/ref_checks.npz)
+def ref_row(result):
+    """(response, mean, covariance) of one MatchScan -> 13 doubles"""
+    r, mean, cov = result
+    return np.concatenate([[r], np.asarray(mean, dtype=np.float64).reshape(3), np.asarray(cov, dtype=np.float64).reshape(9)])
+
+
+def ref_digest(a):
+    """sha256 of an integer array's values (as int64) and shape: what the recording keeps of grids and lookup tables"""
+    import hashlib
+    a = np.ascontiguousarray(np.asarray(a).astype(np.int64))
+    return hashlib.sha256(a.tobytes() + str(a.shape).encode()).hexdigest()
+
+
+def ref_recorded():
+    """the reference's results recorded by tests/golden/make_golden_ref_checks.py"""
+    return np.load(os.path.join(GOLDEN_DIR, "ref_checks.npz"))

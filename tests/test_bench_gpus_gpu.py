@@ -15,7 +15,7 @@ def test_bench_gpus_2_spawns_its_ranks(kartohip_lib):
     env = dict(os.environ, KH_BENCH_BACKEND="gloo", KH_BENCH_WATCHDOG="900")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "64",
-                        "--no-cpu-baseline", "--details", ""], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--details", ""], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]

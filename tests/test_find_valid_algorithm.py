@@ -132,22 +132,31 @@ def _range_cases():
     return [r0, r1, r2]
 
 
+REF_POSE = np.array([2.0, 1.0, -0.4])
+REF_VIEW_OFFSET = np.array([0.3, -0.2])
+
+
 @pytest.mark.parametrize("case", range(3))
 def test_pointer_doubling_against_the_reference_itself(case):
-    """the same flags from the reference's own ScanMatcher::FindValidPoints (oracle/_ref, dev container only) on scans the
-    reference builds from ranges and pose"""
-    from common import OFFLINE_PARAMS, PRESETS
+    """the same flags as the reference's own ScanMatcher::FindValidPoints on scans the reference builds from ranges and pose:
+    live where oracle/_ref is built (and then also against the recording), else against its results recorded in
+    tests/golden/ref_checks.npz (tests/golden/make_golden_ref_checks.py)"""
+    from common import OFFLINE_PARAMS, PRESETS, ref_recorded
     from oracle import ref
-    if not ref.available():
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    ref.init_laser(LASER)
-    pose = np.array([2.0, 1.0, -0.4])
-    rs = ref.RefScan(_range_cases()[case], pose)
-    points = rs.points()
+    rec = ref_recorded()
+    rec_points, rec_want = rec[f"fv_points_{case}"], rec[f"fv_valid_{case}"]
+    view = REF_POSE[:2] + REF_VIEW_OFFSET
+    if ref.available():
+        ref.init_laser(LASER)
+        rs = ref.RefScan(_range_cases()[case], REF_POSE)
+        points = rs.points()
+        rm = ref.RefMatcher(*PRESETS["S"]["create"], OFFLINE_PARAMS)
+        want = rm.find_valid_points(rs, view)
+        assert np.array_equal(points.view(np.uint64), rec_points.view(np.uint64))
+        assert np.array_equal(np.ascontiguousarray(want).view(np.uint64), rec_want.view(np.uint64))
+    else:
+        points, want = rec_points, rec_want
     assert points.shape[0] == LASER.n_beams
-    view = pose[:2] + np.array([0.3, -0.2])
-    rm = ref.RefMatcher(*PRESETS["S"]["create"], OFFLINE_PARAMS)
-    want = rm.find_valid_points(rs, view)
     got = points[flags_by_pointer_doubling(points, view).astype(bool)]
     assert got.shape == want.shape and got.shape[0] > 0
     assert np.array_equal(got.view(np.uint64), np.ascontiguousarray(want).view(np.uint64))

@@ -1,65 +1,92 @@
-"""Dev-container only: the C oracle against the reference's own karto_sdk build (oracle/_ref) on
-fresh random scenarios, beyond the committed golden vectors.  Skipped where oracle/_ref is absent."""
+"""The C oracle against the reference's own karto_sdk build (oracle/_ref) on seeded scenarios beyond the golden fixtures of
+test_oracle_golden.py.  Where oracle/_ref is built the reference runs live beside the oracle and must also reproduce its
+recorded results (tests/golden/ref_checks.npz, tests/golden/make_golden_ref_checks.py); elsewhere the oracle is held to the
+recording: response, mean and covariance bit for bit, grid and lookup table by digest."""
 import numpy as np
 import pytest
 
-from common import LASER, PRESETS, Scenario, bits, make_oracle_matcher
+from common import LASER, PRESETS, Scenario, bits, make_oracle_matcher, ref_digest, ref_recorded, ref_row
 from oracle import ref
 
-pytestmark = pytest.mark.skipif(not ref.available(), reason="oracle/_ref not built (needs /root/reference)")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _laser():
-    ref.init_laser(LASER)
-
-
-@pytest.mark.parametrize("preset,seed,start,n_base,perturb", [
+LIVE = ref.available()
+MATCH_CASES = [
     ("K", 31, 40, 5, (0.08, 0.02, -0.05)),
     ("K", 32, 150, 12, (-0.1, 0.1, 0.2)),
     ("S", 33, 77, 10, (0.02, 0.03, 0.01)),
     ("L", 34, 10, 30, (1.5, -2.0, 0.15)),
     ("L", 35, 300, 15, (-3.0, 0.5, -0.3)),
-])
-def test_match_scan_equals_reference(oracle_lib, preset, seed, start, n_base, perturb):
+]
+MATCH_FLAGS = [(True, True), (False, False)]
+# (seed, n_base, start, perturb, preset), then the calls made in turn on ONE matcher: "*_empty" matches against no base scans
+SINGLE_CASES = [((36, 6, 50, (0.0, 0.0, 1.2), "S"), ("expansion",)),
+                ((37, 3, 90, (25.0, 25.0, 0.0), "K"), ("far_empty", "far_base"))]
+
+
+def match_key(preset, seed, pen, refine):
+    return f"match_{preset}_{seed}_{int(pen)}{int(refine)}"
+
+
+@pytest.fixture(scope="module")
+def recorded():
+    if LIVE:
+        ref.init_laser(LASER)
+    return ref_recorded()
+
+
+def _same_row(a, b):
+    assert np.array_equal(bits(a), bits(b)), (a, b)
+
+
+@pytest.mark.parametrize("preset,seed,start,n_base,perturb", MATCH_CASES)
+def test_match_scan_equals_reference(oracle_lib, recorded, preset, seed, start, n_base, perturb):
     sc = Scenario(seed=seed, n_base=n_base, start=start, perturb=perturb)
-    rq, rb = sc.ref_scans()
     oq, ob = sc.oracle_scans()
     p = PRESETS[preset]
-    mr = ref.RefMatcher(*p["create"], p["params"])
     mo = make_oracle_matcher(preset)
-    for pen, refine in [(True, True), (False, False)]:
-        a = mr.match_scan(rq, rb, pen, refine)
+    if LIVE:
+        rq, rb = sc.ref_scans()
+        mr = ref.RefMatcher(*p["create"], p["params"])
+    for pen, refine in MATCH_FLAGS:
+        key = match_key(preset, seed, pen, refine)
         b = mo.match_scan(oq, ob, pen, refine)
-        assert np.array_equal(bits(a[0]), bits(b[0]))
-        assert np.array_equal(bits(a[1]), bits(b[1]))
-        assert np.array_equal(bits(a[2]), bits(b[2]))
-        assert np.array_equal(mr.grid(), mo.grid())
         lt = mo.lookup_table()
-        assert np.array_equal(mr.lookup_table(*lt.shape), lt)
+        if LIVE:
+            a = mr.match_scan(rq, rb, pen, refine)
+            assert np.array_equal(bits(a[0]), bits(b[0]))
+            assert np.array_equal(bits(a[1]), bits(b[1]))
+            assert np.array_equal(bits(a[2]), bits(b[2]))
+            assert np.array_equal(mr.grid(), mo.grid())
+            assert np.array_equal(mr.lookup_table(*lt.shape), lt)
+            _same_row(ref_row(a), recorded[key])
+        _same_row(ref_row(b), recorded[key])
+        assert ref_digest(mo.grid()) == str(recorded[key + "_grid"])
+        assert ref_digest(lt) == str(recorded[key + "_lut"])
 
 
-def test_response_expansion_path(oracle_lib):
+def _singles(case, recorded):
+    (seed, n_base, start, perturb, preset), keys = SINGLE_CASES[case]
+    sc = Scenario(seed=seed, n_base=n_base, start=start, perturb=perturb)
+    oq, ob = sc.oracle_scans()
+    mo = make_oracle_matcher(preset)
+    if LIVE:
+        rq, rb = sc.ref_scans()
+        p = PRESETS[preset]
+        mr = ref.RefMatcher(*p["create"], p["params"])
+    for key in keys:
+        empty = key.endswith("_empty")
+        b = mo.match_scan(oq, [] if empty else ob)
+        if LIVE:
+            a = mr.match_scan(rq, [] if empty else rb)
+            assert np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(bits(a[1]), bits(b[1]))
+            assert np.array_equal(bits(a[2]), bits(b[2]))
+            _same_row(ref_row(a), recorded[key])
+        _same_row(ref_row(b), recorded[key])
+
+
+def test_response_expansion_path(oracle_lib, recorded):
     """Query 90 degrees off: the coarse search finds nothing and the +20 degree expansion loop runs."""
-    sc = Scenario(seed=36, n_base=6, start=50, perturb=(0.0, 0.0, 1.2))
-    rq, rb = sc.ref_scans()
-    oq, ob = sc.oracle_scans()
-    p = PRESETS["S"]
-    a = ref.RefMatcher(*p["create"], p["params"]).match_scan(rq, rb)
-    b = make_oracle_matcher("S").match_scan(oq, ob)
-    assert np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(bits(a[1]), bits(b[1]))
-    assert np.array_equal(bits(a[2]), bits(b[2]))
+    _singles(0, recorded)
 
 
-def test_empty_base_and_far_query(oracle_lib):
-    sc = Scenario(seed=37, n_base=3, start=90, perturb=(25.0, 25.0, 0.0))
-    rq, rb = sc.ref_scans()
-    oq, ob = sc.oracle_scans()
-    p = PRESETS["K"]
-    mr = ref.RefMatcher(*p["create"], p["params"])
-    mo = make_oracle_matcher("K")
-    for base_r, base_o in [([], []), (rb, ob)]:
-        a = mr.match_scan(rq, base_r)
-        b = mo.match_scan(oq, base_o)
-        assert np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(bits(a[1]), bits(b[1]))
-        assert np.array_equal(bits(a[2]), bits(b[2]))
+def test_empty_base_and_far_query(oracle_lib, recorded):
+    _singles(1, recorded)

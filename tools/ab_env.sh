@@ -6,7 +6,7 @@ for round in 1 2; do
   k=0
   for e in "$@"; do
     k=$((k+1)); [ "$e" = "-" ] && e=""
-    env $e timeout 600 python bench.py --no-solver --no-loop --no-cpu-baseline ${AB_FLAGS:---no-variants} --steps 50 --warmup 5 --verbose --details '' > $out/v${k}_$round.json 2> $out/v${k}_$round.err
+    env $e timeout 600 python bench.py --full --no-solver --no-loop --no-cpu-baseline ${AB_FLAGS:---no-variants} --steps 50 --warmup 5 --verbose --details '' > $out/v${k}_$round.json 2> $out/v${k}_$round.err
     python - $out/v${k}_$round.json "$e" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ for round in 1 2; do
   for lib in "$@"; do
     name=$(basename $lib .so); [ "$lib" = "-" ] && name=tree
     if [ "$lib" = "-" ]; then unset KH_LIBRARY; else export KH_LIBRARY=$GRAFT_REPO_ROOT/$lib; fi
-    timeout 600 python bench.py --no-solver --no-loop --no-cpu-baseline ${AB_FLAGS:---no-variants} --steps 50 --warmup 5 --verbose --details '' > $out/${name}_$round.json 2> $out/${name}_$round.err
+    timeout 600 python bench.py --full --no-solver --no-loop --no-cpu-baseline ${AB_FLAGS:---no-variants} --steps 50 --warmup 5 --verbose --details '' > $out/${name}_$round.json 2> $out/${name}_$round.err
     python - $out/${name}_$round.json $name <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ mkdir -p $out
 [ "$lib" != "-" ] && export KH_LIBRARY=$GRAFT_REPO_ROOT/$lib
 for sz in "$@"; do
   if [ "$sz" = "-" ]; then unset KH_CHUNK_SIZES; else export KH_CHUNK_SIZES=$sz; fi
-  timeout 300 python bench.py --no-solver --no-loop --no-cpu-baseline --no-variants --no-replay-50k --steps 40 --warmup 5 --verbose --details '' > $out/c_$sz.json 2> $out/c_$sz.err
+  timeout 300 python bench.py --full --no-solver --no-loop --no-cpu-baseline --no-variants --no-replay-50k --steps 40 --warmup 5 --verbose --details '' > $out/c_$sz.json 2> $out/c_$sz.err
   python - $out/c_$sz.json "$lib $sz" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -36,8 +36,8 @@ python tools/pmc_summary.py gpurun_out/${tag}_spa profiles/${R}_spa_pmc.json "${
 cp profiles/${R}_spa_pmc.json $out/; cp gpurun_out/${tag}_spa/levels_timeline.txt $out/${R}_spa_levels_timeline.txt
 cp gpurun_out/${tag}_spa/trace/t_kernel_stats.csv $out/${R}_spa_kernel_stats.csv
 # ---- the bench itself: default form (details -> the round's line) and the driver's form
-python bench.py --details $out/${R}_bench_line.json > $out/${R}_bench_line_compact.json 2> $out/bench.err
-python bench.py --steps 20 --no-replay-50k --details '' > $out/${R}_bench_line_steps20_compact.json 2> $out/bench20.err
+python bench.py --full --details $out/${R}_bench_line.json > $out/${R}_bench_line_compact.json 2> $out/bench.err
+python bench.py --full --steps 20 --no-replay-50k --details '' > $out/${R}_bench_line_steps20_compact.json 2> $out/bench20.err
 find $out gpurun_out/${tag}_loop gpurun_out/${tag}_spa -name "*kernel_trace.csv" -size +1M -delete
 find $out gpurun_out/${tag}_loop gpurun_out/${tag}_spa -name "p_counter_collection.csv" -size +4M -delete
 missing=0

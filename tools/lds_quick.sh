@@ -1,12 +1,13 @@
 #!/bin/bash
 # quick A/B of the LDS-staged scoring path on the GPU box: parity tests of the path, then the headline leg of bench.py with the
 # default build and every build under variants/ (tools/build_variant.sh).  Outputs under gpurun_out/$1.
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 tag=${1:-ldsq}
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 timeout 600 python -m pytest tests/test_matcher_gpu.py -x -q -m gpu -k "lds" 2>&1 | tail -3
 export KH_LDS_SCORE=1
-cmd="python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-solver --no-loop"
+cmd="python $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-solver --no-loop"
 $cmd > $out/bench_default.json 2> $out/bench_default.err
 
 
@@ -27,7 +28,7 @@ for f in sorted(glob.glob("$out/bench_*.json")):
 PY
 if [ -n "$2" ]; then
   cd /tmp && export TMPDIR=/tmp
-  cmd="python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-solver --no-loop"
+  cmd="python $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-solver --no-loop"
   timeout 300 rocprofv3 --kernel-trace --stats -d $out/trace -o t --output-format csv -- $cmd > $out/bench_trace.json 2> $out/trace.err
   for c in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS" \
            "SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_INSTS_VMEM_RD SQ_INSTS_SMEM" \

@@ -1,12 +1,13 @@
 #!/bin/bash
 # LDS-staged scoring path on the GPU box: variants A/B (KH_LIBRARY builds from tools/build_variant.sh), kernel trace, LDS counters.
 # Outputs under gpurun_out/$1.
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 tag=${1:-lds}
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 export KH_LDS_SCORE=1
-cmd="python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-solver --no-loop"
+cmd="python $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-solver --no-loop"
 for v in $GRAFT_REPO_ROOT/variants/*.so; do
   n=$(basename $v .so)
   KH_BENCH_NO_CHECK=1 KH_LIBRARY=$v timeout 200 $cmd > $out/bench_$n.json 2> $out/bench_$n.err
