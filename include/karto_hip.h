@@ -288,7 +288,7 @@ typedef struct kh_spa_summary {
   double backward_gpu_ms;       /* backward sweeps + step evaluation */
   double linearize_gpu_ms;      /* edge linearisation + gathers of H and g (every evaluation point) */
   double symbolic_ms;           /* host: pattern + ordering + symbolic factorisation + uploads (0 when the topology was cached) */
-  double worst_linear_residual; /* KH_SPA_CHECK=1 only (else 0): max over the iterations of |(Hs + D/radius) step + gs| / |gs|,
+  double worst_linear_residual; /* kh_spa_set_debug bit 0 only (else 0): max over the iterations of |(Hs + D/radius) step + gs| / |gs|,
                                    evaluated from the block-sparse matrix, independent of the factorisation */
   int32_t analysis;             /* symbolic analysis of this Compute(): 0 none (topology unchanged), 1 full nested dissection,
                                    2 incremental (supernodes of the last dissection reused, new nodes as leading leaves) */

@@ -355,8 +355,7 @@ int kh_graph_find_loop_candidates_from(
   for (int32_t i = 0; i < n_queries; ++i) {
     if (query_scans[i] < 0 || query_scans[i] >= g->n) {set_error("kh_graph_find_loop_candidates: unknown scan"); return KH_ERR_NOT_FOUND;}
   }
-  static const bool host_single = !(std::getenv("KH_GRAPH_HOST_SINGLE") && std::atoi(std::getenv("KH_GRAPH_HOST_SINGLE")) == 0);
-  if (n_queries == 1 && host_single) {
+  if (n_queries == 1) {
     if (start_scans && start_scans[0] < 0) {set_error("kh_graph_find_loop_candidates_from: negative start"); return KH_ERR_INVALID_ARG;}
     const double sq1 = max_distance * max_distance;
     std::vector<std::pair<int32_t, int32_t>> v;

@@ -16,6 +16,8 @@
 #include <thread>
 #include <vector>
 
+#include "host_wait.hpp"
+
 namespace kh
 {
 
@@ -61,7 +63,7 @@ public:
     for (;;) {
       const uint32_t left = pending_.load(std::memory_order_acquire);
       if (left == 0) {break;}
-      if (ticks() - t0 < kSpinTicks) {__builtin_ia32_pause();} else {futex_wait(&pending_, left);}
+      if (ticks() - t0 < kSpinTicks) {KH_CPU_PAUSE();} else {futex_wait(&pending_, left);}
     }
     fn_ = nullptr;
     if (failed_.load(std::memory_order_acquire)) {
@@ -131,7 +133,7 @@ private:
     uint64_t idle_since = ticks(), spin_for = kSpinTicks;
     for (;;) {
       if (generation_.load(std::memory_order_acquire) == seen) {
-        if (ticks() - idle_since < spin_for) {__builtin_ia32_pause();} else {futex_wait(&generation_, seen);}
+        if (ticks() - idle_since < spin_for) {KH_CPU_PAUSE();} else {futex_wait(&generation_, seen);}
         continue;
       }
       if (stop_.load(std::memory_order_acquire)) {return;}

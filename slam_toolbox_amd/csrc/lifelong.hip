@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/karto_hip.h"
+#include "host_wait.hpp"
 
 namespace kh
 {
@@ -264,16 +265,9 @@ int decay_scores(int32_t device, const kh_scan_box * reference, int32_t n, const
     hipLaunchKernelGGL(k_decay, dim3((n + 3) / 4), dim3(256), 0, st, ref, d_boxes, n, d_masks, mask_words, *params, d_iou, d_area, d_read, d_score, d_kept,
                        scratch.d_ticket, scratch.tickets, scratch.h_flag, scratch.seq);
     if (hipGetLastError() != hipSuccess) {scratch.tickets -= static_cast<unsigned int>(n); return fail("launch failed");}
-    volatile int32_t * flag = scratch.h_flag;
-    uint64_t spins = 0;
-    while (*flag != scratch.seq) {
-      __builtin_ia32_pause();
-      if ((++spins & 0x3fff) == 0) {
-        const hipError_t e = hipStreamQuery(st);
-        if (e == hipSuccess) {if (*flag == scratch.seq) {break;} scratch.release(); return fail("the stream drained without the result flag");}
-        if (e != hipErrorNotReady) {scratch.release(); return fail("kernel failed");}
-      }
-    }
+    const FlagWait w = wait_device_flag(scratch.h_flag, scratch.seq, st);
+    if (w == FlagWait::kDrained) {scratch.release(); return fail("the stream drained without the result flag");}
+    if (w == FlagWait::kFailed) {scratch.release(); return fail("kernel failed");}
   } else {
     if (hipMemcpyAsync(scratch.d_in, scratch.h_in, in_bytes, hipMemcpyHostToDevice, st) != hipSuccess) {return fail("upload failed");}
     hipLaunchKernelGGL(k_decay, dim3((n + 3) / 4), dim3(256), 0, st, ref, d_boxes, n, d_masks, mask_words, *params, d_iou, d_area, d_read, d_score, d_kept,

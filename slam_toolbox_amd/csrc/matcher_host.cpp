@@ -838,11 +838,10 @@ static int correlate_stage(kh_matcher * m, CorrReq * reqs, size_t n, CorrBatch &
   }
   // LDS-staged scoring (k_offsets_lds / k_score_lds): by default for the searches it was measured faster on -- windows of at most
   // 61 bytes x 64 rows with >= 1e8 lookups per search, in launches of >= 512 angle pairs (the config-2 CorrelateScan in batches:
-  // 0.48 against 0.60 ms per 51 matches); smaller searches and small launches keep the windowed kernel, whose fixed costs are lower.  KH_LDS_SCORE=1 / kh_matcher_set_debug bit 1:
-  // every search the path can take; KH_LDS_SCORE=0 / bit 6: none.
-  static const int lds_env = std::getenv("KH_LDS_SCORE") ? std::atoi(std::getenv("KH_LDS_SCORE")) : -1;
-  const bool lds_never = lds_env == 0 || m->windowed_score;
-  const bool lds_always = !lds_never && (lds_env > 0 || m->lds_score);
+  // 0.48 against 0.60 ms per 51 matches); smaller searches and small launches keep the windowed kernel, whose fixed costs are lower.  kh_matcher_set_debug bit 1:
+  // every search the path can take; bit 6: none.
+  const bool lds_never = m->windowed_score;
+  const bool lds_always = !lds_never && m->lds_score;
   std::vector<JobShape> shapes(n);
   HostPool::instance().run(n, [&](size_t i) {
     prepare_job(m, reqs[i], ctx[i], lay[i], B.h_stage + stride * i, B.d_stage + stride * i, B.d_out + out_words * i, out_words, n,
@@ -876,9 +875,8 @@ static int correlate_stage(kh_matcher * m, CorrReq * reqs, size_t n, CorrBatch &
   // ---- 2. upload, launch, download ----
   lap(0, t_enter);
   const auto t_enqueue = std::chrono::steady_clock::now();
-  // overlap (chunked batches): the uploads, the table / list kernel K2, the tie scan K4 and the downloads go on the
-  // side stream, ordered against the scoring kernel by events: the main stream then runs K3 after K3, and everything
-  // else of a chunk happens under the scoring of its neighbours
+  // overlap (chunked batches): everything of a chunk -- uploads, the table / list kernel K2, the scoring kernel K3, the tie scan K4
+  // and the downloads -- goes on its staging set's side stream, and happens under the scoring of its neighbours
   hipStream_t cs = overlap ? B.side : m->stream;
   KH_HIP(hipMemcpyAsync(B.d_stage, B.h_stage, stride * n, hipMemcpyHostToDevice, cs));
   // (the result blocks are zeroed by K2)
@@ -889,41 +887,28 @@ static int correlate_stage(kh_matcher * m, CorrReq * reqs, size_t n, CorrBatch &
     launch_offsets(B.d_stage, stride, static_cast<int32_t>(n), max_na, cs);
   }
   if (m->profiling) {KH_HIP(hipEventRecord(B.evs[1], cs));}
-  // The scoring kernel of a chunk goes on the chunk's own side stream as well (KH_K3_MAIN=1: on the handle's main stream, one
-  // scoring kernel after the other, as through round 3): the two staging sets then are two independent in-order queues, and the
-  // workgroups of chunk i + 1 fill the compute units the tail of chunk i leaves idle (2099 workgroups on 512 slots are 4.1
-  // rounds: a fifth of the kernel's time ran at a tenth of the occupancy).
-  static const bool k3_main = std::getenv("KH_K3_MAIN") != nullptr;
-  hipStream_t ks = (overlap && !k3_main) ? cs : m->stream;
-  if (overlap && ks != cs) {
-    KH_HIP(hipEventRecord(B.up, cs));
-    KH_HIP(hipStreamWaitEvent(ks, B.up, 0));
-  }
-  if (m->profiling) {KH_HIP(hipEventRecord(B.ev[0], ks));}
+  // The scoring kernel of a chunk goes on the chunk's own side stream as well: the two staging sets then are two independent
+  // in-order queues, and the workgroups of chunk i + 1 fill the compute units the tail of chunk i leaves idle (2099 workgroups on
+  // 512 slots are 4.1 rounds: a fifth of the kernel's time ran at a tenth of the occupancy).
+  if (m->profiling) {KH_HIP(hipEventRecord(B.ev[0], cs));}
   if (use_lds) {
     bool full_rows = true;
     for (size_t i = 0; i < n; ++i) {full_rows = full_rows && lds_row_waves(ctx[i].ny) == 4;}
-    launch_score_lds(B.d_stage, stride, static_cast<int32_t>(n), max_na, sx_variant, full_rows, ks);
+    launch_score_lds(B.d_stage, stride, static_cast<int32_t>(n), max_na, sx_variant, full_rows, cs);
   } else if (uniform_kernel) {
-    launch_score(B.d_stage, stride, static_cast<int32_t>(n), max_tiles, max_na, sx_variant, ry, ks, m->mfma_score);
+    launch_score(B.d_stage, stride, static_cast<int32_t>(n), max_tiles, max_na, sx_variant, ry, cs, m->mfma_score);
   } else {
     for (size_t i = 0; i < n; ++i) {
       const CorrJob * job = reinterpret_cast<const CorrJob *>(B.h_stage + stride * i);
       launch_score(B.d_stage + stride * i, stride, 1, job->tiles_x * job->tiles_y, job->na,
-        (job->linear && job->sx == 2 && !job->dec) ? 2 : 1, job->ry, ks, m->mfma_score);
+        (job->linear && job->sx == 2 && !job->dec) ? 2 : 1, job->ry, cs, m->mfma_score);
     }
   }
-  if (m->profiling) {KH_HIP(hipEventRecord(B.ev[1], ks));}
-  if (overlap && ks != cs) {
-    KH_HIP(hipEventRecord(B.kdone, ks));
-    KH_HIP(hipStreamWaitEvent(cs, B.kdone, 0));
-  }
-  hipStream_t ts = cs;
-  if (m->profiling) {KH_HIP(hipEventRecord(B.evs[2], ts));}
-  launch_ties(B.d_stage, stride, static_cast<int32_t>(n), max_poses, B.tile_pairs, ts);
-  if (m->profiling) {KH_HIP(hipEventRecord(B.evs[3], ts));}
+  if (m->profiling) {KH_HIP(hipEventRecord(B.ev[1], cs)); KH_HIP(hipEventRecord(B.evs[2], cs));}
+  launch_ties(B.d_stage, stride, static_cast<int32_t>(n), max_poses, B.tile_pairs, cs);
+  if (m->profiling) {KH_HIP(hipEventRecord(B.evs[3], cs));}
   KH_HIP(hipGetLastError());
-  KH_HIP(hipMemcpyAsync(B.h_out, B.d_out, out_words * 8 * n, hipMemcpyDeviceToHost, ts));
+  KH_HIP(hipMemcpyAsync(B.h_out, B.d_out, out_words * 8 * n, hipMemcpyDeviceToHost, cs));
   // fine passes need the raw sums of every angle at the best cell (ComputeAngularCovariance): their
   // volumes are tiny (3 x 3 x nA), so they ride along with the batch download instead of costing one
   // synchronous copy per match afterwards
@@ -937,11 +922,11 @@ static int correlate_stage(kh_matcher * m, CorrReq * reqs, size_t n, CorrBatch &
     if (max_small) {
       rc = ensure_pinned(B.h_sums, B.cap_hsums, B.small_stride * n, m->stream); if (rc) {return rc;}
       rc = ensure_device(B.d_small, B.cap_dsmall, B.small_stride * n, m->stream); if (rc) {return rc;}
-      launch_gather_small(B.d_stage, stride, static_cast<int32_t>(n), B.d_small, static_cast<int32_t>(B.small_stride), ts);
-      KH_HIP(hipMemcpyAsync(B.h_sums, B.d_small, B.small_stride * n * 4, hipMemcpyDeviceToHost, ts));
+      launch_gather_small(B.d_stage, stride, static_cast<int32_t>(n), B.d_small, static_cast<int32_t>(B.small_stride), cs);
+      KH_HIP(hipMemcpyAsync(B.h_sums, B.d_small, B.small_stride * n * 4, hipMemcpyDeviceToHost, cs));
     }
   }
-  KH_HIP(hipEventRecord(B.done, ts));
+  KH_HIP(hipEventRecord(B.done, cs));
   lap(1, t_enqueue);
   return KH_OK;
   }   // phase 0
@@ -1025,16 +1010,15 @@ int correlate_batch(kh_matcher * m, std::vector<CorrReq> & reqs)
   // chunk i run, the host prepares chunk i + 1 and finalises chunk i - 1 (the exact host half costs ~5 us per match
   // on the worker pool, the scoring kernel ~13 us).  Chunks of 64 keep the scoring launches at full efficiency;
   // splitting a batch of 32 into halves was measured slower than not splitting (0.85 against 0.76 ms), so batches
-  // below 2 * kChunk are not split.  KH_PIPELINE=0 switches the chunking off.
-  static const size_t kChunk = std::getenv("KH_CHUNK") ? static_cast<size_t>(std::max(8, std::atoi(std::getenv("KH_CHUNK")))) : 64;
-  static const bool pipeline = !(std::getenv("KH_PIPELINE") && std::atoi(std::getenv("KH_PIPELINE")) == 0);
+  // below 2 * kChunk are not split.
+  constexpr size_t kChunk = 64;
   // ... and only searches whose scoring kernel dwarfs the hand-overs between the streams: a chunk of 64 config-2
   // searches scores for 0.85 ms, a chunk of loop-closure coarse searches (half the lookups, a quarter of the loads)
   // for 0.2 ms, and batches of those were measured 25 % slower chunked than whole
   const CorrReq & r0 = reqs[0];
   const double work0 = (round_half_away(r0.off_x * 2.0 / r0.res_x) + 1) * (round_half_away(r0.off_y * 2.0 / r0.res_y) + 1) *
     (round_half_away(r0.ang_off * 2.0 / r0.ang_res) + 1) * static_cast<double>(r0.scan->n);
-  if (!pipeline || n < 2 * kChunk || (work0 < 2.5e8 && !m->force_chunks)) {
+  if (n < 2 * kChunk || (work0 < 2.5e8 && !m->force_chunks)) {
     int rc = correlate_stage(m, reqs.data(), n, m->batch[0], 0);
     if (rc) {return rc;}
     return correlate_stage(m, reqs.data(), n, m->batch[0], 1);
@@ -1048,31 +1032,11 @@ int correlate_batch(kh_matcher * m, std::vector<CorrReq> & reqs)
   // K4, download and finalisation are).  256 config-2 matches as 24 + 64 + 64 + 64 + 40 measured 79.9 k and 81.4 k matches/s
   // on two boxes where 32 + 64 + 64 + 64 + 32 (the split of rounds 2-3) gave 78.4 k and 76.5 k, a first chunk of 16 74.4 k,
   // uniform chunks of 64 less again; splits sized to whole rounds of workgroups (24 + 62 + 62 + 62 + 46) measured no better
-  // than the plain one.  KH_CHUNK_EDGE=64 restores the uniform split, KH_CHUNK_SIZES=a,b,... sets one by hand.
-  static const size_t edge = std::getenv("KH_CHUNK_EDGE") ? static_cast<size_t>(std::max(8, std::min(256, std::atoi(std::getenv("KH_CHUNK_EDGE"))))) : 24;
-  std::vector<size_t> bounds;
-  // KH_CHUNK_SIZES=a,b,c,...: an explicit split (measurements); the last size is repeated / cut to cover the batch
-  static const char * sizes_env = std::getenv("KH_CHUNK_SIZES");
-  if (sizes_env) {
-    size_t at = 0, last = kChunk;
-    const char * p = sizes_env;
-    while (at < n) {
-      if (*p) {
-        char * end = nullptr;
-        const long v = std::strtol(p, &end, 10);
-        if (end != p && v > 0) {last = static_cast<size_t>(v);}
-        p = (*end == ',') ? end + 1 : end;
-      }
-      bounds.push_back(at);
-      at += last;
-    }
-  } else if (edge < kChunk && n >= 2 * edge + kChunk) {
-    bounds.push_back(0);
-    for (size_t at = edge; at + edge < n; at += kChunk) {bounds.push_back(at);}
-    if (n - bounds.back() > kChunk) {bounds.push_back(n - edge);}
-  } else {
-    for (size_t at = 0; at < n; at += kChunk) {bounds.push_back(at);}
-  }
+  // than the plain one.
+  constexpr size_t kEdgeChunk = 24;
+  std::vector<size_t> bounds{0};
+  for (size_t at = kEdgeChunk; at + kEdgeChunk < n; at += kChunk) {bounds.push_back(at);}
+  if (n - bounds.back() > kChunk) {bounds.push_back(n - kEdgeChunk);}
   bounds.push_back(n);
   const size_t chunks = bounds.size() - 1;
   auto begin_of = [&](size_t c) {return bounds[c];};
@@ -1220,7 +1184,6 @@ int kh_matcher_create(double search_size, double resolution, double smear, doubl
       if ((e = hipEventCreate(&ev)) != hipSuccess) {return fail(e, "hipEventCreate");}
     }
     if ((e = hipEventCreateWithFlags(&b.done, hipEventDisableTiming)) != hipSuccess) {return fail(e, "hipEventCreate");}
-    if ((e = hipEventCreateWithFlags(&b.up, hipEventDisableTiming)) != hipSuccess) {return fail(e, "hipEventCreate");}
     if ((e = hipEventCreateWithFlags(&b.kdone, hipEventDisableTiming)) != hipSuccess) {return fail(e, "hipEventCreate");}
     if ((e = hipStreamCreateWithFlags(&b.side, hipStreamNonBlocking)) != hipSuccess) {return fail(e, "hipStreamCreate");}
   }
@@ -1254,12 +1217,10 @@ int kh_matcher_create(double search_size, double resolution, double smear, doubl
   m->bm_w = (((m->ws >> m->bshift) + 1) + 31) / 32 + 1;     // words per block row (+1 padding word)
   m->bm_h = (m->data_size / m->ws >> m->bshift) + 2;
   // Batches take the first-point rasteriser (matcher_seq.hip) where every slot can have its table over the region of interest --
-  // 4 bytes per cell: 66 MB for the sequential preset, 260 MB for the config-2 geometry -- within 24 GB per handle; KH_TABLE_RASTER=0
-  // keeps the hash-table passes (measurements)
+  // 4 bytes per cell: 66 MB for the sequential preset, 260 MB for the config-2 geometry -- within 24 GB per handle
   {
     const double table_bytes = 4.0 * static_cast<double>(m->roi_w) * m->roi_h * max_batch;
-    static const bool env_off = std::getenv("KH_TABLE_RASTER") != nullptr && std::atoi(std::getenv("KH_TABLE_RASTER")) == 0;
-    m->table_raster = !env_off && table_bytes <= 24e9 && m->rt_w * m->rt_h <= 16384;
+    m->table_raster = table_bytes <= 24e9 && m->rt_w * m->rt_h <= 16384;
   }
   m->slots.resize(max_batch);
   for (auto & s : m->slots) {
@@ -1302,7 +1263,6 @@ void kh_matcher_destroy(kh_matcher * m)
     for (auto & ev : b.ev) {if (ev) {hipEventDestroy(ev);}}
     for (auto & ev : b.evs) {if (ev) {hipEventDestroy(ev);}}
     if (b.done) {hipEventDestroy(b.done);}
-    if (b.up) {hipEventDestroy(b.up);}
     if (b.kdone) {hipEventDestroy(b.kdone);}
     if (b.side) {hipStreamSynchronize(b.side); hipStreamDestroy(b.side);}
   }
@@ -1337,7 +1297,7 @@ int kh_matcher_set_debug(kh_matcher * m, int32_t keep_response_volume)
   m->no_seq = (keep_response_volume & 128) != 0;
   m->dense_score = (keep_response_volume & 4) != 0;
   if (keep_response_volume & 32) {m->mfma_score = true;}
-  m->force_chunks = (keep_response_volume & 8) != 0 || std::getenv("KH_FORCE_CHUNKS") != nullptr;
+  m->force_chunks = (keep_response_volume & 8) != 0;
   m->dual_copy = (keep_response_volume & 16) == 0;
   return KH_OK;
 }

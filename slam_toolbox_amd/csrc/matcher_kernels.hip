@@ -760,8 +760,8 @@ void launch_raster_tiles(const RasterJob * d_jobs, int32_t n_jobs, int32_t max_p
   if (n_jobs <= 0 || max_points <= 0) {return;}
   hipStream_t s = (hipStream_t)stream;
   // non-empty tiles <= 4 per point and <= all tiles; a workgroup walks several when there are more
-  static const int tile_blocks = std::getenv("KH_TILE_BLOCKS") ? std::atoi(std::getenv("KH_TILE_BLOCKS")) : 2048;
-  int blocks = std::min(std::min(max_tiles, 4 * max_points), tile_blocks);
+  constexpr int kTileBlocks = 2048;
+  int blocks = std::min(std::min(max_tiles, 4 * max_points), kTileBlocks);
   // kernels of >= 8 x 8 cells: tile in registers; smaller ones: LDS atomics, a lane per footprint cell
   if (kernel_size >= 8) {
     hipLaunchKernelGGL(k_raster_tile_reg, dim3(blocks, n_jobs), dim3(256), 0, s, d_jobs, d_kernel);

@@ -123,7 +123,7 @@ struct CorrBatch
   hipEvent_t ev[2] = {nullptr, nullptr};      // around the scoring kernel (profiling)
   hipEvent_t evs[4] = {nullptr, nullptr, nullptr, nullptr};   // around the table / list kernel (K2) and the tie kernel (K4) (profiling)
   hipEvent_t done = nullptr;                  // everything of the sub-batch, downloads included
-  hipEvent_t up = nullptr, kdone = nullptr;   // chunked batches: tables + lists ready (side stream) / scoring finished (main stream)
+  hipEvent_t kdone = nullptr;                 // chunked batches (batch[0]'s): the side streams start behind the main stream's queue
   hipStream_t side = nullptr;                 // side stream of this staging set (uploads, K2, K4, downloads of its chunks)
 };
 
@@ -189,7 +189,7 @@ struct kh_matcher
   int32_t * h_meta = nullptr; int32_t * d_meta = nullptr; size_t cap_hmeta = 0, cap_dmeta = 0;
   RasterJob * h_rjobs = nullptr; RasterJob * d_rjobs = nullptr;
   bool keep_responses = false;
-  bool force_chunks = std::getenv("KH_FORCE_CHUNKS") != nullptr;       // kh_matcher_set_debug bit 3: chunk every batch of >= 128 (tests)
+  bool force_chunks = false;       // kh_matcher_set_debug bit 3: chunk every batch of >= 128 (tests)
   bool dense_score = false;        // kh_matcher_set_debug bit 2: do not skip beams whose window is empty
   int32_t bm_w = 0, bm_h = 0, bshift = kBlockShift;    // occupancy block map: words per row, rows, log2 of the block side
   int32_t rt_w = 0, rt_h = 0;      // rasteriser tiles over the grid
@@ -198,7 +198,7 @@ struct kh_matcher
   size_t grid_pad = 0;             // the same in bytes of the grid's own pitch, rounded up to 256, plus kGridPad
   int32_t pitch_d = 0, copy_q = 0; // column-decimated copies: row pitch and bytes of one of the four; copy_q 0 = too large for int32 offsets
   bool dual_copy = true;           // kh_matcher_set_debug bit 4 switches the re-pitched copies off (measurements)
-  bool mfma_score = std::getenv("KH_K3_MFMA") != nullptr;   // kh_matcher_set_debug bit 5: byte sums on the matrix cores (k_score<.., MF>)
+  bool mfma_score = false;         // kh_matcher_set_debug bit 5: byte sums on the matrix cores (k_score<.., MF>)
   bool lds_score = false;          // kh_matcher_set_debug bit 1: LDS-staged scoring path for every search it can take (default: the large ones)
   bool windowed_score = false;     // kh_matcher_set_debug bit 6: never (the windowed kernel k_score scores everything)
   uint8_t * d_tab = nullptr;       // padded image of the smear kernel for kseq_tile (kernels of >= 8 x 8 cells)

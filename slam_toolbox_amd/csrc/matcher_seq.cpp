@@ -7,8 +7,7 @@
 // off-lattice best pose, a degenerate search) is handed back to the general path, pass by pass.
 #include "matcher_private.hpp"
 #include "matcher_seq.hpp"
-
-#include <immintrin.h>
+#include "host_wait.hpp"
 
 namespace kh
 {
@@ -98,8 +97,7 @@ int seq_match(kh_matcher * m, const kh_scan * query, const kh_scan * base, int32
   double mean[3], double cov[9], double * response, int * status, bool * coarse_done, bool * fine_done)
 {
   *coarse_done = false; *fine_done = false;
-  static const bool env_off = std::getenv("KH_SEQ_FUSED") != nullptr && std::atoi(std::getenv("KH_SEQ_FUSED")) == 0;
-  if (env_off || m->no_seq) {return KH_OK;}
+  if (m->no_seq) {return KH_OK;}
   if (!m->seq) {m->seq = new SeqState();}
   if (m->seq->unavailable) {return KH_OK;}
   // a call the kernels' fixed-size tables cannot take goes the general way; stats [6] counts them, [7] keeps the last reason
@@ -342,19 +340,10 @@ int seq_match(kh_matcher * m, const kh_scan * query, const kh_scan * base, int32
   // ---- 4. wait for the flag (the kernel's last store, system scope); the stream is asked now and then so that a failed launch
   // cannot hang the caller
   {
-    volatile int32_t * flag = Q.h_flag;
-    uint64_t spins = 0;
-    while (*flag != Q.seq) {
-      _mm_pause();
-      if ((++spins & 0x3fff) == 0) {
-        const hipError_t e = hipStreamQuery(st);
-        if (e == hipSuccess) {
-          if (*flag == Q.seq) {break;}
-          set_error("fused MatchScan: the stream drained without the result flag"); return KH_ERR_HIP;
-        }
-        if (e != hipErrorNotReady) {set_error(std::string("fused MatchScan: ") + hipGetErrorString(e)); return KH_ERR_HIP;}
-      }
-    }
+    hipError_t e = hipSuccess;
+    const FlagWait w = wait_device_flag(Q.h_flag, Q.seq, st, &e);
+    if (w == FlagWait::kDrained) {set_error("fused MatchScan: the stream drained without the result flag"); return KH_ERR_HIP;}
+    if (w == FlagWait::kFailed) {set_error(std::string("fused MatchScan: ") + hipGetErrorString(e)); return KH_ERR_HIP;}
   }
   if (Q.d_dbg) {
     // measurement aid: where kseq_bin and kseq_final spend their time (wall_clock64 = 100 MHz), averaged over 64 calls

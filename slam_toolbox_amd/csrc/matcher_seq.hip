@@ -613,9 +613,8 @@ void launch_seq_tile(const RasterJob * d_jobs, int32_t n_jobs, const uint8_t * d
   // one job: a workgroup per tile (latency).  A batch: 64 workgroups per job, each walking its share of the job's tiles with the next
   // tile's record and list on their way -- one copy of the kernel image into LDS per ~6 tiles instead of one per tile, and no
   // workgroups that find nothing to do (2048 per job, ~370 of them with a tile: 1070 us per 224 jobs; 64: 822; 16 or 256: 880)
-  static const int env_blocks = std::getenv("KH_TILE_BLOCKS") ? std::atoi(std::getenv("KH_TILE_BLOCKS")) : 0;
-  const int batch_blocks = env_blocks > 0 ? env_blocks : 64;
-  const int tile_blocks = std::max(1, std::min(std::min(max_tiles, 4 * max_points), n_jobs > 1 ? batch_blocks : 1024));
+  constexpr int kBatchTileBlocks = 64;
+  const int tile_blocks = std::max(1, std::min(std::min(max_tiles, 4 * max_points), n_jobs > 1 ? kBatchTileBlocks : 1024));
   hipLaunchKernelGGL(kseq_tile, dim3(tile_blocks + (a ? kTileStageBlocks : 4), n_jobs), dim3(512), 0, (hipStream_t)stream, d_jobs,
     reinterpret_cast<const uint4 *>(d_tab), tile_blocks, g);
 }

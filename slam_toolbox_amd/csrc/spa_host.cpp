@@ -14,7 +14,6 @@
 // the elimination tree is processed level by level.
 #include <hip/hip_runtime.h>
 
-#include <immintrin.h>
 #include <algorithm>
 #include <array>
 #include <atomic>
@@ -35,6 +34,7 @@
 #include <vector>
 
 #include "../../include/karto_hip.h"
+#include "host_wait.hpp"
 #include "spa_internal.hpp"
 #include "spa_symbolic.hpp"
 
@@ -101,8 +101,6 @@ struct kh_spa
 {
   int32_t device = 0;
   hipStream_t stream = nullptr;
-  hipStream_t stream2 = nullptr;               // the part of a level's extend-add that k_potrf does not read
-  hipEvent_t ev_level[2] = {};
   // self-cleaning fronts (scatter mode): the buffers these pointers name are all zeros (every kernel of the last factorisation
   // and its backward sweep ran, each zeroing what it was the last to read)
   const double * clean_a = nullptr; const double * clean_b = nullptr;
@@ -376,20 +374,21 @@ static int prepare_problem(kh_spa * s, SpaDev & dev, bool & has_work)
     // or after kMaxReuse re-analyses.  kh_spa_reset() forgets the supernodes (a reloaded graph is analysed from scratch).
     const auto t_sym0 = std::chrono::steady_clock::now();
     SymbolicOptions sopt;
-    // the independent subsets of a dissection level run on the library's persistent host pool (KH_SPA_ND_SERIAL=1: in line)
-    static const bool nd_serial = std::getenv("KH_SPA_ND_SERIAL") != nullptr;
-    if (!nd_serial) {sopt.parallel_for = [](size_t n, const std::function<void(size_t)> & fn) {host_parallel_for(n, fn);};}
+    // the independent subsets of a dissection level run on the library's persistent host pool
+    sopt.parallel_for = [](size_t n, const std::function<void(size_t)> & fn) {host_parallel_for(n, fn);};
     if (const char * e = std::getenv("KH_SPA_LEAF")) {sopt.leaf_nodes = std::max(1, std::atoi(e));}
-    if (const char * e = std::getenv("KH_SPA_PMAX")) {sopt.max_pivot_nodes = std::min(42, std::max(1, std::atoi(e)));}
-    if (const char * e = std::getenv("KH_SPA_CANDS")) {sopt.separator_candidates = std::max(1, std::atoi(e));}
-    static const bool incremental_on = !(std::getenv("KH_SPA_INCREMENTAL") && std::atoi(std::getenv("KH_SPA_INCREMENTAL")) == 0);
+    // how many levels taller than the last full dissection left it an incremental analysis may make the tree (the level guard
+    // below).  Read here, on the caller's thread, before the analysis may start on a thread of its own: tests/test_spa_gpu.py
+    // switches the guard off around one Compute().
+    const char * guard_env = std::getenv("KH_SPA_EXTRA_LEVELS");
+    const int extra_levels = guard_env ? std::atoi(guard_env) : (nf <= 6000 ? 2 : 6);
     int sym_rc = KH_OK;
     bool sym_incremental = false;
     std::string sym_error;
     auto analyse = [&]() {
       constexpr int kMaxReuse = 24;
       std::vector<std::vector<int32_t>> sn;
-      if (incremental_on && !s->cached_sn_ids.empty() && s->reuse_count < kMaxReuse) {
+      if (!s->cached_sn_ids.empty() && s->reuse_count < kMaxReuse) {
         // node id -> free index of this problem: a table when the ids are dense (a mapper's scan ids are), a hash map otherwise
         int32_t id_lo = INT32_MAX, id_hi = INT32_MIN;
         for (int32_t f = 0; f < nf; ++f) {const int32_t id = s->nodes[s->node_of_free[f]].id; id_lo = std::min(id_lo, id); id_hi = std::max(id_hi, id);}
@@ -438,9 +437,6 @@ static int prepare_problem(kh_spa * s, SpaDev & dev, bool & has_work)
           // 499 / 810, 5 levels 418 / 647, 3: 384 / 642, 2: 364-377 / 508, 1: 366 / 518, 0: 370 / 602, never incremental 358 / 621.
           // On the 50 000-scan lifelong replay (12 000 free nodes in thousands of components: a dissection costs 5-7 ms, the tree
           // grows slowly) 2 / 6 / no guard gave 2772 / 2576 / 2606 ms (medians of three alternating runs): 6 from 6000 free nodes on.
-          // (KH_SPA_EXTRA_LEVELS is read at every analysis: tests/test_spa_gpu.py switches the guard off around one Compute().)
-          const char * guard_env = std::getenv("KH_SPA_EXTRA_LEVELS");
-          const int extra_levels = guard_env ? std::atoi(guard_env) : (nf <= 6000 ? 2 : 6);
           const bool levels_ok = static_cast<int>(s->sym.levels.size()) <= s->cached_full_levels + extra_levels;
           if (sym_rc == KH_OK && static_cast<double>(s->sym.factor_flops) <= allowed && levels_ok) {
             sym_incremental = true;
@@ -560,14 +556,14 @@ static int prepare_problem(kh_spa * s, SpaDev & dev, bool & has_work)
       for (int32_t k : lv) {mm = std::max(mm, sym.front_m[k]); mns = std::max(mns, sym.front_ns[k]);}
       s->level_max_m.push_back(mm); s->level_max_ns.push_back(mns);
       // the fronts of a level are numbered largest first: the ones that do not fit k_front_update are (nearly) a prefix
-      static const int fuse_min = std::getenv("KH_SPA_FUSE_MIN") ? std::atoi(std::getenv("KH_SPA_FUSE_MIN")) : 256;
+      constexpr int kFuseMin = 256;         // fronts of a level from which k_front_update takes the ones that fit it
       int32_t split = 0;
       size_t lds = 0;
       for (size_t q = 0; q < lv.size(); ++q) {
         const size_t b = spa_front_update_lds(sym.front_m[lv[q]], sym.front_ns[lv[q]]);
         if (b == 0 && sym.front_m[lv[q]] > sym.front_ns[lv[q]]) {split = static_cast<int32_t>(q) + 1; lds = 0;} else {lds = std::max(lds, b);}
       }
-      if (static_cast<int32_t>(lv.size()) - split < fuse_min) {split = static_cast<int32_t>(lv.size());}
+      if (static_cast<int32_t>(lv.size()) - split < kFuseMin) {split = static_cast<int32_t>(lv.size());}
       s->level_split.push_back(split); s->level_fused_lds.push_back(lds);
       int32_t mnu = 0;
       for (int32_t k : lv) {mnu = std::max(mnu, sym.front_m[k] - sym.front_ns[k]);}
@@ -747,8 +743,6 @@ int kh_spa_create(int32_t device, kh_spa ** out)
   kh_spa_options_default(&s->opt);
   KS_HIP(hipSetDevice(device));
   KS_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-  KS_HIP(hipStreamCreateWithFlags(&s->stream2, hipStreamNonBlocking));
-  for (auto & e : s->ev_level) {KS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));}
   KS_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->h_scal), sizeof(double) * 32, hipHostMallocDefault));
   KS_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->h_fail), sizeof(int32_t) * 4, hipHostMallocDefault));
   // (a platform without host-coherent mappings keeps the copies + stream drain)
@@ -786,8 +780,6 @@ void kh_spa_destroy(kh_spa * s)
   if (s->h_res) {(void)hipHostFree(s->h_res);}
   if (s->h_upload) {(void)hipHostFree(s->h_upload);}
   if (s->h_fail) {(void)hipHostFree(s->h_fail);}
-  if (s->stream2) {(void)hipStreamSynchronize(s->stream2); (void)hipStreamDestroy(s->stream2);}
-  for (auto & e : s->ev_level) {if (e) {(void)hipEventDestroy(e);}}
   if (s->stream) {(void)hipStreamDestroy(s->stream);}
   delete s;
 }
@@ -1412,30 +1404,16 @@ int kh_spa_compute(kh_spa * s, kh_spa_summary * summary)
     // right-hand side in elimination order (factorisation and forward solve are one kernel per level) and the fail word's reset
     spa_launch_assemble(dev, s->d_scale.p, s->d_diag.p, 1.0 / radius, new_diagonal, opt.min_lm_diagonal, opt.max_lm_diagonal, s->d_rhs.p, s->d_fail.p, st);
     if (!pipeline) {KS_HIP(hipMemsetAsync(s->d_sync.p, 0, sizeof(int32_t) * 4 * static_cast<size_t>(sym.n_fronts), st));}
-    static const int ea_limit = std::getenv("KH_SPA_EXTEND_ADD") ? std::atoi(std::getenv("KH_SPA_EXTEND_ADD")) : 128;
+    constexpr int32_t kNarrowLevel = 128;      // levels of at most this many fronts take the chip-wide extend-add
     for (int l = 0; l < n_levels; ++l) {
       const int32_t n_level = s->level_offsets[l + 1] - s->level_offsets[l];
       const int32_t * lf = s->d_level_fronts.p + s->level_offsets[l];
       if (pipeline) {
-        // The children's update matrices go into the pivot blocks first (all k_potrf reads); the rest of the extend-add
-        // runs on a second stream BESIDE the pivot chains and is waited for before the row solves.
-        // (measured on the 10k / 30k graph: 14.7 ms per solve with the split against 13.2 without -- two event records and two
-        // stream waits per level on the critical stream cost more than the overlap wins; off unless KH_SPA_EA_OVERLAP=1)
-        static const bool overlap_ea = std::getenv("KH_SPA_EA_OVERLAP") && std::atoi(std::getenv("KH_SPA_EA_OVERLAP")) != 0;
-        const bool split_ea = l > 0 && !dev.gather && !dev.scatter && overlap_ea && s->stream2;
-        if (l > 0 && !dev.gather && !dev.scatter) {
-          if (split_ea) {
-            KS_HIP(hipEventRecord(s->ev_level[0], st));                    // the level below is complete
-            KS_HIP(hipStreamWaitEvent(s->stream2, s->ev_level[0], 0));
-            spa_launch_extend_add(dev, lf, n_level, s->level_max_m[l], s->stream2, 2, s->level_max_ns[l]);
-            KS_HIP(hipEventRecord(s->ev_level[1], s->stream2));
-            spa_launch_extend_add(dev, lf, n_level, s->level_max_m[l], st, 1, s->level_max_ns[l]);
-          } else {
-            spa_launch_extend_add(dev, lf, n_level, s->level_max_m[l], st);
-          }
-        }
+        // (running the part of the extend-add that k_potrf does not read on a second stream beside the pivot chains was measured
+        // slower on the 10k / 30k graph: 14.7 ms per solve against 13.2 -- the event records and stream waits on the critical
+        // stream cost more than the overlap wins)
+        if (l > 0 && !dev.gather && !dev.scatter) {spa_launch_extend_add(dev, lf, n_level, s->level_max_m[l], st);}
         spa_launch_potrf_level(dev, s->level_offsets[l], n_level, s->level_max_m[l], s->level_max_ns[l], s->d_fail.p, s->d_rhs.p, s->d_upd.p, st);
-        if (split_ea) {KS_HIP(hipStreamWaitEvent(st, s->ev_level[1], 0));}
         // the update of the level: the fronts that fit one workgroup's LDS whole in k_front_update (when there are enough of them), the
         // larger ones -- the head of the level -- in k_trsm / k_syrk
         if (s->level_max_nu[l] == 0) {continue;}                   // (the root: nothing below the pivot block)
@@ -1445,7 +1423,7 @@ int kh_spa_compute(kh_spa * s, kh_spa_summary * summary)
         continue;
       }
       // narrow levels: the extend-add runs chip-wide in its own launch instead of on each front's single CU
-      const bool split = l > 0 && n_level <= ea_limit;
+      const bool split = l > 0 && n_level <= kNarrowLevel;
       if (split) {spa_launch_extend_add(dev, lf, n_level, s->level_max_m[l], st);}
       spa_launch_factor_level(dev, lf, n_level, s->level_max_m[l], s->level_max_ns[l], s->d_fail.p,
         s->d_rhs.p, s->d_upd.p, s->d_fsb.p, s->d_sync.p + 4 * s->level_offsets[l], split ? 1 : 0, st);
@@ -1464,55 +1442,28 @@ int kh_spa_compute(kh_spa * s, kh_spa_summary * summary)
       spa_launch_zero_update_blocks(dev, s->d_deferred.p, s->n_deferred_fronts, s->deferred_max_m, st);
       s->clean_a = dev.fronts; s->clean_b = dev.fronts_b;
     }
-    static const bool speculate = !(std::getenv("KH_SPA_SPECULATE") && std::atoi(std::getenv("KH_SPA_SPECULATE")) == 0);
-    static const bool lin_check_env = std::getenv("KH_SPA_CHECK") != nullptr;
-    const bool lin_check = lin_check_env || (s->debug_flags & 1);
-    bool direct = false;
-    const bool fused_step = speculate && !(std::getenv("KH_SPA_FUSED_STEP") && std::atoi(std::getenv("KH_SPA_FUSED_STEP")) == 0);
-    if (fused_step) {
-      // the candidate's cost AND its normal equations (speculative: a step is nearly always accepted) ride in the same batch
-      const bool timed_lin = phase_events && n_lin < 2 * kh_spa::kMaxTimed + 2;
-      if (timed_lin) {KS_HIP(hipEventRecord(s->ev_lin[n_lin][0], st));}
-      spa_launch_step_and_linearize(dev, alt, s->d_scale.p, s->d_rhs.p, x, s->d_step.p, s->d_delta.p, cand, s->d_partial.p, e_lo, e_hi, st);
-      if (timed_lin) {KS_HIP(hipEventRecord(s->ev_lin[n_lin][1], st)); ++n_lin;}
-      // a communicator (or a sharding callback) sums this rank's H || g with the others', also with one rank (identity)
-      rc = allreduce_Hg(alt); if (rc) {return finish(rc);}
-      direct = s->h_res != nullptr && !lin_check;
-      if (direct) {s->res_seq = s->res_seq == 0x7fffffff ? 1 : s->res_seq + 1;}
-      spa_launch_step_scalars(alt, cand, s->d_partial.p, e_lo > 0 || e_hi < dev.n_edges, scal, st, direct ? s->h_res : nullptr, s->h_res_flag, s->d_fail.p,
-                              s->res_seq);
-      if (lin_check) {spa_launch_lin_check(dev, s->d_scale.p, s->d_diag.p, 1.0 / radius, s->d_step.p, scal + 12, st);}
-      if (timed) {KS_HIP(hipEventRecord(s->ev_phase[n_timed][2], st)); ++n_timed;}
-    } else {
-      spa_launch_finish_step(dev, s->d_scale.p, s->d_rhs.p, s->d_step.p, s->d_delta.p, st);
-      if (lin_check) {spa_launch_lin_check(dev, s->d_scale.p, s->d_diag.p, 1.0 / radius, s->d_step.p, scal + 12, st);}
-      spa_launch_model(dev, s->d_scale.p, s->d_step.p, scal + 3, st);
-      spa_launch_plus(dev, x, s->d_delta.p, cand, scal + 6, st);
-      if (timed) {KS_HIP(hipEventRecord(s->ev_phase[n_timed][2], st)); ++n_timed;}
-      if (speculate) {
-        rc = linearize(alt, cand, scal + 8); if (rc) {return finish(rc);}      // cost of the candidate + its H, g
-        spa_launch_grad_norms(alt, cand, scal + 9, st);
-      } else {
-        spa_launch_cost(dev, cand, scal + 8, st);
-      }
-    }
+    const bool lin_check = (s->debug_flags & 1) != 0;
+    // the candidate's cost AND its normal equations (speculative: a step is nearly always accepted) ride in the same batch
+    const bool timed_lin = phase_events && n_lin < 2 * kh_spa::kMaxTimed + 2;
+    if (timed_lin) {KS_HIP(hipEventRecord(s->ev_lin[n_lin][0], st));}
+    spa_launch_step_and_linearize(dev, alt, s->d_scale.p, s->d_rhs.p, x, s->d_step.p, s->d_delta.p, cand, s->d_partial.p, e_lo, e_hi, st);
+    if (timed_lin) {KS_HIP(hipEventRecord(s->ev_lin[n_lin][1], st)); ++n_lin;}
+    // a communicator (or a sharding callback) sums this rank's H || g with the others', also with one rank (identity)
+    rc = allreduce_Hg(alt); if (rc) {return finish(rc);}
+    const bool direct = s->h_res != nullptr && !lin_check;
+    if (direct) {s->res_seq = s->res_seq == 0x7fffffff ? 1 : s->res_seq + 1;}
+    spa_launch_step_scalars(alt, cand, s->d_partial.p, e_lo > 0 || e_hi < dev.n_edges, scal, st, direct ? s->h_res : nullptr, s->h_res_flag, s->d_fail.p,
+                            s->res_seq);
+    if (lin_check) {spa_launch_lin_check(dev, s->d_scale.p, s->d_diag.p, 1.0 / radius, s->d_step.p, scal + 12, st);}
+    if (timed) {KS_HIP(hipEventRecord(s->ev_phase[n_timed][2], st)); ++n_timed;}
     KS_HIP(hipGetLastError());
     if (direct) {
       // the iteration's last kernel writes its scalars to host-coherent memory and raises the flag behind them; the stream is asked
       // now and then so that a failed launch cannot hang the caller
-      volatile int32_t * flag = s->h_res_flag;
-      uint64_t spins = 0;
-      while (*flag != s->res_seq) {
-        _mm_pause();
-        if ((++spins & 0x3fff) == 0) {
-          const hipError_t e = hipStreamQuery(st);
-          if (e == hipSuccess) {
-            if (*flag == s->res_seq) {break;}
-            set_error("kh_spa: the stream drained without the iteration's result flag"); return finish(KH_ERR_HIP);
-          }
-          if (e != hipErrorNotReady) {set_error(std::string("kh_spa: ") + hipGetErrorString(e)); return finish(KH_ERR_HIP);}
-        }
-      }
+      hipError_t e = hipSuccess;
+      const FlagWait w = wait_device_flag(s->h_res_flag, s->res_seq, st, &e);
+      if (w == FlagWait::kDrained) {set_error("kh_spa: the stream drained without the iteration's result flag"); return finish(KH_ERR_HIP);}
+      if (w == FlagWait::kFailed) {set_error(std::string("kh_spa: ") + hipGetErrorString(e)); return finish(KH_ERR_HIP);}
       for (int q = 3; q <= 10; ++q) {s->h_scal[q] = s->h_res[q];}
       s->h_fail[0] = static_cast<int32_t>(s->h_res[11]);
     } else {
@@ -1570,15 +1521,8 @@ int kh_spa_compute(kh_spa * s, kh_spa_summary * summary)
       }
       std::swap(x, cand);
       x_norm = cand_norm;
-      if (speculate) {
-        std::swap(dev.H, alt.H); std::swap(dev.g, alt.g);          // the speculative linearisation is the current one now
-        x_cost = s->h_scal[8]; gmax = s->h_scal[9];
-      } else {
-        rc = linearize(dev, x, scal + 0); if (rc) {return finish(rc);}
-        spa_launch_grad_norms(dev, x, scal + 1, st);
-        rc = fetch(); if (rc) {return finish(rc);}
-        x_cost = s->h_scal[0]; gmax = s->h_scal[1];
-      }
+      std::swap(dev.H, alt.H); std::swap(dev.g, alt.g);          // the speculative linearisation is the current one now
+      x_cost = s->h_scal[8]; gmax = s->h_scal[9];
       step_successful = true;
       ++sum.successful_steps;
       const double radius_used = radius;

@@ -94,7 +94,6 @@ struct SpaDev
 
 // [e_lo, e_hi): edge block linearised by this rank (0, n_edges on a single GPU)
 void spa_launch_linearize(const SpaDev & d, const double * x, double * cost_out, int e_lo, int e_hi, void * stream);
-void spa_launch_cost(const SpaDev & d, const double * x, double * cost_out, void * stream);
 void spa_launch_jacobi_scale(const SpaDev & d, double * scale_out, void * stream);
 // the head of a factorisation: scaled + damped H into the fronts; with compute_diag the LM diagonal clamp(diag(S H S)) is formed
 // (and left in `diagonal`) on the way; rhs (elimination order) <- scale * g; *fail_flag <- 0
@@ -109,9 +108,7 @@ void spa_launch_factor_level(const SpaDev & d, const int32_t * level_fronts, int
                              double * rhs, double * upd, double * fsb, int32_t * sync, int32_t matrix_added, void * stream);
 // the children's update matrices of every front of the level summed into the fronts, one workgroup per (front, 16
 // destination columns); follow with spa_launch_factor_level(..., matrix_added = 1, ...)
-// part 0: everything; 1: only the pivot blocks (max_ns = most pivot columns of a front of the level); 2: everything else
-void spa_launch_extend_add(const SpaDev & d, const int32_t * level_fronts, int32_t n, int32_t max_m, void * stream, int32_t part = 0,
-                           int32_t max_ns = 0);
+void spa_launch_extend_add(const SpaDev & d, const int32_t * level_fronts, int32_t n, int32_t max_m, void * stream);
 // upd: per-front forward-solve contributions to the ancestors, 3 * front_rows_ptr[n_fronts] doubles
 void spa_launch_backward_level(const SpaDev & d, const int32_t * level_fronts, int32_t n, int32_t max_m, double * rhs, void * stream);
 // round-3 level pipeline (potrf -> trsm -> syrk, see spa_kernels.hip): the children's update matrices must already be summed
@@ -132,10 +129,6 @@ void spa_launch_zero_update_blocks(const SpaDev & d, const int32_t * list, int32
 void spa_launch_count_nonzero(const double * p, int64_t n, int32_t * count, void * stream);
 // whether the largest front of a problem fits the LDS budgets of the level pipeline (otherwise: panel-pair kernels)
 bool spa_level_pipeline_fits(int32_t max_m, int32_t max_ns);
-// step = -y (free order), delta = step * scale
-void spa_launch_finish_step(const SpaDev & d, const double * scale, const double * rhs, double * step, double * delta, void * stream);
-// out[0] = step.gs, out[1] = step^T Hs step, out[2] = any non-finite in step
-void spa_launch_model(const SpaDev & d, const double * scale, const double * step, double * out3, void * stream);
 // step = -y, delta, cand = Plus(x, delta), the model-cost terms and step norms from `cur`; cost and normal equations of
 // the candidate (this rank's edge block [e_lo, e_hi)) into `alt`.  A sharded caller sums alt.H || alt.g over the ranks, then
 // spa_launch_step_scalars leaves scal[3..7] (step), scal[8] (cost), scal[9..10] (gradient norms).
@@ -147,11 +140,9 @@ void spa_launch_step_and_linearize(const SpaDev & cur, const SpaDev & alt, const
 // system-scope store h_flag <- seq
 void spa_launch_step_scalars(const SpaDev & alt, const double * cand, double * partial, bool sharded, double * scal, void * stream,
                              double * h_out = nullptr, int32_t * h_flag = nullptr, const int32_t * fail_flag = nullptr, int32_t seq = 0);
-// debugging aid (KH_SPA_CHECK): out[0] = |(Hs + D / radius) step + gs|^2, out[1] = |gs|^2 from the BSR matrix
+// debugging aid (kh_spa_set_debug bit 0): out[0] = |(Hs + D / radius) step + gs|^2, out[1] = |gs|^2 from the BSR matrix
 void spa_launch_lin_check(const SpaDev & d, const double * scale, const double * diagonal, double inv_radius, const double * step, double * out2,
                           void * stream);
-// cand = Plus(x, delta); out[0] = |x - cand|^2 over free params, out[1] = |cand|^2 over free params
-void spa_launch_plus(const SpaDev & d, const double * x, const double * delta, double * cand, double * out2, void * stream);
 // projected-gradient norms: out[0] = max |x - Plus(x, -g)|, out[1] = |x_free|^2
 void spa_launch_grad_norms(const SpaDev & d, const double * x, double * out2, void * stream);
 

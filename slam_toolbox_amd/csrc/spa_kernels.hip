@@ -190,15 +190,6 @@ void spa_launch_linearize(const SpaDev & d, const double * x, double * cost_out,
   hipLaunchKernelGGL(k_sum, dim3(1), dim3(1024), 0, s, d.edge_cost, d.n_edges, 0.5, cost_out);
 }
 
-void spa_launch_cost(const SpaDev & d, const double * x, double * cost_out, void * stream)
-{
-  hipStream_t s = (hipStream_t)stream;
-  if (d.n_edges > 0) {
-    hipLaunchKernelGGL(k_edge_lin<false>, dim3((d.n_edges + 255) / 256), dim3(256), 0, s, d, x, 0, d.n_edges, (double *)nullptr);
-  }
-  hipLaunchKernelGGL(k_sum, dim3(1), dim3(1024), 0, s, d.edge_cost, d.n_edges, 0.5, cost_out);
-}
-
 // ---------------------------------------------------------------------------------------------
 // small vector kernels
 __global__ void k_jacobi_scale(SpaDev d, double * scale)
@@ -265,66 +256,7 @@ void spa_launch_assemble(const SpaDev & d, const double * scale, double * diagon
                      max_diag, rhs, fail_flag, nbm);
 }
 
-__global__ void k_finish_step(SpaDev d, const double * scale, const double * rhs, double * step, double * delta)
-{
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= d.n_free * 3) {return;}
-  const int i = t / 3, c = t - i * 3;
-  const double y = rhs[3 * d.elim_of_free[i] + c];
-  step[t] = -y;                   // levenberg_marquardt_strategy.cc: step *= -1
-  delta[t] = -y * scale[t];       // trust_region_minimizer.cc: delta = step .* jacobian_scaling
-}
-void spa_launch_finish_step(const SpaDev & d, const double * scale, const double * rhs, double * step, double * delta, void * stream)
-{
-  hipLaunchKernelGGL(k_finish_step, dim3((d.n_free * 3 + 255) / 256), dim3(256), 0, (hipStream_t)stream, d, scale, rhs, step, delta);
-}
-
-// model cost change pieces: tmp[row] = step_row * gs_row, tmp2[row] = step_row * (Hs step)_row
-__global__ void k_model(SpaDev d, const double * scale, const double * step, double * tmp)
-{
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int n3 = d.n_free * 3;
-  if (t >= n3) {return;}
-  const int i = t / 3, r = t - i * 3;
-  double acc = 0.0;
-  for (int k = d.bsr_row_ptr[i]; k < d.bsr_row_ptr[i + 1]; ++k) {
-    const int j = d.bsr_col[k];
-    const double * blk = d.H + (size_t)k * 9 + r * 3;
-    acc += blk[0] * scale[3 * j] * step[3 * j] + blk[1] * scale[3 * j + 1] * step[3 * j + 1] + blk[2] * scale[3 * j + 2] * step[3 * j + 2];
-  }
-  acc *= scale[t];
-  tmp[t] = step[t] * scale[t] * d.g[t];
-  tmp[n3 + t] = step[t] * acc;
-  tmp[2 * n3 + t] = (step[t] - step[t] == 0.0) ? 0.0 : 1.0;    // non-finite marker
-}
-void spa_launch_model(const SpaDev & d, const double * scale, const double * step, double * out3, void * stream)
-{
-  hipStream_t s = (hipStream_t)stream;
-  const int n3 = d.n_free * 3;
-  double * tmp = d.edge_lin;     // scratch: 21*E >= 9*n_free is guaranteed by the host
-  hipLaunchKernelGGL(k_model, dim3((n3 + 255) / 256), dim3(256), 0, s, d, scale, step, tmp);
-  hipLaunchKernelGGL(k_sum, dim3(1), dim3(1024), 0, s, tmp, n3, 1.0, out3);
-  hipLaunchKernelGGL(k_sum, dim3(1), dim3(1024), 0, s, tmp + n3, n3, 1.0, out3 + 1);
-  hipLaunchKernelGGL(k_sum, dim3(1), dim3(1024), 0, s, tmp + 2 * n3, n3, 1.0, out3 + 2);
-}
-
-__global__ void k_plus(SpaDev d, const double * x, const double * delta, double * cand, double * tmp)
-{
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= d.n_nodes) {return;}
-  const int f = d.free_of_node[n];
-  double px = x[3 * n], py = x[3 * n + 1], pt = x[3 * n + 2];
-  if (f >= 0) {
-    const double nx = px + delta[3 * f], ny = py + delta[3 * f + 1];
-    const double nt = d_normalize_angle(pt + delta[3 * f + 2]);     // AngleLocalParameterization, ceres_utils.h:38-55
-    const double ex = px - nx, ey = py - ny, et = pt - nt;
-    tmp[f] = ex * ex + ey * ey + et * et;
-    tmp[d.n_free + f] = nx * nx + ny * ny + nt * nt;
-    px = nx; py = ny; pt = nt;
-  }
-  cand[3 * n] = px; cand[3 * n + 1] = py; cand[3 * n + 2] = pt;
-}
-// KH_SPA_CHECK=1 (debugging aid): the linear system of this iteration, (Hs + D / radius) step + gs = 0 in the scaled
+// kh_spa_set_debug bit 0 (debugging aid): the linear system of this iteration, (Hs + D / radius) step + gs = 0 in the scaled
 // variables, evaluated with the BSR matrix -- independent of the fronts.  out[0] = |residual|^2, out[1] = |gs|^2.
 __global__ __launch_bounds__(1024) void k_lin_check(SpaDev d, const double * scale, const double * diagonal, double inv_radius,
                                                      const double * step, double * out2)
@@ -357,15 +289,6 @@ void spa_launch_lin_check(const SpaDev & d, const double * scale, const double *
                           void * stream)
 {
   hipLaunchKernelGGL(k_lin_check, dim3(1), dim3(1024), 0, (hipStream_t)stream, d, scale, diagonal, inv_radius, step, out2);
-}
-
-void spa_launch_plus(const SpaDev & d, const double * x, const double * delta, double * cand, double * out2, void * stream)
-{
-  hipStream_t s = (hipStream_t)stream;
-  double * tmp = d.edge_lin;
-  hipLaunchKernelGGL(k_plus, dim3((d.n_nodes + 255) / 256), dim3(256), 0, s, d, x, delta, cand, tmp);
-  hipLaunchKernelGGL(k_sum, dim3(1), dim3(1024), 0, s, tmp, d.n_free, 1.0, out2);
-  hipLaunchKernelGGL(k_sum, dim3(1), dim3(1024), 0, s, tmp + d.n_free, d.n_free, 1.0, out2 + 1);
 }
 
 __global__ __launch_bounds__(1024) void k_grad_norms(SpaDev d, const double * x, double * out2)
@@ -775,15 +698,11 @@ __device__ __forceinline__ void trailing_update(double * F, const double * Xs, i
 // where most of the chip idles.  A child's struct rows map to INCREASING positions in the parent (both are in
 // elimination order), so the child columns that land in this workgroup's destination block are one contiguous range;
 // every entry of the block is summed by this workgroup alone, children in turn: no atomics, the same order every run.
-// part: 0 everything; 1 only the front's PIVOT BLOCK (destination rows and columns < ns: what k_potrf reads); 2 everything
-// else (it runs on a second stream beside k_potrf of the same level).
-__global__ __launch_bounds__(1024) void k_extend_add(SpaDev d, const int32_t * __restrict__ level_fronts, int part)
+__global__ __launch_bounds__(1024) void k_extend_add(SpaDev d, const int32_t * __restrict__ level_fronts)
 {
   const int nw = (int)blockDim.x >> 6;
   const int k = level_fronts[blockIdx.x];
   const int m = d.front_m[k];
-  const int nsp_front = d.front_ns[k];
-  if (part == 1 && 16 * (int)blockIdx.y >= nsp_front) {return;}
   const int c_lo = 16 * (int)blockIdx.y, c_hi = min(m, c_lo + 16);
   if (c_lo >= m) {return;}
   double * F = d.fronts + d.front_off[k];
@@ -821,34 +740,24 @@ __global__ __launch_bounds__(1024) void k_extend_add(SpaDev d, const int32_t * _
     hi = nuc;
     while (lo < hi) {const int mid = (lo + hi) >> 1; if (pos(mid) < c_hi) {lo = mid + 1;} else {hi = mid;}}
     const int b_hi = lo;
-    // first child row that lands below the front's pivot block
-    int a_piv = nuc;
-    if (part != 0) {
-      int l2 = 0, h2 = nuc;
-      while (l2 < h2) {const int mid = (l2 + h2) >> 1; if (pos(mid) < nsp_front) {l2 = mid + 1;} else {h2 = mid;}}
-      a_piv = l2;
-    }
     for (int b = b_lo + wave; b < b_hi; b += nw) {
       double * dst = F + (int64_t)pos(b) * m;
       const double * src = Uc + (int64_t)b * mc;
-      const bool pivot_col = b < a_piv;
-      const int a_begin = part == 2 && pivot_col ? max(b, a_piv) : b;
-      const int a_end = part == 1 ? (pivot_col ? a_piv : 0) : nuc;
-      for (int a0 = a_begin; a0 < a_end; a0 += 256) {
-        // four rows per lane in flight: unconditional loads at a clamped row (as `a < a_end ? load : 0` every load sat in a branch
+      for (int a0 = b; a0 < nuc; a0 += 256) {
+        // four rows per lane in flight: unconditional loads at a clamped row (as `a < nuc ? load : 0` every load sat in a branch
         // of its own with a wait behind it: twelve dependent round trips per 256 rows where two do)
         double u[4], f[4];
         int pa[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const int ac = min(a0 + lane + 64 * q, a_end - 1);
+          const int ac = min(a0 + lane + 64 * q, nuc - 1);
           pa[q] = pos(ac);
           u[q] = src[ac];
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {f[q] = dst[pa[q]];}
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {if (a0 + lane + 64 * q < a_end) {dst[pa[q]] = f[q] + u[q];}}
+        for (int q = 0; q < 4; ++q) {if (a0 + lane + 64 * q < nuc) {dst[pa[q]] = f[q] + u[q];}}
       }
     }
     __syncthreads();       // the next child may add into the same entries (and restages s_rp)
@@ -856,15 +765,13 @@ __global__ __launch_bounds__(1024) void k_extend_add(SpaDev d, const int32_t * _
   }
 }
 
-void spa_launch_extend_add(const SpaDev & d, const int32_t * level_fronts, int32_t n, int32_t max_m, void * stream, int32_t part, int32_t max_ns)
+void spa_launch_extend_add(const SpaDev & d, const int32_t * level_fronts, int32_t n, int32_t max_m, void * stream)
 {
   if (n <= 0) {return;}
-  if (part == 1) {max_m = std::min(max_m, max_ns);}      // only the column blocks of the pivot block have work
   // one wave per destination column of the block of 16 (with four waves a workgroup walked its columns four at a time, each
   // walk a round trip to memory); wide levels keep the small workgroups
-  static const int ea_threads = std::getenv("KH_SPA_EA_THREADS") ? std::atoi(std::getenv("KH_SPA_EA_THREADS")) : 0;
-  const int threads = ea_threads ? ea_threads : ((int64_t)n * ((max_m + 15) / 16) > 512 ? 256 : 1024);
-  hipLaunchKernelGGL(k_extend_add, dim3(n, (max_m + 15) / 16), dim3(threads), 0, (hipStream_t)stream, d, level_fronts, (int)part);
+  const int threads = (int64_t)n * ((max_m + 15) / 16) > 512 ? 256 : 1024;
+  hipLaunchKernelGGL(k_extend_add, dim3(n, (max_m + 15) / 16), dim3(threads), 0, (hipStream_t)stream, d, level_fronts);
 }
 
 // ---- workgroup-level hand-offs between the workgroups that share one front (agent scope: the L1 of a CU is never
@@ -2530,10 +2437,8 @@ void spa_launch_update_level(const SpaDev & d, int32_t first_front, int32_t n, i
   if (max_nu <= 0) {return;}
   // slabs / tiles: small enough that a narrow level still spreads over the chip, large enough that a wide one does not
   // drown in workgroups
-  static const int force_r = std::getenv("KH_SPA_TRSM_R") ? std::atoi(std::getenv("KH_SPA_TRSM_R")) : 0;
-  static const int force_ts = std::getenv("KH_SPA_SYRK_TS") ? std::atoi(std::getenv("KH_SPA_SYRK_TS")) : 0;
   const int slabs32 = (max_nu + 31) / 32;
-  const bool r64 = force_r ? force_r == 64 : (int64_t)n * slabs32 >= 1024;
+  const bool r64 = (int64_t)n * slabs32 >= 1024;
   if (r64) {
     hipLaunchKernelGGL(k_trsm<64>, dim3(n, (max_nu + 63) / 64), dim3(256), sizeof(double) * ((size_t)64 * (nsp + 2) + nsp + 8 * 64 + 8), s, d, first_front, rhs, upd, nsp);
   } else {
@@ -2542,7 +2447,7 @@ void spa_launch_update_level(const SpaDev & d, int32_t first_front, int32_t n, i
     hipLaunchKernelGGL(k_trsm<32>, dim3(n, slabs32), dim3(threads), sizeof(double) * ((size_t)32 * (nsp + 2) + nsp + 8 * 32 + 8), s, d, first_front, rhs, upd, nsp);
   }
   const int nt32 = (max_nu + 31) / 32, nt64 = (max_nu + 63) / 64;
-  const bool t64 = force_ts ? force_ts == 64 : (int64_t)n * (nt32 * (nt32 + 1) / 2) >= 2048;
+  const bool t64 = (int64_t)n * (nt32 * (nt32 + 1) / 2) >= 2048;
   if (t64) {
     hipLaunchKernelGGL(k_syrk<64>, dim3(n, nt64 * (nt64 + 1) / 2), dim3(512), sizeof(double) * ((size_t)2 * 64 * (nsp + 2) + 8), s, d, first_front, nsp);
   } else {

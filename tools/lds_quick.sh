@@ -6,7 +6,6 @@ tag=${1:-ldsq}
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 timeout 600 python -m pytest tests/test_matcher_gpu.py -x -q -m gpu -k "lds" 2>&1 | tail -3
-export KH_LDS_SCORE=1
 cmd="python $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-solver --no-loop"
 $cmd > $out/bench_default.json 2> $out/bench_default.err
 

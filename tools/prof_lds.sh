@@ -6,7 +6,6 @@ tag=${1:-lds}
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-export KH_LDS_SCORE=1
 cmd="python $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-solver --no-loop"
 for v in $GRAFT_REPO_ROOT/variants/*.so; do
   n=$(basename $v .so)
