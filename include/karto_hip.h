@@ -443,6 +443,28 @@ KH_API int kh_graph_set_scan_limit(kh_graph * g, int32_t n_visit);
 KH_API int kh_graph_append_scan(kh_graph * g, const double ref_xy[2]);
 KH_API int kh_graph_add_edge(kh_graph * g, int32_t scan_a, int32_t scan_b);
 KH_API int kh_graph_set_position(kh_graph * g, int32_t scan, const double ref_xy[2]);
+/* The store's second point per vertex: GetCorrectedPose() x, y of the scan, which is what the reference's KD-tree adaptor reads
+ * (nanoflann_adaptors.h:44-49) -- not ref_xy, which is the sensor pose or the barycentre.  It follows the store's life cycle:
+ * kh_graph_set drops the poses (kh_graph_set_poses gives all of them, also after CorrectPoses), kh_graph_append_scan_with_pose appends
+ * vertex and pose (the pose-less kh_graph_append_scan leaves the store without poses), kh_graph_set_pose re-poses one vertex.
+ * The near-by queries answer KH_ERR_INVALID_ARG on a non-empty store without poses. */
+KH_API int kh_graph_set_poses(kh_graph * g, int32_t n_scans, const double * pose_xy /* 2n */);
+KH_API int kh_graph_set_pose(kh_graph * g, int32_t scan, const double pose_xy[2]);
+KH_API int kh_graph_append_scan_with_pose(kh_graph * g, const double ref_xy[2], const double pose_xy[2]);
+/* MapperGraph::FindNearByScan (Mapper.cpp:1877-1912) for n_queries poses in ONE kernel launch: nearest[i] = the vertex whose pose
+ * has the smallest squared distance (dx * dx) + (dy * dy) to query i -- nanoflann's L2_Simple_Adaptor sum (nanoflann.hpp:475-485),
+ * each operation rounded on its own, so dist_sq[i] (may be NULL) has the bits of the host expression; between equal distances
+ * the lower index (nanoflann's own answer to an exact tie depends on the shape of its tree).  An empty store answers
+ * nearest = -1 (the reference returns NULL) and dist_sq = +inf. */
+KH_API int kh_graph_find_near_by_scan(kh_graph * g, int32_t n_queries, const double * query_xy /* 2q */, int32_t * nearest /* q */,
+                                      double * dist_sq /* q */);
+/* MapperGraph::FindNearByVertices (Mapper.cpp:1837-1875), i.e. radiusSearch exactly as the reference calls it: max_distance is
+ * handed to an L2 metric that compares it with the SQUARED distance (dist < radius, strict, nanoflann.hpp:274), and the hits come
+ * back by ascending distance (SearchParams::sorted defaults to true, nanoflann.hpp:630, 1418; lower index first between equal
+ * distances).  *n_found is the total even beyond cap; 0 for an empty store. */
+KH_API int kh_graph_find_near_by_vertices(kh_graph * g, const double query_xy[2], double max_distance, int32_t * scans, int32_t cap,
+                                          int32_t * n_found);
+KH_API double kh_graph_last_near_by_kernel_ms(kh_graph * g);       /* device time of the last near-by kernel (HIP events) */
 /* MapperGraph::FindNearLinkedVertices (Mapper.cpp:1808-1819): the vertices a breadth-first traversal from the scan
  * reaches through vertices within max_distance of it, in visiting order (the scan itself first).  *n_found is the total. */
 KH_API int kh_graph_find_near_linked(kh_graph * g, int32_t query_scan, double max_distance, int32_t * scans, int32_t cap,
@@ -523,8 +545,8 @@ KH_API int kh_lifelong_scores(int32_t device, const kh_scan_box * reference, int
  * scans, links to the previous scan, the running chain and the near chains (matched as one batch), loop closure as
  * speculative batches (all candidate chains enumerated by kh_graph_find_loop_candidates_from, coarse-matched in one
  * kh_matcher_match_batch, the ones passing the coarse gate fine-matched in a second, results consumed in the reference's
- * order up to the first accepted closure, then kh_spa_compute and re-enumeration behind it).  One laser, zero mount
- * offset, mapping mode.  The values are AS STORED by karto::Mapper (loop_match_maximum_variance_coarse and the two
+ * order up to the first accepted closure, then kh_spa_compute and re-enumeration behind it).  One laser.  Mapping mode is
+ * kh_mapper_process; localization mode is the group of calls below it.  The values are AS STORED by karto::Mapper (loop_match_maximum_variance_coarse and the two
  * variance penalties of `match` are the squared values). */
 typedef struct kh_mapper kh_mapper;
 typedef struct kh_laser {                       /* karto::LaserRangeFinder (Karto.h:4060-4330) */
@@ -567,6 +589,32 @@ KH_API void kh_mapper_destroy(kh_mapper * m);
  * *accepted = 0 when the scan is dropped by HasMovedEnough (Mapper.cpp:3110-3142).  corrected_pose / covariance may be NULL. */
 KH_API int kh_mapper_process(kh_mapper * m, const double * ranges, const double odometric_pose[3], double time,
                              int32_t * accepted, double corrected_pose[3], double covariance[9]);
+/* ---- localization mode (slam_toolbox_localization.cpp) ----
+ * Mapper::ProcessLocalization (Mapper.cpp:2831-2909) = Process + AddScanToLocalizationBuffer (:2911-2937): the accepted scan enters
+ * a rolling buffer; once the buffer holds more than scan_buffer_size scans its oldest one leaves the graph, the solver and the scan
+ * list like kh_mapper_remove_node (RemoveNodeFromGraph + RemoveScan).  Scans accepted by kh_mapper_process never enter the buffer:
+ * a map built or loaded with it is permanent.  scan_buffer_size < 1 is KH_ERR_INVALID_ARG (the scan would evict itself). */
+KH_API int kh_mapper_process_localization(kh_mapper * m, const double * ranges, const double odometric_pose[3], double time,
+                                          int32_t * accepted, double corrected_pose[3], double covariance[9]);
+/* Mapper::ProcessAgainstNode (Mapper.cpp:3023-3096; ProcessAtDock :3098-3102 is node_id 0): the running scans are cleared and
+ * re-seeded with the node's scan, which becomes the last scan; the scan is matched against it WITHOUT the HasMovedEnough gate
+ * (*accepted is always 1), its odometric pose is overwritten with the corrected pose (:3065), so the next scan's odometry
+ * delta starts there; then vertex, edges, running scan and TryCloseLoop as in Process.  A removed or unknown node is
+ * KH_ERR_NOT_FOUND (the reference dereferences NULL). */
+KH_API int kh_mapper_process_against_node(kh_mapper * m, const double * ranges, const double odometric_pose[3], double time,
+                                          int32_t node_id, int32_t * accepted, double corrected_pose[3], double covariance[9]);
+/* Mapper::ProcessAgainstNodesNearBy (Mapper.cpp:2751-2829; "start near pose" / /initialpose, slam_toolbox_common.cpp:818-832,
+ * slam_toolbox_localization.cpp:195-217): the node is kh_graph_find_near_by_scan of the odometric pose over the scans still in
+ * the graph; with an empty graph there is no match and the scan becomes the first vertex.  add_to_localization_buffer != 0
+ * puts the scan into the rolling buffer (what the localization node does). */
+KH_API int kh_mapper_process_against_nodes_near_by(kh_mapper * m, const double * ranges, const double odometric_pose[3], double time,
+                                                   int32_t add_to_localization_buffer, int32_t * accepted, double corrected_pose[3],
+                                                   double covariance[9]);
+/* Mapper::ClearLocalizationBuffer (Mapper.cpp:2939-2962): every buffered scan removed, oldest first; then the running scans and
+ * the last scan are cleared, so the next scan is a first scan (no gate, no match). */
+KH_API int kh_mapper_clear_localization_buffer(kh_mapper * m);
+/* ids of the buffered scans, oldest first: *n = their number, `ids` (may be NULL) receives at most `cap` */
+KH_API int kh_mapper_localization_buffer(const kh_mapper * m, int32_t * ids, int32_t cap, int32_t * n);
 KH_API int32_t kh_mapper_num_scans(const kh_mapper * m);
 KH_API int64_t kh_mapper_num_edges(const kh_mapper * m);
 KH_API int kh_mapper_get_poses(const kh_mapper * m, double * corrected_poses /* 3 * num_scans */);

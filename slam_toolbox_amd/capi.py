@@ -90,6 +90,10 @@ SYMBOLS = [
     "kh_mapper_num_edges", "kh_mapper_get_poses", "kh_mapper_get_scan", "kh_mapper_get_stats", "kh_mapper_solver",
     "kh_mapper_set_log", "kh_mapper_remove_node", "kh_mapper_get_adjacency", "kh_mapper_set_node_score", "kh_mapper_set_lifelong", "kh_mapper_num_alive", "kh_mapper_get_alive",
     "kh_graph_set_scan_limit", "kh_graph_find_near_linked", "kh_graph_append_scan", "kh_graph_add_edge", "kh_graph_set_position",
+    "kh_graph_set_poses", "kh_graph_set_pose", "kh_graph_append_scan_with_pose", "kh_graph_find_near_by_scan", "kh_graph_find_near_by_vertices",
+    "kh_graph_last_near_by_kernel_ms",
+    "kh_mapper_process_localization", "kh_mapper_process_against_node", "kh_mapper_process_against_nodes_near_by",
+    "kh_mapper_clear_localization_buffer", "kh_mapper_localization_buffer",
 ]
 
 
@@ -285,6 +289,19 @@ def lib():
         L.kh_graph_add_edge.argtypes = [vp, i32, i32]
         L.kh_graph_set_position.argtypes = [vp, i32, dptr]
         L.kh_graph_find_near_linked.argtypes = [vp, i32, dbl, iptr, i32, C.POINTER(i32)]
+    if hasattr(L, "kh_graph_find_near_by_scan"):
+        L.kh_graph_set_poses.argtypes = [vp, i32, vp]
+        L.kh_graph_set_pose.argtypes = [vp, i32, vp]
+        L.kh_graph_append_scan_with_pose.argtypes = [vp, vp, vp]
+        L.kh_graph_find_near_by_scan.argtypes = [vp, i32, vp, vp, vp]
+        L.kh_graph_find_near_by_vertices.argtypes = [vp, vp, dbl, vp, i32, C.POINTER(i32)]
+        L.kh_graph_last_near_by_kernel_ms.argtypes = [vp]
+        L.kh_graph_last_near_by_kernel_ms.restype = dbl
+        L.kh_mapper_process_localization.argtypes = [vp, vp, vp, dbl, C.POINTER(i32), vp, vp]
+        L.kh_mapper_process_against_node.argtypes = [vp, vp, vp, dbl, i32, C.POINTER(i32), vp, vp]
+        L.kh_mapper_process_against_nodes_near_by.argtypes = [vp, vp, vp, dbl, i32, C.POINTER(i32), vp, vp]
+        L.kh_mapper_clear_localization_buffer.argtypes = [vp]
+        L.kh_mapper_localization_buffer.argtypes = [vp, vp, i32, C.POINTER(i32)]
     if hasattr(L, "kh_lifelong_scores"):
         L.kh_decay_params_default.argtypes = [C.POINTER(KhDecayParams)]
         L.kh_decay_params_default.restype = None

@@ -136,6 +136,90 @@ static int ensure(T *& p, size_t & cap, size_t need)
   return KH_OK;
 }
 
+// ---- nearest vertex / vertices within a radius of a pose --------------------------------------------------------------
+// MapperGraph::FindNearByScan (Mapper.cpp:1877-1912) and FindNearByVertices (:1837-1875) build a nanoflann KD-tree over
+// GetCorrectedPose() of every vertex (nanoflann_adaptors.h:44-49) on every call and ask it one question.  The store keeps
+// those points in HBM; a pass over all of them is 16 bytes per vertex (800 KB at 50 000 vertices) and latency-bound, so
+// there is no tree: one workgroup per query reads every point once.
+//
+// nanoflann's L2_Simple_Adaptor::evalMetric (nanoflann.hpp:475-485) sums (a - b)^2 per dimension: (dx * dx) + (dy * dy), each
+// operation rounded on its own -- an FMA here would change the last bit and with it the order of near ties.
+__device__ __forceinline__ double near_by_dist_sq(double qx, double qy, double2 p)
+{
+#pragma clang fp contract(off)
+  const double dx = qx - p.x, dy = qy - p.y;
+  const double xx = dx * dx, yy = dy * dy;
+  return xx + yy;
+}
+
+// (distance, index) order of the library: the smaller distance, and the lower index between equal distances
+__device__ __forceinline__ bool near_by_less(double da, int32_t ia, double db, int32_t ib) {return da < db || (da == db && ia < ib);}
+
+// One workgroup of 256 per query: lane t looks at vertices t, t + 256, ... (one 16-byte load each, a wave reads 1 KB in a row),
+// keeps its best (distance, index); the wave reduces over its 64 lanes with cross-lane shuffles, the four waves through LDS.
+// nearest[q] = -1 and dist_sq[q] = +inf for an empty store.
+__global__ __launch_bounds__(256) void k_near_by_scan(
+  const double2 * __restrict__ pose, int32_t n, const double2 * __restrict__ queries, int32_t * __restrict__ nearest, double * __restrict__ dist_sq)
+{
+  const int qi = blockIdx.x;
+  const double2 q = queries[qi];
+  double best = HUGE_VAL;
+  int32_t best_i = 0x7fffffff;
+  // four loads in flight per lane (the pass is a chain of load latencies); an index past the end reads the last vertex and is not used
+  for (int32_t base = threadIdx.x; base < n; base += 1024) {
+    double2 p[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {p[k] = pose[min(base + 256 * k, n - 1)];}
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int32_t i = base + 256 * k;
+      const double d = near_by_dist_sq(q.x, q.y, p[k]);
+      if (i < n && (d < best || best_i == 0x7fffffff)) {best = d; best_i = i;}       // ascending i: the first of equal distances stays
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const double od = __shfl_xor(best, off, 64);
+    const int32_t oi = __shfl_xor(best_i, off, 64);
+    if (near_by_less(od, oi, best, best_i)) {best = od; best_i = oi;}
+  }
+  __shared__ double s_d[4];
+  __shared__ int32_t s_i[4];
+  if ((threadIdx.x & 63) == 0) {s_d[threadIdx.x >> 6] = best; s_i[threadIdx.x >> 6] = best_i;}
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) {
+      if (near_by_less(s_d[w], s_i[w], best, best_i)) {best = s_d[w]; best_i = s_i[w];}
+    }
+    nearest[qi] = best_i == 0x7fffffff ? -1 : best_i;
+    if (dist_sq) {dist_sq[qi] = best_i == 0x7fffffff ? HUGE_VAL : best;}
+  }
+}
+
+// radiusSearch as FindNearByVertices calls it: every vertex with dist_sq < radius (see kh_graph_find_near_by_vertices), as a
+// compacted list of (index, dist_sq) in no particular order -- the slot counter is a 32-bit integer atomic, one per wave that
+// has a hit; the host sorts the few hits.  hit_idx / hit_d2 hold n entries, so every hit has a slot.
+__global__ __launch_bounds__(256) void k_near_by_radius(
+  const double2 * __restrict__ pose, int32_t n, double qx, double qy, double radius, int32_t * __restrict__ count,
+  int32_t * __restrict__ hit_idx, double * __restrict__ hit_d2)
+{
+  for (int32_t base = blockIdx.x * 256; base < n; base += gridDim.x * 256) {
+    const int32_t i = base + threadIdx.x;
+    double d = 0.0;
+    bool hit = false;
+    if (i < n) {d = near_by_dist_sq(qx, qy, pose[i]); hit = d < radius;}
+    const unsigned long long votes = __ballot(hit);
+    if (votes == 0) {continue;}
+    const int lane = threadIdx.x & 63;
+    int32_t first = 0;
+    if (lane == 0) {first = atomicAdd(count, __popcll(votes));}
+    first = __shfl(first, 0, 64);
+    if (hit) {
+      const int32_t slot = first + __popcll(votes & ((1ull << lane) - 1ull));
+      if (slot < n) {hit_idx[slot] = i; hit_d2[slot] = d;}
+    }
+  }
+}
+
 }  // namespace kh
 
 using namespace kh;
@@ -160,6 +244,16 @@ struct kh_graph
   // host copy of the store: the neighbourhood walks of FindNearChains touch tens of vertices (no kernel)
   std::vector<double> h_xy;
   std::vector<int32_t> h_adj_ptr, h_adj_idx;
+  // the second per-vertex point: GetCorrectedPose() x, y, what the near-by queries measure to (ref_xy is the pose or the barycentre).
+  // Host copy + device copy with a stale flag of its own: a near-by query uploads 16 bytes per vertex, not the adjacency.
+  std::vector<double> h_pose;
+  bool has_poses = true;        // every vertex of the store has its pose (an empty store has; kh_graph_set / the pose-less append clear it)
+  bool pose_stale = false;
+  double * d_pose = nullptr; size_t cap_pose = 0;
+  double * d_nb_query = nullptr; size_t cap_nb_query = 0;      // queries (2q), behind them dist_sq (q)
+  int32_t * d_nb_idx = nullptr; size_t cap_nb_idx = 0;         // nearest (q) / radius hits (n) + their count (1)
+  double * d_nb_d2 = nullptr; size_t cap_nb_d2 = 0;            // dist_sq of the radius hits (n)
+  double last_near_by_ms = 0.0;
 };
 
 extern "C" {
@@ -193,6 +287,7 @@ void kh_graph_destroy(kh_graph * g)
   if (g->stream) {(void)hipStreamSynchronize(g->stream);}
   (void)hipFree(g->d_xy); (void)hipFree(g->d_adj_ptr); (void)hipFree(g->d_adj_idx); (void)hipFree(g->d_queries);
   (void)hipFree(g->d_flags); (void)hipFree(g->d_frontier); (void)hipFree(g->d_count); (void)hipFree(g->d_chains);
+  (void)hipFree(g->d_pose); (void)hipFree(g->d_nb_query); (void)hipFree(g->d_nb_idx); (void)hipFree(g->d_nb_d2);
   if (g->ev[0]) {(void)hipEventDestroy(g->ev[0]);}
   if (g->ev[1]) {(void)hipEventDestroy(g->ev[1]);}
   if (g->stream) {(void)hipStreamDestroy(g->stream);}
@@ -216,6 +311,7 @@ int kh_graph_set(kh_graph * g, int32_t n_scans, const double * ref_xy, const int
   g->h_xy.assign(ref_xy, ref_xy + 2 * n);
   g->h_adj_ptr.assign(adj_ptr, adj_ptr + (n ? n + 1 : 0));
   g->h_adj_idx.assign(adj_idx, adj_idx + n_adj);
+  g->h_pose.clear(); g->has_poses = n_scans == 0; g->pose_stale = true;      // kh_graph_set_poses follows for the near-by queries
   return KH_OK;
 }
 
@@ -225,12 +321,15 @@ namespace kh
 // (library-internal, the mapper's sync_graph) kh_graph_set without the copies: the store takes the caller's arrays and hands its old
 // ones back (same capacity next time); the caller built adj_idx from its own tables, so the range check is skipped.  A lifelong mapper
 // rebuilds the store after every node removal -- once per accepted scan, 18 000 scans alive in the 50 000-scan replay.
-int graph_swap(kh_graph * g, int32_t n_scans, std::vector<double> & ref_xy, std::vector<int32_t> & adj_ptr, std::vector<int32_t> & adj_idx)
+int graph_swap(kh_graph * g, int32_t n_scans, std::vector<double> & ref_xy, std::vector<int32_t> & adj_ptr, std::vector<int32_t> & adj_idx,
+  std::vector<double> & pose_xy)
 {
-  if (!g || n_scans < 0 || ref_xy.size() != 2 * static_cast<size_t>(n_scans) || adj_ptr.size() != static_cast<size_t>(n_scans) + 1) {return KH_ERR_INVALID_ARG;}
+  if (!g || n_scans < 0 || ref_xy.size() != 2 * static_cast<size_t>(n_scans) || adj_ptr.size() != static_cast<size_t>(n_scans) + 1 ||
+    pose_xy.size() != ref_xy.size()) {return KH_ERR_INVALID_ARG;}
   g->device_stale = true;
   g->n = n_scans; g->n_visit = n_scans;
   g->h_xy.swap(ref_xy); g->h_adj_ptr.swap(adj_ptr); g->h_adj_idx.swap(adj_idx);
+  g->h_pose.swap(pose_xy); g->has_poses = true; g->pose_stale = true;
   return KH_OK;
 }
 }  // namespace kh
@@ -245,6 +344,36 @@ int kh_graph_append_scan(kh_graph * g, const double ref_xy[2])
   if (g->n_visit == g->n) {++g->n_visit;}
   ++g->n;
   g->device_stale = true;
+  g->has_poses = false;                  // this vertex has no pose: kh_graph_append_scan_with_pose is the form that keeps the near-by queries
+  return KH_OK;
+}
+
+int kh_graph_append_scan_with_pose(kh_graph * g, const double ref_xy[2], const double pose_xy[2])
+{
+  if (!g || !ref_xy || !pose_xy) {return KH_ERR_INVALID_ARG;}
+  const bool had_poses = g->has_poses;
+  const int rc = kh_graph_append_scan(g, ref_xy);
+  if (rc) {return rc;}
+  if (had_poses) {
+    g->h_pose.push_back(pose_xy[0]); g->h_pose.push_back(pose_xy[1]);
+    g->has_poses = true; g->pose_stale = true;
+  }
+  return KH_OK;
+}
+
+int kh_graph_set_poses(kh_graph * g, int32_t n_scans, const double * pose_xy)
+{
+  if (!g || n_scans != g->n || (n_scans > 0 && !pose_xy)) {return KH_ERR_INVALID_ARG;}
+  g->h_pose.assign(pose_xy, pose_xy + 2 * static_cast<size_t>(n_scans));
+  g->has_poses = true; g->pose_stale = true;
+  return KH_OK;
+}
+
+int kh_graph_set_pose(kh_graph * g, int32_t scan, const double pose_xy[2])
+{
+  if (!g || !pose_xy || scan < 0 || scan >= g->n || !g->has_poses) {return KH_ERR_INVALID_ARG;}
+  g->h_pose[2 * static_cast<size_t>(scan)] = pose_xy[0]; g->h_pose[2 * static_cast<size_t>(scan) + 1] = pose_xy[1];
+  g->pose_stale = true;
   return KH_OK;
 }
 
@@ -434,6 +563,107 @@ int kh_graph_find_loop_candidates_from(
 }
 
 double kh_graph_last_kernel_ms(kh_graph * g) {return g ? g->last_ms : 0.0;}
+
+// ---- near-by queries (k_near_by_scan / k_near_by_radius) -----------------------------------------------------------------
+namespace
+{
+int near_by_ready(kh_graph * g, const char * who)
+{
+  if (!g->has_poses) {set_error(std::string(who) + ": the store has no poses (kh_graph_set_poses)"); return KH_ERR_INVALID_ARG;}
+  if (hipSetDevice(g->device) != hipSuccess) {return KH_ERR_HIP;}
+  if (g->pose_stale && g->n > 0) {
+    const size_t ns = static_cast<size_t>(g->n);
+    const int rc = ensure(g->d_pose, g->cap_pose, 2 * ns); if (rc) {return rc;}
+    if (hipMemcpyAsync(g->d_pose, g->h_pose.data(), 2 * ns * sizeof(double), hipMemcpyHostToDevice, g->stream) != hipSuccess ||
+      hipStreamSynchronize(g->stream) != hipSuccess)
+    {
+      set_error(std::string(who) + ": upload failed");
+      return KH_ERR_HIP;
+    }
+  }
+  g->pose_stale = false;
+  return KH_OK;
+}
+}  // namespace
+
+int kh_graph_find_near_by_scan(kh_graph * g, int32_t n_queries, const double * query_xy, int32_t * nearest, double * dist_sq)
+{
+  if (!g || n_queries < 0 || (n_queries > 0 && (!query_xy || !nearest))) {return KH_ERR_INVALID_ARG;}
+  if (n_queries == 0) {return KH_OK;}
+  const size_t nq = static_cast<size_t>(n_queries);
+  if (g->n == 0) {                                      // FindNearByScan returns NULL (Mapper.cpp:1907-1911)
+    for (size_t i = 0; i < nq; ++i) {nearest[i] = -1; if (dist_sq) {dist_sq[i] = HUGE_VAL;}}
+    return KH_OK;
+  }
+  int rc = near_by_ready(g, "kh_graph_find_near_by_scan"); if (rc) {return rc;}
+  rc = ensure(g->d_nb_query, g->cap_nb_query, 3 * nq); if (rc) {return rc;}
+  rc = ensure(g->d_nb_idx, g->cap_nb_idx, nq); if (rc) {return rc;}
+  double * d_d2 = g->d_nb_query + 2 * nq;
+  if (hipMemcpyAsync(g->d_nb_query, query_xy, 2 * nq * sizeof(double), hipMemcpyHostToDevice, g->stream) != hipSuccess) {return KH_ERR_HIP;}
+  (void)hipEventRecord(g->ev[0], g->stream);
+  hipLaunchKernelGGL(k_near_by_scan, dim3(static_cast<unsigned>(nq)), dim3(256), 0, g->stream, reinterpret_cast<const double2 *>(g->d_pose),
+    g->n, reinterpret_cast<const double2 *>(g->d_nb_query), g->d_nb_idx, d_d2);
+  (void)hipEventRecord(g->ev[1], g->stream);
+  if (hipMemcpyAsync(nearest, g->d_nb_idx, nq * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
+    (dist_sq && hipMemcpyAsync(dist_sq, d_d2, nq * sizeof(double), hipMemcpyDeviceToHost, g->stream) != hipSuccess) ||
+    hipStreamSynchronize(g->stream) != hipSuccess)
+  {
+    set_error(std::string("kh_graph_find_near_by_scan: ") + hipGetErrorString(hipGetLastError()));
+    return KH_ERR_HIP;
+  }
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, g->ev[0], g->ev[1]);
+  g->last_near_by_ms = ms;
+  return KH_OK;
+}
+
+int kh_graph_find_near_by_vertices(kh_graph * g, const double query_xy[2], double max_distance, int32_t * scans, int32_t cap, int32_t * n_found)
+{
+  if (!g || !query_xy || !n_found || cap < 0 || (cap > 0 && !scans)) {return KH_ERR_INVALID_ARG;}
+  *n_found = 0;
+  if (g->n == 0) {return KH_OK;}
+  int rc = near_by_ready(g, "kh_graph_find_near_by_vertices"); if (rc) {return rc;}
+  const size_t n = static_cast<size_t>(g->n);
+  rc = ensure(g->d_nb_idx, g->cap_nb_idx, n + 1); if (rc) {return rc;}
+  rc = ensure(g->d_nb_d2, g->cap_nb_d2, n); if (rc) {return rc;}
+  int32_t * d_count = g->d_nb_idx + n;
+  if (hipMemsetAsync(d_count, 0, sizeof(int32_t), g->stream) != hipSuccess) {return KH_ERR_HIP;}
+  // FindNearByVertices hands maxDistance to radiusSearch (Mapper.cpp:1865) as the search RADIUS of an L2 metric, whose result set
+  // keeps a point when `dist < radius` (nanoflann.hpp:274) with dist the SQUARED distance of L2_Simple_Adaptor: the reference
+  // compares the squared distance with the unsquared maxDistance, strictly, and so does this
+  const unsigned blocks = static_cast<unsigned>(std::min<size_t>((n + 255) / 256, 256));
+  (void)hipEventRecord(g->ev[0], g->stream);
+  hipLaunchKernelGGL(k_near_by_radius, dim3(blocks), dim3(256), 0, g->stream, reinterpret_cast<const double2 *>(g->d_pose), g->n,
+    query_xy[0], query_xy[1], max_distance, d_count, g->d_nb_idx, g->d_nb_d2);
+  (void)hipEventRecord(g->ev[1], g->stream);
+  int32_t count = 0;
+  if (hipMemcpyAsync(&count, d_count, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream) != hipSuccess || hipStreamSynchronize(g->stream) != hipSuccess) {
+    set_error(std::string("kh_graph_find_near_by_vertices: ") + hipGetErrorString(hipGetLastError()));
+    return KH_ERR_HIP;
+  }
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, g->ev[0], g->ev[1]);
+  g->last_near_by_ms = ms;
+  if (count < 0 || static_cast<size_t>(count) > n) {set_error("kh_graph_find_near_by_vertices: hit count out of range"); return KH_ERR_HIP;}
+  std::vector<int32_t> idx(static_cast<size_t>(count));
+  std::vector<double> d2(static_cast<size_t>(count));
+  if (count > 0 && (hipMemcpy(idx.data(), g->d_nb_idx, idx.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+    hipMemcpy(d2.data(), g->d_nb_d2, d2.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
+  {
+    set_error("kh_graph_find_near_by_vertices: download failed");
+    return KH_ERR_HIP;
+  }
+  // SearchParams::sorted defaults to true (nanoflann.hpp:630): radiusSearch sorts the matches by ascending distance (:1418,
+  // IndexDist_Sorter :227); between equal distances the library's rule is the lower index
+  std::vector<int32_t> order(static_cast<size_t>(count));
+  for (int32_t k = 0; k < count; ++k) {order[k] = k;}
+  std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {return d2[a] < d2[b] || (d2[a] == d2[b] && idx[a] < idx[b]);});
+  for (int32_t k = 0; k < count && k < cap; ++k) {scans[k] = idx[order[k]];}
+  *n_found = count;
+  return KH_OK;
+}
+
+double kh_graph_last_near_by_kernel_ms(kh_graph * g) {return g ? g->last_near_by_ms : 0.0;}
 
 int kh_graph_set_scan_limit(kh_graph * g, int32_t n_visit)
 {

@@ -5,7 +5,8 @@
 // small exact host arithmetic (poses, transforms, running-scan buffer, link bookkeeping) in the reference's operation
 // order so that the run is comparable call by call with karto::Mapper driving the same queue.
 //
-// Reference: lib/karto_sdk/src/Mapper.cpp  Process :2679-2748, HasMovedEnough :3110-3142, ScanManager::AddRunningScan
+// Reference: lib/karto_sdk/src/Mapper.cpp  Process :2679-2748, ProcessLocalization :2831-2909 with AddScanToLocalizationBuffer /
+// ClearLocalizationBuffer :2911-2962, ProcessAgainstNodesNearBy :2751-2829, ProcessAgainstNode / ProcessAtDock :3023-3102, HasMovedEnough :3110-3142, ScanManager::AddRunningScan
 // :183-206, MapperGraph::AddVertex :1418-1432, AddEdges :1434-1498, TryCloseLoop :1500-1561, LinkScans :1620-1639,
 // LinkNearChains :1641-1663, LinkChainToScan :1665-1681, CorrectPoses :2012-2030; Karto.h LocalizedRangeScan::Update
 // :5644-5704, GetSensorAt / GetCorrectedAt :5566-5586, Transform :2946-3041, Matrix3::FromAxisAngle :2482-2511.
@@ -17,7 +18,10 @@
 // then moves every pose, so what was computed for later chains is discarded and the enumeration resumes behind the
 // accepted chain with the new poses (closures are rare, the speculation almost always commits).
 //
-// Scope: one laser (mounted anywhere on the robot: kh_laser::offset_*, Karto.h:5566-5586), mapping mode (no localization buffer).
+// The four entry points share one body (process_scan): they differ in where the last scan comes from, in the HasMovedEnough gate
+// and in what happens to the accepted scan at the very end (the localization buffer).
+//
+// Scope: one laser (mounted anywhere on the robot: kh_laser::offset_*, Karto.h:5566-5586).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -41,7 +45,8 @@ int decay_scores(int32_t device, const kh_scan_box * reference, int32_t n, const
   double * reading_overlap, double * scores);                                                                       // lifelong.hip
 void set_pending_query_hook(std::function<void()> fn);       // matcher_seq.cpp (QueryHook, matcher_private.hpp)
 void run_pending_query_hook();
-int graph_swap(kh_graph * g, int32_t n_scans, std::vector<double> & ref_xy, std::vector<int32_t> & adj_ptr, std::vector<int32_t> & adj_idx);   // graph.hip
+int graph_swap(kh_graph * g, int32_t n_scans, std::vector<double> & ref_xy, std::vector<int32_t> & adj_ptr, std::vector<int32_t> & adj_idx,
+  std::vector<double> & pose_xy);   // graph.hip
 
 void set_error(const std::string & s);
 void host_parallel_for(size_t n, const std::function<void(size_t)> & fn);
@@ -243,7 +248,8 @@ struct kh_mapper
   std::vector<std::unique_ptr<MScan>> scans;             // processed scans, index = state id = unique id; null once removed
   std::vector<int32_t> alive;                            // ids still in the scan map, ascending: the graph store's scan list
   std::vector<int32_t> compact_of;                       // id -> position in `alive`, -1 when removed
-  std::vector<double> sync_xy; std::vector<int32_t> sync_ptr, sync_idx;      // sync_graph's scratch (swapped with the store's arrays)
+  std::vector<double> sync_xy, sync_pose; std::vector<int32_t> sync_ptr, sync_idx;      // sync_graph's scratch (swapped with the store's arrays)
+  std::vector<int32_t> loc_buffer;                       // m_LocalizationScanVertices: ids of the scans localization mode accepted, oldest first
   // KH_MAPPER_TIMING=1 (measurement aid): wall time per piece of the host code, printed by kh_mapper_destroy
   double prof_ms[12] = {0}; long prof_n[12] = {0};
   bool lifelong = false;
@@ -346,19 +352,20 @@ int sync_graph(kh_mapper * m)
   }
   const size_t n = m->alive.size();
   // (scratch kept by the mapper and swapped with the store's arrays: no allocation, no copy -- see kh::graph_swap)
-  std::vector<double> & xy = m->sync_xy;
+  std::vector<double> & xy = m->sync_xy, & pose = m->sync_pose;
   std::vector<int32_t> & ptr = m->sync_ptr, & idx = m->sync_idx;
-  xy.resize(2 * n); ptr.resize(n + 1); idx.clear();
+  xy.resize(2 * n); pose.resize(2 * n); ptr.resize(n + 1); idx.clear();
   ptr[0] = 0;
   for (size_t c = 0; c < n; ++c) {
     reference_xy(m, *m->scans[m->alive[c]], &xy[2 * c]);
+    pose[2 * c] = m->scans[m->alive[c]]->corrected.x; pose[2 * c + 1] = m->scans[m->alive[c]]->corrected.y;
     ptr[c + 1] = ptr[c] + static_cast<int32_t>(m->adj[m->alive[c]].size());
   }
   idx.reserve(static_cast<size_t>(ptr[n]));
   for (size_t c = 0; c < n; ++c) {
     for (int32_t w : m->adj[m->alive[c]]) {idx.push_back(m->compact_of[w]);}
   }
-  int rc = kh::graph_swap(m->graph, static_cast<int32_t>(n), xy, ptr, idx);
+  int rc = kh::graph_swap(m->graph, static_cast<int32_t>(n), xy, ptr, idx, pose);
   if (rc) {return rc;}
   // the reference bounds its candidate walks by the scan map's SIZE, in id space (Mapper.cpp:1974-1976, 1751-1756)
   const int32_t n_visit = static_cast<int32_t>(std::lower_bound(m->alive.begin(), m->alive.end(), static_cast<int32_t>(n)) - m->alive.begin());
@@ -377,7 +384,10 @@ void set_sensor_pose(kh_mapper * m, MScan & s, const double pose[3])
   if (!m->graph_dirty && s.id < static_cast<int32_t>(m->compact_of.size()) && m->compact_of[s.id] >= 0) {
     double xy[2];
     reference_xy(m, s, xy);
-    if (kh_graph_set_position(m->graph, m->compact_of[s.id], xy) != KH_OK) {m->graph_dirty = true;}
+    const double pose_xy[2] = {s.corrected.x, s.corrected.y};
+    if (kh_graph_set_position(m->graph, m->compact_of[s.id], xy) != KH_OK || kh_graph_set_pose(m->graph, m->compact_of[s.id], pose_xy) != KH_OK) {
+      m->graph_dirty = true;
+    }
   } else {
     m->graph_dirty = true;
   }
@@ -647,6 +657,8 @@ int remove_node(kh_mapper * m, int32_t id)
     if (m->scans[id]->d_points[q]) {m->d_free_slots[q].push_back(m->scans[id]->d_points[q]);}
   }
   m->scans[id].reset();
+  // a scan that leaves the graph by any way (node decay, kh_mapper_remove_node) leaves the localization buffer with it
+  m->loc_buffer.erase(std::remove(m->loc_buffer.begin(), m->loc_buffer.end(), id), m->loc_buffer.end());
   m->graph_dirty = true;
   m->stats.nodes_removed += 1;
   return KH_OK;
@@ -833,15 +845,59 @@ int kh_mapper_set_log(kh_mapper * m, const char * path)
 
 kh_spa * kh_mapper_solver(kh_mapper * m) {return m ? m->solver : nullptr;}
 
-// Mapper::Process (Mapper.cpp:2679-2748)
-int kh_mapper_process(kh_mapper * m, const double * ranges, const double odometric_pose[3], double time, int32_t * accepted,
-  double corrected_pose[3], double covariance[9])
+}  // extern "C"
+namespace kh
+{
+namespace
+{
+// Mapper::AddScanToLocalizationBuffer's eviction (Mapper.cpp:2919-2936) and the loop body of ClearLocalizationBuffer (:2941-2953):
+// the front of the buffer leaves the graph, the solver and the scan map
+int evict_front(kh_mapper * m)
+{
+  const int32_t old = m->loc_buffer.front();
+  // In a run of ProcessLocalization calls the evicted scan is scan_buffer_size accepted scans behind the newest one and the same
+  // parameter bounds the running window (AddRunningScan :183-206), so it has left the window; the reference relies on that (its
+  // window holds raw pointers).  A window re-seeded by ProcessAgainstNode(sNearBy) with a BUFFERED scan breaks the assumption:
+  // the reference would then match against a deleted scan.  Here the scan leaves the window with the graph.
+  m->running.erase(std::remove(m->running.begin(), m->running.end(), old), m->running.end());
+  if (m->last == old) {m->last = -1;}
+  return remove_node(m, old);                          // (takes `old` out of loc_buffer)
+}
+
+enum class Entry {kProcess, kLocalization, kAgainstNode, kNearBy};
+
+// The body Mapper::Process (Mapper.cpp:2679-2748), ProcessLocalization (:2831-2909), ProcessAgainstNode (:3023-3096) and
+// ProcessAgainstNodesNearBy (:2751-2829) share
+int process_scan(kh_mapper * m, Entry entry, int32_t node_id, bool to_buffer, const double * ranges, const double odometric_pose[3], double time,
+  int32_t * accepted, double corrected_pose[3], double covariance[9])
 {
   if (!m || !ranges || !odometric_pose || !accepted) {return KH_ERR_INVALID_ARG;}
   *accepted = 0;
   if (m->failed) {
     kh::set_error("kh_mapper_process: an earlier call failed after its scan had entered the graph; the handle is unusable");
     return KH_ERR_SOLVER;
+  }
+  if (to_buffer && m->p.scan_buffer_size < 1) {
+    kh::set_error("localization mode needs scan_buffer_size >= 1 (the accepted scan would evict itself)");
+    return KH_ERR_INVALID_ARG;
+  }
+  const bool gated = entry == Entry::kProcess || entry == Entry::kLocalization;
+  if (entry == Entry::kAgainstNode && (node_id < 0 || node_id >= static_cast<int32_t>(m->scans.size()) || !m->scans[node_id])) {
+    kh::set_error("ProcessAgainstNode: no such node (unknown or removed)");         // the reference dereferences NULL (:3043-3046)
+    return KH_ERR_NOT_FOUND;
+  }
+  if (entry == Entry::kNearBy) {
+    // FindNearByScan(sensor name, pScan->GetOdometricPose()) over the vertices still in the graph (:2768-2769)
+    if (m->graph_dirty) {const int rc = sync_graph(m); if (rc) {return rc;}}
+    int32_t nearest = -1;
+    const int rc = kh_graph_find_near_by_scan(m->graph, 1, odometric_pose, &nearest, nullptr);
+    if (rc) {return rc;}
+    node_id = nearest >= 0 ? m->alive[nearest] : -1;
+  }
+  if (!gated && node_id >= 0) {
+    // ClearRunningScans, AddRunningScan(pLastScan), SetLastScan(pLastScan) (:2774-2776, 3046-3048)
+    m->running.assign(1, node_id);
+    m->last = node_id;
   }
   const auto t_begin = std::chrono::steady_clock::now();
   std::unique_ptr<MScan> scan(new MScan());
@@ -850,10 +906,11 @@ int kh_mapper_process(kh_mapper * m, const double * ranges, const double odometr
   scan->odometric.x = odometric_pose[0]; scan->odometric.y = odometric_pose[1]; scan->odometric.h = odometric_pose[2];
   scan->corrected = scan->odometric;                      // the caller's SetCorrectedPose(odometric pose)
   MScan * last = m->last >= 0 ? m->scans[m->last].get() : nullptr;
-  // update the scan's corrected pose based on the last correction (:2699-2703)
-  if (last) {scan->corrected = transform_pose(last->odometric, last->corrected, scan->odometric);}
+  // update the scan's corrected pose based on the last correction (:2699-2703); not on the near-pose entries, whose caller has put
+  // the scan where the match should start
+  if (last && gated) {scan->corrected = transform_pose(last->odometric, last->corrected, scan->odometric);}
   // HasMovedEnough (:3110-3142)
-  if (last) {
+  if (last && gated) {
     bool moved = false;
     if (scan->time - last->time >= m->p.minimum_time_interval) {moved = true;}
     // the scanner's pose for the two odometric poses (GetSensorAt, :3123-3124)
@@ -912,6 +969,8 @@ int kh_mapper_process(kh_mapper * m, const double * ranges, const double odometr
     }
     set_sensor_pose(m, *scan, mean);
   }
+  // pScan->SetOdometricPose(pScan->GetCorrectedPose()) (:2792, 3065): the next scan's odometry delta is measured from here
+  if (!gated) {scan->odometric = scan->corrected;}
   // AddScan: state id = unique id = position in the list (:2727)
   const int32_t id = static_cast<int32_t>(m->scans.size());
   scan->id = id;
@@ -924,7 +983,8 @@ int kh_mapper_process(kh_mapper * m, const double * ranges, const double odometr
     reference_xy(m, *m->scans[id], xy);
     m->compact_of.push_back(static_cast<int32_t>(m->alive.size()));
     m->alive.push_back(id);
-    if (kh_graph_append_scan(m->graph, xy) != KH_OK) {m->graph_dirty = true;}
+    const double pose_xy[2] = {m->scans[id]->corrected.x, m->scans[id]->corrected.y};
+    if (kh_graph_append_scan_with_pose(m->graph, xy, pose_xy) != KH_OK) {m->graph_dirty = true;}
     // the scan map's size in id space bounds the candidate walks (see sync_graph)
     const int32_t n_alive = static_cast<int32_t>(m->alive.size());
     const int32_t n_visit = static_cast<int32_t>(std::lower_bound(m->alive.begin(), m->alive.end(), n_alive) - m->alive.begin());
@@ -1012,6 +1072,14 @@ int kh_mapper_process(kh_mapper * m, const double * ranges, const double odometr
     const int rc = kh::lifelong_step(m, id);
     if (rc) {return rc;}
   }
+  // AddScanToLocalizationBuffer (:2911-2937)
+  if (to_buffer) {
+    m->loc_buffer.push_back(id);
+    if (m->loc_buffer.size() > static_cast<size_t>(m->p.scan_buffer_size)) {
+      const int rc = evict_front(m);
+      if (rc) {return rc;}
+    }
+  }
   guard.armed = false;
   if (m->log && std::getenv("KH_LOG_FINAL_POSES")) {     // debugging aid, see oracle/ref_slam_driver.cpp
     std::fprintf(m->log, "F %d %.17g %.17g %.17g\n", id, s.corrected.x, s.corrected.y, s.corrected.h);
@@ -1021,6 +1089,60 @@ int kh_mapper_process(kh_mapper * m, const double * ranges, const double odometr
   if (covariance) {std::copy(cov, cov + 9, covariance);}
   m->stats.scans_processed += 1;
   m->stats.process_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  return KH_OK;
+}
+}  // namespace
+}  // namespace kh
+
+extern "C" {
+
+// Mapper::Process (Mapper.cpp:2679-2748)
+int kh_mapper_process(kh_mapper * m, const double * ranges, const double odometric_pose[3], double time, int32_t * accepted,
+  double corrected_pose[3], double covariance[9])
+{
+  return kh::process_scan(m, kh::Entry::kProcess, -1, false, ranges, odometric_pose, time, accepted, corrected_pose, covariance);
+}
+
+// Mapper::ProcessLocalization (Mapper.cpp:2831-2909)
+int kh_mapper_process_localization(kh_mapper * m, const double * ranges, const double odometric_pose[3], double time, int32_t * accepted,
+  double corrected_pose[3], double covariance[9])
+{
+  return kh::process_scan(m, kh::Entry::kLocalization, -1, true, ranges, odometric_pose, time, accepted, corrected_pose, covariance);
+}
+
+// Mapper::ProcessAgainstNode (Mapper.cpp:3023-3096); ProcessAtDock (:3098-3102) is node 0
+int kh_mapper_process_against_node(kh_mapper * m, const double * ranges, const double odometric_pose[3], double time, int32_t node_id,
+  int32_t * accepted, double corrected_pose[3], double covariance[9])
+{
+  return kh::process_scan(m, kh::Entry::kAgainstNode, node_id, false, ranges, odometric_pose, time, accepted, corrected_pose, covariance);
+}
+
+// Mapper::ProcessAgainstNodesNearBy (Mapper.cpp:2751-2829)
+int kh_mapper_process_against_nodes_near_by(kh_mapper * m, const double * ranges, const double odometric_pose[3], double time,
+  int32_t add_to_localization_buffer, int32_t * accepted, double corrected_pose[3], double covariance[9])
+{
+  return kh::process_scan(m, kh::Entry::kNearBy, -1, add_to_localization_buffer != 0, ranges, odometric_pose, time, accepted, corrected_pose,
+           covariance);
+}
+
+// Mapper::ClearLocalizationBuffer (Mapper.cpp:2939-2962)
+int kh_mapper_clear_localization_buffer(kh_mapper * m)
+{
+  if (!m) {return KH_ERR_INVALID_ARG;}
+  while (!m->loc_buffer.empty()) {
+    const int rc = kh::evict_front(m);
+    if (rc) {m->failed = true; return rc;}
+  }
+  m->running.clear();                                  // ClearRunningScans / ClearLastScan of every sensor (:2955-2960)
+  m->last = -1;
+  return KH_OK;
+}
+
+int kh_mapper_localization_buffer(const kh_mapper * m, int32_t * ids, int32_t cap, int32_t * n)
+{
+  if (!m || !n || cap < 0) {return KH_ERR_INVALID_ARG;}
+  *n = static_cast<int32_t>(m->loc_buffer.size());
+  if (ids) {std::copy(m->loc_buffer.begin(), m->loc_buffer.begin() + std::min(*n, cap), ids);}
   return KH_OK;
 }
 

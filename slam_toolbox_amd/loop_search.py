@@ -72,8 +72,53 @@ class MapperGraphSearch:
                                                             C.byref(out)), "kh_graph_closest_scan_to_pose")
         return out.value
 
+    def SetPoses(self, pose_xy):
+        """GetCorrectedPose() x, y of every vertex: the points the near-by queries measure to (after SetGraph, and again after
+        CorrectPoses)."""
+        pose_xy = np.ascontiguousarray(pose_xy, dtype=np.float64).reshape(-1, 2)
+        capi.check(capi.lib().kh_graph_set_poses(self._h, pose_xy.shape[0], pose_xy.ctypes.data), "kh_graph_set_poses")
+
+    def SetPose(self, scan, pose_xy):
+        xy = np.ascontiguousarray(pose_xy, dtype=np.float64)[:2].copy()
+        capi.check(capi.lib().kh_graph_set_pose(self._h, int(scan), xy.ctypes.data), "kh_graph_set_pose")
+
+    def AppendScan(self, ref_xy, pose_xy):
+        ref = np.ascontiguousarray(ref_xy, dtype=np.float64)[:2].copy()
+        pose = np.ascontiguousarray(pose_xy, dtype=np.float64)[:2].copy()
+        capi.check(capi.lib().kh_graph_append_scan_with_pose(self._h, ref.ctypes.data, pose.ctypes.data), "kh_graph_append_scan_with_pose")
+        self.n += 1
+
+    def FindNearByScan(self, query_xy):
+        """MapperGraph::FindNearByScan (Mapper.cpp:1877-1912) for one pose (x, y) or a batch (q, 2) in one kernel launch
+        -> (nearest, dist_sq): vertex index (-1 for an empty graph) and squared distance, scalars for one pose."""
+        q = np.ascontiguousarray(query_xy, dtype=np.float64)
+        single = q.ndim == 1
+        q = np.ascontiguousarray(q.reshape(-1, q.shape[-1])[:, :2])
+        nearest = np.full(q.shape[0], -1, dtype=np.int32)
+        dist_sq = np.zeros(q.shape[0])
+        capi.check(capi.lib().kh_graph_find_near_by_scan(self._h, q.shape[0], q.ctypes.data, nearest.ctypes.data, dist_sq.ctypes.data),
+                   "kh_graph_find_near_by_scan")
+        return (int(nearest[0]), float(dist_sq[0])) if single else (nearest, dist_sq)
+
+    def FindNearByVertices(self, query_xy, max_distance):
+        """MapperGraph::FindNearByVertices (Mapper.cpp:1837-1875): the vertices with SQUARED distance < max_distance (the
+        reference's radiusSearch call, nanoflann.hpp:274), by ascending distance."""
+        q = np.ascontiguousarray(query_xy, dtype=np.float64)[:2].copy()
+        cap = 256
+        total = C.c_int32(0)
+        while True:
+            out = np.zeros(cap, dtype=np.int32)
+            capi.check(capi.lib().kh_graph_find_near_by_vertices(self._h, q.ctypes.data, float(max_distance), out.ctypes.data, cap,
+                                                                 C.byref(total)), "kh_graph_find_near_by_vertices")
+            if total.value <= cap:
+                return out[:total.value]
+            cap = total.value
+
     def last_kernel_ms(self):
         return capi.lib().kh_graph_last_kernel_ms(self._h)
+
+    def last_near_by_kernel_ms(self):
+        return capi.lib().kh_graph_last_near_by_kernel_ms(self._h)
 
     def close(self):
         if self._h:

@@ -1,4 +1,5 @@
-"""Host-side mirror of karto::Mapper's processing entry point (lib/karto_sdk/src/Mapper.cpp:2679-2748) over the mapper
+"""Host-side mirror of karto::Mapper's processing entry points (lib/karto_sdk/src/Mapper.cpp: Process :2679-2748, and the
+localization mode's ProcessLocalization, ProcessAgainstNodesNearBy, ProcessAgainstNode / ProcessAtDock, ClearLocalizationBuffer) over the mapper
 front end of libkartohip.so (kh_mapper_*): a ROS-free way to replay a scan queue end to end on the GPU.
 
     mapper = Mapper(laser, loop_search_maximum_distance=3.0)        # parameters of config/mapper_params_offline.yaml
@@ -50,6 +51,46 @@ class Mapper:
         capi.check(capi.lib().kh_mapper_process(self._h, ranges, np.ascontiguousarray(odometric_pose, dtype=np.float64), float(time),
                                                 C.byref(acc), pose, cov), "kh_mapper_process")
         return bool(acc.value), pose, cov.reshape(3, 3)
+
+    def _entry(self, fn, name, ranges, odometric_pose, time, *extra):
+        ranges = np.ascontiguousarray(ranges, dtype=np.float64)
+        assert ranges.shape == (self.n_beams,)
+        odom = np.ascontiguousarray(odometric_pose, dtype=np.float64)
+        acc = C.c_int32(0)
+        pose, cov = np.zeros(3), np.zeros(9)
+        capi.check(fn(self._h, ranges.ctypes.data, odom.ctypes.data, float(time), *extra, C.byref(acc), pose.ctypes.data, cov.ctypes.data), name)
+        return bool(acc.value), pose, cov.reshape(3, 3)
+
+    def ProcessLocalization(self, ranges, odometric_pose, time: float = 0.0):
+        """Mapper::ProcessLocalization (Mapper.cpp:2831-2909): Process, then the scan enters the rolling buffer and the scan
+        scan_buffer_size accepted scans back leaves the graph"""
+        return self._entry(capi.lib().kh_mapper_process_localization, "kh_mapper_process_localization", ranges, odometric_pose, time)
+
+    def ProcessAgainstNodesNearBy(self, ranges, odometric_pose, time: float = 0.0, add_to_localization_buffer: bool = False):
+        """Mapper::ProcessAgainstNodesNearBy (Mapper.cpp:2751-2829): matched against the node nearest to the odometric pose"""
+        return self._entry(capi.lib().kh_mapper_process_against_nodes_near_by, "kh_mapper_process_against_nodes_near_by", ranges,
+                           odometric_pose, time, int(bool(add_to_localization_buffer)))
+
+    def ProcessAgainstNode(self, ranges, odometric_pose, node_id: int, time: float = 0.0):
+        """Mapper::ProcessAgainstNode (Mapper.cpp:3023-3096)"""
+        return self._entry(capi.lib().kh_mapper_process_against_node, "kh_mapper_process_against_node", ranges, odometric_pose, time,
+                           int(node_id))
+
+    def ProcessAtDock(self, ranges, odometric_pose, time: float = 0.0):
+        """Mapper::ProcessAtDock (Mapper.cpp:3098-3102): ProcessAgainstNode with the first node"""
+        return self.ProcessAgainstNode(ranges, odometric_pose, 0, time)
+
+    def ClearLocalizationBuffer(self):
+        """Mapper::ClearLocalizationBuffer (Mapper.cpp:2939-2962)"""
+        capi.check(capi.lib().kh_mapper_clear_localization_buffer(self._h), "kh_mapper_clear_localization_buffer")
+
+    def localization_buffer(self) -> np.ndarray:
+        """ids of the scans in the rolling buffer, oldest first"""
+        n = C.c_int32(0)
+        capi.check(capi.lib().kh_mapper_localization_buffer(self._h, None, 0, C.byref(n)), "kh_mapper_localization_buffer")
+        ids = np.zeros(max(1, n.value), dtype=np.int32)
+        capi.check(capi.lib().kh_mapper_localization_buffer(self._h, ids.ctypes.data, ids.size, C.byref(n)), "kh_mapper_localization_buffer")
+        return ids[:n.value]
 
     def num_scans(self) -> int:
         return capi.lib().kh_mapper_num_scans(self._h)
