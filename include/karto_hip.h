@@ -37,7 +37,7 @@ enum {
   KH_ERR_SEARCH = 4,        /* the reference throws std::runtime_error (Mapper.cpp:786-796, 828) */
   KH_ERR_NOT_FOUND = 5,     /* unknown node / constraint id (reference logs and returns) */
   KH_ERR_SOLVER = 6,        /* solution not usable (ceres_solver.cpp:249-254): state left unchanged */
-  KH_ERR_IO = 7             /* a pose-graph file could not be read / written */
+  KH_ERR_IO = 7             /* a pose-graph or session file could not be read / written */
 };
 
 KH_API const char * kh_last_error(void);
@@ -506,6 +506,8 @@ KH_API int kh_occupancy_update(kh_occupancy * g, uint32_t min_pass_through, doub
 KH_API int kh_occupancy_read(kh_occupancy * g, uint8_t * cells, uint32_t * pass, uint32_t * hits);
 KH_API int kh_occupancy_info(kh_occupancy * g, int32_t * width, int32_t * height, int32_t * width_step,
                              double * trace_ms, int64_t * beams_traced);
+/* the grid's offset (world position of cell 0, 0) and 1 / scale; either pointer may be NULL */
+KH_API int kh_occupancy_geometry(kh_occupancy * g, double offset[2], double * resolution);
 
 /* ---------------------------------------------------------------- lifelong node-decay scoring (next row f-4) */
 /* LifelongSlamToolbox::computeScores (src/experimental/slam_toolbox_lifelong.cpp:295-329) with the metrics
@@ -644,6 +646,47 @@ KH_API kh_spa * kh_mapper_solver(kh_mapper * m);
 /* every solver call the mapper makes, one line each, in the format oracle/ref_slam_driver.cpp logs the reference
  * Mapper's calls with (N id pose, C a b z cov, X n ms, P id pose, K): the two logs of one scan queue must agree */
 KH_API int kh_mapper_set_log(kh_mapper * m, const char * path);
+
+/* ---- mapping sessions: save, load, resume (slam_toolbox's serializePoseGraph / deserializePoseGraph + loadSerializedPoseGraph,
+ * slam_toolbox_common.cpp:952-1017).  The reference writes a Boost binary archive of the Mapper; here the session file is the
+ * library's own little-endian format "KHMS" (DESIGN.md section 7 lists it byte by byte): parameters, laser, the lifelong switch,
+ * every scan still in the map (id, time, odometric and corrected pose, vertex score, ranges), the adjacency lists and edge
+ * sources in insertion order, the running scans, the last scan, the localization buffer, and the solver -- nodes and
+ * constraints in insertion order with the information matrices as stored, the gauge, and the analysis cache that decides
+ * whether the next Compute() dissects from scratch or incrementally.  A mapper loaded from a file continues the run the
+ * saved mapper would have made, call for call.  Point readings, masks, barycentres and boxes are not stored: load recomputes
+ * them with LocalizedRangeScan::Update on the host.  The reference's post-load solver_->Compute() is NOT part of load.
+ * kh_mapper_save refuses (KH_ERR_INVALID_ARG) a mapper whose earlier Process() failed.  kh_mapper_load and kh_session_info answer
+ * KH_ERR_IO with a kh_last_error() text for a missing file, a wrong magic, an unknown version, a truncated file, a checksum
+ * mismatch and counts that do not fit the file; kh_mapper_load validates the whole file BEFORE it touches a device, so a good
+ * file on a machine without one is KH_ERR_NO_DEVICE.  devices / max_candidates as in kh_mapper_create_on_devices. */
+typedef struct kh_session_info_t {
+  int64_t version, file_bytes;
+  int64_t n_beams;
+  int64_t n_scan_slots;            /* kh_mapper_num_scans: ids handed out so far, removed ones included */
+  int64_t n_alive;                 /* kh_mapper_num_alive */
+  int64_t n_edges;                 /* kh_mapper_num_edges */
+  int64_t n_running, last_scan;    /* running-scan window, id of the last scan (-1 none) */
+  int64_t n_localization_buffer;
+  int64_t lifelong;                /* 1: kh_mapper_set_lifelong was on */
+  int64_t n_solver_nodes, n_solver_constraints, n_supernodes;
+} kh_session_info_t;
+KH_API int kh_mapper_save(const kh_mapper * m, const char * path);
+KH_API int kh_mapper_load(const char * path, const int32_t * devices, int32_t n_devices, int32_t max_candidates, kh_mapper ** out);
+KH_API int kh_session_info(const char * path, kh_session_info_t * out);     /* needs no device */
+/* wall time of the pieces of the last successful kh_mapper_load of this process, ms: [0] read + validate, [1] create + Update of
+ * every scan, [2] adjacency + solver rebuild, [3] graph store */
+KH_API int kh_session_last_load_ms(double out[4]);
+/* OccupancyGrid::CreateFromScans (Karto.h:5947-5962) over the scans still in the map, read where the mapper keeps them in HBM:
+ * dimensions from the per-scan boxes (equal to kh_occupancy_compute_dimensions over the same scans with the laser's minimum
+ * range and range threshold), one trace kernel over a table of (points, ranges, sensor position) per scan, then Update.  A
+ * scan's ranges are uploaded once in its life, its point readings only when its pose has moved since the last upload, so a
+ * rebuild after k new scans moves k scans.  *out is an ordinary kh_occupancy (kh_occupancy_read / _info / _destroy). */
+KH_API int kh_mapper_build_map(kh_mapper * m, double resolution, uint32_t min_pass_through, double occupancy_threshold,
+                               kh_occupancy ** out);
+/* counters of kh_mapper_build_map: [0] calls, [1] scans traced by the last call, [2] point-reading uploads and [3] range uploads
+ * the last call made, [4], [5] the same two since the mapper was made */
+KH_API int kh_mapper_map_stats(const kh_mapper * m, int64_t out[6]);
 
 #ifdef __cplusplus
 }

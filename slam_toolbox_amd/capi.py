@@ -94,6 +94,7 @@ SYMBOLS = [
     "kh_graph_last_near_by_kernel_ms",
     "kh_mapper_process_localization", "kh_mapper_process_against_node", "kh_mapper_process_against_nodes_near_by",
     "kh_mapper_clear_localization_buffer", "kh_mapper_localization_buffer",
+    "kh_mapper_save", "kh_mapper_load", "kh_session_info", "kh_session_last_load_ms", "kh_mapper_build_map", "kh_mapper_map_stats", "kh_occupancy_geometry",
 ]
 
 
@@ -133,6 +134,11 @@ class KhMapperStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("scans_processed", "matches", "loop_candidates", "loop_closures", "speculation_discarded", "nodes_removed")] + \
                [(k, C.c_double) for k in ("process_ms", "match_ms", "solver_ms", "update_ms", "lifelong_ms")] + \
                [(k, C.c_int64) for k in ("fused_declined", "fused_declined_reason", "fused_matches", "fused_fine_passes")]
+
+
+class KhSessionInfo(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("version", "file_bytes", "n_beams", "n_scan_slots", "n_alive", "n_edges", "n_running", "last_scan",
+                                         "n_localization_buffer", "lifelong", "n_solver_nodes", "n_solver_constraints", "n_supernodes")]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
@@ -302,6 +308,14 @@ def lib():
         L.kh_mapper_process_against_nodes_near_by.argtypes = [vp, vp, vp, dbl, i32, C.POINTER(i32), vp, vp]
         L.kh_mapper_clear_localization_buffer.argtypes = [vp]
         L.kh_mapper_localization_buffer.argtypes = [vp, vp, i32, C.POINTER(i32)]
+    if hasattr(L, "kh_mapper_save"):
+        L.kh_mapper_save.argtypes = [vp, C.c_char_p]
+        L.kh_mapper_load.argtypes = [C.c_char_p, iptr, i32, i32, C.POINTER(vp)]
+        L.kh_session_info.argtypes = [C.c_char_p, C.POINTER(KhSessionInfo)]
+        L.kh_session_last_load_ms.argtypes = [dptr]
+        L.kh_mapper_build_map.argtypes = [vp, dbl, C.c_uint32, dbl, C.POINTER(vp)]
+        L.kh_occupancy_geometry.argtypes = [vp, dptr, C.POINTER(dbl)]
+        L.kh_mapper_map_stats.argtypes = [vp, np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")]
     if hasattr(L, "kh_lifelong_scores"):
         L.kh_decay_params_default.argtypes = [C.POINTER(KhDecayParams)]
         L.kh_decay_params_default.restype = None

@@ -77,6 +77,60 @@ __global__ __launch_bounds__(256) void k_occ_trace(
   }
 }
 
+// The same trace fed from a mapper's RESIDENT scans (kh_mapper_build_map): one record per scan instead of 40 bytes per beam.
+struct ResidentScan
+{
+  const double * points;     // 2 * n_beams unfiltered point readings, device memory
+  const double * ranges;     // n_beams range readings, device memory
+  double sx, sy;             // sensor position
+};
+
+// One wave per run of 64 neighbouring beams of ONE scan (a workgroup = 4 such runs): the beams of a wave leave the same cell and
+// fan out over neighbouring ones, so its atomics land in neighbouring L2 lines, and neighbouring beams have similar lengths, which
+// bounds the divergence of the walk.  Clip, roundings and walk are k_occ_trace's, operation for operation.
+__global__ __launch_bounds__(256) void k_occ_trace_resident(
+  OccDev g, const ResidentScan * __restrict__ scans, int32_t n_scans, int32_t n_beams, int32_t runs_per_scan, double range_threshold,
+  double min_range, double max_range)
+{
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int32_t lane = threadIdx.x & 63;
+  const int64_t s = wave / runs_per_scan;
+  if (s >= n_scans) {return;}
+  const int32_t i = (int32_t)(wave - s * runs_per_scan) * 64 + lane;
+  if (i >= n_beams) {return;}
+  const ResidentScan sc = scans[s];
+  const double r = sc.ranges[i];
+  double px = sc.points[2 * i], py = sc.points[2 * i + 1];
+  const double sx = sc.sx, sy = sc.sy;
+  const bool valid_end = r < (range_threshold - 1e-06);                  // Karto.h:6167
+  if (r <= min_range || r >= max_range || r != r) {return;}             // Karto.h:6169-6172
+  if (r >= range_threshold) {                                           // Karto.h:6173-6180
+    const double ratio = range_threshold / r;
+    const double dx = px - sx, dy = py - sy;
+    px = sx + ratio * dx; py = sy + ratio * dy;
+  }
+  int32_t x0 = o_to_int(o_round((sx - g.off_x) * g.scale)), y0 = o_to_int(o_round((sy - g.off_y) * g.scale));
+  int32_t x1 = o_to_int(o_round((px - g.off_x) * g.scale)), y1 = o_to_int(o_round((py - g.off_y) * g.scale));
+  const int32_t tx = x1, ty = y1;
+  const bool steep = abs(y1 - y0) > abs(x1 - x0);                       // Grid<kt_int32u>::TraceLine, Karto.h:4874-4927
+  int32_t t;
+  if (steep) {t = x0; x0 = y0; y0 = t; t = x1; x1 = y1; y1 = t;}
+  if (x0 > x1) {t = x0; x0 = x1; x1 = t; t = y0; y0 = y1; y1 = t;}
+  const int32_t deltaX = x1 - x0, deltaY = abs(y1 - y0);
+  int32_t error = 0, y = y0;
+  const int32_t ystep = y0 < y1 ? 1 : -1;
+  for (int32_t x = x0; x <= x1; x++) {
+    const int32_t cx = steep ? y : x, cy = steep ? x : y;
+    error += deltaY;
+    if (2 * error >= deltaX) {y += ystep; error -= deltaX;}
+    if (cx >= 0 && cx < g.width && cy >= 0 && cy < g.height) {atomicAdd(&g.pass[cx + (int64_t)cy * g.ws], 1u);}
+  }
+  if (valid_end && tx >= 0 && tx < g.width && ty >= 0 && ty < g.height) {    // Karto.h:6213-6229
+    atomicAdd(&g.pass[tx + (int64_t)ty * g.ws], 1u);
+    atomicAdd(&g.hits[tx + (int64_t)ty * g.ws], 1u);
+  }
+}
+
 __global__ __launch_bounds__(256) void k_occ_update(OccDev g, uint32_t min_pass, double threshold)
 {
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -103,7 +157,56 @@ struct kh_occupancy
   double * h_beams = nullptr; size_t cap_hbeams = 0;
   hipEvent_t ev[2] = {nullptr, nullptr};
   double trace_ms = 0.0; int64_t beams_traced = 0;
+  ResidentScan * d_scans = nullptr; size_t cap_scans = 0;     // kh::occupancy_add_resident's table
 };
+
+namespace kh
+{
+// the stream the grid's kernels run on: uploads a caller queues there are in place before the next trace reads them
+void * occupancy_stream(kh_occupancy * g) {return g ? g->stream : nullptr;}
+
+// AddScan for n_scans scans whose readings are resident on the grid's device: table[4 * s] = address of the 2 * n_beams point
+// readings, [4 * s + 1] = address of the n_beams ranges, [4 * s + 2], [4 * s + 3] = sensor x, y as the bits of a double.
+// Returns after the trace (and everything queued on the stream before it) has finished.
+int occupancy_add_resident(kh_occupancy * g, int32_t n_scans, const uint64_t * table, int32_t n_beams, double range_threshold,
+  double min_range, double max_range)
+{
+  static_assert(sizeof(ResidentScan) == 32, "one record = 4 x 8 bytes");
+  if (!g || n_scans < 0 || n_beams < 0 || (n_scans > 0 && !table)) {return KH_ERR_INVALID_ARG;}
+  if (hipSetDevice(g->device) != hipSuccess) {return KH_ERR_HIP;}
+  if (n_scans == 0 || n_beams == 0) {return hipStreamSynchronize(g->stream) == hipSuccess ? KH_OK : KH_ERR_HIP;}
+  if (static_cast<size_t>(n_scans) > g->cap_scans) {
+    (void)hipStreamSynchronize(g->stream);
+    if (g->d_scans) {(void)hipFree(g->d_scans); g->d_scans = nullptr;}
+    g->cap_scans = 0;
+    const size_t cap = static_cast<size_t>(n_scans) + static_cast<size_t>(n_scans) / 2;
+    if (hipMalloc(reinterpret_cast<void **>(&g->d_scans), cap * sizeof(ResidentScan)) != hipSuccess) {
+      (void)hipGetLastError();
+      set_error("kh_mapper_build_map: scan table allocation failed");
+      return KH_ERR_HIP;
+    }
+    g->cap_scans = cap;
+  }
+  if (hipMemcpyAsync(g->d_scans, table, static_cast<size_t>(n_scans) * sizeof(ResidentScan), hipMemcpyHostToDevice, g->stream) != hipSuccess) {
+    (void)hipStreamSynchronize(g->stream);
+    return KH_ERR_HIP;
+  }
+  const int32_t runs = (n_beams + 63) / 64;
+  const int64_t waves = static_cast<int64_t>(n_scans) * runs;
+  (void)hipEventRecord(g->ev[0], g->stream);
+  hipLaunchKernelGGL(k_occ_trace_resident, dim3(static_cast<unsigned>((waves + 3) / 4)), dim3(256), 0, g->stream, g->dev, g->d_scans, n_scans,
+    n_beams, runs, range_threshold, min_range, max_range);
+  (void)hipEventRecord(g->ev[1], g->stream);
+  if (hipStreamSynchronize(g->stream) != hipSuccess) {
+    set_error(std::string("kh_mapper_build_map: ") + hipGetErrorString(hipGetLastError()));
+    return KH_ERR_HIP;
+  }
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, g->ev[0], g->ev[1]);
+  g->trace_ms += ms; g->beams_traced += static_cast<int64_t>(n_scans) * n_beams;
+  return KH_OK;
+}
+}  // namespace kh
 
 extern "C" {
 
@@ -176,7 +279,7 @@ void kh_occupancy_destroy(kh_occupancy * g)
   if (!g) {return;}
   (void)hipSetDevice(g->device);
   if (g->stream) {(void)hipStreamSynchronize(g->stream);}
-  (void)hipFree(g->dev.pass); (void)hipFree(g->dev.hits); (void)hipFree(g->dev.cells); (void)hipFree(g->d_beams);
+  (void)hipFree(g->dev.pass); (void)hipFree(g->dev.hits); (void)hipFree(g->dev.cells); (void)hipFree(g->d_beams); (void)hipFree(g->d_scans);
   if (g->h_beams) {(void)hipHostFree(g->h_beams);}
   if (g->ev[0]) {(void)hipEventDestroy(g->ev[0]);}
   if (g->ev[1]) {(void)hipEventDestroy(g->ev[1]);}
@@ -272,6 +375,14 @@ int kh_occupancy_info(kh_occupancy * g, int32_t * width, int32_t * height, int32
   if (width_step) {*width_step = g->dev.ws;}
   if (trace_ms) {*trace_ms = g->trace_ms;}
   if (beams) {*beams = g->beams_traced;}
+  return KH_OK;
+}
+
+int kh_occupancy_geometry(kh_occupancy * g, double offset[2], double * resolution)
+{
+  if (!g) {return KH_ERR_INVALID_ARG;}
+  if (offset) {offset[0] = g->dev.off_x; offset[1] = g->dev.off_y;}
+  if (resolution) {*resolution = 1.0 / g->dev.scale;}
   return KH_OK;
 }
 

@@ -1597,3 +1597,34 @@ int kh_spa_compute(kh_spa * s, kh_spa_summary * summary)
 }
 
 }  // extern "C"
+
+// ---- the part of the solver's state a mapping session file carries besides nodes and constraints (mapper_host.cpp) ----
+// The gauge bookkeeping (first_node_ and whether it was set constant) and the analysis cache that makes the next Compute()
+// history dependent: the supernodes of the last full dissection by node id, its cost and size, and how many incremental
+// re-analyses have leaned on it since.  words: [0] has_first, [1] first_id, [2] was_constant_set, [3] cached_full_flops,
+// [4] cached_full_nf, [5] reuse_count, [6] cached_full_levels; the supernodes as a CSR list of node ids.
+namespace kh
+{
+void spa_export_session_state(kh_spa * s, int64_t words[7], std::vector<int32_t> & sn_ptr, std::vector<int32_t> & sn_ids)
+{
+  settle(s);
+  words[0] = s->has_first ? 1 : 0; words[1] = s->first_id; words[2] = s->was_constant_set ? 1 : 0;
+  words[3] = s->cached_full_flops; words[4] = s->cached_full_nf; words[5] = s->reuse_count; words[6] = s->cached_full_levels;
+  sn_ptr.assign(1, 0); sn_ids.clear();
+  for (const auto & ids : s->cached_sn_ids) {
+    sn_ids.insert(sn_ids.end(), ids.begin(), ids.end());
+    sn_ptr.push_back(static_cast<int32_t>(sn_ids.size()));
+  }
+}
+
+// after kh_spa_reset + AddNode* + AddConstraint* of the stored graph (which leave a first node and an empty cache behind)
+void spa_import_session_state(kh_spa * s, const int64_t words[7], const std::vector<int32_t> & sn_ptr, const std::vector<int32_t> & sn_ids)
+{
+  s->has_first = words[0] != 0; s->first_id = static_cast<int32_t>(words[1]); s->was_constant_set = words[2] != 0;
+  s->cached_full_flops = words[3]; s->cached_full_nf = static_cast<int32_t>(words[4]);
+  s->reuse_count = static_cast<int32_t>(words[5]); s->cached_full_levels = static_cast<int32_t>(words[6]);
+  s->cached_sn_ids.assign(sn_ptr.empty() ? 0 : sn_ptr.size() - 1, {});
+  for (size_t k = 0; k + 1 < sn_ptr.size(); ++k) {s->cached_sn_ids[k].assign(sn_ids.begin() + sn_ptr[k], sn_ids.begin() + sn_ptr[k + 1]);}
+  s->topology_dirty = true;
+}
+}  // namespace kh

@@ -40,10 +40,69 @@ class Mapper:
         capi.check(capi.lib().kh_mapper_create_on_devices(C.byref(p), C.byref(L), devs, len(devs), max_candidates, C.byref(self._h)),
                    "kh_mapper_create_on_devices")
         self.n_beams = laser.n_beams
+        self._start = None
         if log_path:
             capi.check(capi.lib().kh_mapper_set_log(self._h, log_path.encode()), "kh_mapper_set_log")
 
+    START_MODES = ("first_node", "given_pose", "localize_at_pose")
+
+    @classmethod
+    def load(cls, path, devices=None, max_candidates: int = 32, start: str = None, pose=None, log_path: str = None):
+        """kh_mapper_load: the mapper a session file (Mapper.save) describes, ready to continue the run it was saved from.
+        start: how the FIRST Process / ProcessLocalization call after the load enters, as slam_toolbox's addScan does after
+        deserializePoseGraph (slam_toolbox_common.cpp:815-834, 1059-1076; slam_toolbox_localization.cpp:184-209):
+        "first_node" = ProcessAtDock, "given_pose" = ProcessAgainstNodesNearBy with the scan's odometric pose set to `pose`,
+        "localize_at_pose" = the same with the scan entering the localization buffer; every later call is the plain one.
+        None continues where the saved run stopped."""
+        if start is not None and start not in cls.START_MODES:
+            raise ValueError(f"start must be one of {cls.START_MODES}")
+        if start in ("given_pose", "localize_at_pose") and pose is None:
+            raise ValueError(f"start={start!r} needs a pose")
+        from . import session
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        self._start = None
+        devs = np.asarray([0] if devices is None else list(devices), dtype=np.int32)
+        capi.check(capi.lib().kh_mapper_load(str(path).encode(), devs, len(devs), max_candidates, C.byref(self._h)), "kh_mapper_load")
+        self.n_beams = session.info(path)["n_beams"]
+        if start is not None:
+            self._start = (start, None if pose is None else np.ascontiguousarray(pose, dtype=np.float64).copy())
+        if log_path:
+            capi.check(capi.lib().kh_mapper_set_log(self._h, log_path.encode()), "kh_mapper_set_log")
+        return self
+
+    def save(self, path):
+        """kh_mapper_save: everything the continuation of the run depends on, as one session file"""
+        capi.check(capi.lib().kh_mapper_save(self._h, str(path).encode()), "kh_mapper_save")
+
+    def build_map(self, resolution: float = 0.05, min_pass_through: int = 2, occupancy_threshold: float = 0.1):
+        """kh_mapper_build_map: OccupancyGrid::CreateFromScans over the scans still in the map, traced from their resident copies.
+        Returns an occupancy_grid.OccupancyGrid (cells / counters / width / height / offset)."""
+        from .occupancy_grid import OccupancyGrid
+        h = C.c_void_p()
+        capi.check(capi.lib().kh_mapper_build_map(self._h, float(resolution), int(min_pass_through), float(occupancy_threshold), C.byref(h)),
+                   "kh_mapper_build_map")
+        return OccupancyGrid.from_handle(h, resolution)
+
+    def map_stats(self) -> dict:
+        """counters of build_map: calls, scans traced / point uploads / range uploads of the last call, and the two totals"""
+        out = np.zeros(6, dtype=np.int64)
+        capi.check(capi.lib().kh_mapper_map_stats(self._h, out), "kh_mapper_map_stats")
+        return dict(zip(("calls", "scans_traced", "point_uploads", "range_uploads", "point_uploads_total", "range_uploads_total"), out.tolist()))
+
+    def _first_after_load(self, ranges, time):
+        """the entry the first scan after a load goes through when a start mode was asked for; None = none pending"""
+        if self._start is None:
+            return None
+        (start, pose), self._start = self._start, None
+        if start == "first_node":
+            return lambda odom: self.ProcessAtDock(ranges, odom, time)
+        return lambda odom: self.ProcessAgainstNodesNearBy(ranges, pose, time, add_to_localization_buffer=(start == "localize_at_pose"))
+
     def Process(self, ranges, odometric_pose, time: float = 0.0):
+        first = self._first_after_load(ranges, time)
+        if first is not None:
+            return first(odometric_pose)
         ranges = np.ascontiguousarray(ranges, dtype=np.float64)
         assert ranges.shape == (self.n_beams,)
         acc = C.c_int32(0)
@@ -64,6 +123,9 @@ class Mapper:
     def ProcessLocalization(self, ranges, odometric_pose, time: float = 0.0):
         """Mapper::ProcessLocalization (Mapper.cpp:2831-2909): Process, then the scan enters the rolling buffer and the scan
         scan_buffer_size accepted scans back leaves the graph"""
+        first = self._first_after_load(ranges, time)
+        if first is not None:
+            return first(odometric_pose)
         return self._entry(capi.lib().kh_mapper_process_localization, "kh_mapper_process_localization", ranges, odometric_pose, time)
 
     def ProcessAgainstNodesNearBy(self, ranges, odometric_pose, time: float = 0.0, add_to_localization_buffer: bool = False):

@@ -33,6 +33,19 @@ class OccupancyGrid:
         self.offset = np.asarray(offset, dtype=np.float64).copy()
         self.resolution = float(resolution)
 
+    @classmethod
+    def from_handle(cls, handle, resolution):
+        """wraps a kh_occupancy the library made (kh_mapper_build_map); the grid owns it from here on"""
+        g = cls.__new__(cls)
+        g._h = handle
+        w, h, ws = C.c_int32(), C.c_int32(), C.c_int32()
+        capi.check(capi.lib().kh_occupancy_info(handle, C.byref(w), C.byref(h), C.byref(ws), None, None), "kh_occupancy_info")
+        g.width, g.height, g.width_step = w.value, h.value, ws.value
+        g.offset = np.zeros(2)
+        capi.check(capi.lib().kh_occupancy_geometry(handle, g.offset, None), "kh_occupancy_geometry")
+        g.resolution = float(resolution)
+        return g
+
     @staticmethod
     def CreateFromScans(scans, resolution, laser, device: int = 0, min_pass_through=2, occupancy_threshold=0.1):
         """OccupancyGrid::CreateFromScans (Karto.h:5947-5962); `laser` supplies GetRangeThreshold / GetMinimumRange /

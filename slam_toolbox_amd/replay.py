@@ -48,15 +48,29 @@ class LapQueue:
 
 
 def run(n_scans: int, lifelong: bool = True, mode: str = "sync", period_s: float = 0.025, device: int = 0,
-        max_candidates: int = 32, map_resolution: float = 0.05, progress=None, devices=None, queue=None, **mapper_params):
-    """Replays the queue; returns a dict with the throughput, the mapper's own statistics and the map agreement."""
+        max_candidates: int = 32, map_resolution: float = 0.05, progress=None, devices=None, queue=None, save_session=None,
+        save_at=None, load_session=None, **mapper_params):
+    """Replays the queue; returns a dict with the throughput, the mapper's own statistics and the map agreement.
+    save_session: the mapper is saved there (Mapper.save) behind queue scan `save_at` (default: the last one), with the replay's
+    own bookkeeping -- how far the queue got, which queue scan every scan id came from -- beside it in <path>.replay.json;
+    load_session: the run starts from such a pair instead of an empty mapper and continues with the rest of the SAME queue
+    (same n_scans; the session carries its own parameters and lifelong switch)."""
+    import json
     from .mapper import Mapper
     from .occupancy_grid import OccupancyGrid
     from .scan_matcher import LocalizedRangeScan
     q = queue or LapQueue(n_scans)
-    m = Mapper(q.laser, device=device, max_candidates=max_candidates, devices=devices, **mapper_params)
-    if lifelong:
-        m.SetLifelong(True)
+    resume = None
+    if load_session:
+        with open(load_session + ".replay.json") as f:
+            resume = json.load(f)
+        if resume["queue_scans"] != n_scans:
+            raise ValueError(f"the session was saved from a queue of {resume['queue_scans']} scans, not {n_scans}")
+        m = Mapper.load(load_session, devices=devices if devices is not None else [device], max_candidates=max_candidates)
+    else:
+        m = Mapper(q.laser, device=device, max_candidates=max_candidates, devices=devices, **mapper_params)
+        if lifelong:
+            m.SetLifelong(True)
     # the queue is made up front so that the timed region holds the mapper, not the ray casting
     all_ranges = [q.ranges(i) for i in range(n_scans)]
     t0 = time.perf_counter()
@@ -64,6 +78,9 @@ def run(n_scans: int, lifelong: bool = True, mode: str = "sync", period_s: float
     waited_s = 0.0
     queue_index = []                       # scan id -> position in the queue
     i = 0
+    if resume:
+        queue_index, i = list(resume["queue_index"]), int(resume["next_queue_scan"])
+        accepted = len(queue_index)
     while i < n_scans:
         if mode == "async":
             # scan k ARRIVES at k * period_s.  The depth-1 queue holds the most recent arrival: a mapper that is behind
@@ -83,6 +100,10 @@ def run(n_scans: int, lifelong: bool = True, mode: str = "sync", period_s: float
             accepted += 1
             queue_index.append(i)
         i += 1
+        if save_session and i == (n_scans if save_at is None else save_at):
+            m.save(save_session)
+            with open(save_session + ".replay.json", "w") as f:
+                json.dump({"queue_scans": n_scans, "next_queue_scan": i, "queue_index": queue_index}, f)
         if progress and processed % progress == 0:
             st = m.stats()
             print(f"[replay] {i}/{n_scans} scans, {accepted} accepted, {len(m.alive())} alive, {st['loop_closures']} closures, "
