@@ -539,6 +539,15 @@ KH_API void kh_decay_params_default(kh_decay_params * p);
 KH_API int kh_lifelong_scores(int32_t device, const kh_scan_box * reference, int32_t n, const kh_scan_box * candidates,
                               const kh_decay_params * params, int32_t * kept, double * iou, double * area_overlap,
                               double * reading_overlap, double * scores);
+/* The same scoring in the form the mapper calls after every accepted scan (kh_mapper_set_lifelong), for a caller that holds the
+ * readings on the host: candidate k has n_scan UNFILTERED point readings at points_xy[k] (2 * n_scan doubles; NULL = its
+ * readings are not counted, reading overlap 0 / n_points) and (n_scan + 63) / 64 mask words at masks[k], bit i of word i / 64
+ * set where reading i passed the range filter.  candidates[k].n_points is the number of readings that count (the denominator
+ * of the reading overlap); candidates[k].points_xy is not read.  The readings are uploaded for the call.  1 <= n_scan <= 4096. */
+KH_API int kh_lifelong_scores_resident(int32_t device, const kh_scan_box * reference, int32_t n, const kh_scan_box * candidates,
+                                       const double * const * points_xy, const uint64_t * const * masks, int32_t n_scan,
+                                       const kh_decay_params * params, int32_t * kept, double * iou, double * area_overlap,
+                                       double * reading_overlap, double * scores);
 
 /* ---------------------------------------------------------------- mapper front end (BASELINE configs 1 and 5) */
 /* ROS-free restatement of what karto::Mapper::Process does around the scan matcher and the solver plugin
@@ -575,6 +584,8 @@ typedef struct kh_mapper_stats {
   int64_t fused_declined, fused_declined_reason;   /* ... that went the general way, and why the last one did (kh_matcher_seq_stats [6], [7]) */
   int64_t fused_matches, fused_fine_passes;     /* sequential matches that took the fused path of one MatchScan / whose fine pass
                                                    the device finished (kh_matcher_seq_stats of the sequential matcher) */
+  int64_t decay_calls_resident, decay_calls_packed;   /* node-decay calls scored from the resident readings + filter masks / sent
+                                                   down the packed form because a candidate had no device copy */
 } kh_mapper_stats;
 /* config/mapper_params_offline.yaml:31-66 */
 KH_API void kh_mapper_params_default(kh_mapper_params * p);

@@ -81,7 +81,7 @@ SYMBOLS = [
     "kh_graph_last_kernel_ms", "kh_graph_find_near_chains", "kh_graph_closest_scan_to_pose", "kh_weighted_mean",
     "kh_occupancy_compute_dimensions", "kh_occupancy_create", "kh_occupancy_destroy", "kh_occupancy_clear",
     "kh_occupancy_add_scans", "kh_occupancy_update", "kh_occupancy_read", "kh_occupancy_info",
-    "kh_decay_params_default", "kh_lifelong_scores",
+    "kh_decay_params_default", "kh_lifelong_scores", "kh_lifelong_scores_resident",
     "kh_spa_set_comm", "kh_comm_unique_id", "kh_comm_create", "kh_comm_destroy", "kh_comm_rank", "kh_comm_world", "kh_comm_device",
     "kh_comm_allreduce_sum_f64", "kh_comm_allgather_f64",
     "kh_device_malloc", "kh_device_free", "kh_device_upload", "kh_device_upload_on", "kh_device_download", "kh_selftest_lds_attr",
@@ -133,7 +133,8 @@ class KhMapperParams(C.Structure):
 class KhMapperStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("scans_processed", "matches", "loop_candidates", "loop_closures", "speculation_discarded", "nodes_removed")] + \
                [(k, C.c_double) for k in ("process_ms", "match_ms", "solver_ms", "update_ms", "lifelong_ms")] + \
-               [(k, C.c_int64) for k in ("fused_declined", "fused_declined_reason", "fused_matches", "fused_fine_passes")]
+               [(k, C.c_int64) for k in ("fused_declined", "fused_declined_reason", "fused_matches", "fused_fine_passes",
+                                           "decay_calls_resident", "decay_calls_packed")]
 
 
 class KhSessionInfo(C.Structure):
@@ -321,6 +322,8 @@ def lib():
         L.kh_decay_params_default.restype = None
         L.kh_lifelong_scores.argtypes = [i32, C.POINTER(KhScanBox), i32, C.POINTER(KhScanBox), C.POINTER(KhDecayParams),
                                          vp, vp, vp, vp, vp]
+        L.kh_lifelong_scores_resident.argtypes = [i32, C.POINTER(KhScanBox), i32, C.POINTER(KhScanBox), C.POINTER(vp), C.POINTER(vp), i32,
+                                                  C.POINTER(KhDecayParams), vp, vp, vp, vp, vp]
     if hasattr(L, "kh_occupancy_create"):
         L.kh_occupancy_compute_dimensions.argtypes = [i32, C.POINTER(KhScan), dbl, dbl, dbl, C.POINTER(i32), C.POINTER(i32), dptr]
         L.kh_occupancy_create.argtypes = [i32, i32, dbl, dbl, dbl, i32, C.POINTER(vp)]

@@ -307,4 +307,39 @@ int kh_lifelong_scores(int32_t device, const kh_scan_box * reference, int32_t n,
   return kh::decay_scores(device, reference, n, candidates, nullptr, nullptr, 0, params, kept, iou, area_overlap, reading_overlap, scores);
 }
 
+int kh_lifelong_scores_resident(int32_t device, const kh_scan_box * reference, int32_t n, const kh_scan_box * candidates,
+  const double * const * points_xy, const uint64_t * const * masks, int32_t n_scan, const kh_decay_params * params, int32_t * kept,
+  double * iou, double * area_overlap, double * reading_overlap, double * scores)
+{
+  if (!reference || n < 0 || (n > 0 && (!candidates || !points_xy || !masks)) || !params || n_scan <= 0 || n_scan > 4096) {return KH_ERR_INVALID_ARG;}
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
+    set_error("no usable HIP device (libkartohip has no CPU fallback)");
+    return KH_ERR_NO_DEVICE;
+  }
+  if (n == 0) {return KH_OK;}
+  if (hipSetDevice(device) != hipSuccess) {return KH_ERR_HIP;}
+  // one slab for the call, candidate k's readings at k * n_scan points (16-byte aligned: the kernel reads them as double2)
+  const size_t per = static_cast<size_t>(n_scan) * 2;
+  double * slab = nullptr;
+  if (hipMalloc(reinterpret_cast<void **>(&slab), static_cast<size_t>(n) * per * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("kh_lifelong_scores_resident: allocation failed");
+    return KH_ERR_HIP;
+  }
+  std::vector<const double *> resident(static_cast<size_t>(n), nullptr);
+  for (int32_t k = 0; k < n; ++k) {
+    if (!points_xy[k]) {continue;}
+    resident[k] = slab + static_cast<size_t>(k) * per;
+    if (hipMemcpy(slab + static_cast<size_t>(k) * per, points_xy[k], per * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(slab);
+      set_error("kh_lifelong_scores_resident: upload failed");
+      return KH_ERR_HIP;
+    }
+  }
+  const int rc = kh::decay_scores(device, reference, n, candidates, resident.data(), masks, n_scan, params, kept, iou, area_overlap, reading_overlap, scores);
+  (void)hipFree(slab);
+  return rc;
+}
+
 }  // extern "C"

@@ -736,6 +736,7 @@ int lifelong_step(kh_mapper * m, int32_t id)
       all_resident ? m->laser.n : 0, &m->decay, kept.data(), nullptr, nullptr, nullptr, scores.data());
   }
   if (rc) {return rc;}
+  (all_resident ? m->stats.decay_calls_resident : m->stats.decay_calls_packed) += 1;
   for (size_t k = 0; k < near.size(); ++k) {
     if (!kept[k]) {continue;}
     if (scores[k] < m->decay.removal_score) {

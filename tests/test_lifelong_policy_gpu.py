@@ -131,3 +131,60 @@ def test_lifelong_removals_do_not_depend_on_the_elimination_order(kartohip_lib, 
     assert np.array_equal(alive_a, alive_b)
     assert np.array_equal(np.isnan(poses_a), np.isnan(poses_b))        # (removed scans have no pose)
     assert np.nanmax(np.abs(poses_a - poses_b)) < 1e-9
+
+
+def _scores(m):
+    """Vertex::GetScore of every scan still in the map"""
+    return np.array([m.scan(int(i))[1].score for i in m.alive()])
+
+
+def test_lifelong_scores_of_the_resident_form_equal_the_oracle(kartohip_lib):
+    """The two tests above compare DECISIONS.  This one compares the SCORES the mapper's own form of k_decay writes back (readings
+    read where the matcher left them in HBM + one filter bit per reading: 1081 beams = 17 mask words, the last one partial,
+    kh::decay_scores with `resident`) with oracle/lifelong.py::compute_scores driving a second, non-lifelong mapper: after every
+    accepted scan the score of every vertex still in the map, as bit patterns."""
+    from oracle import lifelong
+    from slam_toolbox_amd.mapper import Mapper
+    n_scans = 300
+    laser = synth.Laser()
+    assert laser.n_beams == 1081 and (laser.n_beams + 63) // 64 == 17 and laser.n_beams % 64 != 0
+    ranges, odom = _queue(n_scans)
+    a, b = Mapper(laser), Mapper(laser)
+    a.SetLifelong(True)
+    p = lifelong.DecayParams()
+    compared = rewritten = removed = 0
+    for i in range(n_scans):
+        ok_a, _, _ = a.Process(ranges[i], odom[i], 0.1 * i)
+        ok_b, _, _ = b.Process(ranges[i], odom[i], 0.1 * i)
+        assert ok_a == ok_b
+        if not ok_b:
+            continue
+        sid = b.num_scans() - 1
+        boxes, adjacency, ref_xy = {}, {}, {}
+        for v in b.alive():
+            v = int(v)
+            _, box = b.scan(v)
+            pts = np.ctypeslib.as_array(box.points_xy, shape=(box.n_points, 2)).copy() if box.n_points else np.zeros((0, 2))
+            boxes[v] = lifelong.ScanBox((box.barycenter[0], box.barycenter[1]), (box.bbox_size[0], box.bbox_size[1]), pts,
+                                        box.unique_id, box.n_edges, box.score)
+            adjacency[v] = b.adjacency(v)
+            ref_xy[v] = boxes[v].barycenter                      # GetReferencePose(use_scan_barycenter = true)
+        for d in lifelong.evaluate_node_depreciation(sid, boxes, adjacency, ref_xy, p):
+            if d[0] == "remove":
+                b.RemoveNode(d[1])
+                removed += 1
+            else:
+                b.SetNodeScore(d[1], d[2])
+                rewritten += int(d[2] != boxes[d[1]].score)
+        assert np.array_equal(a.alive(), b.alive()), f"queue scan {i}"
+        sa, sb = _scores(a), _scores(b)
+        bad = np.flatnonzero(bits(sa) != bits(sb))
+        assert bad.size == 0, f"queue scan {i}: scores of scans {a.alive()[bad][:8]} differ: {sa[bad][:8]} != {sb[bad][:8]}"
+        compared += sa.size
+    print(f"lifelong scores: {compared} score comparisons, {rewritten} scores rewritten by the objective, {removed} nodes removed")
+    assert rewritten >= 100, "the queue does not exercise the objective score"
+    st = a.stats()
+    # (a candidate without a device copy would send a call down the packed form, silently: then this test would not be
+    # looking at the resident branch)
+    assert st["decay_calls_packed"] == 0 and st["decay_calls_resident"] == a.num_scans(), st
+    a.close(); b.close()
