@@ -699,6 +699,56 @@ KH_API int kh_mapper_build_map(kh_mapper * m, double resolution, uint32_t min_pa
  * the last call made, [4], [5] the same two since the mapper was made */
 KH_API int kh_mapper_map_stats(const kh_mapper * m, int64_t out[6]);
 
+/* ---- merging sessions (slam_toolbox's merge_maps_kinematic, src/merge_maps_kinematic.cpp): several mappers -- live ones, or
+ * sessions loaded from files -- each placed by a rigid correction T = (tx, ty, yaw), and ONE occupancy grid traced from all their
+ * scans where they lie in HBM.  The reference moves a submap by dragging a marker (processInteractiveFeedback :313-352), rewrites
+ * every scan with the correction (transformScan :195-248) and calls OccupancyGrid::CreateFromScans (mergeMapCallback :251-291).
+ * Here a merge never modifies a session: the correction is applied to every point reading inside the trace kernel, so a re-merge
+ * after a correction changed uploads two small tables and no reading.  The arithmetic is this library's own (DESIGN.md section
+ * 7a; tf2 agrees with it to rounding): with c = cos(yaw), s = sin(yaw) taken once per submap,
+ *   point   x' = (c x - s y) + tx,  y' = (s x + c y) + ty
+ *   pose    position as a point, heading' = math::NormalizeAngle(heading + yaw)
+ *   A . B = (A.x + (cA B.x - sA B.y), A.y + (sA B.x + cA B.y), NormalizeAngle(A.yaw + B.yaw))
+ * The sensor position of a scan is GetSensorAt(transformed corrected pose) with the submap's laser; the box of a scan is the
+ * min / max of the four transformed corners of its stored box (loose, like the reference's).  Submaps may have different lasers;
+ * all are on the merger's device.  Submap ids are handed out ascending and never reused; the merged map takes the submaps in id
+ * order, each one's scans in scan-id order. */
+typedef struct kh_merge kh_merge;
+KH_API int kh_merge_create(int32_t device, double resolution, kh_merge ** out);
+KH_API void kh_merge_destroy(kh_merge * g);        /* destroys the mappers it loaded itself, never a borrowed one */
+/* borrows a live mapper: the caller keeps it alive until kh_merge_remove_submap (or kh_merge_destroy) and may go on processing
+ * scans with it between merges.  A mapper on another device is KH_ERR_INVALID_ARG. */
+KH_API int kh_merge_add_mapper(kh_merge * g, kh_mapper * m, int32_t * submap_id);
+/* kh_mapper_load of the file onto the merger's device (error codes as there); the merger owns the mapper */
+KH_API int kh_merge_add_session(kh_merge * g, const char * path, int32_t * submap_id);
+KH_API int kh_merge_remove_submap(kh_merge * g, int32_t submap_id);                     /* unknown id: KH_ERR_NOT_FOUND, as everywhere below */
+KH_API int32_t kh_merge_num_submaps(const kh_merge * g);
+/* out[0] = scans still in the submap's map, out[1] = beams of its laser */
+KH_API int kh_merge_submap_info(const kh_merge * g, int32_t submap_id, int32_t out[2]);
+/* the correction of a submap (the identity (0, 0, 0) when it is added) */
+KH_API int kh_merge_set_transform(kh_merge * g, int32_t submap_id, const double t[3]);
+KH_API int kh_merge_get_transform(const kh_merge * g, int32_t submap_id, double t[3]);
+/* the release of the marker at marker_pose = (x, y, yaw): correction <- correction . inverse(translation(previous location)) .
+ * marker_pose, then location <- (x, y, location yaw + yaw).  The location starts at the centre of the submap's own grid at the
+ * merger's resolution, (offset + width * resolution / 2, offset + height * resolution / 2, 0) (addSubmapCallback :115-122). */
+KH_API int kh_merge_move_submap(kh_merge * g, int32_t submap_id, const double marker_pose[3]);
+KH_API int kh_merge_get_location(const kh_merge * g, int32_t submap_id, double location[3]);
+/* what transformScan leaves on scan `index` (0 .. info[0] - 1, scan-id order) of the submap under its current correction:
+ * corrected, odometric and barycenter pose (the barycenter's heading is 0 before the correction), box = min x, min y, max x,
+ * max y, and the 2 * n_beams unfiltered point readings (computed on the host for this call).  Any output may be NULL. */
+KH_API int kh_merge_get_scan(const kh_merge * g, int32_t submap_id, int32_t index, double corrected_pose[3], double odometric_pose[3],
+                             double barycenter_pose[3], double box[4], double * points_xy);
+/* the submap's own, untransformed grid: kh_mapper_build_map of its mapper at the merger's resolution */
+KH_API int kh_merge_build_submap(kh_merge * g, int32_t submap_id, uint32_t min_pass_through, double occupancy_threshold,
+                                 kh_occupancy ** out);
+/* the merged map: dimensions from the transformed boxes of every scan (rounded like kh_occupancy_compute_dimensions), one trace
+ * kernel over every submap's resident scans, Update.  *out is an ordinary kh_occupancy.  No submap, or no scan in any of them,
+ * is KH_ERR_INVALID_ARG. */
+KH_API int kh_merge_build(kh_merge * g, uint32_t min_pass_through, double occupancy_threshold, kh_occupancy ** out);
+/* [0] merges made, [1] scans and [2] beams traced by the last merge, [3] point-reading and [4] range uploads of the last merge,
+ * [5], [6] the same two since the merger was made, [7] bytes of the two tables the last merge uploaded */
+KH_API int kh_merge_stats(const kh_merge * g, int64_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

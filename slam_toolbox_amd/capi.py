@@ -95,6 +95,9 @@ SYMBOLS = [
     "kh_mapper_process_localization", "kh_mapper_process_against_node", "kh_mapper_process_against_nodes_near_by",
     "kh_mapper_clear_localization_buffer", "kh_mapper_localization_buffer",
     "kh_mapper_save", "kh_mapper_load", "kh_session_info", "kh_session_last_load_ms", "kh_mapper_build_map", "kh_mapper_map_stats", "kh_occupancy_geometry",
+    "kh_merge_create", "kh_merge_destroy", "kh_merge_add_mapper", "kh_merge_add_session", "kh_merge_remove_submap", "kh_merge_num_submaps",
+    "kh_merge_submap_info", "kh_merge_set_transform", "kh_merge_get_transform", "kh_merge_move_submap", "kh_merge_get_location",
+    "kh_merge_get_scan", "kh_merge_build_submap", "kh_merge_build", "kh_merge_stats",
 ]
 
 
@@ -317,6 +320,23 @@ def lib():
         L.kh_mapper_build_map.argtypes = [vp, dbl, C.c_uint32, dbl, C.POINTER(vp)]
         L.kh_occupancy_geometry.argtypes = [vp, dptr, C.POINTER(dbl)]
         L.kh_mapper_map_stats.argtypes = [vp, np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")]
+    if hasattr(L, "kh_merge_create"):
+        L.kh_merge_create.argtypes = [i32, dbl, C.POINTER(vp)]
+        L.kh_merge_destroy.argtypes = [vp]
+        L.kh_merge_destroy.restype = None
+        L.kh_merge_add_mapper.argtypes = [vp, vp, C.POINTER(i32)]
+        L.kh_merge_add_session.argtypes = [vp, C.c_char_p, C.POINTER(i32)]
+        L.kh_merge_remove_submap.argtypes = [vp, i32]
+        L.kh_merge_num_submaps.argtypes = [vp]
+        L.kh_merge_submap_info.argtypes = [vp, i32, iptr]
+        L.kh_merge_set_transform.argtypes = [vp, i32, dptr]
+        L.kh_merge_get_transform.argtypes = [vp, i32, dptr]
+        L.kh_merge_move_submap.argtypes = [vp, i32, dptr]
+        L.kh_merge_get_location.argtypes = [vp, i32, dptr]
+        L.kh_merge_get_scan.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
+        L.kh_merge_build_submap.argtypes = [vp, i32, C.c_uint32, dbl, C.POINTER(vp)]
+        L.kh_merge_build.argtypes = [vp, C.c_uint32, dbl, C.POINTER(vp)]
+        L.kh_merge_stats.argtypes = [vp, np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")]
     if hasattr(L, "kh_lifelong_scores"):
         L.kh_decay_params_default.argtypes = [C.POINTER(KhDecayParams)]
         L.kh_decay_params_default.restype = None

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "../../include/karto_hip.h"
+#include "mapper_internal.hpp"
 
 namespace kh
 {
@@ -1678,6 +1679,93 @@ int kh_session_last_load_ms(double out[4])
   return KH_OK;
 }
 
+}  // extern "C"
+
+namespace kh
+{
+// The residency loop kh_mapper_build_map and the session merger (merge.cpp) share: every scan still in the map gets its ranges
+// (once in its life) and its point readings (again only after its pose moved) into HBM on the mapper's own device, the uploads
+// queued on `stream`; table gains 4 words per scan in id order -- address of the points, address of the ranges, sensor x, y as
+// the bits of a double (the record of kh::occupancy_add_resident).  *up_points / *up_ranges = uploads this call made.
+int mapper_resident_table(kh_mapper * m, void * stream, const char * who, std::vector<uint64_t> & table, int64_t * up_points, int64_t * up_ranges)
+{
+  const int64_t range_bytes = static_cast<int64_t>(sizeof(double)) * m->laser.n;
+  table.clear();
+  table.reserve(4 * m->scans.size());
+  *up_points = 0; *up_ranges = 0;
+  for (auto & sp : m->scans) {
+    if (!sp) {continue;}
+    MScan & s = *sp;
+    if (!s.d_ranges) {
+      if (m->r_free_slots.empty()) {
+        constexpr int kSlabScans = 256;
+        void * p = nullptr;
+        if (kh_device_malloc(m->device, range_bytes * kSlabScans, &p) == KH_OK) {
+          m->r_slabs.push_back(static_cast<double *>(p));
+          for (int k = kSlabScans - 1; k >= 0; --k) {m->r_free_slots.push_back(static_cast<double *>(p) + static_cast<size_t>(k) * static_cast<size_t>(m->laser.n));}
+        }
+      }
+      if (!m->r_free_slots.empty()) {s.d_ranges = m->r_free_slots.back(); m->r_free_slots.pop_back(); s.d_ranges_fresh = false;}
+    }
+    if (s.d_ranges && !s.d_ranges_fresh && s.ranges.size() == static_cast<size_t>(m->laser.n) &&
+      kh_device_upload_on(s.d_ranges, s.ranges.data(), range_bytes, stream) == KH_OK) {s.d_ranges_fresh = true; ++*up_ranges;}
+    const bool points_stale = !(s.d_points[0] && (s.d_fresh & 1u));
+    const double * d_points = resident_points(m, s, 0, stream);
+    if (!d_points || !s.d_ranges || !s.d_ranges_fresh) {
+      set_error(std::string(who) + ": a scan could not be made resident on the device");
+      return KH_ERR_HIP;
+    }
+    *up_points += points_stale ? 1 : 0;
+    uint64_t rec[4];
+    rec[0] = reinterpret_cast<uint64_t>(d_points); rec[1] = reinterpret_cast<uint64_t>(s.d_ranges);
+    std::memcpy(&rec[2], &s.sensor.x, 8); std::memcpy(&rec[3], &s.sensor.y, 8);
+    table.insert(table.end(), rec, rec + 4);
+  }
+  return KH_OK;
+}
+
+// what merge.cpp reads of a mapper (mapper_internal.hpp)
+int32_t mapper_device(const kh_mapper * m) {return m->device;}
+
+kh_laser mapper_laser(const kh_mapper * m)
+{
+  kh_laser l;
+  l.n_beams = m->laser.n; l.minimum_angle = m->laser.min_angle; l.angular_resolution = m->laser.ang_res;
+  l.minimum_range = m->laser.min_range; l.maximum_range = m->laser.max_range; l.range_threshold = m->laser.range_threshold;
+  l.offset_x = m->laser.offset.x; l.offset_y = m->laser.offset.y; l.offset_heading = m->laser.offset.h;
+  return l;
+}
+
+void mapper_alive_scans(const kh_mapper * m, std::vector<ScanView> & out)
+{
+  out.clear();
+  for (const auto & sp : m->scans) {
+    if (!sp) {continue;}
+    ScanView v;
+    v.id = sp->id; v.points = sp->points.data();
+    v.corrected[0] = sp->corrected.x; v.corrected[1] = sp->corrected.y; v.corrected[2] = sp->corrected.h;
+    v.odometric[0] = sp->odometric.x; v.odometric[1] = sp->odometric.y; v.odometric[2] = sp->odometric.h;
+    v.barycenter[0] = sp->barycenter[0]; v.barycenter[1] = sp->barycenter[1];
+    v.barycenter[2] = sp->n_filtered != 0 ? 0.0 : sp->sensor.h;       // Pose2(averagePosition, 0.0), or the sensor pose (Karto.h:5687-5692)
+    std::copy(sp->bbox, sp->bbox + 4, v.bbox);
+    out.push_back(v);
+  }
+}
+
+void laser_sensor_at(const kh_laser & laser, const double robot[3], double sensor[3])
+{
+  Laser L;
+  L.offset.x = laser.offset_x; L.offset.y = laser.offset_y; L.offset.h = laser.offset_heading;
+  Pose r; r.x = robot[0]; r.y = robot[1]; r.h = robot[2];
+  const Pose s = sensor_at(L, r);
+  sensor[0] = s.x; sensor[1] = s.y; sensor[2] = s.h;
+}
+
+double karto_normalize_angle(double angle) {return normalize_angle(angle);}
+}  // namespace kh
+
+extern "C" {
+
 // OccupancyGrid::CreateFromScans (Karto.h:5947-5962) from the scans where they lie in HBM
 int kh_mapper_build_map(kh_mapper * m, double resolution, uint32_t min_pass_through, double occupancy_threshold, kh_occupancy ** out)
 {
@@ -1703,40 +1791,10 @@ int kh_mapper_build_map(kh_mapper * m, double resolution, uint32_t min_pass_thro
   int rc = kh_occupancy_create(width, height, min_x, min_y, resolution, m->device, &g);
   if (rc) {return rc;}
   void * stream = kh::occupancy_stream(g);
-  const int64_t range_bytes = static_cast<int64_t>(sizeof(double)) * m->laser.n;
   std::vector<uint64_t> table;
-  table.reserve(4 * static_cast<size_t>(n_alive));
   int64_t up_points = 0, up_ranges = 0;
-  for (auto & sp : m->scans) {
-    if (!sp) {continue;}
-    MScan & s = *sp;
-    if (!s.d_ranges) {
-      if (m->r_free_slots.empty()) {
-        constexpr int kSlabScans = 256;
-        void * p = nullptr;
-        if (kh_device_malloc(m->device, range_bytes * kSlabScans, &p) == KH_OK) {
-          m->r_slabs.push_back(static_cast<double *>(p));
-          for (int k = kSlabScans - 1; k >= 0; --k) {m->r_free_slots.push_back(static_cast<double *>(p) + static_cast<size_t>(k) * static_cast<size_t>(m->laser.n));}
-        }
-      }
-      if (!m->r_free_slots.empty()) {s.d_ranges = m->r_free_slots.back(); m->r_free_slots.pop_back(); s.d_ranges_fresh = false;}
-    }
-    if (s.d_ranges && !s.d_ranges_fresh && s.ranges.size() == static_cast<size_t>(m->laser.n) &&
-      kh_device_upload_on(s.d_ranges, s.ranges.data(), range_bytes, stream) == KH_OK) {s.d_ranges_fresh = true; ++up_ranges;}
-    const bool points_stale = !(s.d_points[0] && (s.d_fresh & 1u));
-    const double * d_points = kh::resident_points(m, s, 0, stream);
-    if (!d_points || !s.d_ranges || !s.d_ranges_fresh) {
-      kh::stream_synchronize(stream);
-      kh_occupancy_destroy(g);
-      kh::set_error("kh_mapper_build_map: a scan could not be made resident on the device");
-      return KH_ERR_HIP;
-    }
-    up_points += points_stale ? 1 : 0;
-    uint64_t rec[4];
-    rec[0] = reinterpret_cast<uint64_t>(d_points); rec[1] = reinterpret_cast<uint64_t>(s.d_ranges);
-    std::memcpy(&rec[2], &s.sensor.x, 8); std::memcpy(&rec[3], &s.sensor.y, 8);
-    table.insert(table.end(), rec, rec + 4);
-  }
+  rc = kh::mapper_resident_table(m, stream, "kh_mapper_build_map", table, &up_points, &up_ranges);
+  if (rc) {kh::stream_synchronize(stream); kh_occupancy_destroy(g); return rc;}
   rc = kh::occupancy_add_resident(g, n_alive, table.data(), m->laser.n, m->laser.range_threshold, m->laser.min_range, m->laser.max_range);
   if (rc == KH_OK) {rc = kh_occupancy_update(g, min_pass_through, occupancy_threshold);}
   if (rc) {kh::stream_synchronize(stream); kh_occupancy_destroy(g); return rc;}

@@ -131,6 +131,72 @@ __global__ __launch_bounds__(256) void k_occ_trace_resident(
   }
 }
 
+// The trace of a MERGE of mapping sessions (kh_merge_build): the scans of several mappers, each mapper (submap) placed by a rigid
+// correction.  The resident readings stay as their mapper made them; the submap's correction is applied to the point in registers
+// -- x' = (c x - s y) + tx, y' = (s x + c y) + ty, no contraction -- and nothing transformed is written back.  The sensor position
+// arrives transformed (the host does GetSensorAt of the transformed corrected pose, once per scan).
+struct MergeScan
+{
+  const double * points;     // 2 * n_beams UNtransformed unfiltered point readings, device memory
+  const double * ranges;     // n_beams range readings, device memory
+  double sx, sy;             // transformed sensor position
+  int32_t submap, pad;
+};
+struct MergeSubmap
+{
+  double c, s, tx, ty;       // the correction: cos / sin of its yaw (host libm), translation
+  double range_threshold, min_range, max_range;      // the submap's laser
+  int32_t n_beams, pad;
+};
+
+// The same work layout as k_occ_trace_resident.  Submaps may have different lasers: the grid is dealt max_runs waves per scan
+// (the longest laser's), a wave beyond its scan's own beam count leaves at once.  Clip, roundings and walk are k_occ_trace's,
+// operation for operation.
+__global__ __launch_bounds__(256) void k_occ_trace_merged(
+  OccDev g, const MergeScan * __restrict__ scans, const MergeSubmap * __restrict__ submaps, int32_t n_scans, int32_t max_runs)
+{
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int32_t lane = threadIdx.x & 63;
+  const int64_t s = wave / max_runs;
+  if (s >= n_scans) {return;}
+  const MergeScan sc = scans[s];
+  const MergeSubmap sm = submaps[sc.submap];
+  const int32_t i = (int32_t)(wave - s * max_runs) * 64 + lane;
+  if (i >= sm.n_beams) {return;}
+  const double r = sc.ranges[i];
+  const double ux = sc.points[2 * i], uy = sc.points[2 * i + 1];
+  double px = (sm.c * ux - sm.s * uy) + sm.tx, py = (sm.s * ux + sm.c * uy) + sm.ty;
+  const double sx = sc.sx, sy = sc.sy;
+  const double range_threshold = sm.range_threshold;
+  const bool valid_end = r < (range_threshold - 1e-06);                  // Karto.h:6167
+  if (r <= sm.min_range || r >= sm.max_range || r != r) {return;}       // Karto.h:6169-6172
+  if (r >= range_threshold) {                                           // Karto.h:6173-6180
+    const double ratio = range_threshold / r;
+    const double dx = px - sx, dy = py - sy;
+    px = sx + ratio * dx; py = sy + ratio * dy;
+  }
+  int32_t x0 = o_to_int(o_round((sx - g.off_x) * g.scale)), y0 = o_to_int(o_round((sy - g.off_y) * g.scale));
+  int32_t x1 = o_to_int(o_round((px - g.off_x) * g.scale)), y1 = o_to_int(o_round((py - g.off_y) * g.scale));
+  const int32_t tx = x1, ty = y1;
+  const bool steep = abs(y1 - y0) > abs(x1 - x0);                       // Grid<kt_int32u>::TraceLine, Karto.h:4874-4927
+  int32_t t;
+  if (steep) {t = x0; x0 = y0; y0 = t; t = x1; x1 = y1; y1 = t;}
+  if (x0 > x1) {t = x0; x0 = x1; x1 = t; t = y0; y0 = y1; y1 = t;}
+  const int32_t deltaX = x1 - x0, deltaY = abs(y1 - y0);
+  int32_t error = 0, y = y0;
+  const int32_t ystep = y0 < y1 ? 1 : -1;
+  for (int32_t x = x0; x <= x1; x++) {
+    const int32_t cx = steep ? y : x, cy = steep ? x : y;
+    error += deltaY;
+    if (2 * error >= deltaX) {y += ystep; error -= deltaX;}
+    if (cx >= 0 && cx < g.width && cy >= 0 && cy < g.height) {atomicAdd(&g.pass[cx + (int64_t)cy * g.ws], 1u);}
+  }
+  if (valid_end && tx >= 0 && tx < g.width && ty >= 0 && ty < g.height) {    // Karto.h:6213-6229
+    atomicAdd(&g.pass[tx + (int64_t)ty * g.ws], 1u);
+    atomicAdd(&g.hits[tx + (int64_t)ty * g.ws], 1u);
+  }
+}
+
 __global__ __launch_bounds__(256) void k_occ_update(OccDev g, uint32_t min_pass, double threshold)
 {
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -158,6 +224,7 @@ struct kh_occupancy
   hipEvent_t ev[2] = {nullptr, nullptr};
   double trace_ms = 0.0; int64_t beams_traced = 0;
   ResidentScan * d_scans = nullptr; size_t cap_scans = 0;     // kh::occupancy_add_resident's table
+  uint8_t * d_merge = nullptr; size_t cap_merge = 0;          // kh::occupancy_add_merged's two tables (submaps, then scans)
 };
 
 namespace kh
@@ -204,6 +271,52 @@ int occupancy_add_resident(kh_occupancy * g, int32_t n_scans, const uint64_t * t
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, g->ev[0], g->ev[1]);
   g->trace_ms += ms; g->beams_traced += static_cast<int64_t>(n_scans) * n_beams;
+  return KH_OK;
+}
+
+// AddScan for the scans of a merge (k_occ_trace_merged).  scans: 5 words per scan -- address of the point readings, address of the
+// ranges, TRANSFORMED sensor x, y as the bits of a double, submap index (low 32 bits); submaps: 8 words per submap -- c, s, tx, ty,
+// range threshold, minimum range, maximum range as the bits of a double, beam count (low 32 bits).  max_beams = the largest beam
+// count, n_total_beams = the sum over the scans (the grid's beam counter).  Returns after the trace has finished.
+int occupancy_add_merged(kh_occupancy * g, int32_t n_scans, const uint64_t * scans, int32_t n_submaps, const uint64_t * submaps,
+  int32_t max_beams, int64_t n_total_beams)
+{
+  static_assert(sizeof(MergeScan) == 40 && sizeof(MergeSubmap) == 64, "records = 5 and 8 words of 8 bytes");
+  if (!g || n_scans < 0 || n_submaps < 0 || max_beams < 0 || (n_scans > 0 && (!scans || !submaps || n_submaps == 0))) {return KH_ERR_INVALID_ARG;}
+  if (hipSetDevice(g->device) != hipSuccess) {return KH_ERR_HIP;}
+  if (n_scans == 0 || max_beams == 0) {return hipStreamSynchronize(g->stream) == hipSuccess ? KH_OK : KH_ERR_HIP;}
+  const size_t submap_bytes = static_cast<size_t>(n_submaps) * sizeof(MergeSubmap), scan_bytes = static_cast<size_t>(n_scans) * sizeof(MergeScan);
+  if (submap_bytes + scan_bytes > g->cap_merge) {
+    (void)hipStreamSynchronize(g->stream);
+    if (g->d_merge) {(void)hipFree(g->d_merge); g->d_merge = nullptr;}
+    g->cap_merge = 0;
+    if (hipMalloc(reinterpret_cast<void **>(&g->d_merge), submap_bytes + scan_bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      set_error("kh_merge_build: table allocation failed");
+      return KH_ERR_HIP;
+    }
+    g->cap_merge = submap_bytes + scan_bytes;
+  }
+  const MergeSubmap * d_submaps = reinterpret_cast<const MergeSubmap *>(g->d_merge);
+  const MergeScan * d_scans = reinterpret_cast<const MergeScan *>(g->d_merge + submap_bytes);      // (64 * n_submaps: 8-byte aligned)
+  if (hipMemcpyAsync(g->d_merge, submaps, submap_bytes, hipMemcpyHostToDevice, g->stream) != hipSuccess ||
+    hipMemcpyAsync(g->d_merge + submap_bytes, scans, scan_bytes, hipMemcpyHostToDevice, g->stream) != hipSuccess)
+  {
+    (void)hipStreamSynchronize(g->stream);
+    return KH_ERR_HIP;
+  }
+  const int32_t runs = (max_beams + 63) / 64;
+  const int64_t waves = static_cast<int64_t>(n_scans) * runs;
+  (void)hipEventRecord(g->ev[0], g->stream);
+  hipLaunchKernelGGL(k_occ_trace_merged, dim3(static_cast<unsigned>((waves + 3) / 4)), dim3(256), 0, g->stream, g->dev, d_scans, d_submaps, n_scans, runs);
+  (void)hipEventRecord(g->ev[1], g->stream);
+  if (hipStreamSynchronize(g->stream) != hipSuccess) {
+    set_error(std::string("kh_merge_build: ") + hipGetErrorString(hipGetLastError()));
+    return KH_ERR_HIP;
+  }
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, g->ev[0], g->ev[1]);
+  g->trace_ms += ms; g->beams_traced += n_total_beams;
   return KH_OK;
 }
 }  // namespace kh
@@ -279,7 +392,7 @@ void kh_occupancy_destroy(kh_occupancy * g)
   if (!g) {return;}
   (void)hipSetDevice(g->device);
   if (g->stream) {(void)hipStreamSynchronize(g->stream);}
-  (void)hipFree(g->dev.pass); (void)hipFree(g->dev.hits); (void)hipFree(g->dev.cells); (void)hipFree(g->d_beams); (void)hipFree(g->d_scans);
+  (void)hipFree(g->dev.pass); (void)hipFree(g->dev.hits); (void)hipFree(g->dev.cells); (void)hipFree(g->d_beams); (void)hipFree(g->d_scans); (void)hipFree(g->d_merge);
   if (g->h_beams) {(void)hipHostFree(g->h_beams);}
   if (g->ev[0]) {(void)hipEventDestroy(g->ev[0]);}
   if (g->ev[1]) {(void)hipEventDestroy(g->ev[1]);}
