@@ -695,6 +695,11 @@ KH_API int kh_session_last_load_ms(double out[4]);
  * rebuild after k new scans moves k scans.  *out is an ordinary kh_occupancy (kh_occupancy_read / _info / _destroy). */
 KH_API int kh_mapper_build_map(kh_mapper * m, double resolution, uint32_t min_pass_through, double occupancy_threshold,
                                kh_occupancy ** out);
+/* LocalizedRangeScan::SetCorrectedPose + Update (Karto.h:5644-5704) for one scan still in the map: its readings, box and
+ * barycentre follow the new pose at once.  The solver's node is not touched, as in the reference: the next CorrectPoses (a loop
+ * closure) puts the scan back where the solver has it.  For a caller that places scans itself -- a mapper created with
+ * use_scan_matching 0, an interactive tool -- and for the live map's tests.  A removed or unknown id is KH_ERR_NOT_FOUND. */
+KH_API int kh_mapper_set_scan_pose(kh_mapper * m, int32_t scan_id, const double corrected_pose[3]);
 /* counters of kh_mapper_build_map: [0] calls, [1] scans traced by the last call, [2] point-reading uploads and [3] range uploads
  * the last call made, [4], [5] the same two since the mapper was made */
 KH_API int kh_mapper_map_stats(const kh_mapper * m, int64_t out[6]);
@@ -748,6 +753,60 @@ KH_API int kh_merge_build(kh_merge * g, uint32_t min_pass_through, double occupa
 /* [0] merges made, [1] scans and [2] beams traced by the last merge, [3] point-reading and [4] range uploads of the last merge,
  * [5], [6] the same two since the merger was made, [7] bytes of the two tables the last merge uploaded */
 KH_API int kh_merge_stats(const kh_merge * g, int64_t out[8]);
+
+/* ---- the live map: the occupancy map slam_toolbox republishes every map_update_interval, kept on the mapper's device and brought
+ * up to date by the DIFFERENCE since the last update instead of a fresh kh_mapper_build_map over every scan.  After
+ * kh_live_map_update the pass / hit / cell grids are, bit for bit, what a fresh trace of the mapper's scans at their current poses
+ * gives on the same lattice; the work is proportional to the scans that entered, left or moved.
+ *
+ * Lattice: an anchor (ax, ay) and a resolution, fixed at creation.  The cell of a world point is
+ * o_to_int(o_round((x - ax) * scale)), scale = 1 / resolution -- k_occ_trace's own operations -- and may be negative.
+ * Window: the grids cover lattice cells [ox, ox + width) x [oy, oy + height), row stride width_step = (width + 7) & ~7.  With
+ * reach = ceil(range_threshold / resolution) + 2, the window holds every cell within `reach` of the sensor cell of every scan in
+ * the map, rounded outward to multiples of 64 cells of the lattice, so no beam is ever clipped; it grows when a scan does not fit
+ * (the counters are copied to their new place) and never shrinks.  kh_occupancy_create's size cap applies: an update whose window
+ * would have (width + 7) * height > 2^31 - 4096 returns KH_ERR_INVALID_ARG and leaves the live map exactly as it was.
+ * anchor = NULL: the offset kh_mapper_build_map would choose at that moment (needs a scan in the map); right after creation the
+ * live map then equals kh_mapper_build_map's grid on the whole of that grid's rectangle.
+ *
+ * Each update classifies the mapper's scans against the log of what the map has traced: NEW scans are traced in (+1), GONE scans
+ * (kh_mapper_remove_node, the localization buffer, node decay) are walked out of the counters along the logged lines (-1), MOVED
+ * scans (the bits of the sensor pose differ: a loop closure, kh_mapper_set_scan_pose) have each beam's new line compared with the
+ * logged one and only the beams that differ re-walked.  When more than rebuild_fraction of the scans in the map are in the delta
+ * the update clears the counters and traces everything instead: 0 = always, +inf = never, negative = the library's default.
+ *
+ * The live map BORROWS the mapper: destroy the live map first.  Like kh_mapper_build_map, an update must not run concurrently
+ * with a Process call of its mapper.  A live map is not part of a session file: after kh_mapper_load make a new one, whose first
+ * update is a full pass.  The grids are on the mapper's own device. */
+typedef struct kh_live_map kh_live_map;
+typedef struct kh_live_map_info_t {
+  double anchor[2], resolution, rebuild_fraction;
+  int32_t ox, oy, width, height, width_step;    /* all zero before the first scan */
+  int32_t reach;
+} kh_live_map_info_t;
+typedef struct kh_live_map_counts {
+  int64_t scans_added, scans_removed, scans_moved;    /* the classification, whichever path the update took */
+  int64_t beams_traced;            /* lines walked, +1 or -1 */
+  int64_t beams_skipped;           /* traced beams of moved scans whose line did not change: left alone */
+  int64_t cells_updated;           /* cells given to the cell-state kernel */
+  int64_t relayouts;               /* the window grew */
+  int64_t rebuilds;                /* the update cleared the counters and traced every scan (last: 0 or 1) */
+  double trace_ms;                 /* the trace kernel, by device events */
+} kh_live_map_counts;
+typedef struct kh_live_map_stats_t {
+  kh_live_map_counts last, total;  /* the last update / all updates */
+  int64_t updates, scans_in_map, log_bytes;
+} kh_live_map_stats_t;
+KH_API int kh_live_map_create(kh_mapper * m, double resolution, const double anchor[2], double rebuild_fraction, kh_live_map ** out);
+KH_API void kh_live_map_destroy(kh_live_map * g);
+/* min_pass_through / occupancy_threshold as kh_occupancy_update.  The cell states are recomputed over the rectangle the delta can
+ * have touched; over the whole window on the first call, after the window grew, after a rebuild and when the two parameters
+ * differ from the previous call's. */
+KH_API int kh_live_map_update(kh_live_map * g, uint32_t min_pass_through, double occupancy_threshold);
+KH_API int kh_live_map_info(const kh_live_map * g, kh_live_map_info_t * out);
+/* layout of kh_occupancy_read over the window: width_step * height entries each; any pointer may be NULL */
+KH_API int kh_live_map_read(kh_live_map * g, uint8_t * cells, uint32_t * pass, uint32_t * hits);
+KH_API int kh_live_map_stats(const kh_live_map * g, kh_live_map_stats_t * out);
 
 #ifdef __cplusplus
 }

@@ -98,6 +98,8 @@ SYMBOLS = [
     "kh_merge_create", "kh_merge_destroy", "kh_merge_add_mapper", "kh_merge_add_session", "kh_merge_remove_submap", "kh_merge_num_submaps",
     "kh_merge_submap_info", "kh_merge_set_transform", "kh_merge_get_transform", "kh_merge_move_submap", "kh_merge_get_location",
     "kh_merge_get_scan", "kh_merge_build_submap", "kh_merge_build", "kh_merge_stats",
+    "kh_mapper_set_scan_pose", "kh_live_map_create", "kh_live_map_destroy", "kh_live_map_update", "kh_live_map_info", "kh_live_map_read",
+    "kh_live_map_stats",
 ]
 
 
@@ -143,6 +145,20 @@ class KhMapperStats(C.Structure):
 class KhSessionInfo(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("version", "file_bytes", "n_beams", "n_scan_slots", "n_alive", "n_edges", "n_running", "last_scan",
                                          "n_localization_buffer", "lifelong", "n_solver_nodes", "n_solver_constraints", "n_supernodes")]
+
+
+class KhLiveMapInfo(C.Structure):
+    _fields_ = [("anchor", C.c_double * 2), ("resolution", C.c_double), ("rebuild_fraction", C.c_double)] + \
+               [(k, C.c_int32) for k in ("ox", "oy", "width", "height", "width_step", "reach")]
+
+
+class KhLiveMapCounts(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("scans_added", "scans_removed", "scans_moved", "beams_traced", "beams_skipped", "cells_updated",
+                                         "relayouts", "rebuilds")] + [("trace_ms", C.c_double)]
+
+
+class KhLiveMapStats(C.Structure):
+    _fields_ = [("last", KhLiveMapCounts), ("total", KhLiveMapCounts)] + [(k, C.c_int64) for k in ("updates", "scans_in_map", "log_bytes")]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
@@ -337,6 +353,15 @@ def lib():
         L.kh_merge_build_submap.argtypes = [vp, i32, C.c_uint32, dbl, C.POINTER(vp)]
         L.kh_merge_build.argtypes = [vp, C.c_uint32, dbl, C.POINTER(vp)]
         L.kh_merge_stats.argtypes = [vp, np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")]
+    if hasattr(L, "kh_live_map_create"):
+        L.kh_mapper_set_scan_pose.argtypes = [vp, i32, dptr]
+        L.kh_live_map_create.argtypes = [vp, dbl, vp, dbl, C.POINTER(vp)]
+        L.kh_live_map_destroy.argtypes = [vp]
+        L.kh_live_map_destroy.restype = None
+        L.kh_live_map_update.argtypes = [vp, C.c_uint32, dbl]
+        L.kh_live_map_info.argtypes = [vp, C.POINTER(KhLiveMapInfo)]
+        L.kh_live_map_read.argtypes = [vp, vp, vp, vp]
+        L.kh_live_map_stats.argtypes = [vp, C.POINTER(KhLiveMapStats)]
     if hasattr(L, "kh_lifelong_scores"):
         L.kh_decay_params_default.argtypes = [C.POINTER(KhDecayParams)]
         L.kh_decay_params_default.restype = None

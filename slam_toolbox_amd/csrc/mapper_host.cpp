@@ -1687,15 +1687,23 @@ namespace kh
 // (once in its life) and its point readings (again only after its pose moved) into HBM on the mapper's own device, the uploads
 // queued on `stream`; table gains 4 words per scan in id order -- address of the points, address of the ranges, sensor x, y as
 // the bits of a double (the record of kh::occupancy_add_resident).  *up_points / *up_ranges = uploads this call made.
-int mapper_resident_table(kh_mapper * m, void * stream, const char * who, std::vector<uint64_t> & table, int64_t * up_points, int64_t * up_ranges)
+// ids = NULL: every scan still in the map; otherwise the n_ids scans named (each still in the map), in the order given.
+int mapper_resident_table_of(kh_mapper * m, void * stream, const char * who, const int32_t * ids, size_t n_ids, std::vector<uint64_t> & table,
+  int64_t * up_points, int64_t * up_ranges)
 {
   const int64_t range_bytes = static_cast<int64_t>(sizeof(double)) * m->laser.n;
   table.clear();
-  table.reserve(4 * m->scans.size());
+  table.reserve(4 * (ids ? n_ids : m->scans.size()));
   *up_points = 0; *up_ranges = 0;
-  for (auto & sp : m->scans) {
-    if (!sp) {continue;}
-    MScan & s = *sp;
+  const size_t n_visit = ids ? n_ids : m->scans.size();
+  for (size_t k = 0; k < n_visit; ++k) {
+    const size_t id = ids ? static_cast<size_t>(ids[k]) : k;
+    if (id >= m->scans.size() || !m->scans[id]) {
+      if (!ids) {continue;}
+      set_error(std::string(who) + ": scan " + std::to_string(id) + " is not in the map");
+      return KH_ERR_NOT_FOUND;
+    }
+    MScan & s = *m->scans[id];
     if (!s.d_ranges) {
       if (m->r_free_slots.empty()) {
         constexpr int kSlabScans = 256;
@@ -1722,6 +1730,23 @@ int mapper_resident_table(kh_mapper * m, void * stream, const char * who, std::v
     table.insert(table.end(), rec, rec + 4);
   }
   return KH_OK;
+}
+
+int mapper_resident_table(kh_mapper * m, void * stream, const char * who, std::vector<uint64_t> & table, int64_t * up_points, int64_t * up_ranges)
+{
+  return mapper_resident_table_of(m, stream, who, nullptr, 0, table, up_points, up_ranges);
+}
+
+void mapper_sensor_poses(const kh_mapper * m, std::vector<SensorView> & out)
+{
+  out.clear();
+  for (const auto & sp : m->scans) {
+    if (!sp) {continue;}
+    SensorView v;
+    v.id = sp->id; v.sensor[0] = sp->sensor.x; v.sensor[1] = sp->sensor.y; v.sensor[2] = sp->sensor.h;
+    std::copy(sp->bbox, sp->bbox + 4, v.bbox);
+    out.push_back(v);
+  }
 }
 
 // what merge.cpp reads of a mapper (mapper_internal.hpp)
@@ -1801,6 +1826,22 @@ int kh_mapper_build_map(kh_mapper * m, double resolution, uint32_t min_pass_thro
   m->map_stats[0] += 1; m->map_stats[1] = n_alive; m->map_stats[2] = up_points; m->map_stats[3] = up_ranges;
   m->map_stats[4] += up_points; m->map_stats[5] += up_ranges;
   *out = g;
+  return KH_OK;
+}
+
+// LocalizedRangeScan::SetCorrectedPose followed by Update (Karto.h:5644-5704): the scan's readings, box and barycentre follow the
+// pose.  The solver's node is left alone, as in the reference, so the next CorrectPoses puts the scan where the solver has it.
+int kh_mapper_set_scan_pose(kh_mapper * m, int32_t scan_id, const double corrected_pose[3])
+{
+  if (!m || !corrected_pose) {return KH_ERR_INVALID_ARG;}
+  if (scan_id < 0 || scan_id >= static_cast<int32_t>(m->scans.size()) || !m->scans[scan_id]) {
+    kh::set_error("kh_mapper_set_scan_pose: no such scan (unknown or removed)");
+    return KH_ERR_NOT_FOUND;
+  }
+  MScan & s = *m->scans[scan_id];
+  s.corrected.x = corrected_pose[0]; s.corrected.y = corrected_pose[1]; s.corrected.h = corrected_pose[2];
+  kh::update_scan(s, m->laser);
+  m->graph_dirty = true;
   return KH_OK;
 }
 

@@ -1,4 +1,4 @@
-// What mapper_host.cpp shows of a mapper to the session merger (merge.cpp).  Not part of the public ABI (include/karto_hip.h).
+// What mapper_host.cpp shows of a mapper to the session merger (merge.cpp) and the live map (live_map.cpp).  Not part of the public ABI (include/karto_hip.h).
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -23,6 +23,18 @@ void mapper_alive_scans(const kh_mapper * m, std::vector<ScanView> & out);      
 // makes every scan still in the map resident on the mapper's device (uploads queued on `stream`) and emits 4 words per scan in id
 // order: address of the points, address of the ranges, sensor x, y as the bits of a double
 int mapper_resident_table(kh_mapper * m, void * stream, const char * who, std::vector<uint64_t> & table, int64_t * up_points, int64_t * up_ranges);
+// the same for a subset: ids = NULL is every scan still in the map, otherwise the n_ids scans named, in the order given (a scan
+// that is not in the map is KH_ERR_NOT_FOUND)
+int mapper_resident_table_of(kh_mapper * m, void * stream, const char * who, const int32_t * ids, size_t n_ids, std::vector<uint64_t> & table,
+  int64_t * up_points, int64_t * up_ranges);
+// what the live map (live_map.cpp) classifies a scan by: its sensor pose; and its box (the default anchor)
+struct SensorView
+{
+  int32_t id;
+  double sensor[3];
+  double bbox[4];
+};
+void mapper_sensor_poses(const kh_mapper * m, std::vector<SensorView> & out);     // id order
 void laser_sensor_at(const kh_laser & laser, const double robot[3], double sensor[3]);   // LocalizedRangeScan::GetSensorAt, Karto.h:5566-5569
 double karto_normalize_angle(double angle);                                              // math::NormalizeAngle, Math.h:181-202
 }  // namespace kh

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/karto_hip.h"
+#include "live_map_device.hpp"
 
 namespace kh
 {
@@ -197,17 +198,136 @@ __global__ __launch_bounds__(256) void k_occ_trace_merged(
   }
 }
 
+// UpdateCell (Karto.h:6240-6256) for the cell at index k of the three arrays
+__device__ __forceinline__ void occ_update_cell(const uint32_t * __restrict__ pass, const uint32_t * __restrict__ hits, uint8_t * __restrict__ cells,
+  int64_t k, uint32_t min_pass, double threshold)
+{
+  uint8_t c = 0;                                                       // GridStates_Unknown (Clear())
+  const uint32_t p = pass[k];
+  if (p > min_pass) {                                                   // Karto.h:6244-6252
+    const double ratio = (double)hits[k] / (double)p;
+    c = ratio > threshold ? 100 : 255;
+  }
+  cells[k] = c;
+}
+
 __global__ __launch_bounds__(256) void k_occ_update(OccDev g, uint32_t min_pass, double threshold)
 {
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= (int64_t)g.ws * g.height) {return;}
-  uint8_t c = 0;                                                       // GridStates_Unknown (Clear())
-  const uint32_t p = g.pass[k];
-  if (p > min_pass) {                                                   // Karto.h:6244-6252
-    const double ratio = (double)g.hits[k] / (double)p;
-    c = ratio > threshold ? 100 : 255;
+  occ_update_cell(g.pass, g.hits, g.cells, k, min_pass, threshold);
+}
+
+// The same rule over a rectangle of a live map's window (kh_live_map_update: the cells a delta can have touched)
+__global__ __launch_bounds__(256) void k_occ_update_rect(LiveWindow g, int32_t x0, int32_t y0, int32_t rect_w, int32_t rect_h, uint32_t min_pass,
+  double threshold)
+{
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= (int64_t)rect_w * rect_h) {return;}
+  const int64_t y = k / rect_w, x = k - y * rect_w;
+  occ_update_cell(g.pass, g.hits, g.cells, (x0 + x) + (y0 + y) * (int64_t)g.ws, min_pass, threshold);
+}
+
+// ---- the live map's trace (kh_live_map_update) ----
+// what AddScan (Karto.h:6148-6189) decides about one beam, on the live map's fixed lattice: k_occ_trace's gate, clip and roundings,
+// operation for operation, with the anchor in the place of the grid offset
+struct BeamTrace
+{
+  int32_t ex, ey;            // end cell
+  bool kept, hit;            // traced at all / the end point counts as a hit
+};
+__device__ __forceinline__ BeamTrace live_beam(const DeltaRecord & rec, int32_t i, double ax, double ay, double scale, double range_threshold,
+  double min_range, double max_range)
+{
+  BeamTrace b;
+  b.ex = 0; b.ey = 0; b.kept = false; b.hit = false;
+  const double r = rec.ranges[i];
+  double px = rec.points[2 * i], py = rec.points[2 * i + 1];
+  const double sx = rec.sx, sy = rec.sy;
+  const bool valid_end = r < (range_threshold - 1e-06);                  // Karto.h:6167
+  if (r <= min_range || r >= max_range || r != r) {return b;}           // Karto.h:6169-6172
+  if (r >= range_threshold) {                                           // Karto.h:6173-6180
+    const double ratio = range_threshold / r;
+    const double dx = px - sx, dy = py - sy;
+    px = sx + ratio * dx; py = sy + ratio * dy;
   }
-  g.cells[k] = c;
+  b.ex = o_to_int(o_round((px - ax) * scale)); b.ey = o_to_int(o_round((py - ay) * scale));
+  b.kept = true; b.hit = valid_end;
+  return b;
+}
+
+// Grid<kt_int32u>::TraceLine (Karto.h:4874-4927) + the end point (Karto.h:6213-6229) in lattice cells, adding `delta` (1, or
+// 0xFFFFFFFF = -1) to the counters.  The window holds every cell of every beam (coverage rule); the bounds test is a guard.
+__device__ __forceinline__ void live_walk(const LiveWindow & g, int32_t x0, int32_t y0, int32_t x1, int32_t y1, bool hit, uint32_t delta)
+{
+  const int32_t tx = x1, ty = y1;
+  const bool steep = abs(y1 - y0) > abs(x1 - x0);
+  int32_t t;
+  if (steep) {t = x0; x0 = y0; y0 = t; t = x1; x1 = y1; y1 = t;}
+  if (x0 > x1) {t = x0; x0 = x1; x1 = t; t = y0; y0 = y1; y1 = t;}
+  const int32_t deltaX = x1 - x0, deltaY = abs(y1 - y0);
+  int32_t error = 0, y = y0;
+  const int32_t ystep = y0 < y1 ? 1 : -1;
+  for (int32_t x = x0; x <= x1; x++) {
+    const int32_t cx = steep ? y : x, cy = steep ? x : y;
+    error += deltaY;
+    if (2 * error >= deltaX) {y += ystep; error -= deltaX;}
+    const int64_t wx = (int64_t)cx - g.ox, wy = (int64_t)cy - g.oy;
+    if (wx >= 0 && wx < g.width && wy >= 0 && wy < g.height) {atomicAdd(&g.pass[wx + wy * g.ws], delta);}
+  }
+  const int64_t wx = (int64_t)tx - g.ox, wy = (int64_t)ty - g.oy;
+  if (hit && wx >= 0 && wx < g.width && wy >= 0 && wy < g.height) {
+    atomicAdd(&g.pass[wx + wy * g.ws], delta);
+    atomicAdd(&g.hits[wx + wy * g.ws], delta);
+  }
+}
+
+// The work layout of k_occ_trace_resident -- one wave per run of 64 neighbouring beams of one scan -- over a table of ADD / SUB /
+// MOVE records (live_map_device.hpp).  ADD traces from the resident readings and writes the scan's slot of the log; SUB walks the
+// logged lines with -1 and reads nothing else; MOVE compares the beam's new trace record with the logged one and walks (old line
+// -1, new line +1) only where something differs.  One scan is one record, so no two waves touch the same log words: a beam's two
+// words belong to its lane, and the slot's sensor cell is written by beam 0's lane and read by SUB records only (MOVE gets the old
+// cell in its record).
+__global__ __launch_bounds__(256) void k_occ_trace_delta(
+  LiveWindow g, double ax, double ay, double scale, const DeltaRecord * __restrict__ records, int32_t n_records, int32_t n_beams,
+  int32_t runs_per_scan, double range_threshold, double min_range, double max_range, int32_t * __restrict__ log, int64_t slot_words,
+  unsigned long long * __restrict__ counters)
+{
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int32_t lane = threadIdx.x & 63;
+  const int64_t s = wave / runs_per_scan;
+  if (s >= n_records) {return;}
+  const int32_t i = (int32_t)(wave - s * runs_per_scan) * 64 + lane;
+  if (i >= n_beams) {return;}
+  const DeltaRecord rec = records[s];
+  int32_t * const slot = log + rec.slot * slot_words;
+  int2 * const entry = reinterpret_cast<int2 *>(slot + 2) + i;
+  // the logged line (SUB, MOVE) and the new one (ADD, MOVE)
+  int32_t ocx = rec.old_cx, ocy = rec.old_cy, ncx = 0, ncy = 0;
+  int2 was = make_int2(0, 0), now = make_int2(0, 0);
+  if (rec.kind != kDeltaAdd) {was = *entry;}
+  if (rec.kind == kDeltaSub) {ocx = slot[0]; ocy = slot[1];}
+  if (rec.kind != kDeltaSub) {
+    ncx = o_to_int(o_round((rec.sx - ax) * scale)); ncy = o_to_int(o_round((rec.sy - ay) * scale));
+    const BeamTrace b = live_beam(rec, i, ax, ay, scale, range_threshold, min_range, max_range);
+    if (b.kept) {now = make_int2(b.ex, (int32_t)(((uint32_t)(b.ey - ncy) << 2) | (b.hit ? 3u : 1u)));}
+  }
+  const bool same = rec.kind == kDeltaMove && was.x == now.x && was.y == now.y && ocx == ncx && ocy == ncy;
+  const bool walk_old = rec.kind != kDeltaAdd && !same && (was.y & 1);
+  const bool walk_new = rec.kind != kDeltaSub && !same && (now.y & 1);
+  if (walk_old) {live_walk(g, ocx, ocy, was.x, ocy + (was.y >> 2), (was.y & 2) != 0, 0xFFFFFFFFu);}
+  if (walk_new) {live_walk(g, ncx, ncy, now.x, ncy + (now.y >> 2), (now.y & 2) != 0, 1u);}
+  if (rec.kind != kDeltaSub) {
+    if (!same) {*entry = now;}
+    if (i == 0) {slot[0] = ncx; slot[1] = ncy;}
+  }
+  // lane 0 holds the run's first beam, so it is here whenever the wave is
+  const int walked = __popcll(__ballot(walk_old)) + __popcll(__ballot(walk_new));
+  const int skipped = __popcll(__ballot(same && (now.y & 1)));
+  if (lane == 0) {
+    if (walked) {atomicAdd(&counters[0], (unsigned long long)walked);}
+    if (skipped) {atomicAdd(&counters[1], (unsigned long long)skipped);}
+  }
 }
 
 }  // namespace kh
@@ -318,6 +438,26 @@ int occupancy_add_merged(kh_occupancy * g, int32_t n_scans, const uint64_t * sca
   (void)hipEventElapsedTime(&ms, g->ev[0], g->ev[1]);
   g->trace_ms += ms; g->beams_traced += n_total_beams;
   return KH_OK;
+}
+
+void live_trace_delta(void * stream, const LiveWindow & w, double anchor_x, double anchor_y, double scale, const DeltaRecord * d_records,
+  int32_t n_records, int32_t n_beams, double range_threshold, double min_range, double max_range, int32_t * d_log,
+  unsigned long long * d_counters)
+{
+  if (n_records <= 0 || n_beams <= 0) {return;}
+  const int32_t runs = (n_beams + 63) / 64;
+  const int64_t waves = static_cast<int64_t>(n_records) * runs;
+  hipLaunchKernelGGL(k_occ_trace_delta, dim3(static_cast<unsigned>((waves + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), w, anchor_x,
+    anchor_y, scale, d_records, n_records, n_beams, runs, range_threshold, min_range, max_range, d_log, live_log_slot_words(n_beams), d_counters);
+}
+
+void live_update_cells(void * stream, const LiveWindow & w, int32_t x0, int32_t y0, int32_t rect_w, int32_t rect_h, uint32_t min_pass,
+  double threshold)
+{
+  if (rect_w <= 0 || rect_h <= 0) {return;}
+  const int64_t size = static_cast<int64_t>(rect_w) * rect_h;
+  hipLaunchKernelGGL(k_occ_update_rect, dim3(static_cast<unsigned>((size + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), w, x0, y0,
+    rect_w, rect_h, min_pass, threshold);
 }
 }  // namespace kh
 

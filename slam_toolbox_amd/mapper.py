@@ -84,6 +84,18 @@ class Mapper:
                    "kh_mapper_build_map")
         return OccupancyGrid.from_handle(h, resolution)
 
+    def live_map(self, resolution: float = 0.05, anchor=None, rebuild_fraction: float = None):
+        """kh_live_map_create: an occupancy map that stays on the device next to this mapper and is brought up to date by the scans
+        that entered, left or moved since its last update (live_map.LiveMap).  anchor None = the offset build_map would choose now;
+        rebuild_fraction None = the library's default.  Close the live map before the mapper."""
+        from .live_map import LiveMap
+        return LiveMap(self, resolution, anchor, rebuild_fraction)
+
+    def set_scan_pose(self, scan_id: int, corrected_pose):
+        """kh_mapper_set_scan_pose: LocalizedRangeScan::SetCorrectedPose + Update of one scan (the solver is not told)"""
+        capi.check(capi.lib().kh_mapper_set_scan_pose(self._h, int(scan_id), np.ascontiguousarray(corrected_pose, dtype=np.float64)),
+                   "kh_mapper_set_scan_pose")
+
     def map_stats(self) -> dict:
         """counters of build_map: calls, scans traced / point uploads / range uploads of the last call, and the two totals"""
         out = np.zeros(6, dtype=np.int64)
