@@ -20,7 +20,7 @@
 #include <vector>
 
 #include "../../include/karto_hip.h"
-#include "live_map_device.hpp"
+#include "occupancy_device.hpp"
 #include "mapper_internal.hpp"
 
 namespace kh
@@ -34,7 +34,6 @@ constexpr int32_t kMargin = 2;              // cells beyond ceil(range_threshold
 constexpr double kDefaultRebuildFraction = 0.5;      // provisional: the crossover has not been measured yet
 constexpr double kCellLimit = 1073741824.0;          // |cell index| a scan may have (2^30): index +- reach stays an int32
 
-double round_half_away(double v) {return v >= 0.0 ? std::floor(v + 0.5) : std::ceil(v - 0.5);}     // o_round, occupancy.hip
 int32_t floor_block(int64_t c) {return static_cast<int32_t>((c >= 0 ? c / kBlock : -((-c + kBlock - 1) / kBlock)) * kBlock);}
 
 struct Entry
@@ -78,7 +77,7 @@ namespace
 {
 bool cell_of(const kh_live_map * g, const double sensor[3], int32_t * cx, int32_t * cy)
 {
-  // the operations of k_occ_trace: o_to_int(o_round((x - anchor) * scale))
+  // the operations of occ_cell (occupancy.hip): o_to_int(o_round((x - anchor) * scale))
   const double x = round_half_away((sensor[0] - g->ax) * g->scale), y = round_half_away((sensor[1] - g->ay) * g->scale);
   if (!(std::fabs(x) < kCellLimit && std::fabs(y) < kCellLimit)) {return false;}
   *cx = static_cast<int32_t>(x); *cy = static_cast<int32_t>(y);
@@ -296,7 +295,7 @@ int kh_live_map_update(kh_live_map * g, uint32_t min_pass_through, double occupa
   std::vector<int32_t> read_ids;
   for (const Change & c : moved) {read_ids.push_back(c.id);}
   for (const Change & c : added) {read_ids.push_back(c.id);}
-  std::vector<uint64_t> resident;
+  std::vector<ResidentScan> resident;
   int64_t up_points = 0, up_ranges = 0;
   int rc = kh::mapper_resident_table_of(g->mapper, g->stream, "kh_live_map_update", read_ids.data(), read_ids.size(), resident, &up_points, &up_ranges);
   if (rc) {(void)hipStreamSynchronize(g->stream); g->counters_suspect = g->counters_suspect || rebuild; return rc;}
@@ -307,7 +306,7 @@ int kh_live_map_update(kh_live_map * g, uint32_t min_pass_through, double occupa
     std::memset(&r, 0, sizeof(r));
     r.kind = kind; r.slot = slot;
     if (c) {
-      r.points = reinterpret_cast<const double *>(resident[4 * k]); r.ranges = reinterpret_cast<const double *>(resident[4 * k + 1]);
+      r.points = resident[k].points; r.ranges = resident[k].ranges;
       r.sx = c->view->sensor[0]; r.sy = c->view->sensor[1];
       const Entry & e = g->entries[static_cast<size_t>(c->id)];
       r.old_cx = e.cx; r.old_cy = e.cy;

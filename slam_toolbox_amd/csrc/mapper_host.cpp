@@ -46,9 +46,6 @@ int decay_scores(int32_t device, const kh_scan_box * reference, int32_t n, const
   double * reading_overlap, double * scores);                                                                       // lifelong.hip
 void set_pending_query_hook(std::function<void()> fn);       // matcher_seq.cpp (QueryHook, matcher_private.hpp)
 void run_pending_query_hook();
-void * occupancy_stream(kh_occupancy * g);                                                                            // occupancy.hip
-int occupancy_add_resident(kh_occupancy * g, int32_t n_scans, const uint64_t * table, int32_t n_beams, double range_threshold, double min_range,
-  double max_range);
 void spa_export_session_state(kh_spa * s, int64_t words[7], std::vector<int32_t> & sn_ptr, std::vector<int32_t> & sn_ids);
 void spa_import_session_state(kh_spa * s, const int64_t words[7], const std::vector<int32_t> & sn_ptr, const std::vector<int32_t> & sn_ids);
 int graph_swap(kh_graph * g, int32_t n_scans, std::vector<double> & ref_xy, std::vector<int32_t> & adj_ptr, std::vector<int32_t> & adj_idx,
@@ -1685,15 +1682,15 @@ namespace kh
 {
 // The residency loop kh_mapper_build_map and the session merger (merge.cpp) share: every scan still in the map gets its ranges
 // (once in its life) and its point readings (again only after its pose moved) into HBM on the mapper's own device, the uploads
-// queued on `stream`; table gains 4 words per scan in id order -- address of the points, address of the ranges, sensor x, y as
-// the bits of a double (the record of kh::occupancy_add_resident).  *up_points / *up_ranges = uploads this call made.
+// queued on `stream`; table gains one record per scan in id order (ResidentScan, the record of kh::occupancy_add_resident).
+// *up_points / *up_ranges = uploads this call made.
 // ids = NULL: every scan still in the map; otherwise the n_ids scans named (each still in the map), in the order given.
-int mapper_resident_table_of(kh_mapper * m, void * stream, const char * who, const int32_t * ids, size_t n_ids, std::vector<uint64_t> & table,
+int mapper_resident_table_of(kh_mapper * m, void * stream, const char * who, const int32_t * ids, size_t n_ids, std::vector<ResidentScan> & table,
   int64_t * up_points, int64_t * up_ranges)
 {
   const int64_t range_bytes = static_cast<int64_t>(sizeof(double)) * m->laser.n;
   table.clear();
-  table.reserve(4 * (ids ? n_ids : m->scans.size()));
+  table.reserve(ids ? n_ids : m->scans.size());
   *up_points = 0; *up_ranges = 0;
   const size_t n_visit = ids ? n_ids : m->scans.size();
   for (size_t k = 0; k < n_visit; ++k) {
@@ -1724,15 +1721,12 @@ int mapper_resident_table_of(kh_mapper * m, void * stream, const char * who, con
       return KH_ERR_HIP;
     }
     *up_points += points_stale ? 1 : 0;
-    uint64_t rec[4];
-    rec[0] = reinterpret_cast<uint64_t>(d_points); rec[1] = reinterpret_cast<uint64_t>(s.d_ranges);
-    std::memcpy(&rec[2], &s.sensor.x, 8); std::memcpy(&rec[3], &s.sensor.y, 8);
-    table.insert(table.end(), rec, rec + 4);
+    table.push_back(ResidentScan{d_points, s.d_ranges, s.sensor.x, s.sensor.y});
   }
   return KH_OK;
 }
 
-int mapper_resident_table(kh_mapper * m, void * stream, const char * who, std::vector<uint64_t> & table, int64_t * up_points, int64_t * up_ranges)
+int mapper_resident_table(kh_mapper * m, void * stream, const char * who, std::vector<ResidentScan> & table, int64_t * up_points, int64_t * up_ranges)
 {
   return mapper_resident_table_of(m, stream, who, nullptr, 0, table, up_points, up_ranges);
 }
@@ -1798,25 +1792,22 @@ int kh_mapper_build_map(kh_mapper * m, double resolution, uint32_t min_pass_thro
   *out = nullptr;
   // ComputeDimensions (Karto.h:6086-6112): every scan's box is the min / max of its sensor position and its in-range readings
   // (update_scan), so the min / max over the boxes are the min / max kh_occupancy_compute_dimensions finds beam by beam
-  double min_x = 999999999999999999.99999, min_y = 999999999999999999.99999;
-  double max_x = -999999999999999999.99999, max_y = -999999999999999999.99999;
+  kh::Box box;
   int32_t n_alive = 0;
   for (const auto & sp : m->scans) {
     if (!sp) {continue;}
     ++n_alive;
-    min_x = sp->bbox[0] < min_x ? sp->bbox[0] : min_x; min_y = sp->bbox[1] < min_y ? sp->bbox[1] : min_y;
-    max_x = sp->bbox[2] > max_x ? sp->bbox[2] : max_x; max_y = sp->bbox[3] > max_y ? sp->bbox[3] : max_y;
+    box.add(sp->bbox[0], sp->bbox[1]); box.add(sp->bbox[2], sp->bbox[3]);
   }
   if (n_alive == 0) {kh::set_error("kh_mapper_build_map: no scan in the map"); return KH_ERR_INVALID_ARG;}
-  const double scale = 1.0 / resolution;
-  auto round_half_away = [](double v) {return v >= 0.0 ? std::floor(v + 0.5) : std::ceil(v - 0.5);};
-  const int32_t width = static_cast<int32_t>(round_half_away((max_x - min_x) * scale));
-  const int32_t height = static_cast<int32_t>(round_half_away((max_y - min_y) * scale));
+  int32_t width, height;
+  double offset[2];
+  kh::grid_dimensions(box, resolution, &width, &height, offset);
   kh_occupancy * g = nullptr;
-  int rc = kh_occupancy_create(width, height, min_x, min_y, resolution, m->device, &g);
+  int rc = kh_occupancy_create(width, height, offset[0], offset[1], resolution, m->device, &g);
   if (rc) {return rc;}
   void * stream = kh::occupancy_stream(g);
-  std::vector<uint64_t> table;
+  std::vector<kh::ResidentScan> table;
   int64_t up_points = 0, up_ranges = 0;
   rc = kh::mapper_resident_table(m, stream, "kh_mapper_build_map", table, &up_points, &up_ranges);
   if (rc) {kh::stream_synchronize(stream); kh_occupancy_destroy(g); return rc;}

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "../../include/karto_hip.h"
+#include "occupancy_device.hpp"
 
 namespace kh
 {
@@ -20,12 +21,12 @@ struct ScanView
 int32_t mapper_device(const kh_mapper * m);
 kh_laser mapper_laser(const kh_mapper * m);
 void mapper_alive_scans(const kh_mapper * m, std::vector<ScanView> & out);        // id order
-// makes every scan still in the map resident on the mapper's device (uploads queued on `stream`) and emits 4 words per scan in id
-// order: address of the points, address of the ranges, sensor x, y as the bits of a double
-int mapper_resident_table(kh_mapper * m, void * stream, const char * who, std::vector<uint64_t> & table, int64_t * up_points, int64_t * up_ranges);
+// makes every scan still in the map resident on the mapper's device (uploads queued on `stream`) and emits one record per scan in
+// id order: where its readings lie on the device, and its sensor position
+int mapper_resident_table(kh_mapper * m, void * stream, const char * who, std::vector<ResidentScan> & table, int64_t * up_points, int64_t * up_ranges);
 // the same for a subset: ids = NULL is every scan still in the map, otherwise the n_ids scans named, in the order given (a scan
 // that is not in the map is KH_ERR_NOT_FOUND)
-int mapper_resident_table_of(kh_mapper * m, void * stream, const char * who, const int32_t * ids, size_t n_ids, std::vector<uint64_t> & table,
+int mapper_resident_table_of(kh_mapper * m, void * stream, const char * who, const int32_t * ids, size_t n_ids, std::vector<ResidentScan> & table,
   int64_t * up_points, int64_t * up_ranges);
 // what the live map (live_map.cpp) classifies a scan by: its sensor pose; and its box (the default anchor)
 struct SensorView

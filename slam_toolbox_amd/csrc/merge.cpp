@@ -13,7 +13,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstring>
 #include <string>
 #include <vector>
 
@@ -24,9 +23,6 @@ namespace kh
 {
 void set_error(const std::string & s);
 void stream_synchronize(void * hip_stream);      // comm.cpp
-void * occupancy_stream(kh_occupancy * g);       // occupancy.hip
-int occupancy_add_merged(kh_occupancy * g, int32_t n_scans, const uint64_t * scans, int32_t n_submaps, const uint64_t * submaps,
-  int32_t max_beams, int64_t n_total_beams);
 
 namespace
 {
@@ -66,18 +62,6 @@ Rigid inverse(const Rigid & a)
   return Rigid(-(c * a.x - s * a.y), -(s * a.x + c * a.y), yaw);
 }
 
-// BoundingBox2 (Karto.h:2846-2903) as ComputeDimensions uses it
-struct Box
-{
-  double min_x = 999999999999999999.99999, min_y = 999999999999999999.99999;
-  double max_x = -999999999999999999.99999, max_y = -999999999999999999.99999;
-  void add(double x, double y)
-  {
-    min_x = x < min_x ? x : min_x; min_y = y < min_y ? y : min_y;
-    max_x = x > max_x ? x : max_x; max_y = y > max_y ? y : max_y;
-  }
-};
-
 // transformScan's box: the axis-aligned box of the four transformed corners of the scan's own box
 void loose_box(const Rigid & t, const double bbox[4], Box * out)
 {
@@ -88,8 +72,6 @@ void loose_box(const Rigid & t, const double bbox[4], Box * out)
     out->add(x, y);
   }
 }
-
-double round_half_away(double v) {return v >= 0.0 ? std::floor(v + 0.5) : std::ceil(v - 0.5);}
 
 struct Submap
 {
@@ -138,11 +120,11 @@ int add_submap(kh_merge * g, kh_mapper * m, bool owned, int32_t * submap_id)
   if (!views.empty()) {
     Box box;
     for (const ScanView & v : views) {box.add(v.bbox[0], v.bbox[1]); box.add(v.bbox[2], v.bbox[3]);}
-    const double scale = 1.0 / g->resolution;
-    const int32_t width = static_cast<int32_t>(round_half_away((box.max_x - box.min_x) * scale));
-    const int32_t height = static_cast<int32_t>(round_half_away((box.max_y - box.min_y) * scale));
-    s.location[0] = box.min_x + static_cast<double>(width) * g->resolution / 2.0;
-    s.location[1] = box.min_y + static_cast<double>(height) * g->resolution / 2.0;
+    int32_t width, height;
+    double offset[2];
+    grid_dimensions(box, g->resolution, &width, &height, offset);
+    s.location[0] = offset[0] + static_cast<double>(width) * g->resolution / 2.0;
+    s.location[1] = offset[1] + static_cast<double>(height) * g->resolution / 2.0;
   }
   g->submaps.push_back(s);
   if (submap_id) {*submap_id = s.id;}
@@ -318,39 +300,42 @@ int kh_merge_build(kh_merge * g, uint32_t min_pass_through, double occupancy_thr
   }
   if (n_scans == 0) {kh::set_error("kh_merge_build: no scan in any submap"); return KH_ERR_INVALID_ARG;}
   if (n_scans > INT32_MAX) {kh::set_error("kh_merge_build: too many scans"); return KH_ERR_INVALID_ARG;}
-  const double scale = 1.0 / g->resolution;
-  const int32_t width = static_cast<int32_t>(round_half_away((box.max_x - box.min_x) * scale));
-  const int32_t height = static_cast<int32_t>(round_half_away((box.max_y - box.min_y) * scale));
+  int32_t width, height;
+  double offset[2];
+  kh::grid_dimensions(box, g->resolution, &width, &height, offset);
   kh_occupancy * grid = nullptr;
-  int rc = kh_occupancy_create(width, height, box.min_x, box.min_y, g->resolution, g->device, &grid);
+  int rc = kh_occupancy_create(width, height, offset[0], offset[1], g->resolution, g->device, &grid);
   if (rc) {return rc;}
   void * stream = kh::occupancy_stream(grid);
   auto fail = [&](int code) {kh::stream_synchronize(stream); kh_occupancy_destroy(grid); return code;};
-  std::vector<uint64_t> scan_table, submap_table, resident;
-  scan_table.reserve(5 * static_cast<size_t>(n_scans));
+  std::vector<MergeScan> scan_table;
+  std::vector<MergeSubmap> submap_table;
+  std::vector<ResidentScan> resident;
+  scan_table.reserve(static_cast<size_t>(n_scans));
   int64_t up_points = 0, up_ranges = 0;
   for (size_t k = 0; k < g->submaps.size(); ++k) {
     const Submap & s = g->submaps[k];
     const Rigid & t = s.correction;
-    const double fields[7] = {t.c, t.s, t.x, t.y, s.laser.range_threshold, s.laser.minimum_range, s.laser.maximum_range};
-    uint64_t rec[8];
-    std::memcpy(rec, fields, sizeof(fields));
-    rec[7] = static_cast<uint64_t>(static_cast<uint32_t>(s.laser.n_beams));
-    submap_table.insert(submap_table.end(), rec, rec + 8);
+    MergeSubmap rec = {};                          // (value-initialised: the pad words are uploaded too)
+    rec.c = t.c; rec.s = t.s; rec.tx = t.x; rec.ty = t.y;
+    rec.range_threshold = s.laser.range_threshold; rec.min_range = s.laser.minimum_range; rec.max_range = s.laser.maximum_range;
+    rec.n_beams = s.laser.n_beams;
+    submap_table.push_back(rec);
     // the residency loop kh_mapper_build_map runs: the correction is no reason to upload
     int64_t up_p = 0, up_r = 0;
     rc = kh::mapper_resident_table(s.mapper, stream, "kh_merge_build", resident, &up_p, &up_r);
     if (rc) {return fail(rc);}
     up_points += up_p; up_ranges += up_r;
-    if (resident.size() != 4 * views[k].size()) {kh::set_error("kh_merge_build: a submap changed during the merge"); return fail(KH_ERR_INVALID_ARG);}
+    if (resident.size() != views[k].size()) {kh::set_error("kh_merge_build: a submap changed during the merge"); return fail(KH_ERR_INVALID_ARG);}
     for (size_t i = 0; i < views[k].size(); ++i) {
       // GetSensorPose() of the transformed scan = GetSensorAt(transformed corrected pose), Karto.h:5566-5569
       double corrected[3], sensor[3];
       t.pose(views[k][i].corrected, corrected);
       kh::laser_sensor_at(s.laser, corrected, sensor);
-      uint64_t scan[5] = {resident[4 * i], resident[4 * i + 1], 0, 0, static_cast<uint64_t>(k)};
-      std::memcpy(&scan[2], &sensor[0], 8); std::memcpy(&scan[3], &sensor[1], 8);
-      scan_table.insert(scan_table.end(), scan, scan + 5);
+      MergeScan scan = {};
+      scan.points = resident[i].points; scan.ranges = resident[i].ranges;
+      scan.sx = sensor[0]; scan.sy = sensor[1]; scan.submap = static_cast<int32_t>(k);
+      scan_table.push_back(scan);
     }
   }
   rc = kh::occupancy_add_merged(grid, static_cast<int32_t>(n_scans), scan_table.data(), static_cast<int32_t>(g->submaps.size()), submap_table.data(),
@@ -359,7 +344,7 @@ int kh_merge_build(kh_merge * g, uint32_t min_pass_through, double occupancy_thr
   if (rc) {return fail(rc);}
   g->stats[0] += 1; g->stats[1] = n_scans; g->stats[2] = n_beams; g->stats[3] = up_points; g->stats[4] = up_ranges;
   g->stats[5] += up_points; g->stats[6] += up_ranges;
-  g->stats[7] = static_cast<int64_t>(8 * (scan_table.size() + submap_table.size()));
+  g->stats[7] = static_cast<int64_t>(scan_table.size() * sizeof(MergeScan) + submap_table.size() * sizeof(MergeSubmap));
   *out = grid;
   return KH_OK;
 }

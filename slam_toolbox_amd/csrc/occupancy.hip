@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "../../include/karto_hip.h"
-#include "live_map_device.hpp"
+#include "occupancy_device.hpp"
 
 namespace kh
 {
@@ -39,26 +39,64 @@ struct OccDev
   uint8_t * cells;
 };
 
-// beams: [n_beams] of (range, point x, point y, sensor x, sensor y) packed as 5 doubles
-__global__ __launch_bounds__(256) void k_occ_trace(
-  OccDev g, const double * __restrict__ beams, int64_t n_beams, double range_threshold, double min_range, double max_range)
+// ---- the one statement of AddScan / RayTrace / TraceLine every trace kernel below uses ----
+// what AddScan (Karto.h:6148-6189) decides about one beam: whether it is traced at all, whether its end point counts as a hit, and
+// the end point, clipped to the range threshold where the reading lies beyond it
+struct Beam
 {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_beams) {return;}
-  const double r = beams[5 * i];
-  double px = beams[5 * i + 1], py = beams[5 * i + 2];
-  const double sx = beams[5 * i + 3], sy = beams[5 * i + 4];
+  double px, py;
+  bool kept, hit;
+};
+__device__ __forceinline__ Beam occ_gate(double r, double px, double py, double sx, double sy, double range_threshold, double min_range,
+  double max_range)
+{
   const bool valid_end = r < (range_threshold - 1e-06);                  // Karto.h:6167
-  if (r <= min_range || r >= max_range || r != r) {return;}             // Karto.h:6169-6172
+  if (r <= min_range || r >= max_range || r != r) {return Beam{0.0, 0.0, false, false};}      // Karto.h:6169-6172
   if (r >= range_threshold) {                                           // Karto.h:6173-6180
     const double ratio = range_threshold / r;
     const double dx = px - sx, dy = py - sy;
     px = sx + ratio * dx; py = sy + ratio * dy;
   }
-  int32_t x0 = o_to_int(o_round((sx - g.off_x) * g.scale)), y0 = o_to_int(o_round((sy - g.off_y) * g.scale));
-  int32_t x1 = o_to_int(o_round((px - g.off_x) * g.scale)), y1 = o_to_int(o_round((py - g.off_y) * g.scale));
+  return Beam{px, py, true, valid_end};
+}
+
+// CoordinateConverter::WorldToGrid (Karto.h:4421-4436, called at Karto.h:6208-6209) of one coordinate: origin = the grid's offset, or a
+// live map's anchor
+__device__ __forceinline__ int32_t occ_cell(double v, double origin, double scale) {return o_to_int(o_round((v - origin) * scale));}
+
+// Where the cells of a walk live.  add() counts one visit of cell (cx, cy) -- and one hit, at a hit end -- if the cell exists.
+struct GridCells                 // a whole grid: cell (0, 0) is the first, a visit adds 1
+{
+  const OccDev & g;
+  __device__ __forceinline__ void add(int32_t cx, int32_t cy, bool hit) const
+  {
+    if (cx >= 0 && cx < g.width && cy >= 0 && cy < g.height) {
+      atomicAdd(&g.pass[cx + (int64_t)cy * g.ws], 1u);
+      if (hit) {atomicAdd(&g.hits[cx + (int64_t)cy * g.ws], 1u);}
+    }
+  }
+};
+struct WindowCells               // a live map's window of the lattice: cell (ox, oy) is the first, a visit adds delta (1, or 0xFFFFFFFF = -1)
+{
+  const LiveWindow & g;
+  uint32_t delta;
+  // 64-bit: a logged cell is any int32, the window's origin too.  The window holds every cell of every beam (coverage rule); the
+  // bounds test is a guard.
+  __device__ __forceinline__ void add(int32_t cx, int32_t cy, bool hit) const
+  {
+    const int64_t wx = (int64_t)cx - g.ox, wy = (int64_t)cy - g.oy;
+    if (wx >= 0 && wx < g.width && wy >= 0 && wy < g.height) {
+      atomicAdd(&g.pass[wx + wy * g.ws], delta);
+      if (hit) {atomicAdd(&g.hits[wx + wy * g.ws], delta);}
+    }
+  }
+};
+
+// Grid<kt_int32u>::TraceLine (Karto.h:4874-4927) from cell (x0, y0) to cell (x1, y1), then the end point (Karto.h:6213-6229)
+template <typename Cells>
+__device__ __forceinline__ void occ_walk(const Cells & cells, int32_t x0, int32_t y0, int32_t x1, int32_t y1, bool hit)
+{
   const int32_t tx = x1, ty = y1;
-  // Grid<kt_int32u>::TraceLine, Karto.h:4874-4927
   const bool steep = abs(y1 - y0) > abs(x1 - x0);
   int32_t t;
   if (steep) {t = x0; x0 = y0; y0 = t; t = x1; x1 = y1; y1 = t;}
@@ -70,25 +108,37 @@ __global__ __launch_bounds__(256) void k_occ_trace(
     const int32_t cx = steep ? y : x, cy = steep ? x : y;
     error += deltaY;
     if (2 * error >= deltaX) {y += ystep; error -= deltaX;}
-    if (cx >= 0 && cx < g.width && cy >= 0 && cy < g.height) {atomicAdd(&g.pass[cx + (int64_t)cy * g.ws], 1u);}
+    cells.add(cx, cy, false);
   }
-  if (valid_end && tx >= 0 && tx < g.width && ty >= 0 && ty < g.height) {    // Karto.h:6213-6229
-    atomicAdd(&g.pass[tx + (int64_t)ty * g.ws], 1u);
-    atomicAdd(&g.hits[tx + (int64_t)ty * g.ws], 1u);
-  }
+  if (hit) {cells.add(tx, ty, true);}
 }
 
-// The same trace fed from a mapper's RESIDENT scans (kh_mapper_build_map): one record per scan instead of 40 bytes per beam.
-struct ResidentScan
+// AddScan + RayTrace of one beam into a whole grid: what the three kernels below do once a thread has found its beam and its gates
+// (the inputs by reference: a kernel that passes fields of a record it fetched leaves the fetch of the fields a dropped beam never
+// needs behind the drop test, as when the statements stood in the kernel itself)
+__device__ __forceinline__ void occ_trace_beam(const OccDev & g, const double & r, double px, double py, const double & sx, const double & sy,
+  const double & range_threshold, const double & min_range, const double & max_range)
 {
-  const double * points;     // 2 * n_beams unfiltered point readings, device memory
-  const double * ranges;     // n_beams range readings, device memory
-  double sx, sy;             // sensor position
-};
+  const Beam b = occ_gate(r, px, py, sx, sy, range_threshold, min_range, max_range);
+  if (!b.kept) {return;}
+  const int32_t x0 = occ_cell(sx, g.off_x, g.scale), y0 = occ_cell(sy, g.off_y, g.scale);
+  const int32_t x1 = occ_cell(b.px, g.off_x, g.scale), y1 = occ_cell(b.py, g.off_y, g.scale);
+  occ_walk(GridCells{g}, x0, y0, x1, y1, b.hit);
+}
 
+// beams: [n_beams] of (range, point x, point y, sensor x, sensor y) packed as 5 doubles
+__global__ __launch_bounds__(256) void k_occ_trace(
+  OccDev g, const double * __restrict__ beams, int64_t n_beams, double range_threshold, double min_range, double max_range)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_beams) {return;}
+  occ_trace_beam(g, beams[5 * i], beams[5 * i + 1], beams[5 * i + 2], beams[5 * i + 3], beams[5 * i + 4], range_threshold, min_range, max_range);
+}
+
+// The same trace fed from a mapper's RESIDENT scans (kh_mapper_build_map): one ResidentScan per scan instead of 40 bytes per beam.
 // One wave per run of 64 neighbouring beams of ONE scan (a workgroup = 4 such runs): the beams of a wave leave the same cell and
 // fan out over neighbouring ones, so its atomics land in neighbouring L2 lines, and neighbouring beams have similar lengths, which
-// bounds the divergence of the walk.  Clip, roundings and walk are k_occ_trace's, operation for operation.
+// bounds the divergence of the walk.
 __global__ __launch_bounds__(256) void k_occ_trace_resident(
   OccDev g, const ResidentScan * __restrict__ scans, int32_t n_scans, int32_t n_beams, int32_t runs_per_scan, double range_threshold,
   double min_range, double max_range)
@@ -100,59 +150,15 @@ __global__ __launch_bounds__(256) void k_occ_trace_resident(
   const int32_t i = (int32_t)(wave - s * runs_per_scan) * 64 + lane;
   if (i >= n_beams) {return;}
   const ResidentScan sc = scans[s];
-  const double r = sc.ranges[i];
-  double px = sc.points[2 * i], py = sc.points[2 * i + 1];
-  const double sx = sc.sx, sy = sc.sy;
-  const bool valid_end = r < (range_threshold - 1e-06);                  // Karto.h:6167
-  if (r <= min_range || r >= max_range || r != r) {return;}             // Karto.h:6169-6172
-  if (r >= range_threshold) {                                           // Karto.h:6173-6180
-    const double ratio = range_threshold / r;
-    const double dx = px - sx, dy = py - sy;
-    px = sx + ratio * dx; py = sy + ratio * dy;
-  }
-  int32_t x0 = o_to_int(o_round((sx - g.off_x) * g.scale)), y0 = o_to_int(o_round((sy - g.off_y) * g.scale));
-  int32_t x1 = o_to_int(o_round((px - g.off_x) * g.scale)), y1 = o_to_int(o_round((py - g.off_y) * g.scale));
-  const int32_t tx = x1, ty = y1;
-  const bool steep = abs(y1 - y0) > abs(x1 - x0);                       // Grid<kt_int32u>::TraceLine, Karto.h:4874-4927
-  int32_t t;
-  if (steep) {t = x0; x0 = y0; y0 = t; t = x1; x1 = y1; y1 = t;}
-  if (x0 > x1) {t = x0; x0 = x1; x1 = t; t = y0; y0 = y1; y1 = t;}
-  const int32_t deltaX = x1 - x0, deltaY = abs(y1 - y0);
-  int32_t error = 0, y = y0;
-  const int32_t ystep = y0 < y1 ? 1 : -1;
-  for (int32_t x = x0; x <= x1; x++) {
-    const int32_t cx = steep ? y : x, cy = steep ? x : y;
-    error += deltaY;
-    if (2 * error >= deltaX) {y += ystep; error -= deltaX;}
-    if (cx >= 0 && cx < g.width && cy >= 0 && cy < g.height) {atomicAdd(&g.pass[cx + (int64_t)cy * g.ws], 1u);}
-  }
-  if (valid_end && tx >= 0 && tx < g.width && ty >= 0 && ty < g.height) {    // Karto.h:6213-6229
-    atomicAdd(&g.pass[tx + (int64_t)ty * g.ws], 1u);
-    atomicAdd(&g.hits[tx + (int64_t)ty * g.ws], 1u);
-  }
+  occ_trace_beam(g, sc.ranges[i], sc.points[2 * i], sc.points[2 * i + 1], sc.sx, sc.sy, range_threshold, min_range, max_range);
 }
 
 // The trace of a MERGE of mapping sessions (kh_merge_build): the scans of several mappers, each mapper (submap) placed by a rigid
 // correction.  The resident readings stay as their mapper made them; the submap's correction is applied to the point in registers
 // -- x' = (c x - s y) + tx, y' = (s x + c y) + ty, no contraction -- and nothing transformed is written back.  The sensor position
 // arrives transformed (the host does GetSensorAt of the transformed corrected pose, once per scan).
-struct MergeScan
-{
-  const double * points;     // 2 * n_beams UNtransformed unfiltered point readings, device memory
-  const double * ranges;     // n_beams range readings, device memory
-  double sx, sy;             // transformed sensor position
-  int32_t submap, pad;
-};
-struct MergeSubmap
-{
-  double c, s, tx, ty;       // the correction: cos / sin of its yaw (host libm), translation
-  double range_threshold, min_range, max_range;      // the submap's laser
-  int32_t n_beams, pad;
-};
-
 // The same work layout as k_occ_trace_resident.  Submaps may have different lasers: the grid is dealt max_runs waves per scan
-// (the longest laser's), a wave beyond its scan's own beam count leaves at once.  Clip, roundings and walk are k_occ_trace's,
-// operation for operation.
+// (the longest laser's), a wave beyond its scan's own beam count leaves at once.
 __global__ __launch_bounds__(256) void k_occ_trace_merged(
   OccDev g, const MergeScan * __restrict__ scans, const MergeSubmap * __restrict__ submaps, int32_t n_scans, int32_t max_runs)
 {
@@ -164,38 +170,9 @@ __global__ __launch_bounds__(256) void k_occ_trace_merged(
   const MergeSubmap sm = submaps[sc.submap];
   const int32_t i = (int32_t)(wave - s * max_runs) * 64 + lane;
   if (i >= sm.n_beams) {return;}
-  const double r = sc.ranges[i];
   const double ux = sc.points[2 * i], uy = sc.points[2 * i + 1];
-  double px = (sm.c * ux - sm.s * uy) + sm.tx, py = (sm.s * ux + sm.c * uy) + sm.ty;
-  const double sx = sc.sx, sy = sc.sy;
-  const double range_threshold = sm.range_threshold;
-  const bool valid_end = r < (range_threshold - 1e-06);                  // Karto.h:6167
-  if (r <= sm.min_range || r >= sm.max_range || r != r) {return;}       // Karto.h:6169-6172
-  if (r >= range_threshold) {                                           // Karto.h:6173-6180
-    const double ratio = range_threshold / r;
-    const double dx = px - sx, dy = py - sy;
-    px = sx + ratio * dx; py = sy + ratio * dy;
-  }
-  int32_t x0 = o_to_int(o_round((sx - g.off_x) * g.scale)), y0 = o_to_int(o_round((sy - g.off_y) * g.scale));
-  int32_t x1 = o_to_int(o_round((px - g.off_x) * g.scale)), y1 = o_to_int(o_round((py - g.off_y) * g.scale));
-  const int32_t tx = x1, ty = y1;
-  const bool steep = abs(y1 - y0) > abs(x1 - x0);                       // Grid<kt_int32u>::TraceLine, Karto.h:4874-4927
-  int32_t t;
-  if (steep) {t = x0; x0 = y0; y0 = t; t = x1; x1 = y1; y1 = t;}
-  if (x0 > x1) {t = x0; x0 = x1; x1 = t; t = y0; y0 = y1; y1 = t;}
-  const int32_t deltaX = x1 - x0, deltaY = abs(y1 - y0);
-  int32_t error = 0, y = y0;
-  const int32_t ystep = y0 < y1 ? 1 : -1;
-  for (int32_t x = x0; x <= x1; x++) {
-    const int32_t cx = steep ? y : x, cy = steep ? x : y;
-    error += deltaY;
-    if (2 * error >= deltaX) {y += ystep; error -= deltaX;}
-    if (cx >= 0 && cx < g.width && cy >= 0 && cy < g.height) {atomicAdd(&g.pass[cx + (int64_t)cy * g.ws], 1u);}
-  }
-  if (valid_end && tx >= 0 && tx < g.width && ty >= 0 && ty < g.height) {    // Karto.h:6213-6229
-    atomicAdd(&g.pass[tx + (int64_t)ty * g.ws], 1u);
-    atomicAdd(&g.hits[tx + (int64_t)ty * g.ws], 1u);
-  }
+  const double px = (sm.c * ux - sm.s * uy) + sm.tx, py = (sm.s * ux + sm.c * uy) + sm.ty;
+  occ_trace_beam(g, sc.ranges[i], px, py, sc.sx, sc.sy, sm.range_threshold, sm.min_range, sm.max_range);
 }
 
 // UpdateCell (Karto.h:6240-6256) for the cell at index k of the three arrays
@@ -229,61 +206,8 @@ __global__ __launch_bounds__(256) void k_occ_update_rect(LiveWindow g, int32_t x
 }
 
 // ---- the live map's trace (kh_live_map_update) ----
-// what AddScan (Karto.h:6148-6189) decides about one beam, on the live map's fixed lattice: k_occ_trace's gate, clip and roundings,
-// operation for operation, with the anchor in the place of the grid offset
-struct BeamTrace
-{
-  int32_t ex, ey;            // end cell
-  bool kept, hit;            // traced at all / the end point counts as a hit
-};
-__device__ __forceinline__ BeamTrace live_beam(const DeltaRecord & rec, int32_t i, double ax, double ay, double scale, double range_threshold,
-  double min_range, double max_range)
-{
-  BeamTrace b;
-  b.ex = 0; b.ey = 0; b.kept = false; b.hit = false;
-  const double r = rec.ranges[i];
-  double px = rec.points[2 * i], py = rec.points[2 * i + 1];
-  const double sx = rec.sx, sy = rec.sy;
-  const bool valid_end = r < (range_threshold - 1e-06);                  // Karto.h:6167
-  if (r <= min_range || r >= max_range || r != r) {return b;}           // Karto.h:6169-6172
-  if (r >= range_threshold) {                                           // Karto.h:6173-6180
-    const double ratio = range_threshold / r;
-    const double dx = px - sx, dy = py - sy;
-    px = sx + ratio * dx; py = sy + ratio * dy;
-  }
-  b.ex = o_to_int(o_round((px - ax) * scale)); b.ey = o_to_int(o_round((py - ay) * scale));
-  b.kept = true; b.hit = valid_end;
-  return b;
-}
-
-// Grid<kt_int32u>::TraceLine (Karto.h:4874-4927) + the end point (Karto.h:6213-6229) in lattice cells, adding `delta` (1, or
-// 0xFFFFFFFF = -1) to the counters.  The window holds every cell of every beam (coverage rule); the bounds test is a guard.
-__device__ __forceinline__ void live_walk(const LiveWindow & g, int32_t x0, int32_t y0, int32_t x1, int32_t y1, bool hit, uint32_t delta)
-{
-  const int32_t tx = x1, ty = y1;
-  const bool steep = abs(y1 - y0) > abs(x1 - x0);
-  int32_t t;
-  if (steep) {t = x0; x0 = y0; y0 = t; t = x1; x1 = y1; y1 = t;}
-  if (x0 > x1) {t = x0; x0 = x1; x1 = t; t = y0; y0 = y1; y1 = t;}
-  const int32_t deltaX = x1 - x0, deltaY = abs(y1 - y0);
-  int32_t error = 0, y = y0;
-  const int32_t ystep = y0 < y1 ? 1 : -1;
-  for (int32_t x = x0; x <= x1; x++) {
-    const int32_t cx = steep ? y : x, cy = steep ? x : y;
-    error += deltaY;
-    if (2 * error >= deltaX) {y += ystep; error -= deltaX;}
-    const int64_t wx = (int64_t)cx - g.ox, wy = (int64_t)cy - g.oy;
-    if (wx >= 0 && wx < g.width && wy >= 0 && wy < g.height) {atomicAdd(&g.pass[wx + wy * g.ws], delta);}
-  }
-  const int64_t wx = (int64_t)tx - g.ox, wy = (int64_t)ty - g.oy;
-  if (hit && wx >= 0 && wx < g.width && wy >= 0 && wy < g.height) {
-    atomicAdd(&g.pass[wx + wy * g.ws], delta);
-    atomicAdd(&g.hits[wx + wy * g.ws], delta);
-  }
-}
-
 // The work layout of k_occ_trace_resident -- one wave per run of 64 neighbouring beams of one scan -- over a table of ADD / SUB /
-// MOVE records (live_map_device.hpp).  ADD traces from the resident readings and writes the scan's slot of the log; SUB walks the
+// MOVE records (occupancy_device.hpp).  ADD traces from the resident readings and writes the scan's slot of the log; SUB walks the
 // logged lines with -1 and reads nothing else; MOVE compares the beam's new trace record with the logged one and walks (old line
 // -1, new line +1) only where something differs.  One scan is one record, so no two waves touch the same log words: a beam's two
 // words belong to its lane, and the slot's sensor cell is written by beam 0's lane and read by SUB records only (MOVE gets the old
@@ -308,15 +232,15 @@ __global__ __launch_bounds__(256) void k_occ_trace_delta(
   if (rec.kind != kDeltaAdd) {was = *entry;}
   if (rec.kind == kDeltaSub) {ocx = slot[0]; ocy = slot[1];}
   if (rec.kind != kDeltaSub) {
-    ncx = o_to_int(o_round((rec.sx - ax) * scale)); ncy = o_to_int(o_round((rec.sy - ay) * scale));
-    const BeamTrace b = live_beam(rec, i, ax, ay, scale, range_threshold, min_range, max_range);
-    if (b.kept) {now = make_int2(b.ex, (int32_t)(((uint32_t)(b.ey - ncy) << 2) | (b.hit ? 3u : 1u)));}
+    const Beam b = occ_gate(rec.ranges[i], rec.points[2 * i], rec.points[2 * i + 1], rec.sx, rec.sy, range_threshold, min_range, max_range);
+    ncx = occ_cell(rec.sx, ax, scale); ncy = occ_cell(rec.sy, ay, scale);
+    if (b.kept) {now = make_int2(occ_cell(b.px, ax, scale), (int32_t)(((uint32_t)(occ_cell(b.py, ay, scale) - ncy) << 2) | (b.hit ? 3u : 1u)));}
   }
   const bool same = rec.kind == kDeltaMove && was.x == now.x && was.y == now.y && ocx == ncx && ocy == ncy;
   const bool walk_old = rec.kind != kDeltaAdd && !same && (was.y & 1);
   const bool walk_new = rec.kind != kDeltaSub && !same && (now.y & 1);
-  if (walk_old) {live_walk(g, ocx, ocy, was.x, ocy + (was.y >> 2), (was.y & 2) != 0, 0xFFFFFFFFu);}
-  if (walk_new) {live_walk(g, ncx, ncy, now.x, ncy + (now.y >> 2), (now.y & 2) != 0, 1u);}
+  if (walk_old) {occ_walk(WindowCells{g, 0xFFFFFFFFu}, ocx, ocy, was.x, ocy + (was.y >> 2), (was.y & 2) != 0);}
+  if (walk_new) {occ_walk(WindowCells{g, 1u}, ncx, ncy, now.x, ncy + (now.y >> 2), (now.y & 2) != 0);}
   if (rec.kind != kDeltaSub) {
     if (!same) {*entry = now;}
     if (i == 0) {slot[0] = ncx; slot[1] = ncy;}
@@ -339,83 +263,87 @@ struct kh_occupancy
   int32_t device = 0;
   hipStream_t stream = nullptr;
   OccDev dev;
-  double * d_beams = nullptr; size_t cap_beams = 0;
-  double * h_beams = nullptr; size_t cap_hbeams = 0;
+  double * d_beams = nullptr; size_t cap_beams = 0;           // kh_occupancy_add_scans' staging: device (capacity in bytes) ...
+  double * h_beams = nullptr; size_t cap_hbeams = 0;          // ... and pinned host memory (capacity in doubles)
   hipEvent_t ev[2] = {nullptr, nullptr};
   double trace_ms = 0.0; int64_t beams_traced = 0;
-  ResidentScan * d_scans = nullptr; size_t cap_scans = 0;     // kh::occupancy_add_resident's table
-  uint8_t * d_merge = nullptr; size_t cap_merge = 0;          // kh::occupancy_add_merged's two tables (submaps, then scans)
+  ResidentScan * d_scans = nullptr; size_t cap_scans = 0;     // kh::occupancy_add_resident's table (capacity in bytes)
+  uint8_t * d_merge = nullptr; size_t cap_merge = 0;          // kh::occupancy_add_merged's two tables (submaps, then scans; bytes)
 };
 
 namespace kh
 {
-// the stream the grid's kernels run on: uploads a caller queues there are in place before the next trace reads them
-void * occupancy_stream(kh_occupancy * g) {return g ? g->stream : nullptr;}
-
-// AddScan for n_scans scans whose readings are resident on the grid's device: table[4 * s] = address of the 2 * n_beams point
-// readings, [4 * s + 1] = address of the n_beams ranges, [4 * s + 2], [4 * s + 3] = sensor x, y as the bits of a double.
-// Returns after the trace (and everything queued on the stream before it) has finished.
-int occupancy_add_resident(kh_occupancy * g, int32_t n_scans, const uint64_t * table, int32_t n_beams, double range_threshold,
-  double min_range, double max_range)
+namespace
 {
-  static_assert(sizeof(ResidentScan) == 32, "one record = 4 x 8 bytes");
-  if (!g || n_scans < 0 || n_beams < 0 || (n_scans > 0 && !table)) {return KH_ERR_INVALID_ARG;}
-  if (hipSetDevice(g->device) != hipSuccess) {return KH_ERR_HIP;}
-  if (n_scans == 0 || n_beams == 0) {return hipStreamSynchronize(g->stream) == hipSuccess ? KH_OK : KH_ERR_HIP;}
-  if (static_cast<size_t>(n_scans) > g->cap_scans) {
-    (void)hipStreamSynchronize(g->stream);
-    if (g->d_scans) {(void)hipFree(g->d_scans); g->d_scans = nullptr;}
-    g->cap_scans = 0;
-    const size_t cap = static_cast<size_t>(n_scans) + static_cast<size_t>(n_scans) / 2;
-    if (hipMalloc(reinterpret_cast<void **>(&g->d_scans), cap * sizeof(ResidentScan)) != hipSuccess) {
-      (void)hipGetLastError();
-      set_error("kh_mapper_build_map: scan table allocation failed");
-      return KH_ERR_HIP;
-    }
-    g->cap_scans = cap;
-  }
-  if (hipMemcpyAsync(g->d_scans, table, static_cast<size_t>(n_scans) * sizeof(ResidentScan), hipMemcpyHostToDevice, g->stream) != hipSuccess) {
-    (void)hipStreamSynchronize(g->stream);
-    return KH_ERR_HIP;
-  }
-  const int32_t runs = (n_beams + 63) / 64;
-  const int64_t waves = static_cast<int64_t>(n_scans) * runs;
+// makes *buf a device buffer of at least `need` bytes: one that is too small is replaced by one of `cap` bytes (what it held is
+// not kept).  false = the allocation failed, and the buffer is gone.
+bool grow_device(kh_occupancy * g, void ** buf, size_t * have, size_t need, size_t cap)
+{
+  if (need <= *have) {return true;}
+  (void)hipStreamSynchronize(g->stream);
+  if (*buf) {(void)hipFree(*buf); *buf = nullptr;}
+  *have = 0;
+  if (hipMalloc(buf, cap) != hipSuccess) {(void)hipGetLastError(); return false;}
+  *have = cap;
+  return true;
+}
+
+// one wave per run of 64 beams, four waves per workgroup
+dim3 blocks_of_runs(int32_t n_scans, int32_t runs_per_scan) {return dim3(static_cast<unsigned>((static_cast<int64_t>(n_scans) * runs_per_scan + 3) / 4));}
+
+// What every AddScan route ends with: the trace kernel between two events, the wait for it, a failure reported under the caller's
+// (`who`) name, the grid's trace time and beam counter.
+template <typename Launch>
+int timed_trace(kh_occupancy * g, const char * who, int64_t n_beams, Launch launch)
+{
   (void)hipEventRecord(g->ev[0], g->stream);
-  hipLaunchKernelGGL(k_occ_trace_resident, dim3(static_cast<unsigned>((waves + 3) / 4)), dim3(256), 0, g->stream, g->dev, g->d_scans, n_scans,
-    n_beams, runs, range_threshold, min_range, max_range);
+  launch();
   (void)hipEventRecord(g->ev[1], g->stream);
   if (hipStreamSynchronize(g->stream) != hipSuccess) {
-    set_error(std::string("kh_mapper_build_map: ") + hipGetErrorString(hipGetLastError()));
+    set_error(std::string(who) + ": " + hipGetErrorString(hipGetLastError()));
     return KH_ERR_HIP;
   }
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, g->ev[0], g->ev[1]);
-  g->trace_ms += ms; g->beams_traced += static_cast<int64_t>(n_scans) * n_beams;
+  g->trace_ms += ms; g->beams_traced += n_beams;
   return KH_OK;
 }
+}  // namespace
 
-// AddScan for the scans of a merge (k_occ_trace_merged).  scans: 5 words per scan -- address of the point readings, address of the
-// ranges, TRANSFORMED sensor x, y as the bits of a double, submap index (low 32 bits); submaps: 8 words per submap -- c, s, tx, ty,
-// range threshold, minimum range, maximum range as the bits of a double, beam count (low 32 bits).  max_beams = the largest beam
-// count, n_total_beams = the sum over the scans (the grid's beam counter).  Returns after the trace has finished.
-int occupancy_add_merged(kh_occupancy * g, int32_t n_scans, const uint64_t * scans, int32_t n_submaps, const uint64_t * submaps,
+void * occupancy_stream(kh_occupancy * g) {return g ? g->stream : nullptr;}
+
+int occupancy_add_resident(kh_occupancy * g, int32_t n_scans, const ResidentScan * scans, int32_t n_beams, double range_threshold,
+  double min_range, double max_range)
+{
+  if (!g || n_scans < 0 || n_beams < 0 || (n_scans > 0 && !scans)) {return KH_ERR_INVALID_ARG;}
+  if (hipSetDevice(g->device) != hipSuccess) {return KH_ERR_HIP;}
+  if (n_scans == 0 || n_beams == 0) {return hipStreamSynchronize(g->stream) == hipSuccess ? KH_OK : KH_ERR_HIP;}
+  const size_t bytes = static_cast<size_t>(n_scans) * sizeof(ResidentScan);
+  if (!grow_device(g, reinterpret_cast<void **>(&g->d_scans), &g->cap_scans, bytes, bytes + bytes / 2)) {
+    set_error("kh_mapper_build_map: scan table allocation failed");
+    return KH_ERR_HIP;
+  }
+  if (hipMemcpyAsync(g->d_scans, scans, bytes, hipMemcpyHostToDevice, g->stream) != hipSuccess) {
+    (void)hipStreamSynchronize(g->stream);
+    return KH_ERR_HIP;
+  }
+  const int32_t runs = (n_beams + 63) / 64;
+  return timed_trace(g, "kh_mapper_build_map", static_cast<int64_t>(n_scans) * n_beams, [&] {
+    hipLaunchKernelGGL(k_occ_trace_resident, blocks_of_runs(n_scans, runs), dim3(256), 0, g->stream, g->dev, g->d_scans, n_scans, n_beams, runs,
+      range_threshold, min_range, max_range);
+  });
+}
+
+int occupancy_add_merged(kh_occupancy * g, int32_t n_scans, const MergeScan * scans, int32_t n_submaps, const MergeSubmap * submaps,
   int32_t max_beams, int64_t n_total_beams)
 {
-  static_assert(sizeof(MergeScan) == 40 && sizeof(MergeSubmap) == 64, "records = 5 and 8 words of 8 bytes");
   if (!g || n_scans < 0 || n_submaps < 0 || max_beams < 0 || (n_scans > 0 && (!scans || !submaps || n_submaps == 0))) {return KH_ERR_INVALID_ARG;}
   if (hipSetDevice(g->device) != hipSuccess) {return KH_ERR_HIP;}
   if (n_scans == 0 || max_beams == 0) {return hipStreamSynchronize(g->stream) == hipSuccess ? KH_OK : KH_ERR_HIP;}
   const size_t submap_bytes = static_cast<size_t>(n_submaps) * sizeof(MergeSubmap), scan_bytes = static_cast<size_t>(n_scans) * sizeof(MergeScan);
-  if (submap_bytes + scan_bytes > g->cap_merge) {
-    (void)hipStreamSynchronize(g->stream);
-    if (g->d_merge) {(void)hipFree(g->d_merge); g->d_merge = nullptr;}
-    g->cap_merge = 0;
-    if (hipMalloc(reinterpret_cast<void **>(&g->d_merge), submap_bytes + scan_bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      set_error("kh_merge_build: table allocation failed");
-      return KH_ERR_HIP;
-    }
-    g->cap_merge = submap_bytes + scan_bytes;
+  if (!grow_device(g, reinterpret_cast<void **>(&g->d_merge), &g->cap_merge, submap_bytes + scan_bytes, submap_bytes + scan_bytes)) {
+    set_error("kh_merge_build: table allocation failed");
+    return KH_ERR_HIP;
   }
   const MergeSubmap * d_submaps = reinterpret_cast<const MergeSubmap *>(g->d_merge);
   const MergeScan * d_scans = reinterpret_cast<const MergeScan *>(g->d_merge + submap_bytes);      // (64 * n_submaps: 8-byte aligned)
@@ -426,18 +354,9 @@ int occupancy_add_merged(kh_occupancy * g, int32_t n_scans, const uint64_t * sca
     return KH_ERR_HIP;
   }
   const int32_t runs = (max_beams + 63) / 64;
-  const int64_t waves = static_cast<int64_t>(n_scans) * runs;
-  (void)hipEventRecord(g->ev[0], g->stream);
-  hipLaunchKernelGGL(k_occ_trace_merged, dim3(static_cast<unsigned>((waves + 3) / 4)), dim3(256), 0, g->stream, g->dev, d_scans, d_submaps, n_scans, runs);
-  (void)hipEventRecord(g->ev[1], g->stream);
-  if (hipStreamSynchronize(g->stream) != hipSuccess) {
-    set_error(std::string("kh_merge_build: ") + hipGetErrorString(hipGetLastError()));
-    return KH_ERR_HIP;
-  }
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, g->ev[0], g->ev[1]);
-  g->trace_ms += ms; g->beams_traced += n_total_beams;
-  return KH_OK;
+  return timed_trace(g, "kh_merge_build", n_total_beams, [&] {
+    hipLaunchKernelGGL(k_occ_trace_merged, blocks_of_runs(n_scans, runs), dim3(256), 0, g->stream, g->dev, d_scans, d_submaps, n_scans, runs);
+  });
 }
 
 void live_trace_delta(void * stream, const LiveWindow & w, double anchor_x, double anchor_y, double scale, const DeltaRecord * d_records,
@@ -446,9 +365,8 @@ void live_trace_delta(void * stream, const LiveWindow & w, double anchor_x, doub
 {
   if (n_records <= 0 || n_beams <= 0) {return;}
   const int32_t runs = (n_beams + 63) / 64;
-  const int64_t waves = static_cast<int64_t>(n_records) * runs;
-  hipLaunchKernelGGL(k_occ_trace_delta, dim3(static_cast<unsigned>((waves + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), w, anchor_x,
-    anchor_y, scale, d_records, n_records, n_beams, runs, range_threshold, min_range, max_range, d_log, live_log_slot_words(n_beams), d_counters);
+  hipLaunchKernelGGL(k_occ_trace_delta, blocks_of_runs(n_records, runs), dim3(256), 0, static_cast<hipStream_t>(stream), w, anchor_x, anchor_y,
+    scale, d_records, n_records, n_beams, runs, range_threshold, min_range, max_range, d_log, live_log_slot_words(n_beams), d_counters);
 }
 
 void live_update_cells(void * stream, const LiveWindow & w, int32_t x0, int32_t y0, int32_t rect_w, int32_t rect_h, uint32_t min_pass,
@@ -469,25 +387,16 @@ int kh_occupancy_compute_dimensions(
 {
   if (n_scans <= 0 || !scans || !width || !height || !offset || !(resolution > 0)) {return KH_ERR_INVALID_ARG;}
   // BoundingBox2 (Karto.h:2846-2903) over every scan's box = sensor position + in-range points (Karto.h:5694-5700)
-  double min_x = 999999999999999999.99999, min_y = 999999999999999999.99999;
-  double max_x = -999999999999999999.99999, max_y = -999999999999999999.99999;
-  auto add = [&](double x, double y) {
-    min_x = x < min_x ? x : min_x; min_y = y < min_y ? y : min_y;
-    max_x = x > max_x ? x : max_x; max_y = y > max_y ? y : max_y;
-  };
+  Box box;
   for (int32_t s = 0; s < n_scans; ++s) {
     if (scans[s].n < 0 || (scans[s].n > 0 && (!scans[s].ranges || !scans[s].points_xy))) {return KH_ERR_INVALID_ARG;}
-    add(scans[s].sensor_pose[0], scans[s].sensor_pose[1]);
+    box.add(scans[s].sensor_pose[0], scans[s].sensor_pose[1]);
     for (int32_t i = 0; i < scans[s].n; ++i) {
       const double r = scans[s].ranges[i];
-      if (r >= min_range && r <= range_threshold) {add(scans[s].points_xy[2 * i], scans[s].points_xy[2 * i + 1]);}   // math::InRange
+      if (r >= min_range && r <= range_threshold) {box.add(scans[s].points_xy[2 * i], scans[s].points_xy[2 * i + 1]);}   // math::InRange
     }
   }
-  const double scale = 1.0 / resolution;
-  auto round_half_away = [](double v) {return v >= 0.0 ? std::floor(v + 0.5) : std::ceil(v - 0.5);};
-  *width = static_cast<int32_t>(round_half_away((max_x - min_x) * scale));     // Karto.h:6106-6111
-  *height = static_cast<int32_t>(round_half_away((max_y - min_y) * scale));
-  offset[0] = min_x; offset[1] = min_y;
+  grid_dimensions(box, resolution, width, height, offset);
   return KH_OK;
 }
 
@@ -564,13 +473,12 @@ int kh_occupancy_add_scans(kh_occupancy * g, int32_t n_scans, const kh_scan * sc
   if (total == 0) {return KH_OK;}
   if (total * 5 > g->cap_hbeams) {
     if (g->h_beams) {(void)hipStreamSynchronize(g->stream); (void)hipHostFree(g->h_beams); g->h_beams = nullptr;}
-    if (g->d_beams) {(void)hipFree(g->d_beams); g->d_beams = nullptr;}
     const size_t cap = std::max(total * 5, g->cap_hbeams + g->cap_hbeams / 2);
+    g->cap_hbeams = 0; g->cap_beams = 0;                      // (the device buffer follows the host buffer's size)
     if (hipHostMalloc(reinterpret_cast<void **>(&g->h_beams), cap * 8, hipHostMallocDefault) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void **>(&g->d_beams), cap * 8) != hipSuccess)
+      !grow_device(g, reinterpret_cast<void **>(&g->d_beams), &g->cap_beams, cap * 8, cap * 8))
     {
       set_error("kh_occupancy_add_scans: staging allocation failed");
-      g->cap_hbeams = 0;
       return KH_ERR_HIP;
     }
     g->cap_hbeams = cap;
@@ -584,18 +492,10 @@ int kh_occupancy_add_scans(kh_occupancy * g, int32_t n_scans, const kh_scan * sc
     }
   }
   if (hipMemcpyAsync(g->d_beams, g->h_beams, total * 5 * 8, hipMemcpyHostToDevice, g->stream) != hipSuccess) {return KH_ERR_HIP;}
-  (void)hipEventRecord(g->ev[0], g->stream);
-  hipLaunchKernelGGL(k_occ_trace, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, g->stream, g->dev, g->d_beams,
-    static_cast<int64_t>(total), range_threshold, min_range, max_range);
-  (void)hipEventRecord(g->ev[1], g->stream);
-  if (hipStreamSynchronize(g->stream) != hipSuccess) {
-    set_error(std::string("kh_occupancy_add_scans: ") + hipGetErrorString(hipGetLastError()));
-    return KH_ERR_HIP;
-  }
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, g->ev[0], g->ev[1]);
-  g->trace_ms += ms; g->beams_traced += static_cast<int64_t>(total);
-  return KH_OK;
+  return timed_trace(g, "kh_occupancy_add_scans", static_cast<int64_t>(total), [&] {
+    hipLaunchKernelGGL(k_occ_trace, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, g->stream, g->dev, g->d_beams,
+      static_cast<int64_t>(total), range_threshold, min_range, max_range);
+  });
 }
 
 int kh_occupancy_update(kh_occupancy * g, uint32_t min_pass_through, double occupancy_threshold)

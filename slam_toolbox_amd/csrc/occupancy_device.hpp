@@ -1,0 +1,111 @@
+// What the occupancy module shares between occupancy.hip (the kernels and their launchers) and the host files that feed it:
+// mapper_host.cpp (kh_mapper_build_map), merge.cpp (kh_merge_build), live_map.cpp (kh_live_map_*).  Not part of the public ABI
+// (include/karto_hip.h).  The live map's lattice, window and log are stated in DESIGN.md section 7b.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/karto_hip.h"
+
+namespace kh
+{
+// ---- host arithmetic of ComputeDimensions ----
+inline double round_half_away(double v) {return v >= 0.0 ? std::floor(v + 0.5) : std::ceil(v - 0.5);}     // math::Round, Math.h:87-90
+
+// BoundingBox2 (Karto.h:2846-2903) as ComputeDimensions uses it
+struct Box
+{
+  double min_x = 999999999999999999.99999, min_y = 999999999999999999.99999;
+  double max_x = -999999999999999999.99999, max_y = -999999999999999999.99999;
+  void add(double x, double y)
+  {
+    min_x = x < min_x ? x : min_x; min_y = y < min_y ? y : min_y;
+    max_x = x > max_x ? x : max_x; max_y = y > max_y ? y : max_y;
+  }
+};
+
+// the box of the scans and the resolution -> the grid's width and height in cells (Karto.h:6106-6111); its offset is the box's minimum
+inline void grid_dimensions(const Box & box, double resolution, int32_t * width, int32_t * height, double offset[2])
+{
+  const double scale = 1.0 / resolution;
+  *width = static_cast<int32_t>(round_half_away((box.max_x - box.min_x) * scale));
+  *height = static_cast<int32_t>(round_half_away((box.max_y - box.min_y) * scale));
+  offset[0] = box.min_x; offset[1] = box.min_y;
+}
+
+// ---- the records of the trace kernels ----
+// one scan whose readings are resident on the grid's device (k_occ_trace_resident)
+struct ResidentScan
+{
+  const double * points;     // 2 * n_beams unfiltered point readings, device memory
+  const double * ranges;     // n_beams range readings, device memory
+  double sx, sy;             // sensor position
+};
+static_assert(sizeof(ResidentScan) == 32, "one record = 4 x 8 bytes");
+
+// one scan and one mapper (submap) of a merge (k_occ_trace_merged)
+struct MergeScan
+{
+  const double * points;     // 2 * n_beams UNtransformed unfiltered point readings, device memory
+  const double * ranges;     // n_beams range readings, device memory
+  double sx, sy;             // transformed sensor position
+  int32_t submap, pad;
+};
+struct MergeSubmap
+{
+  double c, s, tx, ty;       // the correction: cos / sin of its yaw (host libm), translation
+  double range_threshold, min_range, max_range;      // the submap's laser
+  int32_t n_beams, pad;
+};
+static_assert(sizeof(MergeScan) == 40 && sizeof(MergeSubmap) == 64, "records = 5 and 8 words of 8 bytes");
+
+// the grids of a live map: lattice cells [ox, ox + width) x [oy, oy + height), row stride ws = (width + 7) & ~7
+struct LiveWindow
+{
+  int32_t ox, oy, width, height, ws;
+  uint32_t * pass;
+  uint32_t * hits;
+  uint8_t * cells;
+};
+
+enum : int32_t {kDeltaAdd = 0, kDeltaSub = 1, kDeltaMove = 2};
+
+// one scan of a delta table (k_occ_trace_delta)
+struct DeltaRecord
+{
+  const double * points;     // ADD / MOVE: 2 * n_beams unfiltered point readings, device memory (the mapper's resident copy)
+  const double * ranges;     // ADD / MOVE: n_beams range readings, device memory
+  double sx, sy;             // ADD / MOVE: sensor position
+  int32_t kind;              // kDeltaAdd / kDeltaSub / kDeltaMove
+  int32_t slot;              // the scan's slot of the log
+  int32_t old_cx, old_cy;    // MOVE: the sensor cell the log holds (the host keeps a copy: the kernel overwrites the log's)
+};
+static_assert(sizeof(DeltaRecord) == 48, "one record = 6 x 8 bytes");
+
+// The log: one slot per scan of (2 + 2 * n_beams) int32 words.
+//   word 0, 1            sensor cell x, y on the lattice
+//   word 2 + 2 i         beam i: end cell x on the lattice
+//   word 3 + 2 i         beam i: bit 0 = the beam was kept (traced), bit 1 = its end point counts as a hit,
+//                                bits 2..31 = end cell y - sensor cell y (two's complement; the size cap of the window bounds it
+//                                far below 2^29)
+inline int64_t live_log_slot_words(int32_t n_beams) {return 2 + 2 * static_cast<int64_t>(n_beams);}
+
+// ---- the launchers (occupancy.hip) ----
+// the stream the grid's kernels run on: uploads a caller queues there are in place before the next trace reads them
+void * occupancy_stream(kh_occupancy * g);
+// AddScan for n_scans scans of n_beams beams whose readings are resident on the grid's device.  Returns after the trace (and
+// everything queued on the stream before it) has finished.
+int occupancy_add_resident(kh_occupancy * g, int32_t n_scans, const ResidentScan * scans, int32_t n_beams, double range_threshold,
+  double min_range, double max_range);
+// AddScan for the scans of a merge; scans[i].submap indexes submaps.  max_beams = the largest beam count, n_total_beams = the sum
+// over the scans (the grid's beam counter).  Returns after the trace has finished.
+int occupancy_add_merged(kh_occupancy * g, int32_t n_scans, const MergeScan * scans, int32_t n_submaps, const MergeSubmap * submaps,
+  int32_t max_beams, int64_t n_total_beams);
+// n_records records on `stream`; counters[0] += lines walked, counters[1] += kept beams of MOVE records that were left alone
+void live_trace_delta(void * stream, const LiveWindow & w, double anchor_x, double anchor_y, double scale, const DeltaRecord * d_records,
+  int32_t n_records, int32_t n_beams, double range_threshold, double min_range, double max_range, int32_t * d_log,
+  unsigned long long * d_counters);
+// k_occ_update's rule over window columns [x0, x0 + w) and rows [y0, y0 + h) (columns may reach into the row padding)
+void live_update_cells(void * stream, const LiveWindow & w, int32_t x0, int32_t y0, int32_t rect_w, int32_t rect_h, uint32_t min_pass,
+  double threshold);
+}  // namespace kh

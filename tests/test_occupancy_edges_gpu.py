@@ -173,10 +173,13 @@ def _write_bad_readings(ranges, laser):
 
 def test_resident_trace_equals_the_oracle(kartohip_lib, oracle_lib):
     """kh_mapper_build_map (k_occ_trace_resident, fed from the mapper's resident scans) against the CPU oracle over the same scans
-    pulled with kh_mapper_get_scan -- the oracle itself, not only the packed GPU path"""
+    pulled with kh_mapper_get_scan -- the oracle itself, not only the packed GPU path.  The same mapper as the single submap of a
+    MapMerger under the identity (k_occ_trace_merged) gives the same grid: c = 1, s = 0, t = 0 is exact on every finite point, and
+    the kept beams have finite points"""
     import test_localization_gpu as loc
     from oracle import karto
     from slam_toolbox_amd.mapper import Mapper
+    from slam_toolbox_amd.merge import MapMerger
     from slam_toolbox_amd.occupancy_grid import compute_dimensions
     laser = synth.Laser()
     ranges, odom = loc._queue()
@@ -202,5 +205,14 @@ def test_resident_trace_equals_the_oracle(kartohip_lib, oracle_lib):
         want = karto.occupancy_from_scans(g.width, g.height, g.offset, res, oscans, laser, 2, 0.1)
         assert_grid_equals(g, want, f"resolution {res}")
         assert (want[0] == 100).sum() > 100 and (want[0] == 255).sum() > 10000
+        mg = MapMerger(res)
+        mg.add_submap(m)
+        merged = mg.merge()
+        assert (merged.width, merged.height, merged.width_step) == (g.width, g.height, g.width_step)
+        assert np.array_equal(merged.offset.view(np.uint64), g.offset.view(np.uint64))
+        for got, built in zip(merged.counters(), g.counters()):
+            assert np.array_equal(got, built), f"resolution {res}: the merged counters differ from build_map's"
+        assert np.array_equal(merged.cells(), g.cells())
+        merged.close(); mg.close()
         g.close()
     m.close()

@@ -5,6 +5,8 @@
 # (tools/patches/r4_k_score_lds_instrumentation.patch; it applies to the matcher_kernels.hip of the commit that added it).
 out=$1; shift
 src="$(cd "$(dirname "$0")/../slam_toolbox_amd/csrc" && pwd)"
+# the library's sources are the ones slam_toolbox_amd/build.py compiles (SOURCES), so that a variant exports the whole ABI
+sources=$(cd "$src/.." && python3 -c "import build; print(' '.join(build.SOURCES))") || exit 1
 if [ "$1" = "--instrumented" ]; then
   shift
   tmp=$(mktemp -d) && cp "$src"/* "$tmp"/ && (cd "$tmp" && patch -p3 < "$src/../../tools/patches/r4_k_score_lds_instrumentation.patch") || exit 1
@@ -12,4 +14,4 @@ if [ "$1" = "--instrumented" ]; then
 fi
 cd "$src"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -fvisibility=hidden -Wno-unused-value -shared -ldl "$@" -o "$out" \
-  matcher_host.cpp matcher_seq.cpp matcher_seq.hip matcher_group.cpp matcher_kernels.hip spa_host.cpp spa_symbolic.cpp spa_kernels.hip graph.hip occupancy.hip lifelong.hip comm.cpp mapper_host.cpp
+  $sources
