@@ -44,15 +44,23 @@ def near_linked_scans(q, ref_xy, adj_ptr, adj_idx, max_distance):
     return valid
 
 
-def find_possible_loop_closures(q, ref_xy, adj_ptr, adj_idx, max_distance, min_chain_size):
+def find_possible_loop_closures(q, ref_xy, adj_ptr, adj_idx, max_distance, min_chain_size, start=0, n_visit=None):
     """All chains successive FindPossibleLoopClosure(pScan, sensor, rStartNum) calls return, as (first, last)
-    scan indices (chains are runs of consecutive scans)."""
+    scan indices (chains are runs of consecutive scans).
+
+    start: the first call's rStartNum; the chain under construction is empty there (Mapper.cpp:1965, 1976), so scans before it
+    neither form chains nor extend one.  Pinned to the reference by the golden graph: its recording holds successive calls, and
+    the walk resumed behind chain k must give the recorded chains k+1 ... (tests/test_loops_oracle.py).
+    n_visit: nScans, the loop bound, which is the scan map's SIZE (Mapper.cpp:1974-1976) and falls behind the largest list index
+    once scans were removed; None = all scans.  The breadth-first traversal still walks the whole adjacency.  There is no
+    reference recording of a walk with n_visit < n: it is pinned to the reference only indirectly, by the mapper-level node
+    removal tests (which ask one query at a time, the library's host route)."""
     linked = set(near_linked_scans(q, ref_xy, adj_ptr, adj_idx, max_distance))
     lim = max_distance * max_distance + KT_TOLERANCE        # Mapper.cpp:1988-1990
-    n = ref_xy.shape[0]
+    n = ref_xy.shape[0] if n_visit is None else int(n_visit)
     pose = ref_xy[q]
     out = []
-    start = 0
+    start = int(start)
     while True:
         chain = []
         returned = False
@@ -76,10 +84,11 @@ def find_possible_loop_closures(q, ref_xy, adj_ptr, adj_idx, max_distance, min_c
     return out
 
 
-def find_near_chains(q, ref_xy, adj_ptr, adj_idx, link_max_distance):
-    """MapperGraph::FindNearChains (Mapper.cpp:1683-1793) as (first, last) runs, in the reference's order."""
+def find_near_chains(q, ref_xy, adj_ptr, adj_idx, link_max_distance, n_visit=None):
+    """MapperGraph::FindNearChains (Mapper.cpp:1683-1793) as (first, last) runs, in the reference's order.  n_visit bounds the
+    forward walk (the scan map's size, Mapper.cpp:1751-1756); None = all scans."""
     lim = link_max_distance * link_max_distance + KT_TOLERANCE          # Mapper.cpp:1735-1737
-    n = ref_xy.shape[0]
+    n = ref_xy.shape[0] if n_visit is None else int(n_visit)
     pose = ref_xy[q]
     processed = set()
     out = []

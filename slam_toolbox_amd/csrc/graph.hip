@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void k_loop_candidates(
   uint8_t * flags = flags_all + (size_t)qi * ((n + 3) & ~3);       // word-aligned rows: bits are set with 32-bit atomics
   int32_t * cur = frontier_all + (size_t)qi * 2 * n;
   int32_t * nxt = cur + n;
-  __shared__ int32_t s_cur_n, s_nxt_n, s_out_n;
+  __shared__ int32_t s_cur_n, s_nxt_n, s_out_n, s_stop;
   const double qx = g.xy[2 * q], qy = g.xy[2 * q + 1];
   // (1) distance flags
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void k_loop_candidates(
     if (d2 <= max_sq_minus) {f |= kVisitable;}
     flags[i] = f;
   }
-  if (threadIdx.x == 0) {s_cur_n = 1; s_nxt_n = 0; s_out_n = 0; cur[0] = q;}
+  if (threadIdx.x == 0) {s_cur_n = 1; s_nxt_n = 0; s_out_n = 0; s_stop = n_visit; cur[0] = q;}
   __syncthreads();
   if (threadIdx.x == 0) {flags[q] |= kSeen;}
   __syncthreads();
@@ -93,9 +93,19 @@ __global__ __launch_bounds__(256) void k_loop_candidates(
   }
   // (3) chains = maximal runs of good scans with the right terminator
   int32_t * out = chains + (size_t)qi * cap_per_query * 2;
+  // loop_match_minimum_chain_size 0: `chain.size() >= 0` (Mapper.cpp:2001) holds for the EMPTY chain too, so the reference returns at
+  // the first out-of-range scan at or behind `start` with whatever it holds and does not advance; its next call returns the empty
+  // chain from that same scan and TryCloseLoop stops (Mapper.cpp:1508).  The walk ends there: at most one chain per query.
+  if (min_chain <= 0) {
+    for (int i = min(start, n_visit) + threadIdx.x; i < n_visit; i += blockDim.x) {
+      if (!(flags[i] & kInRange)) {atomicMin(&s_stop, i);}
+    }
+    __syncthreads();
+  }
+  const int stop = s_stop;
   // the walk ends at n_visit (the reference's loop bound is the scan MAP's size, which falls behind the largest id
   // once scans have been removed, Mapper.cpp:1974-1976): whatever chain is open there is returned
-  for (int i = threadIdx.x; i < n_visit; i += blockDim.x) {
+  for (int i = threadIdx.x; i < stop; i += blockDim.x) {
     const uint8_t f = flags[i];
     const bool good = i >= start && (f & kInRange) && !(f & kLinked);
     if (!good) {continue;}
@@ -453,6 +463,7 @@ static void loop_candidates_host(const kh_graph * g, int32_t q, int32_t start, d
   out.clear();
   auto good_at = [&](int32_t i) {return (flags[i] & kInRange) && !(flags[i] & kLinked);};
   for (int32_t i = std::max(start, 0); i < n_visit; ++i) {
+    if (min_chain <= 0 && !(flags[i] & kInRange)) {break;}     // minimum chain size 0: the walk ends at the first out-of-range scan (see k_loop_candidates)
     if (!good_at(i)) {continue;}
     bool emit;
     int32_t len_needed;

@@ -32,18 +32,40 @@ class MapperGraphSearch:
         ref_xy = np.ascontiguousarray(ref_xy, dtype=np.float64).reshape(-1, 2)
         capi.check(capi.lib().kh_graph_set_positions(self._h, ref_xy.shape[0], ref_xy.reshape(-1)), "kh_graph_set_positions")
 
-    def FindPossibleLoopClosures(self, query_scans, loop_search_maximum_distance, loop_match_minimum_chain_size):
+    def SetScanLimit(self, n_visit):
+        """The candidate walks visit the first n_visit scans only (the reference's scan map size after removals); SetGraph
+        resets it to n."""
+        capi.check(capi.lib().kh_graph_set_scan_limit(self._h, int(n_visit)), "kh_graph_set_scan_limit")
+
+    def AddEdge(self, scan_a, scan_b):
+        capi.check(capi.lib().kh_graph_add_edge(self._h, int(scan_a), int(scan_b)), "kh_graph_add_edge")
+
+    def SetPosition(self, scan, ref_xy):
+        xy = np.ascontiguousarray(ref_xy, dtype=np.float64)[:2].copy()
+        capi.check(capi.lib().kh_graph_set_position(self._h, int(scan), xy), "kh_graph_set_position")
+
+    def FindPossibleLoopClosures(self, query_scans, loop_search_maximum_distance, loop_match_minimum_chain_size, starts=None):
         """-> list (one entry per query) of [(first, last), ...]: every chain successive
-        MapperGraph::FindPossibleLoopClosure calls would return for that scan (Mapper.cpp:1960-2010)."""
+        MapperGraph::FindPossibleLoopClosure calls would return for that scan (Mapper.cpp:1960-2010); with `starts`, the
+        calls of query i begin at rStartNum = starts[i] (kh_graph_find_loop_candidates_from)."""
         q = np.ascontiguousarray(query_scans, dtype=np.int32)
+        if starts is not None:
+            starts = np.ascontiguousarray(starts, dtype=np.int32)
+            if starts.shape != q.shape:
+                raise ValueError("one start per query")
         begin = np.zeros(q.size + 1, dtype=np.int32)
         cap = max(16, 4 * q.size)
         total = C.c_int32(0)
         while True:
             chains = np.zeros(2 * cap, dtype=np.int32)
-            capi.check(capi.lib().kh_graph_find_loop_candidates(self._h, q.size, q, float(loop_search_maximum_distance),
-                                                                int(loop_match_minimum_chain_size), begin, chains, cap,
-                                                                C.byref(total)), "kh_graph_find_loop_candidates")
+            if starts is None:
+                capi.check(capi.lib().kh_graph_find_loop_candidates(self._h, q.size, q, float(loop_search_maximum_distance),
+                                                                    int(loop_match_minimum_chain_size), begin, chains, cap,
+                                                                    C.byref(total)), "kh_graph_find_loop_candidates")
+            else:
+                capi.check(capi.lib().kh_graph_find_loop_candidates_from(self._h, q.size, q, starts.ctypes.data, float(loop_search_maximum_distance),
+                                                                         int(loop_match_minimum_chain_size), begin, chains, cap,
+                                                                         C.byref(total)), "kh_graph_find_loop_candidates_from")
             if total.value <= cap:
                 break
             cap = total.value

@@ -1,16 +1,21 @@
-"""CPU: the case tables of tests/occupancy_cases.py and tests/lifelong_cases.py run through the ORACLES alone
-(oracle/occupancy_oracle.c, oracle/lifelong.py).  Each check asserts that a case reaches the edge its name says -- a border
+"""CPU: the case tables of tests/occupancy_cases.py, tests/lifelong_cases.py and tests/graph_cases.py run through the ORACLES alone
+(oracle/occupancy_oracle.c, oracle/lifelong.py, oracle/loops.py, tests/near_by_rule.py).  Each check asserts that a case reaches the edge its name says -- a border
 row really is crossed, a cell really sits at pass == min_pass -- so that editing a number cannot quietly turn an edge case
-into an ordinary one.  The GPU side of the same tables: tests/test_occupancy_edges_gpu.py, tests/test_lifelong_edges_gpu.py."""
+into an ordinary one.  The GPU side of the same tables: tests/test_occupancy_edges_gpu.py, tests/test_lifelong_edges_gpu.py,
+tests/test_graph_edges_gpu.py."""
 import numpy as np
 import pytest
 
+import graph_cases as gc
 import lifelong_cases as lc
+import near_by_rule
 import occupancy_cases as oc
-from oracle import karto, lifelong
+from oracle import karto, lifelong, loops
 
 OCC = list(oc.all_cases())
 LIFE = list(lc.all_cases())
+LOOPS = list(gc.loop_cases())
+NEAR = list(gc.near_cases())
 
 
 def oracle_scans(scans):
@@ -24,7 +29,7 @@ def run_oracle(case):
 
 
 def test_case_names_are_unique():
-    for cases in (OCC, LIFE):
+    for cases in (OCC, LIFE, LOOPS, NEAR):
         names = [c.name for c in cases]
         assert len(set(names)) == len(names)
 
@@ -241,3 +246,42 @@ def test_finite_twins_guard_every_case_with_nan_points(oracle_lib):
         assert all(same), "dropped beams do not depend on their points"
         lenient = t._replace(gates=oc.Gates(np.nextafter(t.gates.min_range, 0.0), t.gates.range_threshold, t.gates.max_range))
         assert not np.array_equal(run_oracle(lenient)[1], run_oracle(t)[1]), c.name
+
+
+def loop_oracle(case):
+    starts = case.starts if case.starts is not None else [0] * len(case.queries)
+    return [loops.find_possible_loop_closures(int(q), case.ref_xy, case.adj_ptr, case.adj_idx, case.max_distance, case.min_chain,
+                                              start=int(s), n_visit=case.n_visit) for q, s in zip(case.queries, starts)]
+
+
+def near_rule(case):
+    return [gc.NearResult(near_by_rule.dist_sq(case.poses, q), near_by_rule.find_near_by_scan(case.poses, q),
+                          [near_by_rule.find_near_by_vertices(case.poses, q, r) for r in case.radii]) for q in case.queries]
+
+
+@pytest.mark.parametrize("case", LOOPS, ids=[c.name for c in LOOPS])
+def test_loop_case_sits_on_its_edge(case):
+    n = case.ref_xy.shape[0]
+    assert case.adj_ptr.shape == (n + 1,) and case.adj_ptr[0] == 0 and case.adj_ptr[n] == case.adj_idx.size
+    assert case.adj_idx.size == 0 or (0 <= case.adj_idx.min() and case.adj_idx.max() < n)
+    assert np.isfinite(case.ref_xy).all() and len(case.queries) >= 2 and ((0 <= case.queries) & (case.queries < n)).all()
+    assert case.starts is None or (len(case.starts) == len(case.queries) and (case.starts >= 0).all())
+    assert case.n_visit is None or 0 <= case.n_visit <= n
+    case.check(loop_oracle(case))
+
+
+@pytest.mark.parametrize("case", NEAR, ids=[c.name for c in NEAR])
+def test_near_by_case_sits_on_its_edge(case):
+    assert np.isfinite(case.poses).all() and np.isfinite(case.queries).all(), "non-finite coordinates are out of scope"
+    with np.errstate(over="ignore"):
+        case.check(near_rule(case))
+
+
+def test_graph_table_holds_every_size_and_goes_large_small_large():
+    assert [c.ref_xy.shape[0] for c in LOOPS if c.name.startswith("sizes")] == list(gc.LOOP_SIZES)
+    assert {c.ref_xy.shape[0] % 4 for c in LOOPS} == {0, 1, 2, 3}
+    assert [c.poses.shape[0] for c in NEAR if c.name.startswith("near sizes")] == list(gc.NEAR_SIZES)
+    sizes = [c.ref_xy.shape[0] for c in gc.reuse_order(LOOPS)]
+    assert len(sizes) == len(LOOPS) and sizes[0] == max(sizes) and sizes[1] == min(sizes) and sizes[2] > sizes[1] and sizes[2] > sizes[3]
+    assert any(c.starts is None for c in LOOPS) and any(c.starts is not None and not c.starts.any() for c in LOOPS)
+    assert any(c.name == gc.CAP_CASE for c in NEAR)

@@ -30,6 +30,26 @@ def test_loop_chains_match_the_reference():
     assert np.array_equal(np.asarray(rows, dtype=np.int32).reshape(-1, 3), G["chains"])
 
 
+def test_resumed_walk_returns_the_chains_behind_the_resume_point():
+    """`start`: the golden file records SUCCESSIVE reference calls; after chain k the reference's rStartNum stands on the
+    out-of-range scan last_k + 1 that ended it (it is not advanced on that return, Mapper.cpp:2001-2002).  The oracle started
+    there must give exactly the recorded chains k + 1 ..., for every query with at least two chains and every k."""
+    d = float(G["loop_search_maximum_distance"])
+    m = int(G["loop_match_minimum_chain_size"])
+    chains = G["chains"]
+    n_queries = n_resumes = 0
+    for q in np.unique(chains[:, 0]):
+        mine = [(int(a), int(b)) for _, a, b in chains[chains[:, 0] == q]]
+        if len(mine) < 2:
+            continue
+        n_queries += 1
+        for k, (_, last) in enumerate(mine):
+            got = loops.find_possible_loop_closures(int(q), G["ref_xy"], G["adj_ptr"], G["adj_idx"], d, m, start=last + 1)
+            assert got == mine[k + 1:], (q, k)
+            n_resumes += 1
+    assert n_queries > 0 and n_resumes > 2 * n_queries - 1
+
+
 def _wm_cases():
     for k, row, out in zip(G["wm_k"], G["wm_in"], G["wm_out"]):
         k = int(k)
