@@ -130,6 +130,16 @@ def sqrt_information(cov):
     return np.linalg.cholesky(info).T
 
 
+def sqrt_information_from_upper(w):
+    """AddConstraintInformation: the information's upper triangle (00 01 02 11 12 22) as given, U = llt().matrixU().
+    Raises numpy.linalg.LinAlgError where llt() fails (not positive definite, NaN)."""
+    w = [float(v) for v in w]
+    info = np.array([[w[0], w[1], w[2]], [w[1], w[3], w[4]], [w[2], w[4], w[5]]])
+    if not np.all(np.isfinite(info)):
+        raise np.linalg.LinAlgError("information matrix is not finite")
+    return np.linalg.cholesky(info).T
+
+
 def _residuals(x, ea, eb, z, U):
     """PoseGraph2dErrorTerm (ceres_utils.h:84-100), all edges at once.  x: (N, 3)."""
     xa, xb = x[ea], x[eb]
@@ -174,12 +184,16 @@ def _loss(sq, kind, a):
 class Problem:
     """State the plugin keeps: nodes in insertion order, constraints, gauge node."""
 
-    def __init__(self, poses, edges, z, cov, fixed=0, loss="None", loss_scale=0.7):
+    def __init__(self, poses, edges, z, cov, fixed=0, loss="None", loss_scale=0.7, U=None):
+        """U: the square-root informations (E, 3, 3) themselves, for constraints that did not come in as covariances"""
         self.loss, self.loss_scale = loss, loss_scale
         self.x = np.asarray(poses, dtype=np.float64).copy()
         self.edges = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
         self.z = np.asarray(z, dtype=np.float64).reshape(-1, 3)
-        self.U = np.stack([sqrt_information(c) for c in np.asarray(cov).reshape(-1, 9)]) if len(self.edges) else np.zeros((0, 3, 3))
+        if U is not None:
+            self.U = np.asarray(U, dtype=np.float64).reshape(-1, 3, 3)
+        else:
+            self.U = np.stack([sqrt_information(c) for c in np.asarray(cov).reshape(-1, 9)]) if len(self.edges) else np.zeros((0, 3, 3))
         self.fixed = fixed
         n = self.x.shape[0]
         used = np.zeros(n, dtype=bool)
@@ -254,13 +268,20 @@ class Problem:
         return x[self.free_nodes].reshape(-1)
 
 
-def solve(poses, edges, z, cov, options: Options = None, fixed=0):
+def solve(poses, edges, z, cov, options: Options = None, fixed=0, permc_spec="MMD_AT_PLUS_A", U=None):
     """CeresSolver::Compute (ceres_solver.cpp:214-269) with Ceres' trust-region LM restated.
-    Returns (poses (N,3), info dict)."""
+    Returns (poses (N,3), info dict).  info["log"]: one row per iteration in the columns of kh_spa_iteration_log (iteration, cost
+    of the iterate the step starts from, candidate cost, model cost change, radius used, radius after, step norm, verdict: 1
+    accepted, 0 rejected, -1 invalid, 2 / 3 ended on the parameter / function tolerance); an invalid step has no candidate: NaN
+    in columns 2, 3 and 6.  info["quality"]: the step quality of every accepted or rejected row.  permc_spec: SuperLU's column
+    ordering (the answer does not depend on it beyond rounding; two orderings measure that rounding)."""
     opt = options or Options()
-    prob = Problem(poses, edges, z, cov, fixed, opt.loss_function, opt.loss_scale)
-    info = dict(iterations=0, successful_steps=0, termination="NO_CONVERGENCE", usable=True, message="", costs=[])
+    prob = Problem(poses, edges, z, cov, fixed, opt.loss_function, opt.loss_scale, U=U)
+    info = dict(iterations=0, successful_steps=0, termination="NO_CONVERGENCE", usable=True, message="", costs=[], log=[], quality=[])
+    nan = float("nan")
     x = prob.x.copy()
+    if opt.loss_function not in (None, "None") and not opt.loss_scale > 0.0:
+        raise ValueError("loss_scale must be positive")          # ceres::HuberLoss / CauchyLoss CHECK_GT(a, 0)
     if prob.nfree == 0 or len(prob.edges) == 0:
         info.update(termination="CONVERGENCE", initial_cost=0.0, final_cost=0.0, message="no free parameters")
         return x, info
@@ -268,6 +289,12 @@ def solve(poses, edges, z, cov, options: Options = None, fixed=0):
     # ---- iteration zero (TrustRegionMinimizer::IterationZero / EvaluateGradientAndJacobian) ----
     x_cost, g, H = prob.linearize(x)
     info["initial_cost"] = x_cost
+    if not np.isfinite(x_cost):
+        # TrustRegionMinimizer::IterationZero: the initial evaluation gives no valid cost -> FAILURE before any step, and
+        # CeresSolver::Compute keeps the old state (ceres_solver.cpp:249-254)
+        info.update(termination="FAILURE", usable=False, final_cost=x_cost, log=np.zeros((0, 8)),
+                    message="Initial residual and Jacobian evaluation failed.")
+        return prob.x.copy(), info
     if opt.jacobi_scaling:
         scale = 1.0 / (1.0 + np.sqrt(H.diagonal()))
     else:
@@ -317,7 +344,7 @@ def solve(poses, edges, z, cov, options: Options = None, fixed=0):
         lm = diagonal / radius
         step_valid = True
         try:
-            lu = spla.splu((Hs + sp.diags(lm)).tocsc(), permc_spec="MMD_AT_PLUS_A", diag_pivot_thresh=0.0,
+            lu = spla.splu((Hs + sp.diags(lm)).tocsc(), permc_spec=permc_spec, diag_pivot_thresh=0.0,
                            options=dict(SymmetricMode=True))
             y = lu.solve(gs)
             if not np.all(np.isfinite(y)):
@@ -333,9 +360,11 @@ def solve(poses, edges, z, cov, options: Options = None, fixed=0):
         if not step_valid:
             num_invalid += 1
             if num_invalid >= opt.max_num_consecutive_invalid_steps:
+                info["log"].append([iteration, x_cost, nan, nan, radius, radius, nan, -1.0])
                 info.update(termination="FAILURE", usable=False,
                             message="Number of consecutive invalid steps more than max_num_consecutive_invalid_steps")
                 break
+            info["log"].append([iteration, x_cost, nan, nan, radius, radius / decrease_factor, nan, -1.0])
             radius = radius / decrease_factor      # StepIsInvalid -> StepRejected(0)
             decrease_factor *= 2.0
             reuse_diagonal = True
@@ -348,18 +377,24 @@ def solve(poses, edges, z, cov, options: Options = None, fixed=0):
         cand_cost = prob.cost(cand)
         step_norm = float(np.linalg.norm(prob.free_vector(x) - prob.free_vector(cand)))
         if step_norm <= opt.parameter_tolerance * (x_norm + opt.parameter_tolerance):
+            info["log"].append([iteration, x_cost, cand_cost, model_cost_change, radius, radius, step_norm, 2.0])
             info.update(termination="CONVERGENCE", message="Parameter tolerance reached.")
             break
         cost_change = x_cost - cand_cost
         if abs(cost_change) <= opt.function_tolerance * x_cost:
+            info["log"].append([iteration, x_cost, cand_cost, model_cost_change, radius, radius, step_norm, 3.0])
             info.update(termination="CONVERGENCE", message="Function tolerance reached.")
             break
         # ---- IsStepSuccessful (TrustRegionStepEvaluator::StepQuality) ----
         rel = (ev["current"] - cand_cost) / model_cost_change
         hist = (ev["reference"] - cand_cost) / (ev["acc_ref"] + model_cost_change)
         quality = max(rel, hist)
+        info["quality"].append(quality)
+        row = [iteration, x_cost, cand_cost, model_cost_change, radius, nan, step_norm, 0.0]
+        info["log"].append(row)
         if quality > opt.min_relative_decrease:
             # HandleSuccessfulStep
+            row[7] = 1.0
             x = cand
             x_norm = float(np.linalg.norm(prob.free_vector(x)))
             x_cost, g, H = prob.linearize(x)
@@ -368,6 +403,7 @@ def solve(poses, edges, z, cov, options: Options = None, fixed=0):
             info["successful_steps"] += 1
             radius = radius / max(1.0 / 3.0, 1.0 - (2.0 * quality - 1.0) ** 3)
             radius = min(opt.max_trust_region_radius, radius)
+            row[5] = radius
             decrease_factor = 2.0
             reuse_diagonal = False
             # StepAccepted
@@ -392,11 +428,13 @@ def solve(poses, edges, z, cov, options: Options = None, fixed=0):
                 best_x = x.copy()
             info["costs"].append(x_cost)
         else:
+            row[5] = radius / decrease_factor
             radius = radius / decrease_factor       # StepRejected
             decrease_factor *= 2.0
             reuse_diagonal = True
 
     info["iterations"] = iteration
+    info["log"] = np.asarray(info["log"], dtype=np.float64).reshape(-1, 8)
     info["final_cost"] = minimum_cost
     if not info["usable"]:
         return prob.x.copy(), info          # ceres_solver.cpp:249-254: keep the old state

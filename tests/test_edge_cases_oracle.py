@@ -285,3 +285,62 @@ def test_graph_table_holds_every_size_and_goes_large_small_large():
     assert len(sizes) == len(LOOPS) and sizes[0] == max(sizes) and sizes[1] == min(sizes) and sizes[2] > sizes[1] and sizes[2] > sizes[3]
     assert any(c.starts is None for c in LOOPS) and any(c.starts is not None and not c.starts.any() for c in LOOPS)
     assert any(c.name == gc.CAP_CASE for c in NEAR)
+
+
+# ---- tests/spa_cases.py: the pose-graph solver's table through oracle/spa.py alone (GPU side: tests/test_spa_edges_gpu.py) --------
+import spa_cases as sc      # noqa: E402
+
+SPA = list(sc.all_cases())
+SPA_FAIL = list(sc.failure_cases())
+
+
+def test_spa_case_names_are_unique_and_every_mode_is_there():
+    names = [c.name for c in SPA] + [c.name for c, _ in SPA_FAIL]
+    assert len(set(names)) == len(names)
+    assert {c.mode for c in SPA} == {"zero", "one", "run"} and {c.mode for c, _ in SPA_FAIL} == {"fail"}
+    for c in SPA:
+        assert c.name.endswith(f"[{c.mode}]") and len(c.nodes) <= 71, c.name
+        if c.mode == "zero":
+            assert c.options["initial_trust_region_radius"] < sc.oracle_options(c.options).min_trust_region_radius
+        if c.mode == "one":
+            assert c.options["max_num_iterations"] == 1
+    assert max(len(c.cons) for c in SPA) == 257
+
+
+@pytest.mark.parametrize("case", SPA + [c for c, _ in SPA_FAIL], ids=lambda c: c.name)
+def test_spa_case_reaches_its_edge(case):
+    run = sc.oracle_run(case)
+    if case.mode == "zero":
+        assert run.info["iterations"] == 0 and "Minimum trust region radius" in run.info["message"] and np.array_equal(run.x, run.x0)
+        assert np.isfinite(run.info["initial_cost"]) and run.info["initial_cost"] > 0.0
+    if case.mode == "one":
+        assert run.info["iterations"] == 1 and len(run.info["log"]) == 1 and run.info["log"][0, 7] in (0.0, 1.0, 2.0, 3.0)
+    if case.mode in ("one", "run"):
+        assert run.info["usable"]
+    assert case.check is not None, "a case without a check of its edge"
+    case.check(run)
+
+
+def test_spa_rejected_options_and_reuse_sequence():
+    names = {c.name: c for c in SPA + [c for c, _ in SPA_FAIL]}
+    graph = names[sc.REJECTED_OPTIONS_GRAPH]
+    assert len(sc.REJECTED_OPTIONS) == 6
+    for options in sc.REJECTED_OPTIONS:
+        assert options["loss_function"] != "None" and not options["loss_scale"] > 0.0
+        with pytest.raises(ValueError):
+            sc.oracle_run(graph._replace(options={**graph.options, **options}))
+    assert sc.oracle_run(graph._replace(options={**graph.options, **sc.ACCEPTED_OPTIONS})).info["usable"]
+    seq = [names[n] for n in sc.REUSE_SEQUENCE]
+    assert [c.mode for c in seq] == ["run", "fail", "one", "run", "one"]
+    runs = [sc.oracle_run(c) for c in seq]
+    assert sc.verdicts(runs[0])[0] >= 3 and sc.verdicts(runs[3])[1] >= 1          # doubled decrease factors; a non-monotonic reference
+    assert set(sc.ORDER_ERR) == {c.name for c in sc.modes(SPA, "run")}
+
+
+def test_spa_table_reaches_every_verdict_and_termination():
+    runs = [sc.oracle_run(c) for c in sc.modes(SPA, "run")]
+    verdicts = set(np.concatenate([r.info["log"][:, 7] for r in runs]).tolist())
+    assert verdicts == {0.0, 1.0, 2.0, 3.0}
+    messages = {r.info["message"].split(" reached")[0] for r in runs}
+    assert messages >= {"Maximum number of iterations", "Gradient tolerance", "Parameter tolerance", "Function tolerance", "Minimum trust region radius"}
+    assert any(r.info["log"][0, 7] == 0.0 for r in [sc.oracle_run(c) for c in sc.modes(SPA, "one")]), "no `one` case whose step is rejected"
