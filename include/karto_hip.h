@@ -504,6 +504,10 @@ KH_API int kh_occupancy_update(kh_occupancy * g, uint32_t min_pass_through, doub
 /* cells: width_step * height bytes (0 unknown, 100 occupied, 255 free, Karto.h:4379-4381); pass / hits: the
  * counter grids (same layout, uint32); any pointer may be NULL */
 KH_API int kh_occupancy_read(kh_occupancy * g, uint8_t * cells, uint32_t * pass, uint32_t * hits);
+/* vis_utils::toNavMap (include/slam_toolbox/visualization_utils.hpp:108-146) of the cell states, on the device: out gets
+ * width * height values WITHOUT row padding, row-major -- the data of a nav_msgs/OccupancyGrid: -1 unknown, 100 occupied,
+ * 0 free.  For any kh_occupancy: kh_mapper_build_map's, kh_merge_build's, a hand-made one after kh_occupancy_update. */
+KH_API int kh_occupancy_read_nav(kh_occupancy * g, int8_t * out);
 KH_API int kh_occupancy_info(kh_occupancy * g, int32_t * width, int32_t * height, int32_t * width_step,
                              double * trace_ms, int64_t * beams_traced);
 /* the grid's offset (world position of cell 0, 0) and 1 / scale; either pointer may be NULL */
@@ -807,6 +811,53 @@ KH_API int kh_live_map_info(const kh_live_map * g, kh_live_map_info_t * out);
 /* layout of kh_occupancy_read over the window: width_step * height entries each; any pointer may be NULL */
 KH_API int kh_live_map_read(kh_live_map * g, uint8_t * cells, uint32_t * pass, uint32_t * hits);
 KH_API int kh_live_map_stats(const kh_live_map * g, kh_live_map_stats_t * out);
+
+/* ---- the map feed: the live map's way out, for a costmap, a viewer, a map_msgs/OccupancyGridUpdate publisher.  A feed hands its
+ * consumer, as nav_msgs/OccupancyGrid values (-1 unknown, 100 occupied, 0 free: vis_utils::toNavMap), the 16 x 16 TILES whose
+ * values changed since the consumer last asked, and nothing else.  Several feeds may be bound to one live
+ * map, one per consumer, each polled at its own pace.
+ *
+ * The feed owns the PUBLISHED GRID on the device: one int8 per lattice cell of the window the feed has seen, holding what the
+ * consumer has been told so far.  Every cell the feed has never reported is -1, the cells outside every window it has seen
+ * included: a consumer starts from an all -1 map and grows it with -1.
+ * Tile (tx, ty) covers lattice cells [16 tx, 16 tx + 16) x [16 ty, 16 ty + 16); tx, ty are floor quotients, negative left of and
+ * below the anchor.  The live window's origin and size are multiples of 64, so a tile never straddles its edge.
+ *
+ * kh_live_map_update adds the cells it handed to the cell-state kernel -- a rectangle, or the whole window -- to the PENDING
+ * REGION of every feed attached; updates between two polls accumulate.  kh_map_feed_poll follows the live window (a new
+ * published grid filled with -1, the old content copied to its place), rounds the pending region outward to whole tiles, compares
+ * the nav values of those tiles with the published grid on the device, and downloads the number of tiles that differ, their
+ * coordinates and their 256 bytes each.  The published grid takes the new values of exactly those tiles.  With nothing pending,
+ * or before the live map has a window, a poll launches nothing and reports 0 tiles.
+ *
+ * The feed BORROWS the live map: destroy the feed first.  A poll must not run concurrently with an update of its live map or a
+ * Process call of the mapper.  A poll that meets a HIP error marks the feed's whole window pending, so the next one compares
+ * everything again.  Feeds are not part of a session file, and a merge (kh_merge_build) has none: kh_occupancy_read_nav gives its
+ * values. */
+#define KH_MAP_TILE 16
+typedef struct kh_map_feed kh_map_feed;
+typedef struct kh_map_feed_delta_t {
+  int64_t n_tiles;                 /* tiles that changed: what kh_map_feed_tiles hands out */
+  int64_t tiles_scanned;           /* tiles compared on the device */
+  int64_t bytes_downloaded;        /* device-to-host bytes of this poll: the count, 8 bytes of coordinates and 256 of values per tile */
+  int32_t ox, oy, width, height;   /* the feed's window in lattice cells (= the live map's after a poll) */
+  int32_t x, y, w, h;              /* bounding rectangle of the changed tiles in lattice cells (an OccupancyGridUpdate's); zero without tiles */
+  double kernel_ms;                /* the compare kernel, by device events */
+} kh_map_feed_delta_t;
+typedef struct kh_map_feed_stats_t {
+  int64_t polls, n_tiles, tiles_scanned, bytes_downloaded;      /* totals over every poll */
+  double kernel_ms;
+} kh_map_feed_stats_t;
+KH_API int kh_map_feed_create(kh_live_map * g, kh_map_feed ** out);
+KH_API void kh_map_feed_destroy(kh_map_feed * f);
+KH_API int kh_map_feed_poll(kh_map_feed * f, kh_map_feed_delta_t * out);
+/* what the last poll fetched: n_tiles tiles in ascending (ty, tx) order; tile_xy gets tx, ty per tile, data 256 values per tile,
+ * 16 rows of 16, row-major.  Either pointer may be NULL. */
+KH_API int kh_map_feed_tiles(const kh_map_feed * f, int32_t * tile_xy, int8_t * data);
+/* lattice cells [x, x + w) x [y, y + h) of the published grid, dense (w * h values, row-major): a late joiner's full map, or an
+ * update rectangle.  Cells outside the feed's window read -1; any x, y and any w, h >= 0 whose product fits an int32 are legal. */
+KH_API int kh_map_feed_read(kh_map_feed * f, int32_t x, int32_t y, int32_t w, int32_t h, int8_t * out);
+KH_API int kh_map_feed_stats(const kh_map_feed * f, kh_map_feed_stats_t * out);
 
 #ifdef __cplusplus
 }

@@ -100,6 +100,8 @@ SYMBOLS = [
     "kh_merge_get_scan", "kh_merge_build_submap", "kh_merge_build", "kh_merge_stats",
     "kh_mapper_set_scan_pose", "kh_live_map_create", "kh_live_map_destroy", "kh_live_map_update", "kh_live_map_info", "kh_live_map_read",
     "kh_live_map_stats",
+    "kh_occupancy_read_nav", "kh_map_feed_create", "kh_map_feed_destroy", "kh_map_feed_poll", "kh_map_feed_tiles", "kh_map_feed_read",
+    "kh_map_feed_stats",
 ]
 
 
@@ -159,6 +161,18 @@ class KhLiveMapCounts(C.Structure):
 
 class KhLiveMapStats(C.Structure):
     _fields_ = [("last", KhLiveMapCounts), ("total", KhLiveMapCounts)] + [(k, C.c_int64) for k in ("updates", "scans_in_map", "log_bytes")]
+
+
+KH_MAP_TILE = 16
+
+
+class KhMapFeedDelta(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_tiles", "tiles_scanned", "bytes_downloaded")] + \
+               [(k, C.c_int32) for k in ("ox", "oy", "width", "height", "x", "y", "w", "h")] + [("kernel_ms", C.c_double)]
+
+
+class KhMapFeedStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("polls", "n_tiles", "tiles_scanned", "bytes_downloaded")] + [("kernel_ms", C.c_double)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
@@ -362,6 +376,14 @@ def lib():
         L.kh_live_map_info.argtypes = [vp, C.POINTER(KhLiveMapInfo)]
         L.kh_live_map_read.argtypes = [vp, vp, vp, vp]
         L.kh_live_map_stats.argtypes = [vp, C.POINTER(KhLiveMapStats)]
+    if hasattr(L, "kh_map_feed_create"):
+        L.kh_map_feed_create.argtypes = [vp, C.POINTER(vp)]
+        L.kh_map_feed_destroy.argtypes = [vp]
+        L.kh_map_feed_destroy.restype = None
+        L.kh_map_feed_poll.argtypes = [vp, C.POINTER(KhMapFeedDelta)]
+        L.kh_map_feed_tiles.argtypes = [vp, vp, vp]
+        L.kh_map_feed_read.argtypes = [vp, i32, i32, i32, i32, vp]
+        L.kh_map_feed_stats.argtypes = [vp, C.POINTER(KhMapFeedStats)]
     if hasattr(L, "kh_lifelong_scores"):
         L.kh_decay_params_default.argtypes = [C.POINTER(KhDecayParams)]
         L.kh_decay_params_default.restype = None
@@ -378,6 +400,8 @@ def lib():
         L.kh_occupancy_add_scans.argtypes = [vp, i32, C.POINTER(KhScan), dbl, dbl, dbl]
         L.kh_occupancy_update.argtypes = [vp, C.c_uint32, dbl]
         L.kh_occupancy_read.argtypes = [vp, vp, vp, vp]
+        if hasattr(L, "kh_occupancy_read_nav"):
+            L.kh_occupancy_read_nav.argtypes = [vp, vp]
         L.kh_occupancy_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(dbl), C.POINTER(C.c_int64)]
     _lib = L
     return L

@@ -9,6 +9,9 @@
 //
 // This file is the host side: classification of the mapper's scans against the log (new / gone / moved), the window, the log's
 // slots, the delta table.  The kernels are in occupancy.hip (k_occ_trace_delta, k_occ_update_rect).
+//
+// The map feed (kh_map_feed_*) is at the end: the published grid of one consumer, the pending region the
+// updates leave it, and the poll that hands out the 16 x 16 tiles whose nav values changed (k_nav_feed, occupancy.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -69,6 +72,25 @@ struct kh_live_map
   bool all_cells_stale = true;               // the next update runs the cell-state kernel over the whole window
   bool counters_suspect = false;             // an update failed half-way: the next one rebuilds
   kh_live_map_stats_t stats;
+  std::vector<kh_map_feed *> feeds;          // the feeds attached (they borrow the live map); none: nothing below looks at them
+};
+
+struct kh_map_feed
+{
+  kh_live_map * live = nullptr;              // nullptr once the live map has been destroyed under the feed
+  int32_t device = 0;
+  int32_t ox = 0, oy = 0, width = 0, height = 0;       // the window the published grid covers; its row stride is width
+  int8_t * d_pub = nullptr;
+  // the pending region in lattice cells: the whole window, or the union [x0, x1) x [y0, y1) of what the updates handed over
+  bool pending_whole = true, pending_rect = false;
+  int64_t x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+  uint32_t * d_count = nullptr;
+  int32_t * d_xy = nullptr; uint32_t * d_packed = nullptr; int64_t cap_tiles = 0;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  std::vector<int32_t> tile_xy, raw_xy;      // the last poll's tiles in ascending (ty, tx) order / as the kernel dealt the slots
+  std::vector<int8_t> data, raw_data;
+  kh_map_feed_delta_t last;
+  kh_map_feed_stats_t stats;
 };
 
 namespace kh
@@ -88,6 +110,28 @@ void free_window(LiveWindow & w)
 {
   (void)hipFree(w.pass); (void)hipFree(w.hits); (void)hipFree(w.cells);
   w.pass = nullptr; w.hits = nullptr; w.cells = nullptr;
+}
+
+// the cells an update handed to the cell-state kernel, for every feed attached: window columns / rows -> lattice cells
+void feeds_pending(kh_live_map * g, bool whole, int64_t wx0, int64_t wy0, int64_t wx1, int64_t wy1)
+{
+  for (kh_map_feed * f : g->feeds) {
+    if (whole) {f->pending_whole = true; continue;}
+    const int64_t x0 = wx0 + g->win.ox, y0 = wy0 + g->win.oy, x1 = wx1 + g->win.ox, y1 = wy1 + g->win.oy;
+    if (!f->pending_rect) {f->x0 = x0; f->y0 = y0; f->x1 = x1; f->y1 = y1; f->pending_rect = true; continue;}
+    f->x0 = std::min(f->x0, x0); f->y0 = std::min(f->y0, y0); f->x1 = std::max(f->x1, x1); f->y1 = std::max(f->y1, y1);
+  }
+}
+
+int64_t floor_div(int64_t a, int64_t b) {return a >= 0 ? a / b : -((-a + b - 1) / b);}
+
+int fail_feed(kh_map_feed * f, const char * what)
+{
+  const hipError_t err = hipGetLastError();
+  if (f->live) {(void)hipStreamSynchronize(f->live->stream);}
+  set_error(std::string("kh_map_feed_poll: ") + what + ": " + hipGetErrorString(err));
+  f->pending_whole = true;
+  return KH_ERR_HIP;
 }
 
 int fail_hip(kh_live_map * g, const char * what)
@@ -161,6 +205,7 @@ void kh_live_map_destroy(kh_live_map * g)
   if (!g) {return;}
   (void)hipSetDevice(g->device);
   if (g->stream) {(void)hipStreamSynchronize(g->stream);}
+  for (kh_map_feed * f : g->feeds) {f->live = nullptr;}         // (feeds are to be destroyed first; one that was not must not follow us)
   kh::free_window(g->win);
   (void)hipFree(g->d_log); (void)hipFree(g->d_records); (void)hipFree(g->d_counters);
   if (g->ev[0]) {(void)hipEventDestroy(g->ev[0]);}
@@ -359,10 +404,13 @@ int kh_live_map_update(kh_live_map * g, uint32_t min_pass_through, double occupa
   const bool params_changed = !g->have_params || g->min_pass != min_pass_through ||
     std::memcmp(&g->threshold, &occupancy_threshold, sizeof(double)) != 0;
   int64_t cells_given = 0;
+  bool given_whole = false;
+  int64_t gx0 = 0, gy0 = 0, gx1 = 0, gy1 = 0;                     // the rectangle given, window columns [gx0, gx1) and rows [gy0, gy1)
   if (g->win.width > 0) {
     if (g->all_cells_stale || params_changed) {
       kh::live_update_cells(g->stream, g->win, 0, 0, g->win.ws, g->win.height, min_pass_through, occupancy_threshold);
       cells_given = static_cast<int64_t>(g->win.ws) * g->win.height;
+      given_whole = true;
     } else if (!records.empty()) {
       int64_t x0 = std::numeric_limits<int64_t>::max(), y0 = x0, x1 = std::numeric_limits<int64_t>::min(), y1 = x1;
       auto touch = [&](int32_t cx, int32_t cy) {
@@ -378,6 +426,7 @@ int kh_live_map_update(kh_live_map * g, uint32_t min_pass_through, double occupa
         kh::live_update_cells(g->stream, g->win, static_cast<int32_t>(x0), static_cast<int32_t>(y0), static_cast<int32_t>(x1 - x0 + 1),
           static_cast<int32_t>(y1 - y0 + 1), min_pass_through, occupancy_threshold);
         cells_given = (x1 - x0 + 1) * (y1 - y0 + 1);
+        gx0 = x0; gy0 = y0; gx1 = x1 + 1; gy1 = y1 + 1;
       }
     }
   }
@@ -408,6 +457,7 @@ int kh_live_map_update(kh_live_map * g, uint32_t min_pass_through, double occupa
   for (const SensorView & v : views) {g->logged.push_back(v.id);}
   g->have_params = true; g->min_pass = min_pass_through; g->threshold = occupancy_threshold;
   g->all_cells_stale = false; g->counters_suspect = false;
+  if (cells_given > 0) {kh::feeds_pending(g, given_whole, gx0, gy0, gx1, gy1);}
   kh_live_map_counts & last = g->stats.last;
   std::memset(&last, 0, sizeof(last));
   last.scans_added = n_added; last.scans_removed = static_cast<int64_t>(gone.size()); last.scans_moved = n_moved;
@@ -449,6 +499,209 @@ int kh_live_map_stats(const kh_live_map * g, kh_live_map_stats_t * out)
 {
   if (!g || !out) {return KH_ERR_INVALID_ARG;}
   *out = g->stats;
+  return KH_OK;
+}
+
+// ---------------------------------------------------------------- the map feed
+
+int kh_map_feed_create(kh_live_map * g, kh_map_feed ** out)
+{
+  if (!out) {return KH_ERR_INVALID_ARG;}
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    (void)hipGetLastError();
+    kh::set_error("no usable HIP device (libkartohip has no CPU fallback)");
+    return KH_ERR_NO_DEVICE;
+  }
+  if (!g) {return KH_ERR_INVALID_ARG;}
+  kh_map_feed * f = new kh_map_feed();
+  f->live = g; f->device = g->device;
+  std::memset(&f->last, 0, sizeof(f->last));
+  std::memset(&f->stats, 0, sizeof(f->stats));
+  if (hipSetDevice(f->device) != hipSuccess || hipEventCreate(&f->ev[0]) != hipSuccess || hipEventCreate(&f->ev[1]) != hipSuccess ||
+    hipMalloc(reinterpret_cast<void **>(&f->d_count), sizeof(uint32_t)) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    kh::set_error("kh_map_feed_create: HIP allocation failed");
+    kh_map_feed_destroy(f);
+    return KH_ERR_HIP;
+  }
+  g->feeds.push_back(f);
+  *out = f;
+  return KH_OK;
+}
+
+void kh_map_feed_destroy(kh_map_feed * f)
+{
+  if (!f) {return;}
+  (void)hipSetDevice(f->device);
+  if (f->live) {
+    (void)hipStreamSynchronize(f->live->stream);
+    std::vector<kh_map_feed *> & feeds = f->live->feeds;
+    feeds.erase(std::remove(feeds.begin(), feeds.end(), f), feeds.end());
+  }
+  (void)hipFree(f->d_pub); (void)hipFree(f->d_count); (void)hipFree(f->d_xy); (void)hipFree(f->d_packed);
+  if (f->ev[0]) {(void)hipEventDestroy(f->ev[0]);}
+  if (f->ev[1]) {(void)hipEventDestroy(f->ev[1]);}
+  delete f;
+}
+
+int kh_map_feed_poll(kh_map_feed * f, kh_map_feed_delta_t * out)
+{
+  if (!f || !out) {return KH_ERR_INVALID_ARG;}
+  kh_live_map * g = f->live;
+  if (!g) {kh::set_error("kh_map_feed_poll: the feed's live map has been destroyed"); return KH_ERR_INVALID_ARG;}
+  kh_map_feed_delta_t & d = f->last;
+  auto done = [&]() {
+    d.ox = f->ox; d.oy = f->oy; d.width = f->width; d.height = f->height;
+    f->stats.polls += 1; f->stats.n_tiles += d.n_tiles; f->stats.tiles_scanned += d.tiles_scanned;
+    f->stats.bytes_downloaded += d.bytes_downloaded; f->stats.kernel_ms += d.kernel_ms;
+    *out = d;
+    return KH_OK;
+  };
+  std::memset(&d, 0, sizeof(d));
+  f->tile_xy.clear(); f->data.clear();
+  const LiveWindow & w = g->win;
+  if (w.width == 0 || !(f->pending_whole || f->pending_rect)) {return done();}
+  // what the tile rule stands on: no tile straddles the window's edge, and the cells have no row padding
+  if (w.ox % kBlock || w.oy % kBlock || w.width % kBlock || w.height % kBlock || w.ws != w.width) {
+    kh::set_error("kh_map_feed_poll: the live window is not made of whole 64-cell blocks without row padding");
+    return KH_ERR_INVALID_ARG;
+  }
+  if (hipSetDevice(f->device) != hipSuccess) {return KH_ERR_HIP;}
+  // ---- 1. the published grid follows the window: a new array of -1, the old content at its place
+  if (w.ox != f->ox || w.oy != f->oy || w.width != f->width || w.height != f->height) {
+    const bool inside = f->width == 0 || (f->ox >= w.ox && f->oy >= w.oy && static_cast<int64_t>(f->ox) + f->width <= static_cast<int64_t>(w.ox) + w.width &&
+      static_cast<int64_t>(f->oy) + f->height <= static_cast<int64_t>(w.oy) + w.height);
+    if (!inside) {kh::set_error("kh_map_feed_poll: the live window shrank"); return KH_ERR_INVALID_ARG;}
+    const size_t size = static_cast<size_t>(w.width) * static_cast<size_t>(w.height);
+    int8_t * d_new = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&d_new), size) != hipSuccess) {
+      (void)hipGetLastError();
+      kh::set_error("kh_map_feed_poll: published grid allocation failed");
+      return KH_ERR_HIP;                       // (the feed is as it was, its region still pending)
+    }
+    bool ok = hipMemsetAsync(d_new, 0xFF, size, g->stream) == hipSuccess;
+    if (ok && f->width > 0) {
+      const size_t at = static_cast<size_t>(f->ox - w.ox) + static_cast<size_t>(f->oy - w.oy) * static_cast<size_t>(w.width);
+      ok = hipMemcpy2DAsync(d_new + at, static_cast<size_t>(w.width), f->d_pub, static_cast<size_t>(f->width), static_cast<size_t>(f->width),
+          static_cast<size_t>(f->height), hipMemcpyDeviceToDevice, g->stream) == hipSuccess;
+    }
+    if (!ok || hipStreamSynchronize(g->stream) != hipSuccess) {
+      const int rc = kh::fail_feed(f, "relayout");
+      (void)hipFree(d_new);
+      return rc;
+    }
+    (void)hipFree(f->d_pub);
+    f->d_pub = d_new; f->ox = w.ox; f->oy = w.oy; f->width = w.width; f->height = w.height;
+    f->pending_whole = true;                   // (a window that grew was given to the cell-state kernel whole: this restates it)
+  }
+  // ---- 2. the pending region, rounded outward to whole tiles and clipped to the window
+  const int64_t wx1 = static_cast<int64_t>(f->ox) + f->width, wy1 = static_cast<int64_t>(f->oy) + f->height;
+  int64_t x0 = f->ox, y0 = f->oy, x1 = wx1, y1 = wy1;
+  if (!f->pending_whole) {
+    x0 = std::max<int64_t>(f->x0, f->ox); y0 = std::max<int64_t>(f->y0, f->oy); x1 = std::min(f->x1, wx1); y1 = std::min(f->y1, wy1);
+  }
+  if (x1 <= x0 || y1 <= y0) {f->pending_whole = false; f->pending_rect = false; return done();}
+  NavFeedJob job;
+  job.tx0 = static_cast<int32_t>(kh::floor_div(x0, kMapTile)); job.ty0 = static_cast<int32_t>(kh::floor_div(y0, kMapTile));
+  job.tx1 = static_cast<int32_t>(kh::floor_div(x1 - 1, kMapTile) + 1); job.ty1 = static_cast<int32_t>(kh::floor_div(y1 - 1, kMapTile) + 1);
+  // (the window is made of whole tiles, so the rounding cannot leave it; the clamp is a guard)
+  job.tx0 = std::max<int32_t>(job.tx0, f->ox / kMapTile); job.ty0 = std::max<int32_t>(job.ty0, f->oy / kMapTile);
+  job.tx1 = std::min<int32_t>(job.tx1, static_cast<int32_t>(wx1 / kMapTile)); job.ty1 = std::min<int32_t>(job.ty1, static_cast<int32_t>(wy1 / kMapTile));
+  const int64_t tiles = static_cast<int64_t>(job.tx1 - job.tx0) * (job.ty1 - job.ty0);
+  if (tiles > f->cap_tiles) {
+    (void)hipFree(f->d_xy); (void)hipFree(f->d_packed);
+    f->d_xy = nullptr; f->d_packed = nullptr; f->cap_tiles = 0;
+    if (hipMalloc(reinterpret_cast<void **>(&f->d_xy), static_cast<size_t>(tiles) * 2 * sizeof(int32_t)) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void **>(&f->d_packed), static_cast<size_t>(tiles) * kTileWords * sizeof(uint32_t)) != hipSuccess)
+    {
+      (void)hipGetLastError();
+      (void)hipFree(f->d_xy); f->d_xy = nullptr;
+      kh::set_error("kh_map_feed_poll: tile buffer allocation failed");
+      return KH_ERR_HIP;
+    }
+    f->cap_tiles = tiles;
+  }
+  job.cells = w.cells; job.cells_ox = w.ox; job.cells_oy = w.oy; job.cells_ws = w.ws;
+  job.published = f->d_pub; job.pub_ox = f->ox; job.pub_oy = f->oy; job.pub_ws = f->width;
+  job.count = f->d_count; job.tile_xy = f->d_xy; job.packed = f->d_packed;
+  // ---- 3. compare and pack
+  if (hipMemsetAsync(f->d_count, 0, sizeof(uint32_t), g->stream) != hipSuccess) {return kh::fail_feed(f, "count");}
+  (void)hipEventRecord(f->ev[0], g->stream);
+  kh::nav_feed(g->stream, job);
+  (void)hipEventRecord(f->ev[1], g->stream);
+  // ---- 4. the count, then that many coordinates and tiles
+  uint32_t count = 0;
+  if (hipMemcpyAsync(&count, f->d_count, sizeof(count), hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
+    hipStreamSynchronize(g->stream) != hipSuccess) {return kh::fail_feed(f, "compare");}
+  if (static_cast<int64_t>(count) > tiles) {kh::set_error("kh_map_feed_poll: more tiles reported than compared"); f->pending_whole = true; return KH_ERR_HIP;}
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, f->ev[0], f->ev[1]);
+  const size_t n = count;
+  f->raw_xy.resize(2 * n); f->raw_data.resize(256 * n);
+  if (n > 0 && (hipMemcpyAsync(f->raw_xy.data(), f->d_xy, n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
+    hipMemcpyAsync(f->raw_data.data(), f->d_packed, n * 256, hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
+    hipStreamSynchronize(g->stream) != hipSuccess)) {return kh::fail_feed(f, "download");}
+  f->pending_whole = false; f->pending_rect = false;
+  // ascending (ty, tx): the kernel deals its slots in no order
+  std::vector<uint32_t> order(n);
+  for (size_t k = 0; k < n; ++k) {order[k] = static_cast<uint32_t>(k);}
+  const int32_t * xy = f->raw_xy.data();
+  std::sort(order.begin(), order.end(), [xy](uint32_t a, uint32_t b) {
+    return xy[2 * a + 1] != xy[2 * b + 1] ? xy[2 * a + 1] < xy[2 * b + 1] : xy[2 * a] < xy[2 * b];
+  });
+  f->tile_xy.resize(2 * n); f->data.resize(256 * n);
+  int32_t bx0 = INT32_MAX, by0 = INT32_MAX, bx1 = INT32_MIN, by1 = INT32_MIN;
+  for (size_t k = 0; k < n; ++k) {
+    const int32_t tx = xy[2 * order[k]], ty = xy[2 * order[k] + 1];
+    f->tile_xy[2 * k] = tx; f->tile_xy[2 * k + 1] = ty;
+    std::memcpy(f->data.data() + 256 * k, f->raw_data.data() + 256 * static_cast<size_t>(order[k]), 256);
+    bx0 = std::min(bx0, tx); by0 = std::min(by0, ty); bx1 = std::max(bx1, tx); by1 = std::max(by1, ty);
+  }
+  // ---- 5. the counts
+  d.n_tiles = static_cast<int64_t>(n); d.tiles_scanned = tiles;
+  d.bytes_downloaded = static_cast<int64_t>(sizeof(count) + n * (2 * sizeof(int32_t) + 256));
+  d.kernel_ms = static_cast<double>(ms);
+  if (n > 0) {d.x = bx0 * kMapTile; d.y = by0 * kMapTile; d.w = (bx1 - bx0 + 1) * kMapTile; d.h = (by1 - by0 + 1) * kMapTile;}
+  return done();
+}
+
+int kh_map_feed_tiles(const kh_map_feed * f, int32_t * tile_xy, int8_t * data)
+{
+  if (!f) {return KH_ERR_INVALID_ARG;}
+  if (tile_xy && !f->tile_xy.empty()) {std::memcpy(tile_xy, f->tile_xy.data(), f->tile_xy.size() * sizeof(int32_t));}
+  if (data && !f->data.empty()) {std::memcpy(data, f->data.data(), f->data.size());}
+  return KH_OK;
+}
+
+int kh_map_feed_read(kh_map_feed * f, int32_t x, int32_t y, int32_t w, int32_t h, int8_t * out)
+{
+  if (!f || w < 0 || h < 0 || static_cast<int64_t>(w) * h > INT32_MAX) {return KH_ERR_INVALID_ARG;}
+  if (w == 0 || h == 0) {return KH_OK;}
+  if (!out) {return KH_ERR_INVALID_ARG;}
+  std::memset(out, 0xFF, static_cast<size_t>(w) * static_cast<size_t>(h));
+  const int64_t x0 = std::max<int64_t>(x, f->ox), y0 = std::max<int64_t>(y, f->oy);
+  const int64_t x1 = std::min<int64_t>(static_cast<int64_t>(x) + w, static_cast<int64_t>(f->ox) + f->width);
+  const int64_t y1 = std::min<int64_t>(static_cast<int64_t>(y) + h, static_cast<int64_t>(f->oy) + f->height);
+  if (x1 <= x0 || y1 <= y0) {return KH_OK;}
+  if (hipSetDevice(f->device) != hipSuccess) {return KH_ERR_HIP;}
+  const int8_t * src = f->d_pub + (x0 - f->ox) + (y0 - f->oy) * f->width;
+  int8_t * dst = out + (x0 - x) + (y0 - y) * static_cast<int64_t>(w);
+  if (hipMemcpy2D(dst, static_cast<size_t>(w), src, static_cast<size_t>(f->width), static_cast<size_t>(x1 - x0), static_cast<size_t>(y1 - y0),
+      hipMemcpyDeviceToHost) != hipSuccess)
+  {
+    kh::set_error(std::string("kh_map_feed_read: ") + hipGetErrorString(hipGetLastError()));
+    return KH_ERR_HIP;
+  }
+  return KH_OK;
+}
+
+int kh_map_feed_stats(const kh_map_feed * f, kh_map_feed_stats_t * out)
+{
+  if (!f || !out) {return KH_ERR_INVALID_ARG;}
+  *out = f->stats;
   return KH_OK;
 }
 

@@ -254,6 +254,81 @@ __global__ __launch_bounds__(256) void k_occ_trace_delta(
   }
 }
 
+// ---- nav_msgs/OccupancyGrid values (vis_utils::toNavMap, visualization_utils.hpp:108-146) ----
+// Four cell states of one dword at once: 0 (unknown) -> -1 (0xFF), 100 (occupied) -> 100, 255 (free) -> 0.  Of the three states
+// bit 2 is set in 100 and 255 and bit 7 in 255 only; a 0 / 1 byte times 0xFF is a 0x00 / 0xFF byte and carries nothing.
+__device__ __forceinline__ uint32_t occ_nav4(uint32_t v)
+{
+  const uint32_t known = (v >> 2) & 0x01010101u, is_free = (v >> 7) & 0x01010101u;
+  return (v & ~(is_free * 0xFFu)) | ((known ^ 0x01010101u) * 0xFFu);
+}
+
+// toNavMap of a whole grid (kh_occupancy_read_nav): from the ws-strided cells into a DENSE width x height array, so that an output
+// dword may span rows (any width, width < 4 too).  One thread per output dword; the bytes past `total` of the last one are padding
+// of the buffer.
+__global__ __launch_bounds__(256) void k_occ_to_nav(const uint8_t * __restrict__ cells, int32_t width, int32_t ws, int64_t total,
+  uint32_t * __restrict__ out)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t k = 4 * i;
+  if (k >= total) {return;}
+  int64_t y = k / width;
+  int32_t x = (int32_t)(k - y * width);
+  uint32_t v = 0;
+  for (int32_t b = 0; b < 4 && k + b < total; ++b) {
+    v |= (uint32_t)cells[x + y * ws] << (8 * b);
+    if (++x == width) {x = 0; ++y;}
+  }
+  out[i] = occ_nav4(v);
+}
+
+// The map feed's compare-and-pack (kh_map_feed_poll).  One wave per STRIP of four horizontally adjacent
+// tiles, 64 cells x 16 rows: a load instruction of the wave reads four whole 64-byte row segments.  A lane owns the dword column
+// lane & 15 of the strip -- so tile (lane & 15) >> 2 -- and the rows lane >> 4, + 4, + 8, + 12.  It turns its four dwords of cell
+// states into nav values, compares them with the same four dwords of the published grid, and a ballot masked per tile says which
+// of the four tiles changed.  A changed tile takes a slot (one atomic per wave) and its lanes write the new values to the packed
+// buffer and to the published grid, and the tile's coordinates; an unchanged tile writes nothing.  Slots are dealt in no order: the
+// host sorts the coordinates.  Strips are aligned to 64 lattice cells, as both windows are, so every dword is aligned; the tiles
+// of a strip outside [tx0, tx1) are not read.
+__global__ __launch_bounds__(256) void k_nav_feed(NavFeedJob j, int32_t strip0, int32_t strips_x, int64_t n_strips)
+{
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (wave >= n_strips) {return;}
+  const int32_t lane = threadIdx.x & 63, col = lane & 15, row0 = lane >> 4, t = col >> 2;
+  const int32_t sy = (int32_t)(wave / strips_x), sx = (int32_t)(wave - (int64_t)sy * strips_x);
+  const int32_t tx = (strip0 + sx) * kStripTiles + t, ty = j.ty0 + sy;
+  const bool active = tx >= j.tx0 && tx < j.tx1;
+  const int64_t x = (int64_t)(strip0 + sx) * (kStripTiles * kMapTile) + 4 * col, y = (int64_t)ty * kMapTile + row0;
+  const uint8_t * const src = j.cells + (x - j.cells_ox) + (y - j.cells_oy) * j.cells_ws;
+  int8_t * const pub = j.published + (x - j.pub_ox) + (y - j.pub_oy) * j.pub_ws;
+  uint32_t nav[4] = {0, 0, 0, 0};
+  uint32_t differs = 0;                                 // (bitwise, not ||: all eight loads are issued before the first is waited for)
+  if (active) {
+#pragma unroll
+    for (int32_t k = 0; k < 4; ++k) {
+      nav[k] = occ_nav4(*reinterpret_cast<const uint32_t *>(src + (int64_t)(4 * k) * j.cells_ws));
+      differs |= nav[k] ^ *reinterpret_cast<const uint32_t *>(pub + (int64_t)(4 * k) * j.pub_ws);
+    }
+  }
+  const unsigned long long changed = __ballot(differs != 0);
+  uint32_t flags = 0;                                   // bit t: tile t of the strip changed (its lanes: lane & 12 == 4 t)
+#pragma unroll
+  for (int32_t k = 0; k < kStripTiles; ++k) {flags |= (changed & (0x000F000F000F000Full << (4 * k))) ? 1u << k : 0u;}
+  if (flags == 0) {return;}                             // (the whole wave leaves: nothing of the strip is written)
+  uint32_t base = 0;
+  if (lane == 0) {base = atomicAdd(j.count, (uint32_t)__popc(flags));}
+  base = __shfl(base, 0);
+  if (!((flags >> t) & 1u)) {return;}
+  const int64_t slot = (int64_t)base + __popc(flags & ((1u << t) - 1u));
+  uint32_t * const out = j.packed + slot * kTileWords + (col & 3);
+#pragma unroll
+  for (int32_t k = 0; k < 4; ++k) {
+    out[(row0 + 4 * k) * (kMapTile / 4)] = nav[k];
+    *reinterpret_cast<uint32_t *>(pub + (int64_t)(4 * k) * j.pub_ws) = nav[k];
+  }
+  if ((lane & 0x33) == 0) {j.tile_xy[2 * slot] = tx; j.tile_xy[2 * slot + 1] = ty;}
+}
+
 }  // namespace kh
 
 using namespace kh;
@@ -269,6 +344,7 @@ struct kh_occupancy
   double trace_ms = 0.0; int64_t beams_traced = 0;
   ResidentScan * d_scans = nullptr; size_t cap_scans = 0;     // kh::occupancy_add_resident's table (capacity in bytes)
   uint8_t * d_merge = nullptr; size_t cap_merge = 0;          // kh::occupancy_add_merged's two tables (submaps, then scans; bytes)
+  uint32_t * d_nav = nullptr; size_t cap_nav = 0;             // kh_occupancy_read_nav's dense output (capacity in bytes)
 };
 
 namespace kh
@@ -377,6 +453,17 @@ void live_update_cells(void * stream, const LiveWindow & w, int32_t x0, int32_t 
   hipLaunchKernelGGL(k_occ_update_rect, dim3(static_cast<unsigned>((size + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), w, x0, y0,
     rect_w, rect_h, min_pass, threshold);
 }
+
+void nav_feed(void * stream, const NavFeedJob & job)
+{
+  if (job.tx1 <= job.tx0 || job.ty1 <= job.ty0) {return;}
+  // the strips of 4 tiles that hold tile columns [tx0, tx1): floor quotients, tiles left of the anchor are negative
+  auto strip_of = [](int32_t tx) {return tx >= 0 ? tx / kStripTiles : -((-tx + kStripTiles - 1) / kStripTiles);};
+  const int32_t strip0 = strip_of(job.tx0), strips_x = strip_of(job.tx1 - 1) - strip0 + 1;
+  const int64_t n_strips = static_cast<int64_t>(strips_x) * (job.ty1 - job.ty0);
+  hipLaunchKernelGGL(k_nav_feed, dim3(static_cast<unsigned>((n_strips + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), job, strip0,
+    strips_x, n_strips);
+}
 }  // namespace kh
 
 extern "C" {
@@ -442,6 +529,7 @@ void kh_occupancy_destroy(kh_occupancy * g)
   (void)hipSetDevice(g->device);
   if (g->stream) {(void)hipStreamSynchronize(g->stream);}
   (void)hipFree(g->dev.pass); (void)hipFree(g->dev.hits); (void)hipFree(g->dev.cells); (void)hipFree(g->d_beams); (void)hipFree(g->d_scans); (void)hipFree(g->d_merge);
+  (void)hipFree(g->d_nav);
   if (g->h_beams) {(void)hipHostFree(g->h_beams);}
   if (g->ev[0]) {(void)hipEventDestroy(g->ev[0]);}
   if (g->ev[1]) {(void)hipEventDestroy(g->ev[1]);}
@@ -517,6 +605,26 @@ int kh_occupancy_read(kh_occupancy * g, uint8_t * cells, uint32_t * pass, uint32
   if (cells && hipMemcpy(cells, g->dev.cells, size, hipMemcpyDeviceToHost) != hipSuccess) {return KH_ERR_HIP;}
   if (pass && hipMemcpy(pass, g->dev.pass, size * 4, hipMemcpyDeviceToHost) != hipSuccess) {return KH_ERR_HIP;}
   if (hits && hipMemcpy(hits, g->dev.hits, size * 4, hipMemcpyDeviceToHost) != hipSuccess) {return KH_ERR_HIP;}
+  return KH_OK;
+}
+
+int kh_occupancy_read_nav(kh_occupancy * g, int8_t * out)
+{
+  if (!g || !out) {return KH_ERR_INVALID_ARG;}
+  if (hipSetDevice(g->device) != hipSuccess) {return KH_ERR_HIP;}
+  const int64_t total = static_cast<int64_t>(g->dev.width) * g->dev.height, words = (total + 3) / 4;
+  if (!grow_device(g, reinterpret_cast<void **>(&g->d_nav), &g->cap_nav, static_cast<size_t>(words) * 4, static_cast<size_t>(words) * 4)) {
+    set_error("kh_occupancy_read_nav: output allocation failed");
+    return KH_ERR_HIP;
+  }
+  hipLaunchKernelGGL(k_occ_to_nav, dim3(static_cast<unsigned>((words + 255) / 256)), dim3(256), 0, g->stream, g->dev.cells, g->dev.width,
+    g->dev.ws, total, g->d_nav);
+  if (hipMemcpyAsync(out, g->d_nav, static_cast<size_t>(total), hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
+    hipStreamSynchronize(g->stream) != hipSuccess)
+  {
+    set_error(std::string("kh_occupancy_read_nav: ") + hipGetErrorString(hipGetLastError()));
+    return KH_ERR_HIP;
+  }
   return KH_OK;
 }
 

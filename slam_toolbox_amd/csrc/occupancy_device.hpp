@@ -1,6 +1,6 @@
 // What the occupancy module shares between occupancy.hip (the kernels and their launchers) and the host files that feed it:
 // mapper_host.cpp (kh_mapper_build_map), merge.cpp (kh_merge_build), live_map.cpp (kh_live_map_*).  Not part of the public ABI
-// (include/karto_hip.h).  The live map's lattice, window and log are stated in DESIGN.md section 7b.
+// (include/karto_hip.h).  The live map's lattice, window and log are stated in DESIGN.md section 7b, the map feed's tiles in 7c.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -90,6 +90,25 @@ static_assert(sizeof(DeltaRecord) == 48, "one record = 6 x 8 bytes");
 //                                far below 2^29)
 inline int64_t live_log_slot_words(int32_t n_beams) {return 2 + 2 * static_cast<int64_t>(n_beams);}
 
+// ---- the map feed (kh_map_feed_*) ----
+constexpr int32_t kMapTile = KH_MAP_TILE;            // a tile: kMapTile x kMapTile lattice cells
+constexpr int32_t kStripTiles = 4;                   // k_nav_feed: one wave compares a strip of 4 tiles, 64 cells x 16 rows
+constexpr int32_t kTileWords = kMapTile * kMapTile / 4;      // dwords of a packed tile
+static_assert(kMapTile == 16 && kStripTiles * kMapTile == 64, "k_nav_feed's lane layout is written for 64 x 16 strips");
+
+// one launch of k_nav_feed: tile columns [tx0, tx1) and tile rows [ty0, ty1) of the lattice, inside both windows
+struct NavFeedJob
+{
+  const uint8_t * cells;     // the live window's cell states, lattice cell (cells_ox, cells_oy) first, row stride cells_ws
+  int8_t * published;        // the feed's published grid, lattice cell (pub_ox, pub_oy) first, row stride pub_ws
+  int32_t cells_ox, cells_oy, cells_ws;
+  int32_t pub_ox, pub_oy, pub_ws;
+  int32_t tx0, ty0, tx1, ty1;
+  uint32_t * count;          // changed tiles so far: a tile's slot of the two arrays below
+  int32_t * tile_xy;         // 2 per slot: tx, ty
+  uint32_t * packed;         // kTileWords per slot: the tile's new nav values, row-major
+};
+
 // ---- the launchers (occupancy.hip) ----
 // the stream the grid's kernels run on: uploads a caller queues there are in place before the next trace reads them
 void * occupancy_stream(kh_occupancy * g);
@@ -108,4 +127,7 @@ void live_trace_delta(void * stream, const LiveWindow & w, double anchor_x, doub
 // k_occ_update's rule over window columns [x0, x0 + w) and rows [y0, y0 + h) (columns may reach into the row padding)
 void live_update_cells(void * stream, const LiveWindow & w, int32_t x0, int32_t y0, int32_t rect_w, int32_t rect_h, uint32_t min_pass,
   double threshold);
+// k_nav_feed over the job's tiles on `stream`: every tile whose nav values differ from the published grid takes a slot, in no
+// particular order.  The caller has set *job.count to 0 and holds room for every tile of the job.
+void nav_feed(void * stream, const NavFeedJob & job);
 }  // namespace kh

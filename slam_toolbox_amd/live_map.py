@@ -7,6 +7,13 @@ are brought up to date by the difference since the last update (include/karto_hi
     cells = live.cells()               # (height, width_step) uint8: 0 unknown, 100 occupied, 255 free
     live.close()                       # before mapper.close()
 
+The way out for a consumer that wants nav_msgs/OccupancyGrid values and only what changed (kh_map_feed_*):
+
+    feed = live.feed()                 # one per consumer
+    delta, tile_xy, data = feed.poll() # after live.update(): the 16 x 16 tiles whose values changed since the last poll
+    full = feed.read(x, y, w, h)       # any lattice rectangle of what the consumer has been told, -1 outside
+    feed.close()                       # before live.close()
+
 Nothing here computes: every call lands in the library."""
 from __future__ import annotations
 
@@ -61,11 +68,56 @@ class LiveMap:
         return {"last": counts(st.last), "total": counts(st.total), "updates": st.updates, "scans_in_map": st.scans_in_map,
                 "log_bytes": st.log_bytes}
 
+    def feed(self) -> "MapFeed":
+        """kh_map_feed_create: a feed of changed tiles for one consumer.  Close it before the live map."""
+        return MapFeed(self)
+
     def close(self):
         if self._h:
             capi.lib().kh_live_map_destroy(self._h)
             self._h = C.c_void_p()
         self._mapper = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MapFeed:
+    def __init__(self, live: LiveMap):
+        self._live = live                  # the feed borrows the live map: keep it alive
+        self._h = C.c_void_p()
+        capi.check(capi.lib().kh_map_feed_create(live._h, C.byref(self._h)), "kh_map_feed_create")
+
+    def poll(self):
+        """kh_map_feed_poll + kh_map_feed_tiles -> (delta dict, tile_xy (n, 2) int32 of (tx, ty), data (n, 16, 16) int8), the tiles
+        in ascending (ty, tx) order"""
+        d = capi.KhMapFeedDelta()
+        capi.check(capi.lib().kh_map_feed_poll(self._h, C.byref(d)), "kh_map_feed_poll")
+        delta = {k: getattr(d, k) for k, _ in capi.KhMapFeedDelta._fields_}
+        t = capi.KH_MAP_TILE
+        xy, data = np.zeros((d.n_tiles, 2), dtype=np.int32), np.zeros((d.n_tiles, t, t), dtype=np.int8)
+        capi.check(capi.lib().kh_map_feed_tiles(self._h, xy.ctypes.data, data.ctypes.data), "kh_map_feed_tiles")
+        return delta, xy, data
+
+    def read(self, x: int, y: int, w: int, h: int) -> np.ndarray:
+        """kh_map_feed_read: lattice cells [x, x + w) x [y, y + h) of the published grid as (h, w) int8, -1 outside the window"""
+        out = np.zeros((int(h), int(w)), dtype=np.int8)
+        capi.check(capi.lib().kh_map_feed_read(self._h, int(x), int(y), int(w), int(h), out.ctypes.data), "kh_map_feed_read")
+        return out
+
+    def stats(self) -> dict:
+        st = capi.KhMapFeedStats()
+        capi.check(capi.lib().kh_map_feed_stats(self._h, C.byref(st)), "kh_map_feed_stats")
+        return {k: getattr(st, k) for k, _ in capi.KhMapFeedStats._fields_}
+
+    def close(self):
+        if self._h:
+            capi.lib().kh_map_feed_destroy(self._h)
+            self._h = C.c_void_p()
+        self._live = None
 
     def __del__(self):
         try:

@@ -79,6 +79,13 @@ class OccupancyGrid:
         capi.check(capi.lib().kh_occupancy_read(self._h, out.ctypes.data, None, None), "kh_occupancy_read")
         return out.reshape(self.height, self.width_step)
 
+    def nav(self):
+        """kh_occupancy_read_nav: (height, width) int8 without row padding, the data of a nav_msgs/OccupancyGrid (vis_utils::toNavMap):
+        -1 unknown, 100 occupied, 0 free"""
+        out = np.zeros((self.height, self.width), dtype=np.int8)
+        capi.check(capi.lib().kh_occupancy_read_nav(self._h, out.ctypes.data), "kh_occupancy_read_nav")
+        return out
+
     def counters(self):
         p = np.zeros(self.width_step * self.height, dtype=np.uint32)
         h = np.zeros(self.width_step * self.height, dtype=np.uint32)
