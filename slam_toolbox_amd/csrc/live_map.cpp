@@ -5,68 +5,50 @@
 // The counters are integer sums over beams, so a scan leaves the map exactly as it entered it -- provided the same cells are
 // walked.  The map therefore keeps a log of what it traced (the end cell and two flags per beam, the sensor cell per scan) on a
 // lattice that never moves: a fixed anchor and resolution, with a window of cells that grows in blocks.  DESIGN.md section 7b
-// states the lattice, the window rule, the log and the rebuild policy; tests/live_map_rule.py restates the window rule.
+// states the lattice, the window rule, the log and the rebuild policy.
 //
-// This file is the host side: classification of the mapper's scans against the log (new / gone / moved), the window, the log's
-// slots, the delta table.  The kernels are in occupancy.hip (k_occ_trace_delta, k_occ_update_rect).
+// The host's rules -- classification of the mapper's scans against the log (new / gone / moved), the window, the log's slots, the
+// touched rectangle, the feed's tile job -- are plain functions in live_map_plan.hpp, checked on the CPU by
+// tests/test_live_map_plan.py.  This file is what needs the device: kh_live_map_update plans with them and then runs its stages
+// (re-layout, log, records, launch, commit), kh_map_feed_poll likewise; each states its failure rule at its top.  The kernels are
+// in occupancy.hip (k_occ_trace_delta, k_occ_update_rect, k_nav_feed).
 //
 // The map feed (kh_map_feed_*) is at the end: the published grid of one consumer, the pending region the
-// updates leave it, and the poll that hands out the 16 x 16 tiles whose nav values changed (k_nav_feed, occupancy.hip).
+// updates leave it, and the poll that hands out the 16 x 16 tiles whose nav values changed.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <limits>
 #include <string>
 #include <vector>
 
 #include "../../include/karto_hip.h"
 #include "occupancy_device.hpp"
+#include "live_map_plan.hpp"
 #include "mapper_internal.hpp"
 
-namespace kh
-{
-void set_error(const std::string & s);
+using namespace kh;
 
 namespace
 {
-constexpr int32_t kBlock = 64;              // the window grows in blocks of kBlock x kBlock lattice cells
-constexpr int32_t kMargin = 2;              // cells beyond ceil(range_threshold * scale) the window keeps around a sensor cell
 constexpr double kDefaultRebuildFraction = 0.5;      // provisional: the crossover has not been measured yet
-constexpr double kCellLimit = 1073741824.0;          // |cell index| a scan may have (2^30): index +- reach stays an int32
-
-int32_t floor_block(int64_t c) {return static_cast<int32_t>((c >= 0 ? c / kBlock : -((-c + kBlock - 1) / kBlock)) * kBlock);}
-
-struct Entry
-{
-  int32_t slot = -1;         // slot of the log, -1 = the scan is not in the map
-  int32_t cx = 0, cy = 0;    // the sensor cell the log holds
-  double sensor[3] = {0.0, 0.0, 0.0};      // the sensor pose the scan was traced at
-};
-
-struct Window {int64_t ox = 0, oy = 0, width = 0, height = 0;};
-}  // namespace
-}  // namespace kh
-
-using namespace kh;
+}
 
 struct kh_live_map
 {
   kh_mapper * mapper = nullptr;
   int32_t device = 0;
   kh_laser laser;
-  double ax = 0.0, ay = 0.0, resolution = 0.05, scale = 20.0, rebuild_fraction = kDefaultRebuildFraction;
-  int64_t reach = 0;                         // ceil(range_threshold * scale) + kMargin
+  Lattice lat;
+  double resolution = 0.05, rebuild_fraction = kDefaultRebuildFraction;
   hipStream_t stream = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};
   LiveWindow win = {0, 0, 0, 0, 0, nullptr, nullptr, nullptr};
-  int32_t * d_log = nullptr; int64_t cap_slots = 0, next_slot = 0;
-  std::vector<int32_t> free_slots;
-  std::vector<Entry> entries;                // by scan id
-  std::vector<int32_t> logged;               // ids of the scans in the map, ascending
-  DeltaRecord * d_records = nullptr; size_t cap_records = 0;
+  int32_t * d_log = nullptr; size_t cap_log = 0;             // capacity in bytes, whole slots
+  HostLog log;                               // the host's copy: who is in the map, in which slot, traced at which pose
+  DeltaRecord * d_records = nullptr; size_t cap_records = 0;             // capacity in bytes
   unsigned long long * d_counters = nullptr;
   bool have_params = false; uint32_t min_pass = 0; double threshold = 0.0;
   bool all_cells_stale = true;               // the next update runs the cell-state kernel over the whole window
@@ -79,13 +61,14 @@ struct kh_map_feed
 {
   kh_live_map * live = nullptr;              // nullptr once the live map has been destroyed under the feed
   int32_t device = 0;
-  int32_t ox = 0, oy = 0, width = 0, height = 0;       // the window the published grid covers; its row stride is width
+  Rect window;                               // the window the published grid covers; its row stride is the window's width
   int8_t * d_pub = nullptr;
-  // the pending region in lattice cells: the whole window, or the union [x0, x1) x [y0, y1) of what the updates handed over
-  bool pending_whole = true, pending_rect = false;
-  int64_t x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+  // the pending region in lattice cells: the whole window, or the union of what the updates handed over (empty = nothing)
+  bool pending_whole = true;
+  Rect pending;
   uint32_t * d_count = nullptr;
-  int32_t * d_xy = nullptr; uint32_t * d_packed = nullptr; int64_t cap_tiles = 0;
+  int32_t * d_xy = nullptr; size_t cap_xy = 0;               // capacities in bytes
+  uint32_t * d_packed = nullptr; size_t cap_packed = 0;
   hipEvent_t ev[2] = {nullptr, nullptr};
   std::vector<int32_t> tile_xy, raw_xy;      // the last poll's tiles in ascending (ty, tx) order / as the kernel dealt the slots
   std::vector<int8_t> data, raw_data;
@@ -93,56 +76,224 @@ struct kh_map_feed
   kh_map_feed_stats_t stats;
 };
 
-namespace kh
-{
 namespace
 {
-bool cell_of(const kh_live_map * g, const double sensor[3], int32_t * cx, int32_t * cy)
-{
-  // the operations of occ_cell (occupancy.hip): o_to_int(o_round((x - anchor) * scale))
-  const double x = round_half_away((sensor[0] - g->ax) * g->scale), y = round_half_away((sensor[1] - g->ay) * g->scale);
-  if (!(std::fabs(x) < kCellLimit && std::fabs(y) < kCellLimit)) {return false;}
-  *cx = static_cast<int32_t>(x); *cy = static_cast<int32_t>(y);
-  return true;
-}
-
 void free_window(LiveWindow & w)
 {
   (void)hipFree(w.pass); (void)hipFree(w.hits); (void)hipFree(w.cells);
   w.pass = nullptr; w.hits = nullptr; w.cells = nullptr;
 }
 
+// A plane for a window that grew: ws x height elements of `elem` bytes filled with byte `fill`, the old plane (old_w x old_h
+// elements, row stride old_ws; nullptr = there is none to keep) copied in at column dx, row dy -- all queued on `stream`.  The
+// caller synchronises once and swaps only after everything succeeded.  hipErrorOutOfMemory = the allocation failed.
+hipError_t new_plane(hipStream_t stream, void ** out, size_t ws, size_t height, size_t elem, int fill, const void * old, size_t old_ws,
+  size_t old_w, size_t old_h, size_t dx, size_t dy)
+{
+  *out = nullptr;
+  if (hipMalloc(out, ws * height * elem) != hipSuccess) {(void)hipGetLastError(); *out = nullptr; return hipErrorOutOfMemory;}
+  hipError_t err = hipMemsetAsync(*out, fill, ws * height * elem, stream);
+  if (err == hipSuccess && old && old_w > 0 && old_h > 0) {
+    err = hipMemcpy2DAsync(static_cast<char *>(*out) + (dx + dy * ws) * elem, ws * elem, old, old_ws * elem, old_w * elem, old_h,
+        hipMemcpyDeviceToDevice, stream);
+  }
+  return err;
+}
+
+int fail_hip(hipStream_t stream, const char * who, const char * what)
+{
+  const hipError_t err = hipGetLastError();
+  (void)hipStreamSynchronize(stream);
+  set_error(std::string(who) + ": " + what + ": " + hipGetErrorString(err));
+  return KH_ERR_HIP;
+}
+
+// ---------------------------------------------------------------- the stages of kh_live_map_update
+
+// The one statement of "after a failure past the point of no return the next update rebuilds": alive from the first thing queued
+// on the map's own arrays to the commit.
+struct RebuildNextUnlessCommitted
+{
+  kh_live_map * g;
+  bool committed = false;
+  ~RebuildNextUnlessCommitted() {if (!committed) {g->counters_suspect = true;}}
+};
+
+// what the device stages leave for the commit
+struct Traced
+{
+  std::vector<DeltaRecord> records;          // the delta table (it outlives the copy that reads it)
+  unsigned long long counters[2] = {0, 0};
+  float ms = 0.f;
+  bool relayout = false, given_whole = false;
+  Rect given;                                // the cells handed to the cell-state kernel, window columns and rows
+  int64_t cells_given = 0;
+};
+
+// classify, window, slots: on the plan alone.  A refusal leaves the map untouched.
+int plan_stage(const kh_live_map * g, const std::vector<SensorView> & views, UpdatePlan & plan)
+{
+  if (!plan_update(g->lat, views, g->log, rect_of(g->win), g->counters_suspect, g->rebuild_fraction, plan)) {
+    set_error("kh_live_map_update: scan " + std::to_string(plan.too_far) + " is too far from the anchor for this resolution");
+    return KH_ERR_INVALID_ARG;
+  }
+  if (plan.window != rect_of(g->win) && grid_too_large(plan.window.width(), plan.window.height())) {
+    set_error("kh_live_map_update: the window would be " + std::to_string(plan.window.width()) + " x " + std::to_string(plan.window.height()) +
+      " cells, beyond the size cap of an occupancy grid");
+    return KH_ERR_INVALID_ARG;
+  }
+  return KH_OK;
+}
+
+// The window grew: new arrays, the counters copied to their new place (a rebuild starts from zero, and the cell states are
+// computed anew either way).  A failure leaves the map as it was.
+int relayout_stage(kh_live_map * g, const UpdatePlan & plan, Traced & t)
+{
+  if (plan.window == rect_of(g->win)) {return KH_OK;}
+  const LiveWindow & old = g->win;
+  LiveWindow w;
+  w.ox = static_cast<int32_t>(plan.window.x0); w.oy = static_cast<int32_t>(plan.window.y0);
+  w.width = static_cast<int32_t>(plan.window.width()); w.height = static_cast<int32_t>(plan.window.height()); w.ws = (w.width + 7) & ~7;
+  w.pass = nullptr; w.hits = nullptr; w.cells = nullptr;
+  const bool keep = old.width > 0 && !plan.rebuild;
+  const size_t ws = static_cast<size_t>(w.ws), height = static_cast<size_t>(w.height), old_ws = static_cast<size_t>(old.ws);
+  const size_t old_w = static_cast<size_t>(old.width), old_h = static_cast<size_t>(old.height);
+  const size_t dx = static_cast<size_t>(old.ox - w.ox), dy = static_cast<size_t>(old.oy - w.oy);
+  hipError_t err = new_plane(g->stream, reinterpret_cast<void **>(&w.pass), ws, height, 4, 0, keep ? old.pass : nullptr, old_ws, old_w, old_h, dx, dy);
+  if (err == hipSuccess) {err = new_plane(g->stream, reinterpret_cast<void **>(&w.hits), ws, height, 4, 0, keep ? old.hits : nullptr, old_ws, old_w, old_h, dx, dy);}
+  if (err == hipSuccess) {err = new_plane(g->stream, reinterpret_cast<void **>(&w.cells), ws, height, 1, 0, nullptr, 0, 0, 0, 0, 0);}
+  if (err == hipSuccess) {err = hipStreamSynchronize(g->stream);}
+  if (err != hipSuccess) {
+    int rc = KH_ERR_HIP;
+    if (err == hipErrorOutOfMemory) {
+      (void)hipStreamSynchronize(g->stream);
+      set_error("kh_live_map_update: window allocation failed");
+    } else {
+      rc = fail_hip(g->stream, "kh_live_map_update", "relayout");
+    }
+    free_window(w);
+    return rc;
+  }
+  free_window(g->win);
+  g->win = w;
+  g->all_cells_stale = true;
+  t.relayout = true;
+  return KH_OK;
+}
+
+// room in the log for the slots the plan dealt; what the log holds is kept unless a rebuild forgets it
+int log_stage(kh_live_map * g, const UpdatePlan & plan)
+{
+  const size_t slot_bytes = static_cast<size_t>(live_log_slot_words(g->laser.n_beams)) * 4;
+  const size_t slots = static_cast<size_t>(plan.next_slot), cap = std::max<size_t>(slots + slots / 2, 64);
+  const size_t used = plan.rebuild ? 0 : static_cast<size_t>(g->log.next_slot) * slot_bytes;
+  const hipError_t err = grow_device_keeping(reinterpret_cast<void **>(&g->d_log), &g->cap_log, slots * slot_bytes, cap * slot_bytes, used);
+  if (err == hipErrorOutOfMemory) {set_error("kh_live_map_update: log allocation failed"); return KH_ERR_HIP;}
+  return err == hipSuccess ? KH_OK : fail_hip(g->stream, "kh_live_map_update", "log copy");
+}
+
+// residency of what will be read, and the delta table on the device: SUB, MOVE, ADD
+int records_stage(kh_live_map * g, const UpdatePlan & plan, Traced & t)
+{
+  std::vector<int32_t> read_ids;
+  for (const Change & c : plan.moved) {read_ids.push_back(c.id);}
+  for (const Change & c : plan.added) {read_ids.push_back(c.id);}
+  std::vector<ResidentScan> resident;
+  int64_t up_points = 0, up_ranges = 0;
+  const int rc = mapper_resident_table_of(g->mapper, g->stream, "kh_live_map_update", read_ids.data(), read_ids.size(), resident, &up_points, &up_ranges);
+  if (rc) {(void)hipStreamSynchronize(g->stream); return rc;}
+  std::vector<DeltaRecord> & records = t.records;
+  records.reserve(plan.gone.size() + read_ids.size());
+  size_t k = 0;                              // of `resident`: the moved scans, then the added ones
+  auto record = [&](int32_t kind, int32_t slot, const Change * c) {
+    DeltaRecord r;
+    std::memset(&r, 0, sizeof(r));
+    r.kind = kind; r.slot = slot;
+    if (c) {
+      r.points = resident[k].points; r.ranges = resident[k].ranges; ++k;
+      r.sx = c->view->sensor[0]; r.sy = c->view->sensor[1];
+    }
+    records.push_back(r);
+  };
+  if (!plan.rebuild) {for (int32_t id : plan.gone) {record(kDeltaSub, g->log.entries[static_cast<size_t>(id)].slot, nullptr);}}
+  for (const Change & c : plan.moved) {
+    const Entry & e = g->log.entries[static_cast<size_t>(c.id)];
+    record(kDeltaMove, e.slot, &c);
+    records.back().old_cx = e.cx; records.back().old_cy = e.cy;
+  }
+  for (size_t a = 0; a < plan.added.size(); ++a) {record(kDeltaAdd, plan.new_slots[a], &plan.added[a]);}
+  const size_t bytes = records.size() * sizeof(DeltaRecord);
+  if (!grow_device(g->stream, reinterpret_cast<void **>(&g->d_records), &g->cap_records, bytes, bytes + bytes / 2)) {
+    set_error("kh_live_map_update: delta table allocation failed");
+    return KH_ERR_HIP;
+  }
+  if (bytes > 0 && hipMemcpyAsync(g->d_records, records.data(), bytes, hipMemcpyHostToDevice, g->stream) != hipSuccess) {
+    return fail_hip(g->stream, "kh_live_map_update", "delta table upload");
+  }
+  return KH_OK;
+}
+
+// the trace, then the cell states over the whole window or the rectangle the delta can have touched; returns once both have run
+int launch_stage(kh_live_map * g, const UpdatePlan & plan, uint32_t min_pass_through, double occupancy_threshold, Traced & t)
+{
+  const LiveWindow & w = g->win;
+  const size_t size = static_cast<size_t>(w.ws) * static_cast<size_t>(w.height);
+  if (plan.rebuild && size > 0 && !t.relayout &&
+    (hipMemsetAsync(w.pass, 0, size * 4, g->stream) != hipSuccess || hipMemsetAsync(w.hits, 0, size * 4, g->stream) != hipSuccess)) {
+    return fail_hip(g->stream, "kh_live_map_update", "clear");
+  }
+  if (hipMemsetAsync(g->d_counters, 0, 2 * sizeof(unsigned long long), g->stream) != hipSuccess) {return fail_hip(g->stream, "kh_live_map_update", "counters");}
+  (void)hipEventRecord(g->ev[0], g->stream);
+  live_trace_delta(g->stream, w, g->lat.ax, g->lat.ay, g->lat.scale, g->d_records, static_cast<int32_t>(t.records.size()), g->laser.n_beams,
+    g->laser.range_threshold, g->laser.minimum_range, g->laser.maximum_range, g->d_log, g->d_counters);
+  (void)hipEventRecord(g->ev[1], g->stream);
+  const bool params_changed = !g->have_params || g->min_pass != min_pass_through ||
+    std::memcmp(&g->threshold, &occupancy_threshold, sizeof(double)) != 0;
+  if (w.width > 0) {
+    t.given_whole = g->all_cells_stale || plan.rebuild || params_changed;
+    t.given = t.given_whole ? Rect{0, 0, w.ws, w.height} : touched(plan, g->log, g->lat.reach, rect_of(w));
+    t.cells_given = t.given.width() * t.given.height();
+    live_update_cells(g->stream, w, static_cast<int32_t>(t.given.x0), static_cast<int32_t>(t.given.y0), static_cast<int32_t>(t.given.width()),
+      static_cast<int32_t>(t.given.height()), min_pass_through, occupancy_threshold);
+  }
+  if (hipMemcpyAsync(t.counters, g->d_counters, sizeof(t.counters), hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
+    hipStreamSynchronize(g->stream) != hipSuccess) {return fail_hip(g->stream, "kh_live_map_update", "trace");}
+  (void)hipEventElapsedTime(&t.ms, g->ev[0], g->ev[1]);
+  return KH_OK;
+}
+
 // the cells an update handed to the cell-state kernel, for every feed attached: window columns / rows -> lattice cells
-void feeds_pending(kh_live_map * g, bool whole, int64_t wx0, int64_t wy0, int64_t wx1, int64_t wy1)
+void feeds_pending(kh_live_map * g, const Traced & t)
 {
   for (kh_map_feed * f : g->feeds) {
-    if (whole) {f->pending_whole = true; continue;}
-    const int64_t x0 = wx0 + g->win.ox, y0 = wy0 + g->win.oy, x1 = wx1 + g->win.ox, y1 = wy1 + g->win.oy;
-    if (!f->pending_rect) {f->x0 = x0; f->y0 = y0; f->x1 = x1; f->y1 = y1; f->pending_rect = true; continue;}
-    f->x0 = std::min(f->x0, x0); f->y0 = std::min(f->y0, y0); f->x1 = std::max(f->x1, x1); f->y1 = std::max(f->y1, y1);
+    if (t.given_whole) {f->pending_whole = true; continue;}
+    f->pending = f->pending.join(t.given.moved_by(g->win.ox, g->win.oy));
   }
 }
 
-int64_t floor_div(int64_t a, int64_t b) {return a >= 0 ? a / b : -((-a + b - 1) / b);}
-
-int fail_feed(kh_map_feed * f, const char * what)
+// the update has happened: the host's copy of the log, the parameters, the feeds and the stats follow
+void commit_stage(kh_live_map * g, const std::vector<SensorView> & views, const UpdatePlan & plan, const Traced & t, uint32_t min_pass_through,
+  double occupancy_threshold)
 {
-  const hipError_t err = hipGetLastError();
-  if (f->live) {(void)hipStreamSynchronize(f->live->stream);}
-  set_error(std::string("kh_map_feed_poll: ") + what + ": " + hipGetErrorString(err));
-  f->pending_whole = true;
-  return KH_ERR_HIP;
-}
-
-int fail_hip(kh_live_map * g, const char * what)
-{
-  (void)hipStreamSynchronize(g->stream);
-  set_error(std::string("kh_live_map_update: ") + what + ": " + hipGetErrorString(hipGetLastError()));
-  g->counters_suspect = true;
-  return KH_ERR_HIP;
+  commit(g->log, views, plan);
+  g->have_params = true; g->min_pass = min_pass_through; g->threshold = occupancy_threshold;
+  g->all_cells_stale = false; g->counters_suspect = false;
+  if (t.cells_given > 0) {feeds_pending(g, t);}
+  kh_live_map_counts & last = g->stats.last;
+  std::memset(&last, 0, sizeof(last));
+  last.scans_added = plan.n_added; last.scans_removed = static_cast<int64_t>(plan.gone.size()); last.scans_moved = plan.n_moved;
+  last.beams_traced = static_cast<int64_t>(t.counters[0]); last.beams_skipped = static_cast<int64_t>(t.counters[1]);
+  last.cells_updated = t.cells_given; last.relayouts = t.relayout ? 1 : 0; last.rebuilds = plan.rebuild ? 1 : 0;
+  last.trace_ms = t.records.size() == 0 ? 0.0 : static_cast<double>(t.ms);
+  kh_live_map_counts & total = g->stats.total;
+  total.scans_added += last.scans_added; total.scans_removed += last.scans_removed; total.scans_moved += last.scans_moved;
+  total.beams_traced += last.beams_traced; total.beams_skipped += last.beams_skipped; total.cells_updated += last.cells_updated;
+  total.relayouts += last.relayouts; total.rebuilds += last.rebuilds; total.trace_ms += last.trace_ms;
+  g->stats.updates += 1;
+  g->stats.scans_in_map = static_cast<int64_t>(g->log.logged.size());
+  g->stats.log_bytes = static_cast<int64_t>(g->cap_log);
 }
 }  // namespace
-}  // namespace kh
 
 extern "C" {
 
@@ -150,19 +301,14 @@ int kh_live_map_create(kh_mapper * m, double resolution, const double anchor[2],
 {
   if (!out) {return KH_ERR_INVALID_ARG;}
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    kh::set_error("no usable HIP device (libkartohip has no CPU fallback)");
-    return KH_ERR_NO_DEVICE;
-  }
+  if (require_device(0) != KH_OK) {return KH_ERR_NO_DEVICE;}
   if (!m) {return KH_ERR_INVALID_ARG;}
   if (!(resolution > 0) || !std::isfinite(resolution) || rebuild_fraction != rebuild_fraction) {
-    kh::set_error("kh_live_map_create: the resolution must be positive and finite, the rebuild fraction a number");
+    set_error("kh_live_map_create: the resolution must be positive and finite, the rebuild fraction a number");
     return KH_ERR_INVALID_ARG;
   }
   if (anchor && !(std::isfinite(anchor[0]) && std::isfinite(anchor[1]))) {
-    kh::set_error("kh_live_map_create: the anchor must be finite");
+    set_error("kh_live_map_create: the anchor must be finite");
     return KH_ERR_INVALID_ARG;
   }
   double ax, ay;
@@ -171,28 +317,24 @@ int kh_live_map_create(kh_mapper * m, double resolution, const double anchor[2],
   } else {
     // the offset kh_mapper_build_map would choose now: the minimum of the boxes of the scans still in the map
     std::vector<SensorView> views;
-    kh::mapper_sensor_poses(m, views);
-    if (views.empty()) {kh::set_error("kh_live_map_create: the default anchor needs a scan in the map"); return KH_ERR_INVALID_ARG;}
+    mapper_sensor_poses(m, views);
+    if (views.empty()) {set_error("kh_live_map_create: the default anchor needs a scan in the map"); return KH_ERR_INVALID_ARG;}
     ax = 999999999999999999.99999; ay = 999999999999999999.99999;
     for (const SensorView & v : views) {ax = v.bbox[0] < ax ? v.bbox[0] : ax; ay = v.bbox[1] < ay ? v.bbox[1] : ay;}
   }
-  const int32_t device = kh::mapper_device(m);
-  if (device < 0 || device >= ndev) {
-    kh::set_error("no usable HIP device (libkartohip has no CPU fallback)");
-    return KH_ERR_NO_DEVICE;
-  }
+  const int32_t device = mapper_device(m);
+  if (require_device(device) != KH_OK) {return KH_ERR_NO_DEVICE;}
   kh_live_map * g = new kh_live_map();
-  g->mapper = m; g->device = device; g->laser = kh::mapper_laser(m);
-  g->ax = ax; g->ay = ay; g->resolution = resolution; g->scale = 1.0 / resolution;
+  g->mapper = m; g->device = device; g->laser = mapper_laser(m);
+  g->lat.ax = ax; g->lat.ay = ay; g->resolution = resolution; g->lat.scale = 1.0 / resolution;
   g->rebuild_fraction = rebuild_fraction < 0 ? kDefaultRebuildFraction : rebuild_fraction;
-  const double reach = std::ceil(g->laser.range_threshold * g->scale) + kMargin;
-  g->reach = reach < kCellLimit ? static_cast<int64_t>(reach) : static_cast<int64_t>(kCellLimit);
+  g->lat.reach = reach_of(g->laser.range_threshold, g->lat.scale);
   std::memset(&g->stats, 0, sizeof(g->stats));
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess ||
     hipEventCreate(&g->ev[0]) != hipSuccess || hipEventCreate(&g->ev[1]) != hipSuccess ||
     hipMalloc(reinterpret_cast<void **>(&g->d_counters), 2 * sizeof(unsigned long long)) != hipSuccess)
   {
-    kh::set_error("kh_live_map_create: HIP allocation failed");
+    set_error("kh_live_map_create: HIP allocation failed");
     kh_live_map_destroy(g);
     return KH_ERR_HIP;
   }
@@ -206,7 +348,7 @@ void kh_live_map_destroy(kh_live_map * g)
   (void)hipSetDevice(g->device);
   if (g->stream) {(void)hipStreamSynchronize(g->stream);}
   for (kh_map_feed * f : g->feeds) {f->live = nullptr;}         // (feeds are to be destroyed first; one that was not must not follow us)
-  kh::free_window(g->win);
+  free_window(g->win);
   (void)hipFree(g->d_log); (void)hipFree(g->d_records); (void)hipFree(g->d_counters);
   if (g->ev[0]) {(void)hipEventDestroy(g->ev[0]);}
   if (g->ev[1]) {(void)hipEventDestroy(g->ev[1]);}
@@ -214,272 +356,37 @@ void kh_live_map_destroy(kh_live_map * g)
   delete g;
 }
 
+// The failure rule.  Up to and including the re-layout a failure -- a scan too far from the anchor, the size cap, hipSetDevice, the
+// window's allocation or a re-layout that does not complete -- leaves window, counters, cells, log and stats untouched: the plan is
+// worked out beside the map, and the new window is swapped in only once it is complete.  After any later failure the next update
+// rebuilds (RebuildNextUnlessCommitted).  The host's copy of the log changes in the commit stage alone.
 int kh_live_map_update(kh_live_map * g, uint32_t min_pass_through, double occupancy_threshold)
 {
   if (!g) {return KH_ERR_INVALID_ARG;}
-  if (g->laser.n_beams <= 0) {kh::set_error("kh_live_map_update: the laser has no beams"); return KH_ERR_INVALID_ARG;}
-  // ---- 1. classify the mapper's scans against the log (nothing is touched before the new window is known to fit)
+  if (g->laser.n_beams <= 0) {set_error("kh_live_map_update: the laser has no beams"); return KH_ERR_INVALID_ARG;}
   std::vector<SensorView> views;
-  kh::mapper_sensor_poses(g->mapper, views);
-  struct Change {int32_t id, cx, cy; const SensorView * view;};
-  std::vector<Change> added, moved;
-  std::vector<int32_t> gone;
-  {
-    size_t k = 0;
-    for (const SensorView & v : views) {
-      while (k < g->logged.size() && g->logged[k] < v.id) {gone.push_back(g->logged[k++]);}
-      const bool known = k < g->logged.size() && g->logged[k] == v.id;
-      if (known) {++k;}
-      if (known && std::memcmp(g->entries[static_cast<size_t>(v.id)].sensor, v.sensor, sizeof(v.sensor)) == 0) {continue;}
-      Change c;
-      c.id = v.id; c.view = &v;
-      if (!kh::cell_of(g, v.sensor, &c.cx, &c.cy)) {
-        kh::set_error("kh_live_map_update: scan " + std::to_string(v.id) + " is too far from the anchor for this resolution");
-        return KH_ERR_INVALID_ARG;
-      }
-      (known ? moved : added).push_back(c);
-    }
-    while (k < g->logged.size()) {gone.push_back(g->logged[k++]);}
-  }
-  const int64_t n_alive = static_cast<int64_t>(views.size()), n_delta = static_cast<int64_t>(added.size() + moved.size() + gone.size());
-  const bool rebuild = g->counters_suspect || g->rebuild_fraction == 0.0 ||
-    static_cast<double>(n_delta) > g->rebuild_fraction * static_cast<double>(n_alive);
-  // ---- 2. the window: the old one joined with the blocks around every new position
-  Window now;
-  now.ox = g->win.ox; now.oy = g->win.oy; now.width = g->win.width; now.height = g->win.height;
-  auto cover = [&](int32_t cx, int32_t cy) {
-    const int64_t x0 = kh::floor_block(cx - g->reach), x1 = static_cast<int64_t>(kh::floor_block(cx + g->reach)) + kBlock;
-    const int64_t y0 = kh::floor_block(cy - g->reach), y1 = static_cast<int64_t>(kh::floor_block(cy + g->reach)) + kBlock;
-    if (now.width == 0) {now.ox = x0; now.oy = y0; now.width = x1 - x0; now.height = y1 - y0; return;}
-    const int64_t ex = std::max(now.ox + now.width, x1), ey = std::max(now.oy + now.height, y1);
-    now.ox = std::min(now.ox, x0); now.oy = std::min(now.oy, y0);
-    now.width = ex - now.ox; now.height = ey - now.oy;
-  };
-  for (const Change & c : added) {cover(c.cx, c.cy);}
-  for (const Change & c : moved) {cover(c.cx, c.cy);}
-  const bool relayout = now.ox != g->win.ox || now.oy != g->win.oy || now.width != g->win.width || now.height != g->win.height;
-  if (relayout && (now.width + 7) * now.height > (1ll << 31) - 4096) {
-    kh::set_error("kh_live_map_update: the window would be " + std::to_string(now.width) + " x " + std::to_string(now.height) +
-      " cells, beyond the size cap of an occupancy grid");
-    return KH_ERR_INVALID_ARG;
-  }
+  mapper_sensor_poses(g->mapper, views);
+  UpdatePlan plan;
+  Traced traced;
+  int rc = plan_stage(g, views, plan);
+  if (rc != KH_OK) {return rc;}
   if (hipSetDevice(g->device) != hipSuccess) {return KH_ERR_HIP;}
-  // ---- 3. relayout: new arrays, the counters copied to their new place
-  if (relayout) {
-    LiveWindow w;
-    w.ox = static_cast<int32_t>(now.ox); w.oy = static_cast<int32_t>(now.oy);
-    w.width = static_cast<int32_t>(now.width); w.height = static_cast<int32_t>(now.height); w.ws = (w.width + 7) & ~7;
-    w.pass = nullptr; w.hits = nullptr; w.cells = nullptr;
-    const size_t size = static_cast<size_t>(w.ws) * static_cast<size_t>(w.height);
-    if (hipMalloc(reinterpret_cast<void **>(&w.pass), size * 4) != hipSuccess || hipMalloc(reinterpret_cast<void **>(&w.hits), size * 4) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void **>(&w.cells), size) != hipSuccess)
-    {
-      (void)hipGetLastError();
-      kh::free_window(w);
-      kh::set_error("kh_live_map_update: window allocation failed");
-      return KH_ERR_HIP;                       // (the map is as it was)
-    }
-    if (hipMemsetAsync(w.pass, 0, size * 4, g->stream) != hipSuccess || hipMemsetAsync(w.hits, 0, size * 4, g->stream) != hipSuccess ||
-      hipMemsetAsync(w.cells, 0, size, g->stream) != hipSuccess)
-    {
-      (void)hipStreamSynchronize(g->stream);
-      kh::free_window(w);
-      return KH_ERR_HIP;
-    }
-    if (g->win.width > 0 && !rebuild) {
-      const size_t at = static_cast<size_t>(g->win.ox - w.ox) + static_cast<size_t>(g->win.oy - w.oy) * static_cast<size_t>(w.ws);
-      const size_t row = static_cast<size_t>(g->win.width) * 4;
-      if (hipMemcpy2DAsync(w.pass + at, static_cast<size_t>(w.ws) * 4, g->win.pass, static_cast<size_t>(g->win.ws) * 4, row,
-          static_cast<size_t>(g->win.height), hipMemcpyDeviceToDevice, g->stream) != hipSuccess ||
-        hipMemcpy2DAsync(w.hits + at, static_cast<size_t>(w.ws) * 4, g->win.hits, static_cast<size_t>(g->win.ws) * 4, row,
-          static_cast<size_t>(g->win.height), hipMemcpyDeviceToDevice, g->stream) != hipSuccess)
-      {
-        (void)hipStreamSynchronize(g->stream);
-        kh::free_window(w);
-        return KH_ERR_HIP;
-      }
-    }
-    if (hipStreamSynchronize(g->stream) != hipSuccess) {kh::free_window(w); return kh::fail_hip(g, "relayout");}
-    kh::free_window(g->win);
-    g->win = w;
-    g->all_cells_stale = true;
-  }
-  // ---- 4. the log's slots
-  const int64_t n_added = static_cast<int64_t>(added.size()), n_moved = static_cast<int64_t>(moved.size());
-  if (rebuild) {
-    for (int32_t id : g->logged) {g->entries[static_cast<size_t>(id)].slot = -1;}
-    g->logged.clear(); g->free_slots.clear(); g->next_slot = 0;
-    g->all_cells_stale = true;
-    added.clear(); moved.clear();
-    for (const SensorView & v : views) {
-      Change c;
-      c.id = v.id; c.view = &v;
-      (void)kh::cell_of(g, v.sensor, &c.cx, &c.cy);                 // (every scan passed the test above or at an earlier update)
-      added.push_back(c);
-    }
-  }
-  const int64_t slots_needed = g->next_slot + std::max<int64_t>(0, static_cast<int64_t>(added.size()) - static_cast<int64_t>(g->free_slots.size()));
-  const int64_t slot_words = kh::live_log_slot_words(g->laser.n_beams);
-  if (slots_needed > g->cap_slots) {
-    const int64_t cap = std::max<int64_t>(slots_needed + slots_needed / 2, 64);
-    int32_t * d_new = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&d_new), static_cast<size_t>(cap * slot_words) * 4) != hipSuccess) {
-      (void)hipGetLastError();
-      kh::set_error("kh_live_map_update: log allocation failed");
-      g->counters_suspect = g->counters_suspect || rebuild;          // (a rebuild has already forgotten its slots)
-      return KH_ERR_HIP;
-    }
-    if (g->next_slot > 0 && hipMemcpy(d_new, g->d_log, static_cast<size_t>(g->next_slot * slot_words) * 4, hipMemcpyDeviceToDevice) != hipSuccess) {
-      (void)hipFree(d_new);
-      return kh::fail_hip(g, "log copy");
-    }
-    (void)hipFree(g->d_log);
-    g->d_log = d_new; g->cap_slots = cap;
-  }
-  // ---- 5. residency of what will be read, and the delta table: SUB, MOVE, ADD
-  std::vector<int32_t> read_ids;
-  for (const Change & c : moved) {read_ids.push_back(c.id);}
-  for (const Change & c : added) {read_ids.push_back(c.id);}
-  std::vector<ResidentScan> resident;
-  int64_t up_points = 0, up_ranges = 0;
-  int rc = kh::mapper_resident_table_of(g->mapper, g->stream, "kh_live_map_update", read_ids.data(), read_ids.size(), resident, &up_points, &up_ranges);
-  if (rc) {(void)hipStreamSynchronize(g->stream); g->counters_suspect = g->counters_suspect || rebuild; return rc;}
-  std::vector<DeltaRecord> records;
-  records.reserve(gone.size() + read_ids.size());
-  auto record = [&](int32_t kind, int32_t slot, size_t k, const Change * c) {
-    DeltaRecord r;
-    std::memset(&r, 0, sizeof(r));
-    r.kind = kind; r.slot = slot;
-    if (c) {
-      r.points = resident[k].points; r.ranges = resident[k].ranges;
-      r.sx = c->view->sensor[0]; r.sy = c->view->sensor[1];
-      const Entry & e = g->entries[static_cast<size_t>(c->id)];
-      r.old_cx = e.cx; r.old_cy = e.cy;
-    }
-    records.push_back(r);
-  };
-  if (!rebuild) {for (int32_t id : gone) {record(kDeltaSub, g->entries[static_cast<size_t>(id)].slot, 0, nullptr);}}
-  size_t k = 0;
-  for (const Change & c : moved) {record(kDeltaMove, g->entries[static_cast<size_t>(c.id)].slot, k++, &c);}
-  if (!views.empty() && g->entries.size() <= static_cast<size_t>(views.back().id)) {g->entries.resize(static_cast<size_t>(views.back().id) + 1);}
-  std::vector<int32_t> new_slots;
-  {
-    // (slots are taken from a copy of the free list: the list itself changes only once the update has succeeded)
-    size_t free_left = g->free_slots.size();
-    int64_t next = g->next_slot;
-    for (const Change & c : added) {
-      const int32_t slot = free_left > 0 ? g->free_slots[--free_left] : static_cast<int32_t>(next++);
-      new_slots.push_back(slot);
-      record(kDeltaAdd, slot, k++, &c);
-    }
-  }
-  if (records.size() > g->cap_records) {
-    (void)hipStreamSynchronize(g->stream);
-    (void)hipFree(g->d_records); g->d_records = nullptr; g->cap_records = 0;
-    const size_t cap = records.size() + records.size() / 2;
-    if (hipMalloc(reinterpret_cast<void **>(&g->d_records), cap * sizeof(DeltaRecord)) != hipSuccess) {
-      (void)hipGetLastError();
-      kh::set_error("kh_live_map_update: delta table allocation failed");
-      g->counters_suspect = g->counters_suspect || rebuild;
-      return KH_ERR_HIP;
-    }
-    g->cap_records = cap;
-  }
-  // ---- 6. the trace
-  const size_t size = static_cast<size_t>(g->win.ws) * static_cast<size_t>(g->win.height);
-  if (rebuild && size > 0 && !relayout &&
-    (hipMemsetAsync(g->win.pass, 0, size * 4, g->stream) != hipSuccess || hipMemsetAsync(g->win.hits, 0, size * 4, g->stream) != hipSuccess)) {
-    return kh::fail_hip(g, "clear");
-  }
-  if (hipMemsetAsync(g->d_counters, 0, 2 * sizeof(unsigned long long), g->stream) != hipSuccess) {return kh::fail_hip(g, "counters");}
-  if (!records.empty() &&
-    hipMemcpyAsync(g->d_records, records.data(), records.size() * sizeof(DeltaRecord), hipMemcpyHostToDevice, g->stream) != hipSuccess) {
-    return kh::fail_hip(g, "delta table upload");
-  }
-  (void)hipEventRecord(g->ev[0], g->stream);
-  kh::live_trace_delta(g->stream, g->win, g->ax, g->ay, g->scale, g->d_records, static_cast<int32_t>(records.size()), g->laser.n_beams,
-    g->laser.range_threshold, g->laser.minimum_range, g->laser.maximum_range, g->d_log, g->d_counters);
-  (void)hipEventRecord(g->ev[1], g->stream);
-  // ---- 7. cell states: the whole window, or the rectangle the delta can have touched
-  const bool params_changed = !g->have_params || g->min_pass != min_pass_through ||
-    std::memcmp(&g->threshold, &occupancy_threshold, sizeof(double)) != 0;
-  int64_t cells_given = 0;
-  bool given_whole = false;
-  int64_t gx0 = 0, gy0 = 0, gx1 = 0, gy1 = 0;                     // the rectangle given, window columns [gx0, gx1) and rows [gy0, gy1)
-  if (g->win.width > 0) {
-    if (g->all_cells_stale || params_changed) {
-      kh::live_update_cells(g->stream, g->win, 0, 0, g->win.ws, g->win.height, min_pass_through, occupancy_threshold);
-      cells_given = static_cast<int64_t>(g->win.ws) * g->win.height;
-      given_whole = true;
-    } else if (!records.empty()) {
-      int64_t x0 = std::numeric_limits<int64_t>::max(), y0 = x0, x1 = std::numeric_limits<int64_t>::min(), y1 = x1;
-      auto touch = [&](int32_t cx, int32_t cy) {
-        x0 = std::min<int64_t>(x0, cx - g->reach); x1 = std::max<int64_t>(x1, cx + g->reach);
-        y0 = std::min<int64_t>(y0, cy - g->reach); y1 = std::max<int64_t>(y1, cy + g->reach);
-      };
-      for (int32_t id : gone) {touch(g->entries[static_cast<size_t>(id)].cx, g->entries[static_cast<size_t>(id)].cy);}
-      for (const Change & c : moved) {touch(g->entries[static_cast<size_t>(c.id)].cx, g->entries[static_cast<size_t>(c.id)].cy); touch(c.cx, c.cy);}
-      for (const Change & c : added) {touch(c.cx, c.cy);}
-      x0 = std::max<int64_t>(x0 - g->win.ox, 0); y0 = std::max<int64_t>(y0 - g->win.oy, 0);
-      x1 = std::min<int64_t>(x1 - g->win.ox, g->win.width - 1); y1 = std::min<int64_t>(y1 - g->win.oy, g->win.height - 1);
-      if (x1 >= x0 && y1 >= y0) {
-        kh::live_update_cells(g->stream, g->win, static_cast<int32_t>(x0), static_cast<int32_t>(y0), static_cast<int32_t>(x1 - x0 + 1),
-          static_cast<int32_t>(y1 - y0 + 1), min_pass_through, occupancy_threshold);
-        cells_given = (x1 - x0 + 1) * (y1 - y0 + 1);
-        gx0 = x0; gy0 = y0; gx1 = x1 + 1; gy1 = y1 + 1;
-      }
-    }
-  }
-  unsigned long long counters[2] = {0, 0};
-  if (hipMemcpyAsync(counters, g->d_counters, sizeof(counters), hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
-    hipStreamSynchronize(g->stream) != hipSuccess) {return kh::fail_hip(g, "trace");}
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, g->ev[0], g->ev[1]);
-  // ---- 8. the update has happened: the host's copy of the log follows
-  for (const Change & c : moved) {
-    Entry & e = g->entries[static_cast<size_t>(c.id)];
-    e.cx = c.cx; e.cy = c.cy; std::memcpy(e.sensor, c.view->sensor, sizeof(e.sensor));
-  }
-  for (size_t a = 0; a < added.size(); ++a) {
-    Entry & e = g->entries[static_cast<size_t>(added[a].id)];
-    e.slot = new_slots[a]; e.cx = added[a].cx; e.cy = added[a].cy; std::memcpy(e.sensor, added[a].view->sensor, sizeof(e.sensor));
-    if (!g->free_slots.empty() && g->free_slots.back() == e.slot) {g->free_slots.pop_back();} else {g->next_slot = std::max<int64_t>(g->next_slot, e.slot + 1);}
-  }
-  // (the slots of the scans that left are free from the NEXT update on: this one's ADD records were dealt before)
-  if (!rebuild) {
-    for (int32_t id : gone) {
-      Entry & e = g->entries[static_cast<size_t>(id)];
-      g->free_slots.push_back(e.slot);
-      e.slot = -1;
-    }
-  }
-  g->logged.clear();
-  for (const SensorView & v : views) {g->logged.push_back(v.id);}
-  g->have_params = true; g->min_pass = min_pass_through; g->threshold = occupancy_threshold;
-  g->all_cells_stale = false; g->counters_suspect = false;
-  if (cells_given > 0) {kh::feeds_pending(g, given_whole, gx0, gy0, gx1, gy1);}
-  kh_live_map_counts & last = g->stats.last;
-  std::memset(&last, 0, sizeof(last));
-  last.scans_added = n_added; last.scans_removed = static_cast<int64_t>(gone.size()); last.scans_moved = n_moved;
-  last.beams_traced = static_cast<int64_t>(counters[0]); last.beams_skipped = static_cast<int64_t>(counters[1]);
-  last.cells_updated = cells_given; last.relayouts = relayout ? 1 : 0; last.rebuilds = rebuild ? 1 : 0;
-  last.trace_ms = records.empty() ? 0.0 : static_cast<double>(ms);
-  kh_live_map_counts & total = g->stats.total;
-  total.scans_added += last.scans_added; total.scans_removed += last.scans_removed; total.scans_moved += last.scans_moved;
-  total.beams_traced += last.beams_traced; total.beams_skipped += last.beams_skipped; total.cells_updated += last.cells_updated;
-  total.relayouts += last.relayouts; total.rebuilds += last.rebuilds; total.trace_ms += last.trace_ms;
-  g->stats.updates += 1;
-  g->stats.scans_in_map = static_cast<int64_t>(g->logged.size());
-  g->stats.log_bytes = g->cap_slots * slot_words * 4;
+  if ((rc = relayout_stage(g, plan, traced)) != KH_OK) {return rc;}
+  RebuildNextUnlessCommitted guard{g};
+  if ((rc = log_stage(g, plan)) != KH_OK) {return rc;}
+  if ((rc = records_stage(g, plan, traced)) != KH_OK) {return rc;}
+  if ((rc = launch_stage(g, plan, min_pass_through, occupancy_threshold, traced)) != KH_OK) {return rc;}
+  commit_stage(g, views, plan, traced, min_pass_through, occupancy_threshold);
+  guard.committed = true;
   return KH_OK;
 }
 
 int kh_live_map_info(const kh_live_map * g, kh_live_map_info_t * out)
 {
   if (!g || !out) {return KH_ERR_INVALID_ARG;}
-  out->anchor[0] = g->ax; out->anchor[1] = g->ay; out->resolution = g->resolution; out->rebuild_fraction = g->rebuild_fraction;
+  out->anchor[0] = g->lat.ax; out->anchor[1] = g->lat.ay; out->resolution = g->resolution; out->rebuild_fraction = g->rebuild_fraction;
   out->ox = g->win.ox; out->oy = g->win.oy; out->width = g->win.width; out->height = g->win.height; out->width_step = g->win.ws;
-  out->reach = static_cast<int32_t>(std::min<int64_t>(g->reach, INT32_MAX));
+  out->reach = static_cast<int32_t>(std::min<int64_t>(g->lat.reach, INT32_MAX));
   return KH_OK;
 }
 
@@ -504,16 +411,112 @@ int kh_live_map_stats(const kh_live_map * g, kh_live_map_stats_t * out)
 
 // ---------------------------------------------------------------- the map feed
 
+namespace
+{
+// The one statement of "after a failure the whole window is pending".
+struct WholePendingUnlessDone
+{
+  kh_map_feed * f;
+  bool done = false;
+  ~WholePendingUnlessDone() {if (!done) {f->pending_whole = true;}}
+};
+
+int finish_poll(kh_map_feed * f, kh_map_feed_delta_t * out)
+{
+  kh_map_feed_delta_t & d = f->last;
+  d.ox = static_cast<int32_t>(f->window.x0); d.oy = static_cast<int32_t>(f->window.y0);
+  d.width = static_cast<int32_t>(f->window.width()); d.height = static_cast<int32_t>(f->window.height());
+  f->stats.polls += 1; f->stats.n_tiles += d.n_tiles; f->stats.tiles_scanned += d.tiles_scanned;
+  f->stats.bytes_downloaded += d.bytes_downloaded; f->stats.kernel_ms += d.kernel_ms;
+  *out = d;
+  return KH_OK;
+}
+
+// the published grid follows the window: a new array of -1, the old content at its place
+int follow_window_stage(kh_map_feed * f, const LiveWindow & w)
+{
+  const Rect now = rect_of(w);
+  if (now == f->window) {return KH_OK;}
+  hipStream_t stream = f->live->stream;
+  void * d_new = nullptr;
+  hipError_t err = new_plane(stream, &d_new, static_cast<size_t>(w.width), static_cast<size_t>(w.height), 1, 0xFF, f->d_pub,
+      static_cast<size_t>(f->window.width()), static_cast<size_t>(f->window.width()), static_cast<size_t>(f->window.height()),
+      static_cast<size_t>(f->window.x0 - now.x0), static_cast<size_t>(f->window.y0 - now.y0));
+  if (err == hipErrorOutOfMemory) {set_error("kh_map_feed_poll: published grid allocation failed"); return KH_ERR_HIP;}
+  if (err == hipSuccess) {err = hipStreamSynchronize(stream);}
+  if (err != hipSuccess) {
+    const int rc = fail_hip(stream, "kh_map_feed_poll", "relayout");
+    (void)hipFree(d_new);
+    return rc;
+  }
+  (void)hipFree(f->d_pub);
+  f->d_pub = static_cast<int8_t *>(d_new); f->window = now;
+  f->pending_whole = true;                   // (a window that grew was given to the cell-state kernel whole: this restates it)
+  return KH_OK;
+}
+
+// compare and pack the job's tiles; the count, then that many coordinates and tiles come down as the kernel dealt them
+int compare_stage(kh_map_feed * f, const LiveWindow & w, const Rect & tiles, size_t * n, float * ms)
+{
+  hipStream_t stream = f->live->stream;
+  const size_t n_tiles = static_cast<size_t>(tiles.width() * tiles.height());
+  if (!grow_device(stream, reinterpret_cast<void **>(&f->d_xy), &f->cap_xy, n_tiles * 2 * sizeof(int32_t), n_tiles * 2 * sizeof(int32_t)) ||
+    !grow_device(stream, reinterpret_cast<void **>(&f->d_packed), &f->cap_packed, n_tiles * kTileWords * sizeof(uint32_t), n_tiles * kTileWords * sizeof(uint32_t)))
+  {
+    set_error("kh_map_feed_poll: tile buffer allocation failed");
+    return KH_ERR_HIP;
+  }
+  NavFeedJob job;
+  job.tx0 = static_cast<int32_t>(tiles.x0); job.ty0 = static_cast<int32_t>(tiles.y0);
+  job.tx1 = static_cast<int32_t>(tiles.x1); job.ty1 = static_cast<int32_t>(tiles.y1);
+  job.cells = w.cells; job.cells_ox = w.ox; job.cells_oy = w.oy; job.cells_ws = w.ws;
+  job.published = f->d_pub; job.pub_ox = w.ox; job.pub_oy = w.oy; job.pub_ws = w.width;
+  job.count = f->d_count; job.tile_xy = f->d_xy; job.packed = f->d_packed;
+  if (hipMemsetAsync(f->d_count, 0, sizeof(uint32_t), stream) != hipSuccess) {return fail_hip(stream, "kh_map_feed_poll", "count");}
+  (void)hipEventRecord(f->ev[0], stream);
+  nav_feed(stream, job);
+  (void)hipEventRecord(f->ev[1], stream);
+  uint32_t count = 0;
+  if (hipMemcpyAsync(&count, f->d_count, sizeof(count), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+    hipStreamSynchronize(stream) != hipSuccess) {return fail_hip(stream, "kh_map_feed_poll", "compare");}
+  if (count > n_tiles) {set_error("kh_map_feed_poll: more tiles reported than compared"); return KH_ERR_HIP;}
+  (void)hipEventElapsedTime(ms, f->ev[0], f->ev[1]);
+  *n = count;
+  f->raw_xy.resize(2 * *n); f->raw_data.resize(256 * *n);
+  if (*n > 0 && (hipMemcpyAsync(f->raw_xy.data(), f->d_xy, *n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+    hipMemcpyAsync(f->raw_data.data(), f->d_packed, *n * 256, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+    hipStreamSynchronize(stream) != hipSuccess)) {return fail_hip(stream, "kh_map_feed_poll", "download");}
+  return KH_OK;
+}
+
+// the n tiles in ascending (ty, tx) order -- the kernel deals its slots in no order -- and the rectangle of cells that holds them
+void sort_stage(kh_map_feed * f, size_t n)
+{
+  std::vector<uint32_t> order(n);
+  for (size_t k = 0; k < n; ++k) {order[k] = static_cast<uint32_t>(k);}
+  const int32_t * xy = f->raw_xy.data();
+  std::sort(order.begin(), order.end(), [xy](uint32_t a, uint32_t b) {
+    return xy[2 * a + 1] != xy[2 * b + 1] ? xy[2 * a + 1] < xy[2 * b + 1] : xy[2 * a] < xy[2 * b];
+  });
+  f->tile_xy.resize(2 * n); f->data.resize(256 * n);
+  Rect box;
+  for (size_t k = 0; k < n; ++k) {
+    const int32_t tx = xy[2 * order[k]], ty = xy[2 * order[k] + 1];
+    f->tile_xy[2 * k] = tx; f->tile_xy[2 * k + 1] = ty;
+    std::memcpy(f->data.data() + 256 * k, f->raw_data.data() + 256 * static_cast<size_t>(order[k]), 256);
+    box = box.join(Rect{tx, ty, tx + 1, ty + 1});
+  }
+  kh_map_feed_delta_t & d = f->last;
+  d.x = static_cast<int32_t>(box.x0 * kMapTile); d.y = static_cast<int32_t>(box.y0 * kMapTile);
+  d.w = static_cast<int32_t>(box.width() * kMapTile); d.h = static_cast<int32_t>(box.height() * kMapTile);
+}
+}  // namespace
+
 int kh_map_feed_create(kh_live_map * g, kh_map_feed ** out)
 {
   if (!out) {return KH_ERR_INVALID_ARG;}
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    kh::set_error("no usable HIP device (libkartohip has no CPU fallback)");
-    return KH_ERR_NO_DEVICE;
-  }
+  if (require_device(0) != KH_OK) {return KH_ERR_NO_DEVICE;}
   if (!g) {return KH_ERR_INVALID_ARG;}
   kh_map_feed * f = new kh_map_feed();
   f->live = g; f->device = g->device;
@@ -523,7 +526,7 @@ int kh_map_feed_create(kh_live_map * g, kh_map_feed ** out)
     hipMalloc(reinterpret_cast<void **>(&f->d_count), sizeof(uint32_t)) != hipSuccess)
   {
     (void)hipGetLastError();
-    kh::set_error("kh_map_feed_create: HIP allocation failed");
+    set_error("kh_map_feed_create: HIP allocation failed");
     kh_map_feed_destroy(f);
     return KH_ERR_HIP;
   }
@@ -547,125 +550,42 @@ void kh_map_feed_destroy(kh_map_feed * f)
   delete f;
 }
 
+// The failure rule.  A poll that is refused before it uses the device (a destroyed live map, a window that is not whole blocks or
+// that shrank) leaves the feed as it was.  After any later failure the whole window is pending (WholePendingUnlessDone): the next
+// poll compares everything, and the consumer misses nothing.
 int kh_map_feed_poll(kh_map_feed * f, kh_map_feed_delta_t * out)
 {
   if (!f || !out) {return KH_ERR_INVALID_ARG;}
   kh_live_map * g = f->live;
-  if (!g) {kh::set_error("kh_map_feed_poll: the feed's live map has been destroyed"); return KH_ERR_INVALID_ARG;}
-  kh_map_feed_delta_t & d = f->last;
-  auto done = [&]() {
-    d.ox = f->ox; d.oy = f->oy; d.width = f->width; d.height = f->height;
-    f->stats.polls += 1; f->stats.n_tiles += d.n_tiles; f->stats.tiles_scanned += d.tiles_scanned;
-    f->stats.bytes_downloaded += d.bytes_downloaded; f->stats.kernel_ms += d.kernel_ms;
-    *out = d;
-    return KH_OK;
-  };
-  std::memset(&d, 0, sizeof(d));
+  if (!g) {set_error("kh_map_feed_poll: the feed's live map has been destroyed"); return KH_ERR_INVALID_ARG;}
+  std::memset(&f->last, 0, sizeof(f->last));
   f->tile_xy.clear(); f->data.clear();
   const LiveWindow & w = g->win;
-  if (w.width == 0 || !(f->pending_whole || f->pending_rect)) {return done();}
+  if (w.width == 0 || !(f->pending_whole || !f->pending.empty())) {return finish_poll(f, out);}
   // what the tile rule stands on: no tile straddles the window's edge, and the cells have no row padding
   if (w.ox % kBlock || w.oy % kBlock || w.width % kBlock || w.height % kBlock || w.ws != w.width) {
-    kh::set_error("kh_map_feed_poll: the live window is not made of whole 64-cell blocks without row padding");
+    set_error("kh_map_feed_poll: the live window is not made of whole 64-cell blocks without row padding");
     return KH_ERR_INVALID_ARG;
   }
+  if (!rect_of(w).contains(f->window)) {set_error("kh_map_feed_poll: the live window shrank"); return KH_ERR_INVALID_ARG;}
   if (hipSetDevice(f->device) != hipSuccess) {return KH_ERR_HIP;}
-  // ---- 1. the published grid follows the window: a new array of -1, the old content at its place
-  if (w.ox != f->ox || w.oy != f->oy || w.width != f->width || w.height != f->height) {
-    const bool inside = f->width == 0 || (f->ox >= w.ox && f->oy >= w.oy && static_cast<int64_t>(f->ox) + f->width <= static_cast<int64_t>(w.ox) + w.width &&
-      static_cast<int64_t>(f->oy) + f->height <= static_cast<int64_t>(w.oy) + w.height);
-    if (!inside) {kh::set_error("kh_map_feed_poll: the live window shrank"); return KH_ERR_INVALID_ARG;}
-    const size_t size = static_cast<size_t>(w.width) * static_cast<size_t>(w.height);
-    int8_t * d_new = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&d_new), size) != hipSuccess) {
-      (void)hipGetLastError();
-      kh::set_error("kh_map_feed_poll: published grid allocation failed");
-      return KH_ERR_HIP;                       // (the feed is as it was, its region still pending)
-    }
-    bool ok = hipMemsetAsync(d_new, 0xFF, size, g->stream) == hipSuccess;
-    if (ok && f->width > 0) {
-      const size_t at = static_cast<size_t>(f->ox - w.ox) + static_cast<size_t>(f->oy - w.oy) * static_cast<size_t>(w.width);
-      ok = hipMemcpy2DAsync(d_new + at, static_cast<size_t>(w.width), f->d_pub, static_cast<size_t>(f->width), static_cast<size_t>(f->width),
-          static_cast<size_t>(f->height), hipMemcpyDeviceToDevice, g->stream) == hipSuccess;
-    }
-    if (!ok || hipStreamSynchronize(g->stream) != hipSuccess) {
-      const int rc = kh::fail_feed(f, "relayout");
-      (void)hipFree(d_new);
-      return rc;
-    }
-    (void)hipFree(f->d_pub);
-    f->d_pub = d_new; f->ox = w.ox; f->oy = w.oy; f->width = w.width; f->height = w.height;
-    f->pending_whole = true;                   // (a window that grew was given to the cell-state kernel whole: this restates it)
-  }
-  // ---- 2. the pending region, rounded outward to whole tiles and clipped to the window
-  const int64_t wx1 = static_cast<int64_t>(f->ox) + f->width, wy1 = static_cast<int64_t>(f->oy) + f->height;
-  int64_t x0 = f->ox, y0 = f->oy, x1 = wx1, y1 = wy1;
-  if (!f->pending_whole) {
-    x0 = std::max<int64_t>(f->x0, f->ox); y0 = std::max<int64_t>(f->y0, f->oy); x1 = std::min(f->x1, wx1); y1 = std::min(f->y1, wy1);
-  }
-  if (x1 <= x0 || y1 <= y0) {f->pending_whole = false; f->pending_rect = false; return done();}
-  NavFeedJob job;
-  job.tx0 = static_cast<int32_t>(kh::floor_div(x0, kMapTile)); job.ty0 = static_cast<int32_t>(kh::floor_div(y0, kMapTile));
-  job.tx1 = static_cast<int32_t>(kh::floor_div(x1 - 1, kMapTile) + 1); job.ty1 = static_cast<int32_t>(kh::floor_div(y1 - 1, kMapTile) + 1);
-  // (the window is made of whole tiles, so the rounding cannot leave it; the clamp is a guard)
-  job.tx0 = std::max<int32_t>(job.tx0, f->ox / kMapTile); job.ty0 = std::max<int32_t>(job.ty0, f->oy / kMapTile);
-  job.tx1 = std::min<int32_t>(job.tx1, static_cast<int32_t>(wx1 / kMapTile)); job.ty1 = std::min<int32_t>(job.ty1, static_cast<int32_t>(wy1 / kMapTile));
-  const int64_t tiles = static_cast<int64_t>(job.tx1 - job.tx0) * (job.ty1 - job.ty0);
-  if (tiles > f->cap_tiles) {
-    (void)hipFree(f->d_xy); (void)hipFree(f->d_packed);
-    f->d_xy = nullptr; f->d_packed = nullptr; f->cap_tiles = 0;
-    if (hipMalloc(reinterpret_cast<void **>(&f->d_xy), static_cast<size_t>(tiles) * 2 * sizeof(int32_t)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void **>(&f->d_packed), static_cast<size_t>(tiles) * kTileWords * sizeof(uint32_t)) != hipSuccess)
-    {
-      (void)hipGetLastError();
-      (void)hipFree(f->d_xy); f->d_xy = nullptr;
-      kh::set_error("kh_map_feed_poll: tile buffer allocation failed");
-      return KH_ERR_HIP;
-    }
-    f->cap_tiles = tiles;
-  }
-  job.cells = w.cells; job.cells_ox = w.ox; job.cells_oy = w.oy; job.cells_ws = w.ws;
-  job.published = f->d_pub; job.pub_ox = f->ox; job.pub_oy = f->oy; job.pub_ws = f->width;
-  job.count = f->d_count; job.tile_xy = f->d_xy; job.packed = f->d_packed;
-  // ---- 3. compare and pack
-  if (hipMemsetAsync(f->d_count, 0, sizeof(uint32_t), g->stream) != hipSuccess) {return kh::fail_feed(f, "count");}
-  (void)hipEventRecord(f->ev[0], g->stream);
-  kh::nav_feed(g->stream, job);
-  (void)hipEventRecord(f->ev[1], g->stream);
-  // ---- 4. the count, then that many coordinates and tiles
-  uint32_t count = 0;
-  if (hipMemcpyAsync(&count, f->d_count, sizeof(count), hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
-    hipStreamSynchronize(g->stream) != hipSuccess) {return kh::fail_feed(f, "compare");}
-  if (static_cast<int64_t>(count) > tiles) {kh::set_error("kh_map_feed_poll: more tiles reported than compared"); f->pending_whole = true; return KH_ERR_HIP;}
+  WholePendingUnlessDone guard{f};
+  int rc = follow_window_stage(f, w);
+  if (rc != KH_OK) {return rc;}
+  const Rect tiles = tile_job(f->pending_whole, f->pending, f->window);
+  size_t n = 0;
   float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, f->ev[0], f->ev[1]);
-  const size_t n = count;
-  f->raw_xy.resize(2 * n); f->raw_data.resize(256 * n);
-  if (n > 0 && (hipMemcpyAsync(f->raw_xy.data(), f->d_xy, n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
-    hipMemcpyAsync(f->raw_data.data(), f->d_packed, n * 256, hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
-    hipStreamSynchronize(g->stream) != hipSuccess)) {return kh::fail_feed(f, "download");}
-  f->pending_whole = false; f->pending_rect = false;
-  // ascending (ty, tx): the kernel deals its slots in no order
-  std::vector<uint32_t> order(n);
-  for (size_t k = 0; k < n; ++k) {order[k] = static_cast<uint32_t>(k);}
-  const int32_t * xy = f->raw_xy.data();
-  std::sort(order.begin(), order.end(), [xy](uint32_t a, uint32_t b) {
-    return xy[2 * a + 1] != xy[2 * b + 1] ? xy[2 * a + 1] < xy[2 * b + 1] : xy[2 * a] < xy[2 * b];
-  });
-  f->tile_xy.resize(2 * n); f->data.resize(256 * n);
-  int32_t bx0 = INT32_MAX, by0 = INT32_MAX, bx1 = INT32_MIN, by1 = INT32_MIN;
-  for (size_t k = 0; k < n; ++k) {
-    const int32_t tx = xy[2 * order[k]], ty = xy[2 * order[k] + 1];
-    f->tile_xy[2 * k] = tx; f->tile_xy[2 * k + 1] = ty;
-    std::memcpy(f->data.data() + 256 * k, f->raw_data.data() + 256 * static_cast<size_t>(order[k]), 256);
-    bx0 = std::min(bx0, tx); by0 = std::min(by0, ty); bx1 = std::max(bx1, tx); by1 = std::max(by1, ty);
+  if (!tiles.empty()) {
+    if ((rc = compare_stage(f, w, tiles, &n, &ms)) != KH_OK) {return rc;}
+    sort_stage(f, n);
+    kh_map_feed_delta_t & d = f->last;
+    d.n_tiles = static_cast<int64_t>(n); d.tiles_scanned = tiles.width() * tiles.height();
+    d.bytes_downloaded = static_cast<int64_t>(sizeof(uint32_t) + n * (2 * sizeof(int32_t) + 256));
+    d.kernel_ms = static_cast<double>(ms);
   }
-  // ---- 5. the counts
-  d.n_tiles = static_cast<int64_t>(n); d.tiles_scanned = tiles;
-  d.bytes_downloaded = static_cast<int64_t>(sizeof(count) + n * (2 * sizeof(int32_t) + 256));
-  d.kernel_ms = static_cast<double>(ms);
-  if (n > 0) {d.x = bx0 * kMapTile; d.y = by0 * kMapTile; d.w = (bx1 - bx0 + 1) * kMapTile; d.h = (by1 - by0 + 1) * kMapTile;}
-  return done();
+  f->pending_whole = false; f->pending = Rect{};
+  guard.done = true;
+  return finish_poll(f, out);
 }
 
 int kh_map_feed_tiles(const kh_map_feed * f, int32_t * tile_xy, int8_t * data)
@@ -682,17 +602,15 @@ int kh_map_feed_read(kh_map_feed * f, int32_t x, int32_t y, int32_t w, int32_t h
   if (w == 0 || h == 0) {return KH_OK;}
   if (!out) {return KH_ERR_INVALID_ARG;}
   std::memset(out, 0xFF, static_cast<size_t>(w) * static_cast<size_t>(h));
-  const int64_t x0 = std::max<int64_t>(x, f->ox), y0 = std::max<int64_t>(y, f->oy);
-  const int64_t x1 = std::min<int64_t>(static_cast<int64_t>(x) + w, static_cast<int64_t>(f->ox) + f->width);
-  const int64_t y1 = std::min<int64_t>(static_cast<int64_t>(y) + h, static_cast<int64_t>(f->oy) + f->height);
-  if (x1 <= x0 || y1 <= y0) {return KH_OK;}
+  const Rect asked{x, y, static_cast<int64_t>(x) + w, static_cast<int64_t>(y) + h}, got = asked.clip(f->window);
+  if (got.empty()) {return KH_OK;}
   if (hipSetDevice(f->device) != hipSuccess) {return KH_ERR_HIP;}
-  const int8_t * src = f->d_pub + (x0 - f->ox) + (y0 - f->oy) * f->width;
-  int8_t * dst = out + (x0 - x) + (y0 - y) * static_cast<int64_t>(w);
-  if (hipMemcpy2D(dst, static_cast<size_t>(w), src, static_cast<size_t>(f->width), static_cast<size_t>(x1 - x0), static_cast<size_t>(y1 - y0),
-      hipMemcpyDeviceToHost) != hipSuccess)
+  const int8_t * src = f->d_pub + (got.x0 - f->window.x0) + (got.y0 - f->window.y0) * f->window.width();
+  int8_t * dst = out + (got.x0 - x) + (got.y0 - y) * static_cast<int64_t>(w);
+  if (hipMemcpy2D(dst, static_cast<size_t>(w), src, static_cast<size_t>(f->window.width()), static_cast<size_t>(got.width()),
+      static_cast<size_t>(got.height()), hipMemcpyDeviceToHost) != hipSuccess)
   {
-    kh::set_error(std::string("kh_map_feed_read: ") + hipGetErrorString(hipGetLastError()));
+    set_error(std::string("kh_map_feed_read: ") + hipGetErrorString(hipGetLastError()));
     return KH_ERR_HIP;
   }
   return KH_OK;

@@ -28,13 +28,7 @@ int mapper_resident_table(kh_mapper * m, void * stream, const char * who, std::v
 // that is not in the map is KH_ERR_NOT_FOUND)
 int mapper_resident_table_of(kh_mapper * m, void * stream, const char * who, const int32_t * ids, size_t n_ids, std::vector<ResidentScan> & table,
   int64_t * up_points, int64_t * up_ranges);
-// what the live map (live_map.cpp) classifies a scan by: its sensor pose; and its box (the default anchor)
-struct SensorView
-{
-  int32_t id;
-  double sensor[3];
-  double bbox[4];
-};
+// what the live map (live_map.cpp) classifies a scan by (SensorView, occupancy_device.hpp)
 void mapper_sensor_poses(const kh_mapper * m, std::vector<SensorView> & out);     // id order
 void laser_sensor_at(const kh_laser & laser, const double robot[3], double sensor[3]);   // LocalizedRangeScan::GetSensorAt, Karto.h:5566-5569
 double karto_normalize_angle(double angle);                                              // math::NormalizeAngle, Math.h:181-202

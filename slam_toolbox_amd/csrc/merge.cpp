@@ -140,11 +140,7 @@ int kh_merge_create(int32_t device, double resolution, kh_merge ** out)
   if (!out) {return KH_ERR_INVALID_ARG;}
   *out = nullptr;
   if (!(resolution > 0)) {kh::set_error("kh_merge_create: the resolution must be positive"); return KH_ERR_INVALID_ARG;}
-  const int ndev = kh_device_count();
-  if (ndev <= 0 || device < 0 || device >= ndev) {
-    kh::set_error("no usable HIP device (libkartohip has no CPU fallback)");
-    return KH_ERR_NO_DEVICE;
-  }
+  if (kh::require_device(device) != KH_OK) {return KH_ERR_NO_DEVICE;}
   kh_merge * g = new kh_merge();
   g->device = device; g->resolution = resolution;
   *out = g;

@@ -18,11 +18,10 @@
 
 #include "../../include/karto_hip.h"
 #include "occupancy_device.hpp"
+#include "live_map_plan.hpp"
 
 namespace kh
 {
-void set_error(const std::string & s);
-
 __device__ __forceinline__ double o_round(double v) {return v >= 0.0 ? floor(v + 0.5) : ceil(v - 0.5);}   // Math.h:87-90
 __device__ __forceinline__ int32_t o_to_int(double v)
 {
@@ -351,19 +350,6 @@ namespace kh
 {
 namespace
 {
-// makes *buf a device buffer of at least `need` bytes: one that is too small is replaced by one of `cap` bytes (what it held is
-// not kept).  false = the allocation failed, and the buffer is gone.
-bool grow_device(kh_occupancy * g, void ** buf, size_t * have, size_t need, size_t cap)
-{
-  if (need <= *have) {return true;}
-  (void)hipStreamSynchronize(g->stream);
-  if (*buf) {(void)hipFree(*buf); *buf = nullptr;}
-  *have = 0;
-  if (hipMalloc(buf, cap) != hipSuccess) {(void)hipGetLastError(); return false;}
-  *have = cap;
-  return true;
-}
-
 // one wave per run of 64 beams, four waves per workgroup
 dim3 blocks_of_runs(int32_t n_scans, int32_t runs_per_scan) {return dim3(static_cast<unsigned>((static_cast<int64_t>(n_scans) * runs_per_scan + 3) / 4));}
 
@@ -395,7 +381,7 @@ int occupancy_add_resident(kh_occupancy * g, int32_t n_scans, const ResidentScan
   if (hipSetDevice(g->device) != hipSuccess) {return KH_ERR_HIP;}
   if (n_scans == 0 || n_beams == 0) {return hipStreamSynchronize(g->stream) == hipSuccess ? KH_OK : KH_ERR_HIP;}
   const size_t bytes = static_cast<size_t>(n_scans) * sizeof(ResidentScan);
-  if (!grow_device(g, reinterpret_cast<void **>(&g->d_scans), &g->cap_scans, bytes, bytes + bytes / 2)) {
+  if (!grow_device(g->stream, reinterpret_cast<void **>(&g->d_scans), &g->cap_scans, bytes, bytes + bytes / 2)) {
     set_error("kh_mapper_build_map: scan table allocation failed");
     return KH_ERR_HIP;
   }
@@ -417,7 +403,7 @@ int occupancy_add_merged(kh_occupancy * g, int32_t n_scans, const MergeScan * sc
   if (hipSetDevice(g->device) != hipSuccess) {return KH_ERR_HIP;}
   if (n_scans == 0 || max_beams == 0) {return hipStreamSynchronize(g->stream) == hipSuccess ? KH_OK : KH_ERR_HIP;}
   const size_t submap_bytes = static_cast<size_t>(n_submaps) * sizeof(MergeSubmap), scan_bytes = static_cast<size_t>(n_scans) * sizeof(MergeScan);
-  if (!grow_device(g, reinterpret_cast<void **>(&g->d_merge), &g->cap_merge, submap_bytes + scan_bytes, submap_bytes + scan_bytes)) {
+  if (!grow_device(g->stream, reinterpret_cast<void **>(&g->d_merge), &g->cap_merge, submap_bytes + scan_bytes, submap_bytes + scan_bytes)) {
     set_error("kh_merge_build: table allocation failed");
     return KH_ERR_HIP;
   }
@@ -458,8 +444,8 @@ void nav_feed(void * stream, const NavFeedJob & job)
 {
   if (job.tx1 <= job.tx0 || job.ty1 <= job.ty0) {return;}
   // the strips of 4 tiles that hold tile columns [tx0, tx1): floor quotients, tiles left of the anchor are negative
-  auto strip_of = [](int32_t tx) {return tx >= 0 ? tx / kStripTiles : -((-tx + kStripTiles - 1) / kStripTiles);};
-  const int32_t strip0 = strip_of(job.tx0), strips_x = strip_of(job.tx1 - 1) - strip0 + 1;
+  const int32_t strip0 = static_cast<int32_t>(floor_div(job.tx0, kStripTiles));
+  const int32_t strips_x = static_cast<int32_t>(floor_div(job.tx1 - 1, kStripTiles)) - strip0 + 1;
   const int64_t n_strips = static_cast<int64_t>(strips_x) * (job.ty1 - job.ty0);
   hipLaunchKernelGGL(k_nav_feed, dim3(static_cast<unsigned>((n_strips + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), job, strip0,
     strips_x, n_strips);
@@ -492,15 +478,11 @@ int kh_occupancy_create(int32_t width, int32_t height, double offset_x, double o
 {
   if (!out) {return KH_ERR_INVALID_ARG;}
   *out = nullptr;
-  if (width <= 0 || height <= 0 || !(resolution > 0) || static_cast<int64_t>(width + 7) * height > (1ll << 31) - 4096) {
+  if (width <= 0 || height <= 0 || !(resolution > 0) || grid_too_large(width, height)) {
     set_error("OccupancyGrid: invalid dimensions");
     return KH_ERR_INVALID_ARG;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-    set_error("no usable HIP device (libkartohip has no CPU fallback)");
-    return KH_ERR_NO_DEVICE;
-  }
+  if (require_device(device) != KH_OK) {return KH_ERR_NO_DEVICE;}
   kh_occupancy * g = new kh_occupancy();
   g->device = device;
   g->dev.width = width; g->dev.height = height; g->dev.ws = (width + 7) & ~7;      // Karto.h:4640
@@ -564,7 +546,7 @@ int kh_occupancy_add_scans(kh_occupancy * g, int32_t n_scans, const kh_scan * sc
     const size_t cap = std::max(total * 5, g->cap_hbeams + g->cap_hbeams / 2);
     g->cap_hbeams = 0; g->cap_beams = 0;                      // (the device buffer follows the host buffer's size)
     if (hipHostMalloc(reinterpret_cast<void **>(&g->h_beams), cap * 8, hipHostMallocDefault) != hipSuccess ||
-      !grow_device(g, reinterpret_cast<void **>(&g->d_beams), &g->cap_beams, cap * 8, cap * 8))
+      !grow_device(g->stream, reinterpret_cast<void **>(&g->d_beams), &g->cap_beams, cap * 8, cap * 8))
     {
       set_error("kh_occupancy_add_scans: staging allocation failed");
       return KH_ERR_HIP;
@@ -613,7 +595,7 @@ int kh_occupancy_read_nav(kh_occupancy * g, int8_t * out)
   if (!g || !out) {return KH_ERR_INVALID_ARG;}
   if (hipSetDevice(g->device) != hipSuccess) {return KH_ERR_HIP;}
   const int64_t total = static_cast<int64_t>(g->dev.width) * g->dev.height, words = (total + 3) / 4;
-  if (!grow_device(g, reinterpret_cast<void **>(&g->d_nav), &g->cap_nav, static_cast<size_t>(words) * 4, static_cast<size_t>(words) * 4)) {
+  if (!grow_device(g->stream, reinterpret_cast<void **>(&g->d_nav), &g->cap_nav, static_cast<size_t>(words) * 4, static_cast<size_t>(words) * 4)) {
     set_error("kh_occupancy_read_nav: output allocation failed");
     return KH_ERR_HIP;
   }

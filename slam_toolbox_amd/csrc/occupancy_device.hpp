@@ -4,6 +4,10 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <string>
+#ifdef __HIP__
+#include <hip/hip_runtime.h>
+#endif
 
 #include "../../include/karto_hip.h"
 
@@ -32,6 +36,9 @@ inline void grid_dimensions(const Box & box, double resolution, int32_t * width,
   *height = static_cast<int32_t>(round_half_away((box.max_y - box.min_y) * scale));
   offset[0] = box.min_x; offset[1] = box.min_y;
 }
+
+// the size cap of an occupancy grid and of a live window: (width + 7) * height cells stay below 2^31 - 4096, stated without the product
+inline bool grid_too_large(int64_t width, int64_t height) {return height > 0 && width + 7 > ((1ll << 31) - 4096) / height;}
 
 // ---- the records of the trace kernels ----
 // one scan whose readings are resident on the grid's device (k_occ_trace_resident)
@@ -66,6 +73,14 @@ struct LiveWindow
   uint32_t * pass;
   uint32_t * hits;
   uint8_t * cells;
+};
+
+// what the live map classifies a scan of its mapper by: the sensor pose; and the scan's box (the default anchor)
+struct SensorView
+{
+  int32_t id;
+  double sensor[3];
+  double bbox[4];
 };
 
 enum : int32_t {kDeltaAdd = 0, kDeltaSub = 1, kDeltaMove = 2};
@@ -130,4 +145,46 @@ void live_update_cells(void * stream, const LiveWindow & w, int32_t x0, int32_t 
 // k_nav_feed over the job's tiles on `stream`: every tile whose nav values differ from the published grid takes a slot, in no
 // particular order.  The caller has set *job.count to 0 and holds room for every tile of the job.
 void nav_feed(void * stream, const NavFeedJob & job);
+
+#ifdef __HIP__
+// ---- what the module's host files do with the device the same way (absent from a build without HIP: tests/live_map_plan_check.cpp) ----
+void set_error(const std::string & s);
+
+// KH_OK when `device` can be used, otherwise KH_ERR_NO_DEVICE and its text; require_device(0) asks for any device at all
+inline int require_device(int32_t device)
+{
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) == hipSuccess && device >= 0 && device < ndev) {return KH_OK;}
+  (void)hipGetLastError();
+  set_error("no usable HIP device (libkartohip has no CPU fallback)");
+  return KH_ERR_NO_DEVICE;
+}
+
+// makes *buf a device buffer of at least `need` bytes once `stream` has drained: one that is too small is replaced by one of `cap`
+// bytes (what it held is not kept).  false = the allocation failed, and the buffer is gone.
+inline bool grow_device(hipStream_t stream, void ** buf, size_t * have, size_t need, size_t cap)
+{
+  if (need <= *have) {return true;}
+  (void)hipStreamSynchronize(stream);
+  if (*buf) {(void)hipFree(*buf); *buf = nullptr;}
+  *have = 0;
+  if (hipMalloc(buf, cap) != hipSuccess) {(void)hipGetLastError(); return false;}
+  *have = cap;
+  return true;
+}
+
+// the same for a buffer whose first `used` bytes are kept (the live map's log; nothing is in flight on it between two updates).
+// hipErrorOutOfMemory = the allocation failed and the buffer is as it was; any other error = the copy failed, likewise.
+inline hipError_t grow_device_keeping(void ** buf, size_t * have, size_t need, size_t cap, size_t used)
+{
+  if (need <= *have) {return hipSuccess;}
+  void * d_new = nullptr;
+  if (hipMalloc(&d_new, cap) != hipSuccess) {(void)hipGetLastError(); return hipErrorOutOfMemory;}
+  const hipError_t err = used > 0 ? hipMemcpy(d_new, *buf, used, hipMemcpyDeviceToDevice) : hipSuccess;
+  if (err != hipSuccess) {(void)hipFree(d_new); return err;}
+  (void)hipFree(*buf);
+  *buf = d_new; *have = cap;
+  return hipSuccess;
+}
+#endif
 }  // namespace kh
