@@ -465,6 +465,21 @@ KH_API int kh_graph_find_near_by_scan(kh_graph * g, int32_t n_queries, const dou
 KH_API int kh_graph_find_near_by_vertices(kh_graph * g, const double query_xy[2], double max_distance, int32_t * scans, int32_t cap,
                                           int32_t * n_found);
 KH_API double kh_graph_last_near_by_kernel_ms(kh_graph * g);       /* device time of the last near-by kernel (HIP events) */
+/* Where to try a scan that comes without a pose (global relocalization), over the store's poses:
+ *   seeds   a lattice of side seed_spacing; the cell of a vertex is (floor(x / seed_spacing), floor(y / seed_spacing)) in FP64; the seed
+ *           of a non-empty cell is its vertex with the lowest index; seeds come in ascending index.  With center_xy and radius > 0
+ *           only the seeds with (dx * dx) + (dy * dy) < radius * radius + KT_TOLERANCE from the centre (radius <= 0 or center_xy
+ *           NULL: the whole map).
+ *   bases   seed k owns base_idx[base_begin[k] .. base_begin[k + 1]): every vertex with (dx * dx) + (dy * dy) <
+ *           base_radius * base_radius + KT_TOLERANCE from the seed, ascending; of more than max_base, entries 0, s, 2s, ... of that
+ *           list with s = ceil(count / max_base).
+ * *n_seeds / *n_base are the totals even beyond cap_seeds / cap_base; seeds and base_idx take the first cap entries, base_begin
+ * min(*n_seeds, cap_seeds) + 1.  An empty store answers zero seeds.  Needs the store's poses, like the near-by queries. */
+KH_API int kh_graph_relocalize_candidates(kh_graph * g, double seed_spacing, double base_radius, int32_t max_base,
+                                          const double * center_xy, double radius, int32_t * seeds, int32_t cap_seeds,
+                                          int32_t * n_seeds, int32_t * base_begin, int32_t * base_idx, int32_t cap_base,
+                                          int32_t * n_base);
+KH_API double kh_graph_last_relocalize_kernel_ms(kh_graph * g);    /* device time of the last call's kernels (HIP events) */
 /* MapperGraph::FindNearLinkedVertices (Mapper.cpp:1808-1819): the vertices a breadth-first traversal from the scan
  * reaches through vertices within max_distance of it, in visiting order (the scan itself first).  *n_found is the total. */
 KH_API int kh_graph_find_near_linked(kh_graph * g, int32_t query_scan, double max_distance, int32_t * scans, int32_t cap,
@@ -707,6 +722,49 @@ KH_API int kh_mapper_set_scan_pose(kh_mapper * m, int32_t scan_id, const double 
 /* counters of kh_mapper_build_map: [0] calls, [1] scans traced by the last call, [2] point-reading uploads and [3] range uploads
  * the last call made, [4], [5] the same two since the mapper was made */
 KH_API int kh_mapper_map_stats(const kh_mapper * m, int64_t out[6]);
+
+/* ---- global relocalization: place one scan in the map without a pose guess.  Every hypothesis is
+ * MapperGraph::TryCloseLoop's own test (Mapper.cpp:1515-1549, kh_loop_closure_batch) with the scan placed at a pose taken from the
+ * map: hypothesis k * n_headings + h puts the robot at seed k's corrected position with heading -pi + h * (2 pi / n_headings) (the
+ * sensor through the laser's offset, the readings with kh_scan_points) and matches against the seed's base
+ * (kh_graph_relocalize_candidates with base_radius = loop_search_maximum_distance): coarse match on the loop matcher, the gate
+ * (response > loop_match_minimum_response_coarse, cov(0,0) and cov(1,1) < loop_match_maximum_variance_coarse), fine match of the
+ * temporary scan on the sequential matcher, accepted when fine response >= loop_match_minimum_response_fine.  The accepted ones come
+ * back by fine response (descending), then coarse response (descending), then index. */
+typedef struct kh_relocalize_params {
+  double seed_spacing;      /* side of the seed lattice, > 0 (default: loop_search_maximum_distance / 2) */
+  int32_t n_headings;       /* headings per seed; 0 = ceil(2 pi / (2 * coarse_search_angle_offset)), 10 for the shipped 0.349 rad */
+  int32_t max_base;         /* most base scans per hypothesis, >= 1 (default 40) */
+  int32_t top_k;            /* most hypotheses returned; 0 = as many as `cap` holds (default 8) */
+  int32_t pad;
+  double center_xy[2];      /* with radius > 0: only the seeds within radius of this point */
+  double radius;            /* <= 0: the whole map (default) */
+} kh_relocalize_params;
+typedef struct kh_relocalize_hyp {
+  int32_t index;            /* seed ordinal * n_headings + heading ordinal */
+  int32_t seed_scan;        /* scan id of the seed */
+  double heading;
+  double coarse_mean[3], coarse_cov[9], coarse_response;      /* sensor pose of the coarse match */
+  double fine_mean[3], fine_cov[9], fine_response;            /* sensor pose of the fine match */
+  double robot_pose[3];     /* GetCorrectedAt(fine_mean): what goes to kh_mapper_process_against_nodes_near_by */
+} kh_relocalize_hyp;
+typedef struct kh_relocalize_summary {
+  int32_t n_seeds, n_headings, n_hypotheses, n_passed /* the coarse gate */, n_accepted, n_returned;
+  double kernel_ms;         /* device time of the seed and base kernels */
+  double candidates_ms, scans_ms, batch_ms, total_ms;         /* wall: enumeration, query scans on the host, match batches, the call */
+} kh_relocalize_summary;
+/* the parameters the mapper was created (or loaded) with */
+KH_API int kh_mapper_get_params(const kh_mapper * m, kh_mapper_params * out);
+/* defaults for a mapper with parameters *mapper_params (NULL: kh_mapper_params_default's) */
+KH_API void kh_relocalize_params_default(const kh_mapper_params * mapper_params, kh_relocalize_params * p);
+/* out takes the first min(top_k, cap) accepted hypotheses (top_k 0: cap), the summary the totals.  NULL ranges / params / summary,
+ * out NULL with cap > 0, seed_spacing <= 0, n_headings < 0, max_base < 1, top_k < 0, cap < 0 or a non-finite parameter are
+ * KH_ERR_INVALID_ARG before the device is touched; without a device KH_ERR_NO_DEVICE; an empty map is KH_OK with zero everything.
+ * The mapper is left as it was: no vertex, edge, running scan, last scan or solver state changes (scans the batches read become
+ * resident on the device, as in any loop-closure batch), and a failure leaves it usable.  Like kh_mapper_build_map the call must not
+ * run concurrently with a Process* call. */
+KH_API int kh_mapper_relocalize(kh_mapper * m, const double * ranges, const kh_relocalize_params * params, kh_relocalize_hyp * out,
+                                int32_t cap, kh_relocalize_summary * summary);
 
 /* ---- merging sessions (slam_toolbox's merge_maps_kinematic, src/merge_maps_kinematic.cpp): several mappers -- live ones, or
  * sessions loaded from files -- each placed by a rigid correction T = (tx, ty, yaw), and ONE occupancy grid traced from all their

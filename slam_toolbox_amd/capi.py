@@ -102,6 +102,7 @@ SYMBOLS = [
     "kh_live_map_stats",
     "kh_occupancy_read_nav", "kh_map_feed_create", "kh_map_feed_destroy", "kh_map_feed_poll", "kh_map_feed_tiles", "kh_map_feed_read",
     "kh_map_feed_stats",
+    "kh_graph_relocalize_candidates", "kh_graph_last_relocalize_kernel_ms", "kh_relocalize_params_default", "kh_mapper_relocalize", "kh_mapper_get_params",
 ]
 
 
@@ -173,6 +174,23 @@ class KhMapFeedDelta(C.Structure):
 
 class KhMapFeedStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("polls", "n_tiles", "tiles_scanned", "bytes_downloaded")] + [("kernel_ms", C.c_double)]
+
+
+class KhRelocalizeParams(C.Structure):
+    _fields_ = [("seed_spacing", C.c_double), ("n_headings", C.c_int32), ("max_base", C.c_int32), ("top_k", C.c_int32), ("pad", C.c_int32),
+                ("center_xy", C.c_double * 2), ("radius", C.c_double)]
+
+
+class KhRelocalizeHyp(C.Structure):
+    _fields_ = [("index", C.c_int32), ("seed_scan", C.c_int32), ("heading", C.c_double),
+                ("coarse_mean", C.c_double * 3), ("coarse_cov", C.c_double * 9), ("coarse_response", C.c_double),
+                ("fine_mean", C.c_double * 3), ("fine_cov", C.c_double * 9), ("fine_response", C.c_double),
+                ("robot_pose", C.c_double * 3)]
+
+
+class KhRelocalizeSummary(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_seeds", "n_headings", "n_hypotheses", "n_passed", "n_accepted", "n_returned")] + \
+               [(k, C.c_double) for k in ("kernel_ms", "candidates_ms", "scans_ms", "batch_ms", "total_ms")]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
@@ -384,6 +402,14 @@ def lib():
         L.kh_map_feed_tiles.argtypes = [vp, vp, vp]
         L.kh_map_feed_read.argtypes = [vp, i32, i32, i32, i32, vp]
         L.kh_map_feed_stats.argtypes = [vp, C.POINTER(KhMapFeedStats)]
+    if hasattr(L, "kh_mapper_relocalize"):
+        L.kh_graph_relocalize_candidates.argtypes = [vp, dbl, dbl, i32, vp, dbl, vp, i32, C.POINTER(i32), vp, vp, i32, C.POINTER(i32)]
+        L.kh_graph_last_relocalize_kernel_ms.argtypes = [vp]
+        L.kh_graph_last_relocalize_kernel_ms.restype = dbl
+        L.kh_relocalize_params_default.argtypes = [C.POINTER(KhMapperParams), C.POINTER(KhRelocalizeParams)]
+        L.kh_relocalize_params_default.restype = None
+        L.kh_mapper_get_params.argtypes = [vp, C.POINTER(KhMapperParams)]
+        L.kh_mapper_relocalize.argtypes = [vp, vp, C.POINTER(KhRelocalizeParams), C.POINTER(KhRelocalizeHyp), i32, C.POINTER(KhRelocalizeSummary)]
     if hasattr(L, "kh_lifelong_scores"):
         L.kh_decay_params_default.argtypes = [C.POINTER(KhDecayParams)]
         L.kh_decay_params_default.restype = None

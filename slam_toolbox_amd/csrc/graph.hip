@@ -230,6 +230,119 @@ __global__ __launch_bounds__(256) void k_near_by_radius(
   }
 }
 
+// ---- relocalization candidates: where in the map to try a scan that comes without a pose -------------
+// Seeds: a lattice of side `spacing` over the plane; the cell of a vertex is (floor(x / spacing), floor(y / spacing)), an FP64 divide
+// and floor (a negative coordinate goes down, -0.0 and +0.0 compare equal as cells); the seed of a cell is its vertex with the LOWEST
+// list index.  Base of a seed: every vertex j with (dx * dx) + (dy * dy) < R * R + KT_TOLERANCE from it, in list order, every s-th one
+// when there are more than max_base.  Positions are the store's poses (GetCorrectedPose() x, y), as for the near-by queries.
+__device__ __forceinline__ double2 seed_cell(double2 p, double spacing) {return make_double2(floor(p.x / spacing), floor(p.y / spacing));}
+
+// flag[i] = 1 iff no vertex j < i lies in vertex i's cell, and vertex i passes the region test (use_region: dist_sq to the centre <
+// region_sq_plus = radius^2 + KT_TOLERANCE); a cell's seed that fails the region test is dropped, no other vertex takes its place.
+// One thread per vertex; the cells of the vertices before it pass through LDS in tiles of 256 (block b reads tiles 0 .. b), so the
+// answer is a pure function of the list: the lowest index wins whatever order the blocks run in.
+__global__ __launch_bounds__(256) void k_seed_cover(
+  const double2 * __restrict__ pose, int32_t n, double spacing, int32_t use_region, double cx, double cy, double region_sq_plus,
+  int32_t * __restrict__ flag)
+{
+  __shared__ double2 s_cell[256];
+  const int32_t i = blockIdx.x * 256 + threadIdx.x;
+  const double2 p = pose[min(i, n - 1)];
+  const double2 mine = seed_cell(p, spacing);
+  bool first = true;
+  for (int32_t tile = 0; tile <= static_cast<int32_t>(blockIdx.x); ++tile) {
+    const int32_t j0 = tile * 256;
+    s_cell[threadIdx.x] = seed_cell(pose[min(j0 + static_cast<int32_t>(threadIdx.x), n - 1)], spacing);
+    __syncthreads();
+    const int32_t count = min(256, i - j0);                 // only vertices before i (<= 0 in the block's own tile for its first thread)
+    for (int32_t k = 0; k < count; ++k) {
+      const double2 c = s_cell[k];
+      if (c.x == mine.x && c.y == mine.y) {first = false;}
+    }
+    __syncthreads();
+  }
+  if (i < n) {
+    bool keep = first;
+    if (use_region) {keep = keep && near_by_dist_sq(cx, cy, p) < region_sq_plus;}
+    flag[i] = keep ? 1 : 0;
+  }
+}
+
+// exclusive prefix sum of value[0 .. n) by ONE workgroup of 256, in list order: begin[i] = value[0] + ... + value[i - 1], begin[n] =
+// the total (begin may be NULL); with `list`, the indices i whose value is not zero are written to list[begin[i]] -- the seeds in
+// ascending list index out of k_seed_cover's flags.  Per 256 values: an inclusive scan over the wave's 64 lanes with shuffles, the four
+// wave totals through LDS.  No atomics: the order is the list's.
+__global__ __launch_bounds__(256) void k_prefix_list(const int32_t * __restrict__ value, int32_t n, int32_t * __restrict__ begin, int32_t * __restrict__ list)
+{
+  __shared__ int32_t s_wave[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int32_t running = 0;
+  for (int32_t base = 0; base < n; base += 256) {
+    const int32_t i = base + threadIdx.x;
+    const int32_t v = i < n ? value[i] : 0;
+    int32_t incl = v;
+    for (int off = 1; off < 64; off <<= 1) {
+      const int32_t up = __shfl_up(incl, off, 64);
+      if (lane >= off) {incl += up;}
+    }
+    if (lane == 63) {s_wave[wave] = incl;}
+    __syncthreads();
+    int32_t before = running;
+    for (int w = 0; w < wave; ++w) {before += s_wave[w];}
+    const int32_t excl = before + incl - v;
+    if (i < n) {
+      if (begin) {begin[i] = excl;}
+      if (list && v != 0) {list[excl] = i;}
+    }
+    running += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    __syncthreads();
+  }
+  if (begin && threadIdx.x == 0) {begin[n] = running;}
+}
+
+// how many entries of an ordered list of c are kept, and the stride between them: all of them up to max_base, otherwise entries
+// 0, s, 2s, ... with s = ceil(c / max_base)
+__device__ __forceinline__ int32_t base_stride(int32_t c, int32_t max_base) {return c <= max_base ? 1 : (c + max_base - 1) / max_base;}
+
+// One wave per seed (four seeds per workgroup) over all n vertices, 64 at a time: lane t tests vertex base + t, the wave's ballot
+// gives every hit its rank in list order.  fill = 0: raw[k] = the number of vertices in range, kept[k] = how many of them the stride
+// rule keeps.  fill = 1 (after k_prefix_list has turned kept into base_begin): the hit of rank r with r % s == 0 goes to
+// base_idx[base_begin[k] + r / s].  Two passes instead of an atomically appended list: the order is the list's.
+__global__ __launch_bounds__(256) void k_base_gather(
+  const double2 * __restrict__ pose, int32_t n, const int32_t * __restrict__ seeds, int32_t n_seeds, double range_sq_plus, int32_t max_base,
+  int32_t fill, int32_t * __restrict__ raw, int32_t * __restrict__ kept, const int32_t * __restrict__ base_begin, int32_t * __restrict__ base_idx)
+{
+  const int lane = threadIdx.x & 63;
+  const int32_t k = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (k >= n_seeds) {return;}                              // (the whole wave leaves: no barrier in this kernel)
+  const int32_t seed = seeds[k];
+  if (seed < 0 || seed >= n) {return;}
+  const double2 q = pose[seed];
+  int32_t stride = 1, first = 0, room = 0;
+  if (fill) {
+    stride = base_stride(raw[k], max_base);
+    first = base_begin[k];
+    room = base_begin[k + 1] - first;
+  }
+  int32_t count = 0;
+  for (int32_t base = 0; base < n; base += 64) {
+    const int32_t i = base + lane;
+    const bool hit = i < n && near_by_dist_sq(q.x, q.y, pose[min(i, n - 1)]) < range_sq_plus;
+    const unsigned long long votes = __ballot(hit);
+    if (fill && hit) {
+      const int32_t rank = count + __popcll(votes & ((1ull << lane) - 1ull));
+      const int32_t slot = rank / stride;
+      if (rank % stride == 0 && slot < room) {base_idx[first + slot] = i;}
+    }
+    count += __popcll(votes);
+  }
+  if (!fill && lane == 0) {
+    raw[k] = count;
+    const int32_t s = base_stride(count, max_base);
+    kept[k] = (count + s - 1) / s;
+  }
+}
+
 }  // namespace kh
 
 using namespace kh;
@@ -264,6 +377,15 @@ struct kh_graph
   int32_t * d_nb_idx = nullptr; size_t cap_nb_idx = 0;         // nearest (q) / radius hits (n) + their count (1)
   double * d_nb_d2 = nullptr; size_t cap_nb_d2 = 0;            // dist_sq of the radius hits (n)
   double last_near_by_ms = 0.0;
+  // relocalization candidates (k_seed_cover / k_prefix_list / k_base_gather): seed flags (n), their prefix (n + 1), seeds (n); per seed
+  // the raw and the kept base count (2s), base_begin (s + 1); base_idx (its total)
+  int32_t * d_rl_flag = nullptr; size_t cap_rl_flag = 0;
+  int32_t * d_rl_prefix = nullptr; size_t cap_rl_prefix = 0;
+  int32_t * d_rl_seeds = nullptr; size_t cap_rl_seeds = 0;
+  int32_t * d_rl_count = nullptr; size_t cap_rl_count = 0;
+  int32_t * d_rl_begin = nullptr; size_t cap_rl_begin = 0;
+  int32_t * d_rl_idx = nullptr; size_t cap_rl_idx = 0;
+  double last_relocalize_ms = 0.0;
 };
 
 extern "C" {
@@ -298,6 +420,8 @@ void kh_graph_destroy(kh_graph * g)
   (void)hipFree(g->d_xy); (void)hipFree(g->d_adj_ptr); (void)hipFree(g->d_adj_idx); (void)hipFree(g->d_queries);
   (void)hipFree(g->d_flags); (void)hipFree(g->d_frontier); (void)hipFree(g->d_count); (void)hipFree(g->d_chains);
   (void)hipFree(g->d_pose); (void)hipFree(g->d_nb_query); (void)hipFree(g->d_nb_idx); (void)hipFree(g->d_nb_d2);
+  (void)hipFree(g->d_rl_flag); (void)hipFree(g->d_rl_prefix); (void)hipFree(g->d_rl_seeds); (void)hipFree(g->d_rl_count);
+  (void)hipFree(g->d_rl_begin); (void)hipFree(g->d_rl_idx);
   if (g->ev[0]) {(void)hipEventDestroy(g->ev[0]);}
   if (g->ev[1]) {(void)hipEventDestroy(g->ev[1]);}
   if (g->stream) {(void)hipStreamDestroy(g->stream);}
@@ -675,6 +799,106 @@ int kh_graph_find_near_by_vertices(kh_graph * g, const double query_xy[2], doubl
 }
 
 double kh_graph_last_near_by_kernel_ms(kh_graph * g) {return g ? g->last_near_by_ms : 0.0;}
+
+}  // extern "C"
+namespace kh
+{
+// kh_graph_relocalize_candidates with vectors for the answer (the mapper's kh_mapper_relocalize calls this form).  The arguments
+// have been checked by the caller.
+int graph_relocalize_candidates(kh_graph * g, double seed_spacing, double base_radius, int32_t max_base, const double * center_xy, double radius,
+  std::vector<int32_t> & seeds, std::vector<int32_t> & base_begin, std::vector<int32_t> & base_idx)
+{
+  const char * who = "kh_graph_relocalize_candidates";
+  seeds.clear(); base_begin.assign(1, 0); base_idx.clear();
+  g->last_relocalize_ms = 0.0;
+  if (g->n == 0) {return KH_OK;}
+  int rc = near_by_ready(g, who); if (rc) {return rc;}
+  const size_t n = static_cast<size_t>(g->n);
+  rc = ensure(g->d_rl_flag, g->cap_rl_flag, n); if (rc) {return rc;}
+  rc = ensure(g->d_rl_prefix, g->cap_rl_prefix, n + 1); if (rc) {return rc;}
+  rc = ensure(g->d_rl_seeds, g->cap_rl_seeds, n); if (rc) {return rc;}
+  const double2 * pose = reinterpret_cast<const double2 *>(g->d_pose);
+  const bool use_region = center_xy && radius > 0;
+  double ms_total = 0.0;
+  hipError_t err = hipSuccess;
+  auto failed = [&]() {
+      set_error(std::string(who) + ": " + hipGetErrorString(err));
+      return KH_ERR_HIP;
+    };
+  // the kernels launched since ev[0], then `count` int32 from `src`, and a drained stream
+  auto finish = [&](int32_t * dst, const int32_t * src, size_t count) {
+      (void)hipEventRecord(g->ev[1], g->stream);
+      err = hipGetLastError();
+      if (err == hipSuccess) {err = hipMemcpyAsync(dst, src, count * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream);}
+      if (err == hipSuccess) {err = hipStreamSynchronize(g->stream);}
+      if (err != hipSuccess) {return false;}
+      float ms = 0.f;
+      (void)hipEventElapsedTime(&ms, g->ev[0], g->ev[1]);
+      ms_total += ms;
+      return true;
+    };
+  // (1) seeds: flags, then their ordered list
+  (void)hipEventRecord(g->ev[0], g->stream);
+  hipLaunchKernelGGL(k_seed_cover, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, g->stream, pose, g->n, seed_spacing,
+    use_region ? 1 : 0, use_region ? center_xy[0] : 0.0, use_region ? center_xy[1] : 0.0, radius * radius + kTol, g->d_rl_flag);
+  hipLaunchKernelGGL(k_prefix_list, dim3(1), dim3(256), 0, g->stream, g->d_rl_flag, g->n, g->d_rl_prefix, g->d_rl_seeds);
+  int32_t n_seeds = 0;
+  if (!finish(&n_seeds, g->d_rl_prefix + n, 1)) {return failed();}
+  if (n_seeds < 0 || static_cast<size_t>(n_seeds) > n) {set_error(std::string(who) + ": seed count out of range"); return KH_ERR_HIP;}
+  g->last_relocalize_ms = ms_total;
+  if (n_seeds == 0) {return KH_OK;}
+  // (2) per seed: how many vertices in range, how many kept; base_begin = the prefix of the kept counts
+  const size_t ns = static_cast<size_t>(n_seeds);
+  rc = ensure(g->d_rl_count, g->cap_rl_count, 2 * ns); if (rc) {return rc;}
+  rc = ensure(g->d_rl_begin, g->cap_rl_begin, ns + 1); if (rc) {return rc;}
+  int32_t * d_raw = g->d_rl_count, * d_kept = g->d_rl_count + ns;
+  const double range_sq_plus = base_radius * base_radius + kTol;         // Square(maxDistance) + KT_TOLERANCE, as k_loop_candidates
+  const unsigned gather_blocks = static_cast<unsigned>((ns + 3) / 4);
+  (void)hipEventRecord(g->ev[0], g->stream);
+  hipLaunchKernelGGL(k_base_gather, dim3(gather_blocks), dim3(256), 0, g->stream, pose, g->n, g->d_rl_seeds, n_seeds, range_sq_plus, max_base, 0,
+    d_raw, d_kept, static_cast<const int32_t *>(nullptr), static_cast<int32_t *>(nullptr));
+  hipLaunchKernelGGL(k_prefix_list, dim3(1), dim3(256), 0, g->stream, d_kept, n_seeds, g->d_rl_begin, static_cast<int32_t *>(nullptr));
+  int32_t total = 0;
+  if (!finish(&total, g->d_rl_begin + ns, 1)) {return failed();}
+  if (total < 0 || static_cast<size_t>(total) > ns * static_cast<size_t>(max_base)) {set_error(std::string(who) + ": base total out of range"); return KH_ERR_HIP;}
+  // (3) the base lists, in list order
+  rc = ensure(g->d_rl_idx, g->cap_rl_idx, std::max<size_t>(static_cast<size_t>(total), 1)); if (rc) {return rc;}
+  seeds.resize(ns); base_begin.resize(ns + 1); base_idx.resize(static_cast<size_t>(total));
+  (void)hipEventRecord(g->ev[0], g->stream);
+  hipLaunchKernelGGL(k_base_gather, dim3(gather_blocks), dim3(256), 0, g->stream, pose, g->n, g->d_rl_seeds, n_seeds, range_sq_plus, max_base, 1,
+    d_raw, d_kept, g->d_rl_begin, g->d_rl_idx);
+  if (!finish(base_begin.data(), g->d_rl_begin, ns + 1)) {return failed();}
+  err = hipMemcpyAsync(seeds.data(), g->d_rl_seeds, ns * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream);
+  if (err == hipSuccess && total > 0) {
+    err = hipMemcpyAsync(base_idx.data(), g->d_rl_idx, static_cast<size_t>(total) * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream);
+  }
+  if (err == hipSuccess) {err = hipStreamSynchronize(g->stream);}
+  if (err != hipSuccess) {return failed();}
+  g->last_relocalize_ms = ms_total;
+  return KH_OK;
+}
+}  // namespace kh
+extern "C" {
+
+int kh_graph_relocalize_candidates(kh_graph * g, double seed_spacing, double base_radius, int32_t max_base, const double * center_xy, double radius,
+  int32_t * seeds, int32_t cap_seeds, int32_t * n_seeds, int32_t * base_begin, int32_t * base_idx, int32_t cap_base, int32_t * n_base)
+{
+  if (!g || !n_seeds || !n_base || !base_begin || !(seed_spacing > 0) || !std::isfinite(seed_spacing) || !std::isfinite(base_radius) || base_radius < 0 ||
+    max_base < 1 || radius != radius || cap_seeds < 0 || cap_base < 0 || (cap_seeds > 0 && !seeds) || (cap_base > 0 && !base_idx) ||
+    (center_xy && !(std::isfinite(center_xy[0]) && std::isfinite(center_xy[1])))) {return KH_ERR_INVALID_ARG;}
+  *n_seeds = 0; *n_base = 0; base_begin[0] = 0;
+  std::vector<int32_t> s, b, idx;
+  const int rc = kh::graph_relocalize_candidates(g, seed_spacing, base_radius, max_base, center_xy, radius, s, b, idx);
+  if (rc) {return rc;}
+  *n_seeds = static_cast<int32_t>(s.size()); *n_base = static_cast<int32_t>(idx.size());
+  const size_t ws = std::min(s.size(), static_cast<size_t>(cap_seeds));
+  std::copy(s.begin(), s.begin() + static_cast<std::ptrdiff_t>(ws), seeds);
+  std::copy(b.begin(), b.begin() + static_cast<std::ptrdiff_t>(ws + 1), base_begin);
+  std::copy(idx.begin(), idx.begin() + static_cast<std::ptrdiff_t>(std::min(idx.size(), static_cast<size_t>(cap_base))), base_idx);
+  return KH_OK;
+}
+
+double kh_graph_last_relocalize_kernel_ms(kh_graph * g) {return g ? g->last_relocalize_ms : 0.0;}
 
 int kh_graph_set_scan_limit(kh_graph * g, int32_t n_visit)
 {

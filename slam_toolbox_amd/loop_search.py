@@ -136,6 +136,26 @@ class MapperGraphSearch:
                 return out[:total.value]
             cap = total.value
 
+    def RelocalizeCandidates(self, seed_spacing, base_radius, max_base=40, center_xy=None, radius=0.0):
+        """kh_graph_relocalize_candidates over the store's poses -> (seeds, base_begin, base_idx): the vertex of lowest index of every
+        cell of a lattice of side seed_spacing (inside the region, if one is given), and per seed the vertices within base_radius of it,
+        at most max_base of them by the stride rule, in CSR form"""
+        c = None if center_xy is None else np.ascontiguousarray(center_xy, dtype=np.float64)[:2].copy()
+        cap_s, cap_b = 64, 1024
+        n_s, n_b = C.c_int32(0), C.c_int32(0)
+        while True:
+            seeds, begin, idx = np.zeros(cap_s, dtype=np.int32), np.zeros(cap_s + 1, dtype=np.int32), np.zeros(cap_b, dtype=np.int32)
+            capi.check(capi.lib().kh_graph_relocalize_candidates(self._h, float(seed_spacing), float(base_radius), int(max_base),
+                                                                 None if c is None else c.ctypes.data, float(radius), seeds.ctypes.data, cap_s,
+                                                                 C.byref(n_s), begin.ctypes.data, idx.ctypes.data, cap_b, C.byref(n_b)),
+                       "kh_graph_relocalize_candidates")
+            if n_s.value <= cap_s and n_b.value <= cap_b:
+                return seeds[:n_s.value], begin[:n_s.value + 1], idx[:n_b.value]
+            cap_s, cap_b = max(cap_s, n_s.value), max(cap_b, n_b.value)
+
+    def last_relocalize_kernel_ms(self):
+        return capi.lib().kh_graph_last_relocalize_kernel_ms(self._h)
+
     def last_kernel_ms(self):
         return capi.lib().kh_graph_last_kernel_ms(self._h)
 

@@ -10,10 +10,14 @@ Nothing here computes: every call lands in the library."""
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
 from . import capi
+
+
+Hypothesis = namedtuple("Hypothesis", "index seed_scan heading coarse_mean coarse_cov coarse_response fine_mean fine_cov fine_response robot_pose")
 
 
 class Mapper:
@@ -101,6 +105,36 @@ class Mapper:
         out = np.zeros(6, dtype=np.int64)
         capi.check(capi.lib().kh_mapper_map_stats(self._h, out), "kh_mapper_map_stats")
         return dict(zip(("calls", "scans_traced", "point_uploads", "range_uploads", "point_uploads_total", "range_uploads_total"), out.tolist()))
+
+    def relocalize(self, ranges, cap: int = 64, **params):
+        """kh_mapper_relocalize: where in the map this scan was taken, without a pose guess.  params: fields of
+        kh_relocalize_params (seed_spacing, n_headings, max_base, top_k, center_xy, radius) over the defaults of this mapper's
+        parameters.  Returns (hypotheses, summary): the accepted hypotheses, best first, as Hypothesis records -- robot_pose is what
+        ProcessAgainstNodesNearBy takes -- and the totals as a dict.  The mapper is left as it was."""
+        ranges = np.ascontiguousarray(ranges, dtype=np.float64)
+        assert ranges.shape == (self.n_beams,)
+        p = capi.KhRelocalizeParams()
+        capi.lib().kh_relocalize_params_default(C.byref(self.params()), C.byref(p))
+        for k, v in params.items():
+            if k == "center_xy":
+                p.center_xy[0], p.center_xy[1] = float(v[0]), float(v[1])
+            elif k != "pad" and hasattr(p, k):
+                setattr(p, k, v)
+            else:
+                raise KeyError(k)
+        out = (capi.KhRelocalizeHyp * max(1, int(cap)))()
+        summary = capi.KhRelocalizeSummary()
+        capi.check(capi.lib().kh_mapper_relocalize(self._h, ranges.ctypes.data, C.byref(p), out, int(cap), C.byref(summary)), "kh_mapper_relocalize")
+        hyps = [Hypothesis(h.index, h.seed_scan, h.heading, np.array(h.coarse_mean), np.array(h.coarse_cov).reshape(3, 3), h.coarse_response,
+                           np.array(h.fine_mean), np.array(h.fine_cov).reshape(3, 3), h.fine_response, np.array(h.robot_pose))
+                for h in out[:summary.n_returned]]
+        return hyps, {k: getattr(summary, k) for k, _ in capi.KhRelocalizeSummary._fields_}
+
+    def params(self):
+        """the kh_mapper_params this mapper was made with"""
+        p = capi.KhMapperParams()
+        capi.check(capi.lib().kh_mapper_get_params(self._h, C.byref(p)), "kh_mapper_get_params")
+        return p
 
     def _first_after_load(self, ranges, time):
         """the entry the first scan after a load goes through when a start mode was asked for; None = none pending"""
