@@ -816,6 +816,71 @@ KH_API int kh_merge_build(kh_merge * g, uint32_t min_pass_through, double occupa
  * [5], [6] the same two since the merger was made, [7] bytes of the two tables the last merge uploaded */
 KH_API int kh_merge_stats(const kh_merge * g, int64_t out[8]);
 
+/* ---- how well a correction places a submap, and corrections found automatically ("Fit and alignment").
+ * The REFERENCE GRID of a submap M is the merge of every OTHER submap under its current correction (kh_merge_build without M).
+ * For a candidate correction C of M, M's scans are traced under C on that grid's geometry exactly as kh_merge_build would trace
+ * them -- the same gate, roundings and TraceLine walk -- but every visit looks up the STATE of the cell it would have incremented
+ * (0 unknown, 100 occupied, 255 free) and is counted by state; visits outside the grid are dropped.  pass_s counts all visits of
+ * cells in state s, hits_s those that are the end point of a beam that counts as a hit.  The end cell of a hit beam is visited
+ * twice (by the line, then as the hit), so pass_s - 2 hits_s is the number of visits that are not such an end cell:
+ *   agree    = hits_occupied + (pass_free - 2 hits_free)        beam ends on walls the others saw, rays through what they saw free
+ *   conflict = (pass_occupied - 2 hits_occupied) + hits_free    rays through walls the others saw, beam ends where they saw free
+ *   known    = agree + conflict;  score = agree / known as one FP64 division, 0.0 when known is 0
+ * All sums are integers, so the result does not depend on the order the device adds them in. */
+typedef struct kh_merge_fit_t {
+  uint64_t pass_unknown, pass_occupied, pass_free, hits_unknown, hits_occupied, hits_free;
+  uint64_t agree, conflict, known;
+  double score;
+} kh_merge_fit_t;
+/* n_candidates corrections (tx, ty, yaw) of ONE submap against the merge of all the others: the reference grid is built once, then
+ * one kernel counts every candidate (one wave per candidate, scan and run of 64 beams; k_occ_fit_merged).  Nothing of the merger
+ * changes: no correction, no location.  NULL corrections / out, n_candidates < 1, a non-finite correction or a non-finite
+ * occupancy_threshold are KH_ERR_INVALID_ARG before a device is looked for; without a device KH_ERR_NO_DEVICE; then a NULL merger
+ * is KH_ERR_INVALID_ARG (the handle is looked at after the device, as kh_mapper_relocalize looks at its mapper: a merger cannot
+ * exist without one); an unknown id KH_ERR_NOT_FOUND; no other submap, or no scan in any other submap, KH_ERR_INVALID_ARG as for
+ * kh_merge_build.  Every min_pass_through is valid (a cell is known when it was passed more often), as for kh_occupancy_update.
+ * A failure leaves the merger usable. */
+KH_API int kh_merge_fit(kh_merge * g, int32_t submap_id, int32_t n_candidates, const double * corrections /* 3n */,
+                        uint32_t min_pass_through, double occupancy_threshold, kh_merge_fit_t * out /* n */);
+/* [0] fits made (kh_merge_align makes one), [1] candidates fitted since the merger was made, [2] beams x candidates and [3] kernel
+ * microseconds (HIP events) of the last fit */
+KH_API int kh_merge_fit_stats(const kh_merge * g, int64_t out[4]);
+
+/* Automatic alignment of submap `moving` to submap `target`.  n_probes scans of the moving submap -- entry floor(j * n_alive /
+ * n_probes), j = 0 .. n_probes - 1, of its scans in scan-id order, n_probes clipped to their number -- are relocalized in the
+ * target's map (kh_mapper_relocalize on the target's mapper with the probe's ranges).  Each returned hypothesis implies the
+ * correction C = (T_target . P) . inverse(Q): P the hypothesis' robot_pose, Q the probe's corrected pose in its own session, T_target
+ * the target's correction, `.` and inverse as kh_merge_move_submap composes.  Candidate 0 is the moving submap's current
+ * correction, then the probes in order, each one's hypotheses in rank order; nothing is de-duplicated.  One scan cannot tell two
+ * identical aisles apart, so the candidates are ranked by how the WHOLE session fits (kh_merge_fit against
+ * all other submaps): known >= min_known first, then score descending, agree descending, candidate index ascending. */
+typedef struct kh_merge_align_params {
+  int32_t n_probes;            /* probe scans of the moving submap, >= 1 (default 4) */
+  int32_t top_k;               /* hypotheses kept per probe, >= 1 (default 4) */
+  uint64_t min_known;          /* candidates with fewer known visits rank last (default 0) */
+  uint32_t min_pass_through; uint32_t pad; double occupancy_threshold;        /* the reference grid's Update rule (defaults 2, 0.1) */
+  kh_relocalize_params relocalize;   /* as for kh_mapper_relocalize on the target's mapper; its top_k is overridden by top_k above */
+} kh_merge_align_params;
+typedef struct kh_merge_align_cand {
+  double correction[3];
+  int32_t probe_scan;          /* scan id in the moving submap; -1 for candidate 0 */
+  int32_t hypothesis;          /* rank of the hypothesis in the probe's relocalization; -1 for candidate 0 */
+  double fine_response;        /* 0 for candidate 0 */
+  int32_t index, enough;       /* candidate index before ranking; known >= min_known */
+  kh_merge_fit_t fit;
+} kh_merge_align_cand;
+/* defaults; the relocalization parameters are those of the target's mapper (g NULL or an unknown id: of kh_mapper_params_default) */
+KH_API void kh_merge_align_params_default(const kh_merge * g, int32_t target_submap, kh_merge_align_params * p);
+/* out takes the first min(cap, n) ranked candidates, *n_candidates takes n.  times_ms (may be NULL): [0] the relocalizations, [1]
+ * the fit's reference grid, [2] the fit kernel (HIP events), [3] the whole call.  The merger and both mappers are left as they
+ * were (scans become resident on the device, as in any merge); the caller applies a result with kh_merge_set_transform.
+ * KH_ERR_INVALID_ARG before a device is looked for: NULL params / n_candidates, out NULL with cap > 0, cap < 0, n_probes < 1,
+ * top_k < 1, a non-finite occupancy_threshold, invalid relocalization parameters, moving == target (every min_pass_through and
+ * min_known is valid).  Then: no device KH_ERR_NO_DEVICE, a NULL merger KH_ERR_INVALID_ARG, an unknown id KH_ERR_NOT_FOUND, lasers that differ in any field of kh_laser KH_ERR_INVALID_ARG (the probe's ranges are read by the target's
+ * laser; kh_merge_fit has no such restriction).  A failure leaves the merger usable. */
+KH_API int kh_merge_align(kh_merge * g, int32_t moving_submap, int32_t target_submap, const kh_merge_align_params * params,
+                          kh_merge_align_cand * out, int32_t cap, int32_t * n_candidates, double times_ms[4]);
+
 /* ---- the live map: the occupancy map slam_toolbox republishes every map_update_interval, kept on the mapper's device and brought
  * up to date by the DIFFERENCE since the last update instead of a fresh kh_mapper_build_map over every scan.  After
  * kh_live_map_update the pass / hit / cell grids are, bit for bit, what a fresh trace of the mapper's scans at their current poses

@@ -103,6 +103,7 @@ SYMBOLS = [
     "kh_occupancy_read_nav", "kh_map_feed_create", "kh_map_feed_destroy", "kh_map_feed_poll", "kh_map_feed_tiles", "kh_map_feed_read",
     "kh_map_feed_stats",
     "kh_graph_relocalize_candidates", "kh_graph_last_relocalize_kernel_ms", "kh_relocalize_params_default", "kh_mapper_relocalize", "kh_mapper_get_params",
+    "kh_merge_fit", "kh_merge_fit_stats", "kh_merge_align_params_default", "kh_merge_align",
 ]
 
 
@@ -191,6 +192,21 @@ class KhRelocalizeHyp(C.Structure):
 class KhRelocalizeSummary(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("n_seeds", "n_headings", "n_hypotheses", "n_passed", "n_accepted", "n_returned")] + \
                [(k, C.c_double) for k in ("kernel_ms", "candidates_ms", "scans_ms", "batch_ms", "total_ms")]
+
+
+class KhMergeFit(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("pass_unknown", "pass_occupied", "pass_free", "hits_unknown", "hits_occupied", "hits_free",
+                                          "agree", "conflict", "known")] + [("score", C.c_double)]
+
+
+class KhMergeAlignParams(C.Structure):
+    _fields_ = [("n_probes", C.c_int32), ("top_k", C.c_int32), ("min_known", C.c_uint64), ("min_pass_through", C.c_uint32), ("pad", C.c_uint32),
+                ("occupancy_threshold", C.c_double), ("relocalize", KhRelocalizeParams)]
+
+
+class KhMergeAlignCand(C.Structure):
+    _fields_ = [("correction", C.c_double * 3), ("probe_scan", C.c_int32), ("hypothesis", C.c_int32), ("fine_response", C.c_double),
+                ("index", C.c_int32), ("enough", C.c_int32), ("fit", KhMergeFit)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
@@ -385,6 +401,12 @@ def lib():
         L.kh_merge_build_submap.argtypes = [vp, i32, C.c_uint32, dbl, C.POINTER(vp)]
         L.kh_merge_build.argtypes = [vp, C.c_uint32, dbl, C.POINTER(vp)]
         L.kh_merge_stats.argtypes = [vp, np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")]
+    if hasattr(L, "kh_merge_fit"):
+        L.kh_merge_fit.argtypes = [vp, i32, i32, vp, C.c_uint32, dbl, C.POINTER(KhMergeFit)]
+        L.kh_merge_fit_stats.argtypes = [vp, np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")]
+        L.kh_merge_align_params_default.argtypes = [vp, i32, C.POINTER(KhMergeAlignParams)]
+        L.kh_merge_align_params_default.restype = None
+        L.kh_merge_align.argtypes = [vp, i32, i32, C.POINTER(KhMergeAlignParams), C.POINTER(KhMergeAlignCand), i32, C.POINTER(i32), vp]
     if hasattr(L, "kh_live_map_create"):
         L.kh_mapper_set_scan_pose.argtypes = [vp, i32, dptr]
         L.kh_live_map_create.argtypes = [vp, dbl, vp, dbl, C.POINTER(vp)]

@@ -1763,7 +1763,7 @@ void mapper_alive_scans(const kh_mapper * m, std::vector<ScanView> & out)
   for (const auto & sp : m->scans) {
     if (!sp) {continue;}
     ScanView v;
-    v.id = sp->id; v.points = sp->points.data();
+    v.id = sp->id; v.points = sp->points.data(); v.ranges = sp->ranges.data();
     v.corrected[0] = sp->corrected.x; v.corrected[1] = sp->corrected.y; v.corrected[2] = sp->corrected.h;
     v.odometric[0] = sp->odometric.x; v.odometric[1] = sp->odometric.y; v.odometric[2] = sp->odometric.h;
     v.barycenter[0] = sp->barycenter[0]; v.barycenter[1] = sp->barycenter[1];

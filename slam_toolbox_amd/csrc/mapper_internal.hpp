@@ -8,11 +8,12 @@
 
 namespace kh
 {
-// one scan still in a mapper's map; `points` is the mapper's own host memory (valid until its next process / remove / destroy)
+// one scan still in a mapper's map; `points` is the mapper's own host memory (`ranges` too; valid until its next process / remove / destroy)
 struct ScanView
 {
   int32_t id;
   const double * points;        // 2 * n_beams unfiltered point readings
+  const double * ranges;        // n_beams range readings
   double corrected[3], odometric[3];
   double barycenter[3];         // GetBarycenterPose: heading 0, or the sensor pose when no reading is in range
   double bbox[4];               // min x, min y, max x, max y (LocalizedRangeScan::Update, Karto.h:5694-5700)

@@ -4,6 +4,8 @@
 //   processInteractiveFeedback  :313-352   kh_merge_move_submap (the MOUSE_UP branch: the release of the marker)
 //   transformScan               :195-248   kh_merge_get_scan (what it leaves on one scan), and the trace kernel for the readings
 //   mergeMapCallback            :251-291   kh_merge_build
+//   (no counterpart)                       kh_merge_fit, kh_merge_align: how well a correction places a submap among the others, and
+//                                          corrections proposed by relocalizing probe scans ("Fit and alignment")
 //
 // The reference rewrites every scan with the correction and hands the rewritten scans to OccupancyGrid::CreateFromScans.  Here the
 // scans stay as their mapper holds them -- resident in HBM, untransformed -- and the correction goes to the trace kernel as one
@@ -11,8 +13,10 @@
 // box (ComputeDimensions) and the corrected pose (sensor position).  The arithmetic is stated in DESIGN.md section 7a and restated
 // in numpy by tests/merge_rule.py; every operation below is in that order, and the library is built without FMA contraction.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -95,6 +99,7 @@ struct kh_merge
   int32_t next_id = 0;
   std::vector<Submap> submaps;               // ascending id
   int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int64_t fit_stats[4] = {0, 0, 0, 0};       // kh_merge_fit_stats
 };
 
 namespace kh
@@ -276,41 +281,51 @@ int kh_merge_build_submap(kh_merge * g, int32_t submap_id, uint32_t min_pass_thr
   return kh_mapper_build_map(s->mapper, g->resolution, min_pass_through, occupancy_threshold, out);
 }
 
-int kh_merge_build(kh_merge * g, uint32_t min_pass_through, double occupancy_threshold, kh_occupancy ** out)
+}  // extern "C"
+
+namespace kh
 {
-  if (!g || !out) {return KH_ERR_INVALID_ARG;}
-  *out = nullptr;
-  if (g->submaps.empty()) {kh::set_error("kh_merge_build: no submap"); return KH_ERR_INVALID_ARG;}
+namespace
+{
+// What kh_merge_build does, over every submap but `skip` (-1: none): the grid, traced and updated.  uploads[0], [1] = point-reading
+// and range uploads made, [2] = bytes of the two tables.
+int build_grid(kh_merge * g, int32_t skip, const char * who, uint32_t min_pass_through, double occupancy_threshold, kh_occupancy ** out,
+  int64_t * n_scans_out, int64_t * n_beams_out, int64_t uploads[3])
+{
+  const std::string name(who);
   // ComputeDimensions (Karto.h:6086-6112) over the boxes transformScan leaves
-  std::vector<std::vector<ScanView>> views(g->submaps.size());
+  std::vector<const Submap *> subs;
+  for (const Submap & s : g->submaps) {if (s.id != skip) {subs.push_back(&s);}}
+  if (subs.empty()) {set_error(name + (skip < 0 ? ": no submap" : ": no other submap")); return KH_ERR_INVALID_ARG;}
+  std::vector<std::vector<ScanView>> views(subs.size());
   Box box;
   int64_t n_scans = 0, n_beams = 0;
   int32_t max_beams = 0;
-  for (size_t k = 0; k < g->submaps.size(); ++k) {
-    const Submap & s = g->submaps[k];
-    kh::mapper_alive_scans(s.mapper, views[k]);
+  for (size_t k = 0; k < subs.size(); ++k) {
+    const Submap & s = *subs[k];
+    mapper_alive_scans(s.mapper, views[k]);
     for (const ScanView & v : views[k]) {loose_box(s.correction, v.bbox, &box);}
     n_scans += static_cast<int64_t>(views[k].size());
     n_beams += static_cast<int64_t>(views[k].size()) * s.laser.n_beams;
     if (!views[k].empty()) {max_beams = std::max(max_beams, s.laser.n_beams);}
   }
-  if (n_scans == 0) {kh::set_error("kh_merge_build: no scan in any submap"); return KH_ERR_INVALID_ARG;}
-  if (n_scans > INT32_MAX) {kh::set_error("kh_merge_build: too many scans"); return KH_ERR_INVALID_ARG;}
+  if (n_scans == 0) {set_error(name + (skip < 0 ? ": no scan in any submap" : ": no scan in any other submap")); return KH_ERR_INVALID_ARG;}
+  if (n_scans > INT32_MAX) {set_error(name + ": too many scans"); return KH_ERR_INVALID_ARG;}
   int32_t width, height;
   double offset[2];
-  kh::grid_dimensions(box, g->resolution, &width, &height, offset);
+  grid_dimensions(box, g->resolution, &width, &height, offset);
   kh_occupancy * grid = nullptr;
   int rc = kh_occupancy_create(width, height, offset[0], offset[1], g->resolution, g->device, &grid);
   if (rc) {return rc;}
-  void * stream = kh::occupancy_stream(grid);
-  auto fail = [&](int code) {kh::stream_synchronize(stream); kh_occupancy_destroy(grid); return code;};
+  void * stream = occupancy_stream(grid);
+  auto fail = [&](int code) {stream_synchronize(stream); kh_occupancy_destroy(grid); return code;};
   std::vector<MergeScan> scan_table;
   std::vector<MergeSubmap> submap_table;
   std::vector<ResidentScan> resident;
   scan_table.reserve(static_cast<size_t>(n_scans));
   int64_t up_points = 0, up_ranges = 0;
-  for (size_t k = 0; k < g->submaps.size(); ++k) {
-    const Submap & s = g->submaps[k];
+  for (size_t k = 0; k < subs.size(); ++k) {
+    const Submap & s = *subs[k];
     const Rigid & t = s.correction;
     MergeSubmap rec = {};                          // (value-initialised: the pad words are uploaded too)
     rec.c = t.c; rec.s = t.s; rec.tx = t.x; rec.ty = t.y;
@@ -319,29 +334,125 @@ int kh_merge_build(kh_merge * g, uint32_t min_pass_through, double occupancy_thr
     submap_table.push_back(rec);
     // the residency loop kh_mapper_build_map runs: the correction is no reason to upload
     int64_t up_p = 0, up_r = 0;
-    rc = kh::mapper_resident_table(s.mapper, stream, "kh_merge_build", resident, &up_p, &up_r);
+    rc = mapper_resident_table(s.mapper, stream, who, resident, &up_p, &up_r);
     if (rc) {return fail(rc);}
     up_points += up_p; up_ranges += up_r;
-    if (resident.size() != views[k].size()) {kh::set_error("kh_merge_build: a submap changed during the merge"); return fail(KH_ERR_INVALID_ARG);}
+    if (resident.size() != views[k].size()) {set_error(name + ": a submap changed during the merge"); return fail(KH_ERR_INVALID_ARG);}
     for (size_t i = 0; i < views[k].size(); ++i) {
       // GetSensorPose() of the transformed scan = GetSensorAt(transformed corrected pose), Karto.h:5566-5569
       double corrected[3], sensor[3];
       t.pose(views[k][i].corrected, corrected);
-      kh::laser_sensor_at(s.laser, corrected, sensor);
+      laser_sensor_at(s.laser, corrected, sensor);
       MergeScan scan = {};
       scan.points = resident[i].points; scan.ranges = resident[i].ranges;
       scan.sx = sensor[0]; scan.sy = sensor[1]; scan.submap = static_cast<int32_t>(k);
       scan_table.push_back(scan);
     }
   }
-  rc = kh::occupancy_add_merged(grid, static_cast<int32_t>(n_scans), scan_table.data(), static_cast<int32_t>(g->submaps.size()), submap_table.data(),
+  rc = occupancy_add_merged(grid, static_cast<int32_t>(n_scans), scan_table.data(), static_cast<int32_t>(subs.size()), submap_table.data(),
       max_beams, n_beams);
   if (rc == KH_OK) {rc = kh_occupancy_update(grid, min_pass_through, occupancy_threshold);}
   if (rc) {return fail(rc);}
-  g->stats[0] += 1; g->stats[1] = n_scans; g->stats[2] = n_beams; g->stats[3] = up_points; g->stats[4] = up_ranges;
-  g->stats[5] += up_points; g->stats[6] += up_ranges;
-  g->stats[7] = static_cast<int64_t>(scan_table.size() * sizeof(MergeScan) + submap_table.size() * sizeof(MergeSubmap));
+  *n_scans_out = n_scans; *n_beams_out = n_beams;
+  uploads[0] = up_points; uploads[1] = up_ranges;
+  uploads[2] = static_cast<int64_t>(scan_table.size() * sizeof(MergeScan) + submap_table.size() * sizeof(MergeSubmap));
   *out = grid;
+  return KH_OK;
+}
+
+bool finite3(const double * t) {return std::isfinite(t[0]) && std::isfinite(t[1]) && std::isfinite(t[2]);}
+
+double ms_since(std::chrono::steady_clock::time_point t)
+{
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
+// The fit of n candidate corrections of submap `moving` against the merge of all the others: the reference
+// grid once, then one launch of k_occ_fit_merged.  times_ms[0] = the reference grid (wall), [1] = the fit kernel (events).
+int fit_candidates(kh_merge * g, const Submap & moving, const char * who, int32_t n, const double * corrections, uint32_t min_pass_through,
+  double occupancy_threshold, kh_merge_fit_t * out, double times_ms[2])
+{
+  const auto t_begin = std::chrono::steady_clock::now();
+  kh_occupancy * grid = nullptr;
+  int64_t n_ref_scans = 0, n_ref_beams = 0, uploads[3];
+  int rc = build_grid(g, moving.id, who, min_pass_through, occupancy_threshold, &grid, &n_ref_scans, &n_ref_beams, uploads);
+  if (rc) {return rc;}
+  times_ms[0] = ms_since(t_begin);
+  void * stream = occupancy_stream(grid);
+  auto done = [&](int code) {stream_synchronize(stream); kh_occupancy_destroy(grid); return code;};
+  std::vector<ScanView> views;
+  std::vector<ResidentScan> resident;
+  mapper_alive_scans(moving.mapper, views);
+  int64_t up_p = 0, up_r = 0;
+  rc = mapper_resident_table(moving.mapper, stream, who, resident, &up_p, &up_r);
+  if (rc) {return done(rc);}
+  if (resident.size() != views.size()) {set_error(std::string(who) + ": the submap changed during the fit"); return done(KH_ERR_INVALID_ARG);}
+  const size_t n_scans = views.size();
+  if (n_scans > static_cast<size_t>(INT32_MAX)) {set_error(std::string(who) + ": too many scans"); return done(KH_ERR_INVALID_ARG);}
+  std::vector<FitCandidate> candidates(static_cast<size_t>(n));
+  std::vector<FitSensor> sensors(static_cast<size_t>(n) * n_scans);
+  for (int32_t k = 0; k < n; ++k) {
+    const Rigid t(corrections[3 * k], corrections[3 * k + 1], corrections[3 * k + 2]);
+    candidates[static_cast<size_t>(k)] = FitCandidate{t.c, t.s, t.x, t.y};
+    for (size_t i = 0; i < n_scans; ++i) {
+      // GetSensorAt(transformed corrected pose), as build_grid does once per scan
+      double corrected[3], sensor[3];
+      t.pose(views[i].corrected, corrected);
+      laser_sensor_at(moving.laser, corrected, sensor);
+      sensors[static_cast<size_t>(k) * n_scans + i] = FitSensor{sensor[0], sensor[1]};
+    }
+  }
+  std::vector<uint64_t> sums(static_cast<size_t>(n) * kFitCounters);
+  rc = occupancy_fit_merged(grid, n, candidates.data(), sensors.data(), static_cast<int32_t>(n_scans), resident.data(), moving.laser.n_beams,
+      moving.laser.range_threshold, moving.laser.minimum_range, moving.laser.maximum_range, sums.data(), &times_ms[1]);
+  if (rc) {return done(rc);}
+  for (int32_t k = 0; k < n; ++k) {
+    const uint64_t * c = &sums[static_cast<size_t>(k) * kFitCounters];
+    kh_merge_fit_t & f = out[k];
+    f.pass_unknown = c[kFitPassUnknown]; f.pass_occupied = c[kFitPassOccupied]; f.pass_free = c[kFitPassFree];
+    f.hits_unknown = c[kFitHitsUnknown]; f.hits_occupied = c[kFitHitsOccupied]; f.hits_free = c[kFitHitsFree];
+    // pass - 2 hits = the visits that are not the end cell of a hit beam (that cell is visited twice: by the line, and as the hit)
+    f.agree = f.hits_occupied + (f.pass_free - 2 * f.hits_free);
+    f.conflict = (f.pass_occupied - 2 * f.hits_occupied) + f.hits_free;
+    f.known = f.agree + f.conflict;
+    f.score = f.known == 0 ? 0.0 : static_cast<double>(f.agree) / static_cast<double>(f.known);
+  }
+  g->fit_stats[0] += 1; g->fit_stats[1] += n;
+  g->fit_stats[2] = static_cast<int64_t>(n_scans) * moving.laser.n_beams * n;
+  g->fit_stats[3] = static_cast<int64_t>(times_ms[1] * 1000.0);
+  return done(KH_OK);
+}
+
+// the fit's ranking: enough known visits first, then score descending, agree descending, index ascending
+bool fit_before(const kh_merge_align_cand & a, const kh_merge_align_cand & b)
+{
+  if (a.enough != b.enough) {return a.enough > b.enough;}
+  if (a.fit.score != b.fit.score) {return a.fit.score > b.fit.score;}
+  if (a.fit.agree != b.fit.agree) {return a.fit.agree > b.fit.agree;}
+  return a.index < b.index;
+}
+
+bool same_laser(const kh_laser & a, const kh_laser & b)
+{
+  return a.n_beams == b.n_beams && a.minimum_angle == b.minimum_angle && a.angular_resolution == b.angular_resolution &&
+         a.minimum_range == b.minimum_range && a.maximum_range == b.maximum_range && a.range_threshold == b.range_threshold &&
+         a.offset_x == b.offset_x && a.offset_y == b.offset_y && a.offset_heading == b.offset_heading;
+}
+}  // namespace
+}  // namespace kh
+
+extern "C" {
+
+int kh_merge_build(kh_merge * g, uint32_t min_pass_through, double occupancy_threshold, kh_occupancy ** out)
+{
+  if (!g || !out) {return KH_ERR_INVALID_ARG;}
+  *out = nullptr;
+  int64_t n_scans = 0, n_beams = 0, uploads[3];
+  const int rc = kh::build_grid(g, -1, "kh_merge_build", min_pass_through, occupancy_threshold, out, &n_scans, &n_beams, uploads);
+  if (rc) {return rc;}
+  g->stats[0] += 1; g->stats[1] = n_scans; g->stats[2] = n_beams; g->stats[3] = uploads[0]; g->stats[4] = uploads[1];
+  g->stats[5] += uploads[0]; g->stats[6] += uploads[1];
+  g->stats[7] = uploads[2];
   return KH_OK;
 }
 
@@ -349,6 +460,122 @@ int kh_merge_stats(const kh_merge * g, int64_t out[8])
 {
   if (!g || !out) {return KH_ERR_INVALID_ARG;}
   std::copy(g->stats, g->stats + 8, out);
+  return KH_OK;
+}
+
+int kh_merge_fit(kh_merge * g, int32_t submap_id, int32_t n_candidates, const double * corrections, uint32_t min_pass_through,
+  double occupancy_threshold, kh_merge_fit_t * out)
+{
+  if (!corrections || !out || n_candidates < 1) {return KH_ERR_INVALID_ARG;}
+  if (!std::isfinite(occupancy_threshold)) {kh::set_error("kh_merge_fit: the occupancy threshold is not finite"); return KH_ERR_INVALID_ARG;}
+  for (int32_t k = 0; k < n_candidates; ++k) {
+    if (!kh::finite3(corrections + 3 * k)) {kh::set_error("kh_merge_fit: correction " + std::to_string(k) + " is not finite"); return KH_ERR_INVALID_ARG;}
+  }
+  if (kh::require_device(0) != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!g) {return KH_ERR_INVALID_ARG;}
+  const Submap * s = kh::find_submap(g, submap_id, "kh_merge_fit");
+  if (!s) {return KH_ERR_NOT_FOUND;}
+  double times_ms[2] = {0.0, 0.0};
+  return kh::fit_candidates(g, *s, "kh_merge_fit", n_candidates, corrections, min_pass_through, occupancy_threshold, out, times_ms);
+}
+
+int kh_merge_fit_stats(const kh_merge * g, int64_t out[4])
+{
+  if (!g || !out) {return KH_ERR_INVALID_ARG;}
+  std::copy(g->fit_stats, g->fit_stats + 4, out);
+  return KH_OK;
+}
+
+void kh_merge_align_params_default(const kh_merge * g, int32_t target_submap, kh_merge_align_params * p)
+{
+  if (!p) {return;}
+  std::memset(p, 0, sizeof(*p));
+  p->n_probes = 4; p->top_k = 4; p->min_known = 0;
+  p->min_pass_through = 2; p->occupancy_threshold = 0.1;          // OccupancyGrid's defaults, as slam_toolbox merges with
+  // the relocalization defaults of the target's mapper (of kh_mapper_params_default where there is none to ask)
+  kh_mapper_params mp;
+  const Submap * s = g ? kh::find_submap(g, target_submap, "kh_merge_align_params_default") : nullptr;
+  const bool have = s && kh_mapper_get_params(s->mapper, &mp) == KH_OK;
+  kh_relocalize_params_default(have ? &mp : nullptr, &p->relocalize);
+}
+
+int kh_merge_align(kh_merge * g, int32_t moving_submap, int32_t target_submap, const kh_merge_align_params * params, kh_merge_align_cand * out,
+  int32_t cap, int32_t * n_candidates, double times_ms[4])
+{
+  if (!params || !n_candidates || cap < 0 || (cap > 0 && !out)) {return KH_ERR_INVALID_ARG;}
+  *n_candidates = 0;
+  if (times_ms) {std::fill(times_ms, times_ms + 4, 0.0);}
+  const kh_relocalize_params & rp = params->relocalize;
+  if (params->n_probes < 1 || params->top_k < 1 || !std::isfinite(params->occupancy_threshold) || !(rp.seed_spacing > 0) ||
+    !std::isfinite(rp.seed_spacing) || rp.n_headings < 0 || rp.max_base < 1 || !std::isfinite(rp.radius) || !std::isfinite(rp.center_xy[0]) ||
+    !std::isfinite(rp.center_xy[1]))
+  {
+    kh::set_error("kh_merge_align: n_probes >= 1, top_k >= 1, a finite occupancy_threshold and valid relocalization parameters are required");
+    return KH_ERR_INVALID_ARG;
+  }
+  if (moving_submap == target_submap) {kh::set_error("kh_merge_align: a submap cannot be aligned to itself"); return KH_ERR_INVALID_ARG;}
+  if (kh::require_device(0) != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!g) {return KH_ERR_INVALID_ARG;}
+  const auto t_begin = std::chrono::steady_clock::now();
+  const Submap * moving = kh::find_submap(g, moving_submap, "kh_merge_align");
+  const Submap * target = moving ? kh::find_submap(g, target_submap, "kh_merge_align") : nullptr;
+  if (!moving || !target) {return KH_ERR_NOT_FOUND;}
+  if (!kh::same_laser(moving->laser, target->laser)) {
+    kh::set_error("kh_merge_align: the two submaps have different lasers (the probe's ranges are read by the target's laser)");
+    return KH_ERR_INVALID_ARG;
+  }
+  // candidate 0: what the moving submap has now
+  std::vector<kh_merge_align_cand> cands(1);
+  std::memset(&cands[0], 0, sizeof(cands[0]));
+  cands[0].correction[0] = moving->correction.x; cands[0].correction[1] = moving->correction.y; cands[0].correction[2] = moving->correction.yaw;
+  cands[0].probe_scan = -1; cands[0].hypothesis = -1;
+  // the probes: entry floor(j * n_alive / n_probes) of the alive scans, each relocalized in the target's map
+  std::vector<ScanView> views;
+  kh::mapper_alive_scans(moving->mapper, views);
+  const int64_t n_alive = static_cast<int64_t>(views.size());
+  const int64_t n_probes = std::min<int64_t>(params->n_probes, n_alive);
+  kh_relocalize_params relocalize = rp;
+  relocalize.top_k = params->top_k;
+  std::vector<kh_relocalize_hyp> hyps(static_cast<size_t>(params->top_k));
+  const auto t_relocalize = std::chrono::steady_clock::now();
+  for (int64_t j = 0; j < n_probes; ++j) {
+    const ScanView & probe = views[static_cast<size_t>(j * n_alive / n_probes)];
+    kh_relocalize_summary summary;
+    const int rc = kh_mapper_relocalize(target->mapper, probe.ranges, &relocalize, hyps.data(), params->top_k, &summary);
+    if (rc) {return rc;}
+    const Rigid q(probe.corrected[0], probe.corrected[1], probe.corrected[2]);
+    for (int32_t h = 0; h < summary.n_returned; ++h) {
+      // C = T_target . P . inverse(Q), left to right: the probe, at Q in its own session, stands at P in the target's
+      const double * pose = hyps[static_cast<size_t>(h)].robot_pose;
+      const Rigid c = compose(compose(target->correction, Rigid(pose[0], pose[1], pose[2])), inverse(q));
+      kh_merge_align_cand cand;
+      std::memset(&cand, 0, sizeof(cand));
+      cand.correction[0] = c.x; cand.correction[1] = c.y; cand.correction[2] = c.yaw;
+      cand.probe_scan = probe.id; cand.hypothesis = h; cand.fine_response = hyps[static_cast<size_t>(h)].fine_response;
+      cands.push_back(cand);
+    }
+  }
+  const double relocalize_ms = kh::ms_since(t_relocalize);
+  if (cands.size() > static_cast<size_t>(INT32_MAX)) {kh::set_error("kh_merge_align: too many candidates"); return KH_ERR_INVALID_ARG;}
+  const int32_t n = static_cast<int32_t>(cands.size());
+  std::vector<double> corrections(3 * cands.size());
+  for (size_t k = 0; k < cands.size(); ++k) {
+    if (!kh::finite3(cands[k].correction)) {kh::set_error("kh_merge_align: a candidate correction is not finite"); return KH_ERR_INVALID_ARG;}
+    std::copy(cands[k].correction, cands[k].correction + 3, &corrections[3 * k]);
+  }
+  std::vector<kh_merge_fit_t> fits(cands.size());
+  double fit_ms[2] = {0.0, 0.0};
+  const int rc = kh::fit_candidates(g, *moving, "kh_merge_align", n, corrections.data(), params->min_pass_through, params->occupancy_threshold,
+      fits.data(), fit_ms);
+  if (rc) {return rc;}
+  for (int32_t k = 0; k < n; ++k) {
+    cands[static_cast<size_t>(k)].fit = fits[static_cast<size_t>(k)];
+    cands[static_cast<size_t>(k)].index = k; cands[static_cast<size_t>(k)].enough = fits[static_cast<size_t>(k)].known >= params->min_known ? 1 : 0;
+  }
+  std::sort(cands.begin(), cands.end(), kh::fit_before);
+  std::copy(cands.begin(), cands.begin() + std::min(cap, n), out);
+  *n_candidates = n;
+  if (times_ms) {times_ms[0] = relocalize_ms; times_ms[1] = fit_ms[0]; times_ms[2] = fit_ms[1]; times_ms[3] = kh::ms_since(t_begin);}
   return KH_OK;
 }
 

@@ -91,6 +91,22 @@ struct WindowCells               // a live map's window of the lattice: cell (ox
   }
 };
 
+struct FitCells                  // a whole grid, READ: a visit counts the cell's state (0 unknown, 100 occupied, 255 free) in the lane's registers
+{
+  const OccDev & g;
+  uint32_t & pass_unknown, & pass_occupied, & pass_free, & hits_unknown, & hits_occupied, & hits_free;
+  __device__ __forceinline__ void add(int32_t cx, int32_t cy, bool hit) const
+  {
+    if (cx >= 0 && cx < g.width && cy >= 0 && cy < g.height) {
+      const uint32_t state = g.cells[cx + (int64_t)cy * g.ws];
+      // (three compares, no counter picked by an index computed from the state: that array would live in scratch memory)
+      const uint32_t unknown = state == 0u, occupied = state == 100u, is_free = state == 255u;
+      pass_unknown += unknown; pass_occupied += occupied; pass_free += is_free;
+      if (hit) {hits_unknown += unknown; hits_occupied += occupied; hits_free += is_free;}
+    }
+  }
+};
+
 // Grid<kt_int32u>::TraceLine (Karto.h:4874-4927) from cell (x0, y0) to cell (x1, y1), then the end point (Karto.h:6213-6229)
 template <typename Cells>
 __device__ __forceinline__ void occ_walk(const Cells & cells, int32_t x0, int32_t y0, int32_t x1, int32_t y1, bool hit)
@@ -172,6 +188,53 @@ __global__ __launch_bounds__(256) void k_occ_trace_merged(
   const double ux = sc.points[2 * i], uy = sc.points[2 * i + 1];
   const double px = (sm.c * ux - sm.s * uy) + sm.tx, py = (sm.s * ux + sm.c * uy) + sm.ty;
   occ_trace_beam(g, sc.ranges[i], px, py, sc.sx, sc.sy, sm.range_threshold, sm.min_range, sm.max_range);
+}
+
+// The FIT of candidate corrections of one submap against a finished grid (kh_merge_fit): k_occ_trace_merged's work layout times the
+// candidates -- one wave per (candidate, scan, run of 64 beams) -- and its arithmetic, but the walk looks up the state of every
+// cell it would have incremented and counts, per state, visits and hits in six registers of the lane (FitCells).  The grid is only
+// read.  A workgroup holds waves of ONE candidate (blocks_per_candidate = ceil(n_scans * runs_per_scan / 4)), so its sums go to one
+// row of `out`: lanes -> wave by shuffles, the four waves through LDS, then one vector atomicAdd per non-zero counter.  A wave
+// past the last scan and a lane past the beam count take part in the reduction with zeros: every wave reaches the barrier.
+// The lane counters are uint32 (a walk visits fewer cells than the grid has); the sums are 64-bit from the first shuffle on.
+__global__ __launch_bounds__(256) void k_occ_fit_merged(
+  OccDev g, const ResidentScan * __restrict__ scans, const FitCandidate * __restrict__ candidates, const FitSensor * __restrict__ sensors,
+  int32_t n_scans, int32_t n_beams, int32_t runs_per_scan, int32_t blocks_per_candidate, double range_threshold, double min_range,
+  double max_range, unsigned long long * __restrict__ out)
+{
+  __shared__ unsigned long long part[4][kFitCounters];
+  const int32_t candidate = (int32_t)(blockIdx.x / (uint32_t)blocks_per_candidate);
+  const int64_t wave = (int64_t)(blockIdx.x - (uint32_t)candidate * (uint32_t)blocks_per_candidate) * 4 + (threadIdx.x >> 6);
+  const int32_t lane = threadIdx.x & 63;
+  const int64_t s = wave / runs_per_scan;
+  const int32_t i = (int32_t)(wave - s * runs_per_scan) * 64 + lane;
+  uint32_t n[kFitCounters] = {0u, 0u, 0u, 0u, 0u, 0u};
+  if (s < n_scans && i < n_beams) {
+    const ResidentScan sc = scans[s];
+    const FitCandidate t = candidates[candidate];
+    const FitSensor sensor = sensors[(int64_t)candidate * n_scans + s];
+    const double ux = sc.points[2 * i], uy = sc.points[2 * i + 1];
+    const double px = (t.c * ux - t.s * uy) + t.tx, py = (t.s * ux + t.c * uy) + t.ty;
+    const Beam b = occ_gate(sc.ranges[i], px, py, sensor.sx, sensor.sy, range_threshold, min_range, max_range);
+    if (b.kept) {
+      const int32_t x0 = occ_cell(sensor.sx, g.off_x, g.scale), y0 = occ_cell(sensor.sy, g.off_y, g.scale);
+      const int32_t x1 = occ_cell(b.px, g.off_x, g.scale), y1 = occ_cell(b.py, g.off_y, g.scale);
+      occ_walk(FitCells{g, n[kFitPassUnknown], n[kFitPassOccupied], n[kFitPassFree], n[kFitHitsUnknown], n[kFitHitsOccupied], n[kFitHitsFree]},
+        x0, y0, x1, y1, b.hit);
+    }
+  }
+#pragma unroll
+  for (int32_t k = 0; k < kFitCounters; ++k) {
+    unsigned long long v = n[k];
+#pragma unroll
+    for (int32_t d = 32; d >= 1; d >>= 1) {v += __shfl_xor(v, d);}
+    if (lane == 0) {part[threadIdx.x >> 6][k] = v;}
+  }
+  __syncthreads();
+  if (threadIdx.x < kFitCounters) {
+    const unsigned long long v = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+    if (v) {atomicAdd(&out[(int64_t)candidate * kFitCounters + threadIdx.x], v);}
+  }
 }
 
 // UpdateCell (Karto.h:6240-6256) for the cell at index k of the three arrays
@@ -344,6 +407,7 @@ struct kh_occupancy
   ResidentScan * d_scans = nullptr; size_t cap_scans = 0;     // kh::occupancy_add_resident's table (capacity in bytes)
   uint8_t * d_merge = nullptr; size_t cap_merge = 0;          // kh::occupancy_add_merged's two tables (submaps, then scans; bytes)
   uint32_t * d_nav = nullptr; size_t cap_nav = 0;             // kh_occupancy_read_nav's dense output (capacity in bytes)
+  uint8_t * d_fit = nullptr; size_t cap_fit = 0;              // kh::occupancy_fit_merged's sums and three tables (bytes)
 };
 
 namespace kh
@@ -419,6 +483,53 @@ int occupancy_add_merged(kh_occupancy * g, int32_t n_scans, const MergeScan * sc
   return timed_trace(g, "kh_merge_build", n_total_beams, [&] {
     hipLaunchKernelGGL(k_occ_trace_merged, blocks_of_runs(n_scans, runs), dim3(256), 0, g->stream, g->dev, d_scans, d_submaps, n_scans, runs);
   });
+}
+
+int occupancy_fit_merged(kh_occupancy * g, int32_t n_candidates, const FitCandidate * candidates, const FitSensor * sensors, int32_t n_scans,
+  const ResidentScan * scans, int32_t n_beams, double range_threshold, double min_range, double max_range, uint64_t * out, double * kernel_ms)
+{
+  if (!g || n_candidates < 1 || !candidates || !out || n_scans < 0 || n_beams < 0 || (n_scans > 0 && (!scans || !sensors))) {return KH_ERR_INVALID_ARG;}
+  if (kernel_ms) {*kernel_ms = 0.0;}
+  std::fill(out, out + static_cast<size_t>(n_candidates) * kFitCounters, uint64_t{0});
+  if (hipSetDevice(g->device) != hipSuccess) {return KH_ERR_HIP;}
+  if (n_scans == 0 || n_beams == 0) {return hipStreamSynchronize(g->stream) == hipSuccess ? KH_OK : KH_ERR_HIP;}
+  const int32_t runs = (n_beams + 63) / 64;
+  const int64_t blocks_per_candidate = (static_cast<int64_t>(n_scans) * runs + 3) / 4;
+  if (blocks_per_candidate * n_candidates > INT32_MAX) {set_error("kh_merge_fit: too many candidates for one launch"); return KH_ERR_INVALID_ARG;}
+  // the sums first, then the tables: every part a multiple of 8 bytes
+  const size_t out_bytes = static_cast<size_t>(n_candidates) * kFitCounters * sizeof(unsigned long long);
+  const size_t cand_bytes = static_cast<size_t>(n_candidates) * sizeof(FitCandidate);
+  const size_t sensor_bytes = static_cast<size_t>(n_candidates) * static_cast<size_t>(n_scans) * sizeof(FitSensor);
+  const size_t scan_bytes = static_cast<size_t>(n_scans) * sizeof(ResidentScan);
+  const size_t bytes = out_bytes + cand_bytes + sensor_bytes + scan_bytes;
+  if (!grow_device(g->stream, reinterpret_cast<void **>(&g->d_fit), &g->cap_fit, bytes, bytes)) {
+    set_error("kh_merge_fit: table allocation failed");
+    return KH_ERR_HIP;
+  }
+  unsigned long long * d_out = reinterpret_cast<unsigned long long *>(g->d_fit);
+  uint8_t * const d_cand = g->d_fit + out_bytes, * const d_sensors = d_cand + cand_bytes, * const d_scans = d_sensors + sensor_bytes;
+  if (hipMemsetAsync(d_out, 0, out_bytes, g->stream) != hipSuccess ||
+    hipMemcpyAsync(d_cand, candidates, cand_bytes, hipMemcpyHostToDevice, g->stream) != hipSuccess ||
+    hipMemcpyAsync(d_sensors, sensors, sensor_bytes, hipMemcpyHostToDevice, g->stream) != hipSuccess ||
+    hipMemcpyAsync(d_scans, scans, scan_bytes, hipMemcpyHostToDevice, g->stream) != hipSuccess)
+  {
+    (void)hipStreamSynchronize(g->stream);
+    return KH_ERR_HIP;
+  }
+  (void)hipEventRecord(g->ev[0], g->stream);
+  hipLaunchKernelGGL(k_occ_fit_merged, dim3(static_cast<unsigned>(blocks_per_candidate * n_candidates)), dim3(256), 0, g->stream, g->dev,
+    reinterpret_cast<const ResidentScan *>(d_scans), reinterpret_cast<const FitCandidate *>(d_cand), reinterpret_cast<const FitSensor *>(d_sensors),
+    n_scans, n_beams, runs, static_cast<int32_t>(blocks_per_candidate), range_threshold, min_range, max_range, d_out);
+  (void)hipEventRecord(g->ev[1], g->stream);
+  static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the sums are downloaded as they lie");
+  if (hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, g->stream) != hipSuccess || hipStreamSynchronize(g->stream) != hipSuccess) {
+    set_error(std::string("kh_merge_fit: ") + hipGetErrorString(hipGetLastError()));
+    return KH_ERR_HIP;
+  }
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, g->ev[0], g->ev[1]);
+  if (kernel_ms) {*kernel_ms = ms;}
+  return KH_OK;
 }
 
 void live_trace_delta(void * stream, const LiveWindow & w, double anchor_x, double anchor_y, double scale, const DeltaRecord * d_records,
@@ -511,7 +622,7 @@ void kh_occupancy_destroy(kh_occupancy * g)
   (void)hipSetDevice(g->device);
   if (g->stream) {(void)hipStreamSynchronize(g->stream);}
   (void)hipFree(g->dev.pass); (void)hipFree(g->dev.hits); (void)hipFree(g->dev.cells); (void)hipFree(g->d_beams); (void)hipFree(g->d_scans); (void)hipFree(g->d_merge);
-  (void)hipFree(g->d_nav);
+  (void)hipFree(g->d_nav); (void)hipFree(g->d_fit);
   if (g->h_beams) {(void)hipHostFree(g->h_beams);}
   if (g->ev[0]) {(void)hipEventDestroy(g->ev[0]);}
   if (g->ev[1]) {(void)hipEventDestroy(g->ev[1]);}

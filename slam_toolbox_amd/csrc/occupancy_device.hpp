@@ -66,6 +66,19 @@ struct MergeSubmap
 };
 static_assert(sizeof(MergeScan) == 40 && sizeof(MergeSubmap) == 64, "records = 5 and 8 words of 8 bytes");
 
+// one candidate correction of the moving submap, and the sensor position of one of its scans under one candidate (k_occ_fit_merged)
+struct FitCandidate
+{
+  double c, s, tx, ty;       // cos / sin of the candidate's yaw (host libm), translation
+};
+struct FitSensor
+{
+  double sx, sy;             // GetSensorAt(transformed corrected pose): entry candidate * n_scans + scan
+};
+static_assert(sizeof(FitCandidate) == 32 && sizeof(FitSensor) == 16, "records = 4 and 2 words of 8 bytes");
+// the six counters of one candidate, in this order (kh_merge_fit_t's first six fields)
+enum : int32_t {kFitPassUnknown = 0, kFitPassOccupied = 1, kFitPassFree = 2, kFitHitsUnknown = 3, kFitHitsOccupied = 4, kFitHitsFree = 5, kFitCounters = 6};
+
 // the grids of a live map: lattice cells [ox, ox + width) x [oy, oy + height), row stride ws = (width + 7) & ~7
 struct LiveWindow
 {
@@ -135,6 +148,12 @@ int occupancy_add_resident(kh_occupancy * g, int32_t n_scans, const ResidentScan
 // over the scans (the grid's beam counter).  Returns after the trace has finished.
 int occupancy_add_merged(kh_occupancy * g, int32_t n_scans, const MergeScan * scans, int32_t n_submaps, const MergeSubmap * submaps,
   int32_t max_beams, int64_t n_total_beams);
+// The fit of n_candidates corrections of ONE submap against the grid's cell states (kh_merge_fit): the submap's n_scans resident
+// scans (their sx, sy are not read) of n_beams beams, sensors[candidate * n_scans + scan], the submap's laser gates.  out takes
+// kFitCounters sums per candidate; *kernel_ms the kernel's time by events.  The grid is read, never written.  Returns after the
+// kernel has finished and the sums are in `out`.
+int occupancy_fit_merged(kh_occupancy * g, int32_t n_candidates, const FitCandidate * candidates, const FitSensor * sensors, int32_t n_scans,
+  const ResidentScan * scans, int32_t n_beams, double range_threshold, double min_range, double max_range, uint64_t * out, double * kernel_ms);
 // n_records records on `stream`; counters[0] += lines walked, counters[1] += kept beams of MOVE records that were left alone
 void live_trace_delta(void * stream, const LiveWindow & w, double anchor_x, double anchor_y, double scale, const DeltaRecord * d_records,
   int32_t n_records, int32_t n_beams, double range_threshold, double min_range, double max_range, int32_t * d_log,

@@ -7,6 +7,8 @@
     merger.move_submap(b, (x, y, yaw))            # the release of the reference's interactive marker, or
     merger.set_transform(b, (tx, ty, yaw))        # the correction itself
     grid = merger.merge()                         # occupancy_grid.OccupancyGrid over every submap's scans
+    fits = merger.fit(b, [(tx, ty, yaw), ...])    # how well each correction places b among the others (counters, score)
+    cands, times = merger.align(b, a)             # corrections found by relocalizing probe scans of b in a's map, best fit first
 
 A merge never modifies a session: the correction is applied to the point readings inside the trace kernel, where the scans lie in
 HBM.  Nothing here computes: every call lands in the library."""
@@ -21,6 +23,14 @@ from . import capi
 
 STATS = ("merges", "scans_traced", "beams_traced", "point_uploads", "range_uploads", "point_uploads_total", "range_uploads_total",
          "table_bytes")
+FIT_STATS = ("fits", "candidates_total", "beam_candidates", "kernel_us")
+FIT_DTYPE = np.dtype([(k, np.uint64) for k in ("pass_unknown", "pass_occupied", "pass_free", "hits_unknown", "hits_occupied", "hits_free",
+                                               "agree", "conflict", "known")] + [("score", np.float64)])
+assert FIT_DTYPE.itemsize == C.sizeof(capi.KhMergeFit)
+ALIGN_DTYPE = np.dtype([("correction", np.float64, (3,)), ("probe_scan", np.int32), ("hypothesis", np.int32), ("fine_response", np.float64),
+                        ("index", np.int32), ("enough", np.int32), ("fit", FIT_DTYPE)])
+assert ALIGN_DTYPE.itemsize == C.sizeof(capi.KhMergeAlignCand)
+ALIGN_TIMES = ("relocalize_ms", "reference_grid_ms", "fit_kernel_ms", "total_ms")
 
 
 def _triple(t):
@@ -100,6 +110,47 @@ class MapMerger:
         h = C.c_void_p()
         capi.check(capi.lib().kh_merge_build(self._h, int(min_pass_through), float(occupancy_threshold), C.byref(h)), "kh_merge_build")
         return OccupancyGrid.from_handle(h, self.resolution)
+
+    def fit(self, submap_id: int, corrections, min_pass_through: int = 2, occupancy_threshold: float = 0.1) -> np.ndarray:
+        """kh_merge_fit: candidate corrections (n, 3) of ONE submap against the merge of all the others -> structured array (n,) of
+        FIT_DTYPE: the six counters by cell state, agree / conflict / known and score = agree / known.  Nothing of the merger changes."""
+        c = np.ascontiguousarray(corrections, dtype=np.float64).reshape(-1, 3)
+        out = np.zeros(c.shape[0], dtype=FIT_DTYPE)
+        capi.check(capi.lib().kh_merge_fit(self._h, int(submap_id), c.shape[0], c.ctypes.data, int(min_pass_through), float(occupancy_threshold),
+                                           out.ctypes.data_as(C.POINTER(capi.KhMergeFit))), "kh_merge_fit")
+        return out
+
+    def fit_stats(self) -> dict:
+        out = np.zeros(4, dtype=np.int64)
+        capi.check(capi.lib().kh_merge_fit_stats(self._h, out), "kh_merge_fit_stats")
+        return dict(zip(FIT_STATS, out.tolist()))
+
+    def align_params(self, target: int, **params):
+        """kh_merge_align_params_default for `target`, then params: fields of kh_merge_align_params, and of its kh_relocalize_params
+        (seed_spacing, n_headings, max_base, center_xy, radius) by their own names"""
+        p = capi.KhMergeAlignParams()
+        capi.lib().kh_merge_align_params_default(self._h, int(target), C.byref(p))
+        for k, v in params.items():
+            if k == "center_xy":
+                p.relocalize.center_xy[0], p.relocalize.center_xy[1] = float(v[0]), float(v[1])
+            elif k in ("n_probes", "top_k", "min_known", "min_pass_through", "occupancy_threshold"):
+                setattr(p, k, v)
+            elif k in ("seed_spacing", "n_headings", "max_base", "radius"):
+                setattr(p.relocalize, k, v)
+            else:
+                raise KeyError(k)
+        return p
+
+    def align(self, moving: int, target: int, cap: int = 256, **params):
+        """kh_merge_align: corrections of `moving` proposed by relocalizing probe scans of it in `target`'s map, ranked by how the
+        whole submap fits all the others.  Returns (candidates, times): a structured array of ALIGN_DTYPE, best first (candidate 0
+        -- index 0 -- is the current correction), and the call's split in ms.  Nothing is applied: set_transform does that."""
+        p = self.align_params(target, **params)
+        out = np.zeros(max(1, int(cap)), dtype=ALIGN_DTYPE)
+        n, times = C.c_int32(0), np.zeros(4)
+        capi.check(capi.lib().kh_merge_align(self._h, int(moving), int(target), C.byref(p), out.ctypes.data_as(C.POINTER(capi.KhMergeAlignCand)),
+                                             int(cap), C.byref(n), times.ctypes.data), "kh_merge_align")
+        return out[:min(int(cap), n.value)].copy(), dict(zip(ALIGN_TIMES, times.tolist()), n_candidates=n.value)
 
     def stats(self) -> dict:
         out = np.zeros(8, dtype=np.int64)
