@@ -302,14 +302,15 @@ static int allocate_copies(kh_matcher * m, Slot & s, int32_t kind)
   return KH_OK;
 }
 
-// (the distance penalties -- nx * ny doubles, 52 KB of a loop-closure search's 70 -- are only staged for searches that penalise)
-StageLayout stage_layout(int32_t P, int32_t nx, int32_t ny, int32_t na, bool penalize)
+// (the distance penalties -- nx * ny doubles, 30 KB of a config-2 search's 51, 52 KB of a loop-closure search's 70 -- are staged
+// by the fused path of one match only, and only for a search that penalises: batches read them from the handle's SearchTable)
+StageLayout stage_layout(int32_t P, int32_t nx, int32_t ny, int32_t na, bool stage_penalties)
 {
   StageLayout L;
   size_t o = align_up(sizeof(CorrJob), 256);
   L.bx = o; o = align_up(o + sizeof(int32_t) * nx, 16);
   L.by = o; o = align_up(o + sizeof(int32_t) * ny, 16);
-  L.dist_pen = o; o = align_up(o + (penalize ? sizeof(double) * nx * ny : 0), 16);
+  L.dist_pen = o; L.dist_pen_bytes = stage_penalties ? sizeof(double) * nx * ny : 0; o = align_up(o + L.dist_pen_bytes, 16);
   L.ang_pen = o; o = align_up(o + sizeof(double) * na, 16);
   L.cos_sin = o; o = align_up(o + sizeof(double) * 2 * na, 16);
   L.local = o; o = align_up(o + sizeof(double) * 2 * P, 16);
@@ -329,68 +330,6 @@ int pick_ry(int32_t ny)
     if (cost < best_cost) {best = ry; best_cost = cost;}
   }
   return best;
-}
-
-// Host half of ComputePositionalCovariance (Mapper.cpp:874-966) on the lattice maxima
-static int positional_covariance(
-  const kh_matcher * m, const CorrHost & c, const std::vector<double> & lattice_max, const WalkGeometry & w,
-  const double best_pose[3], double best_response, double * cov)
-{
-  std::fill(cov, cov + 9, 0.0);
-  cov[0] = 1.0; cov[4] = 1.0; cov[8] = 1.0;       // SetToIdentity
-  if (best_response < kTolerance) {
-    cov[0] = kMaxVariance; cov[4] = kMaxVariance; cov[8] = 4 * (w.ang_res * w.ang_res);
-    return KH_OK;
-  }
-  // search-space-probs grid (Grid<kt_double>, side x side, Mapper.cpp:513-514, 726-732, 781-799)
-  const int32_t side = m->side;
-  const double pscale = 1.0 / m->resolution;            // Grid::CreateGrid -> SetScale(1.0 / resolution)
-  const double pox = c.center[0] - c.off_x, poy = c.center[1] - c.off_y;
-  std::vector<double> probs(static_cast<size_t>(side) * side, 0.0);
-  for (int32_t yi = 0; yi < c.ny; ++yi) {
-    for (int32_t xi = 0; xi < c.nx; ++xi) {
-      const double px = c.center[0] + c.x_poses[xi], py = c.center[1] + c.y_poses[yi];
-      const Cell g = world_to_grid(pscale, pox, poy, px, py);
-      if (!(g.x >= 0 && g.x < side) || !(g.y >= 0 && g.y < side)) {return KH_ERR_SEARCH;}   // Mapper.cpp:786-796
-      double & cell = probs[static_cast<size_t>(g.y) * side + g.x];
-      const double v = lattice_max[static_cast<size_t>(yi) * c.nx + xi];
-      cell = v > cell ? v : cell;
-    }
-  }
-  double aXX = 0, aXY = 0, aYY = 0, norm = 0;
-  // the walk uses the CALLER's geometry on the grid the last coarse search left behind (Mapper.cpp:896-923)
-  const double dx = best_pose[0] - w.center[0], dy = best_pose[1] - w.center[1];
-  const uint32_t nX = static_cast<uint32_t>(round_half_away(w.off_x * 2.0 / w.res_x) + 1);
-  const double startX = -w.off_x;
-  const uint32_t nY = static_cast<uint32_t>(round_half_away(w.off_y * 2.0 / w.res_y) + 1);
-  const double startY = -w.off_y;
-  for (uint32_t yi = 0; yi < nY; ++yi) {
-    const double y = startY + yi * w.res_y;
-    for (uint32_t xi = 0; xi < nX; ++xi) {
-      const double x = startX + xi * w.res_x;
-      const Cell g = world_to_grid(pscale, pox, poy, w.center[0] + x, w.center[1] + y);
-      if (!(g.x >= 0 && g.x < side) || !(g.y >= 0 && g.y < side)) {return KH_ERR_SEARCH;}
-      const double response = probs[static_cast<size_t>(g.y) * side + g.x];
-      if (response >= (best_response - 0.1)) {
-        norm += response;
-        aXX += ((x - dx) * (x - dx) * response);
-        aXY += ((x - dx) * (y - dy) * response);
-        aYY += ((y - dy) * (y - dy) * response);
-      }
-    }
-  }
-  if (norm > kTolerance) {
-    double vXX = aXX / norm, vXY = aXY / norm, vYY = aYY / norm;
-    const double vTHTH = 4 * (w.ang_res * w.ang_res);
-    const double minXX = 0.1 * (w.res_x * w.res_x), minYY = 0.1 * (w.res_y * w.res_y);
-    vXX = vXX > minXX ? vXX : minXX;
-    vYY = vYY > minYY ? vYY : minYY;
-    const double mult = 1.0 / best_response;
-    cov[0] = vXX * mult; cov[1] = vXY * mult; cov[3] = vXY * mult; cov[4] = vYY * mult; cov[8] = vTHTH;
-  }
-  if (double_equal(cov[0], 0.0)) {cov[0] = kMaxVariance;}
-  if (double_equal(cov[4], 0.0)) {cov[4] = kMaxVariance;}
-  return KH_OK;
 }
 
 // the accumulation of ComputeAngularCovariance (Mapper.cpp:992-1024) over the raw responses of all angles at the best cell
@@ -420,7 +359,7 @@ static inline double host_response(const CorrHost & c, int32_t sum, int a, int y
 {
   double response = static_cast<double>(sum) / c.denom;
   if (c.penalize && !double_equal(response, 0.0)) {
-    response *= (c.dist_pen[static_cast<size_t>(yi) * c.nx + xi] * c.ang_pen[a]);
+    response *= (c.geo->dist_pen[static_cast<size_t>(yi) * c.nx + xi] * c.ang_pen[a]);
   }
   return response;
 }
@@ -456,12 +395,63 @@ int init_ctx(const CorrReq & q, CorrHost & c)
     set_error("search volume out of range");
     return KH_ERR_INVALID_ARG;
   }
-  const double startX = -q.off_x, startY = -q.off_y;
-  c.x_poses.resize(c.nx); c.y_poses.resize(c.ny);
-  for (int32_t k = 0; k < c.nx; ++k) {c.x_poses[k] = startX + static_cast<uint32_t>(k) * q.res_x;}
-  for (int32_t k = 0; k < c.ny; ++k) {c.y_poses[k] = startY + static_cast<uint32_t>(k) * q.res_y;}
   c.denom = static_cast<double>(static_cast<uint32_t>(c.P) * 100u);     // Mapper.cpp:1204
   return KH_OK;
+}
+
+int attach_table(kh_matcher * m, const CorrReq & q, CorrHost & c, bool on_device)
+{
+  const kh_match_params & mp = m->params;
+  uint64_t key[8] = {static_cast<uint64_t>(static_cast<uint32_t>(c.nx)), static_cast<uint64_t>(static_cast<uint32_t>(c.ny)), 0, 0, 0, 0, 0, 0};
+  const double reals[6] = {q.off_x, q.off_y, q.res_x, q.res_y, mp.distance_variance_penalty, mp.minimum_distance_penalty};
+  std::memcpy(key + 2, reals, sizeof(reals));
+  std::shared_ptr<SearchTable> t;
+  for (const auto & have : m->tables) {
+    if (std::memcmp(have->key, key, sizeof(key)) == 0) {t = have; break;}
+  }
+  if (!t) {
+    t = std::make_shared<SearchTable>();
+    std::memcpy(t->key, key, sizeof(key));
+    t->nx = c.nx; t->ny = c.ny;
+    const double startX = -q.off_x, startY = -q.off_y;
+    t->x_poses.resize(c.nx); t->y_poses.resize(c.ny);
+    for (int32_t k = 0; k < c.nx; ++k) {t->x_poses[k] = startX + static_cast<uint32_t>(k) * q.res_x;}
+    for (int32_t k = 0; k < c.ny; ++k) {t->y_poses[k] = startY + static_cast<uint32_t>(k) * q.res_y;}
+    // penalties, Mapper.cpp:673-677
+    t->dist_pen.resize(static_cast<size_t>(c.nx) * c.ny);
+    for (int32_t yi = 0; yi < c.ny; ++yi) {
+      for (int32_t xi = 0; xi < c.nx; ++xi) {
+        t->dist_pen[static_cast<size_t>(yi) * c.nx + xi] = distance_penalty(mp, t->x_poses[xi], t->y_poses[yi]);
+      }
+    }
+    m->tables.push_back(t);
+  }
+  if (on_device && !t->d_dist_pen) {
+    const size_t bytes = t->dist_pen.size() * sizeof(double);
+    double * d = nullptr;
+    KH_HIP(hipMalloc(reinterpret_cast<void **>(&d), bytes));
+    // blocking: the table is on the device before any stream of the handle is given a job that reads it
+    if (hipMemcpy(d, t->dist_pen.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(d);
+      set_error("upload of a distance-penalty table failed");
+      return KH_ERR_HIP;
+    }
+    t->d_dist_pen = d;
+  }
+  t->used = ++m->table_clock;
+  c.geo = t;
+  return KH_OK;
+}
+
+void trim_tables(kh_matcher * m)
+{
+  while (m->tables.size() > kMaxTables) {
+    auto oldest = std::min_element(m->tables.begin(), m->tables.end(),
+        [](const std::shared_ptr<SearchTable> & a, const std::shared_ptr<SearchTable> & b) {return a->used < b->used;});
+    // (a slot's introspection state may keep the entry's host half alive; the device copy goes now)
+    if ((*oldest)->d_dist_pen) {(void)hipFree((*oldest)->d_dist_pen); (*oldest)->d_dist_pen = nullptr;}
+    m->tables.erase(oldest);
+  }
 }
 
 // device scratch of one slot for the search `c` describes (allocation is serial: called before the pool fills the tables)
@@ -528,7 +518,6 @@ void prepare_job(kh_matcher * m, const CorrReq & q, CorrHost & c, const StageLay
   CorrJob * job = reinterpret_cast<CorrJob *>(hb);
   int32_t * bx = reinterpret_cast<int32_t *>(hb + L.bx);
   int32_t * by = reinterpret_cast<int32_t *>(hb + L.by);
-  double * dist_pen = reinterpret_cast<double *>(hb + L.dist_pen);
   double * ang_pen = reinterpret_cast<double *>(hb + L.ang_pen);
   double * cos_sin = reinterpret_cast<double *>(hb + L.cos_sin);
   double * local = reinterpret_cast<double *>(hb + L.local);
@@ -537,13 +526,13 @@ void prepare_job(kh_matcher * m, const CorrReq & q, CorrHost & c, const StageLay
   // lattice base indices: operator()(y), Mapper.cpp:649-662
   c.bx.resize(c.nx); c.by.resize(c.ny);
   for (int32_t k = 0; k < c.nx; ++k) {
-    const double newPositionX = c.center[0] + c.x_poses[k];
+    const double newPositionX = c.center[0] + c.geo->x_poses[k];
     const double gx = (newPositionX - s.off_x) * m->scale;
     c.bx[k] = to_int32(round_half_away(gx)) + m->roi_x;
     bx[k] = c.bx[k];
   }
   for (int32_t k = 0; k < c.ny; ++k) {
-    const double newPositionY = c.center[1] + c.y_poses[k];
+    const double newPositionY = c.center[1] + c.geo->y_poses[k];
     const double gy = (newPositionY - s.off_y) * m->scale;
     c.by[k] = (to_int32(round_half_away(gy)) + m->roi_y) * m->ws;
     by[k] = c.by[k];
@@ -560,8 +549,7 @@ void prepare_job(kh_matcher * m, const CorrReq & q, CorrHost & c, const StageLay
   }
   if (!linear) {sx = 1; sy_ws = m->ws;}
 
-  // penalties, Mapper.cpp:671-685
-  if (q.penalize) {c.dist_pen.assign(static_cast<size_t>(c.nx) * c.ny, 1.0);} else {c.dist_pen.clear();}
+  // penalties, Mapper.cpp:671-685 (the distance penalties are the SearchTable's)
   c.ang_pen.assign(c.na, 1.0);
   c.angles.resize(c.na);
   const double startAngle = c.center[2] - c.ang_off;
@@ -572,13 +560,7 @@ void prepare_job(kh_matcher * m, const CorrReq & q, CorrHost & c, const StageLay
     c.ang_pen[a] = angle_penalty(mp, angle, c.center[2]);
     ang_pen[a] = c.ang_pen[a];
   }
-  for (int32_t yi = 0; yi < c.ny && q.penalize; ++yi) {
-    for (int32_t xi = 0; xi < c.nx; ++xi) {
-      const size_t at = static_cast<size_t>(yi) * c.nx + xi;
-      c.dist_pen[at] = distance_penalty(mp, c.x_poses[xi], c.y_poses[yi]);
-      dist_pen[at] = c.dist_pen[at];
-    }
-  }
+  if (L.dist_pen_bytes) {std::memcpy(hb + L.dist_pen, c.geo->dist_pen.data(), L.dist_pen_bytes);}
 
   // scan points in the sensor frame: Transform(sensorPose).InverseTransformPose, Karto.h:6813-6824,
   // 2987-2994, 3003-3024, 2482-2511, 2654-2666
@@ -642,7 +624,7 @@ void prepare_job(kh_matcher * m, const CorrReq & q, CorrHost & c, const StageLay
   job->grid_off_x = s.off_x; job->grid_off_y = s.off_y; job->scale = m->scale;
   job->bx = reinterpret_cast<const int32_t *>(db + L.bx);
   job->by = reinterpret_cast<const int32_t *>(db + L.by);
-  job->dist_pen = reinterpret_cast<const double *>(db + L.dist_pen);
+  job->dist_pen = L.dist_pen_bytes ? reinterpret_cast<const double *>(db + L.dist_pen) : c.geo->d_dist_pen;
   job->ang_pen = reinterpret_cast<const double *>(db + L.ang_pen);
   job->cos_sin = reinterpret_cast<const double *>(db + L.cos_sin);
   job->local = reinterpret_cast<const double *>(db + L.local);
@@ -714,8 +696,8 @@ int finalize_job(kh_matcher * m, CorrReq & q, CorrHost & c, const ResultView & v
     const int32_t a = static_cast<int32_t>(t % static_cast<uint32_t>(c.na));
     const uint32_t xy = t / static_cast<uint32_t>(c.na);
     const int32_t xi = static_cast<int32_t>(xy % static_cast<uint32_t>(c.nx)), yi = static_cast<int32_t>(xy / static_cast<uint32_t>(c.nx));
-    ax += c.center[0] + c.x_poses[xi];
-    ay += c.center[1] + c.y_poses[yi];
+    ax += c.center[0] + c.geo->x_poses[xi];
+    ay += c.center[1] + c.geo->y_poses[yi];
     const double heading = normalize_angle(c.angles[a]);
     double sin_h, cos_h;
     ref_sincos(heading, &sin_h, &cos_h);
@@ -727,14 +709,17 @@ int finalize_job(kh_matcher * m, CorrReq & q, CorrHost & c, const ResultView & v
   const double avg[3] = {ax, ay, std::atan2(thetaY, thetaX)};
 
   if (!c.fine) {
-    std::vector<double> lattice(plane);
-    std::memcpy(lattice.data(), out + kOutHeaderWords, plane * 8);
+    const double * lattice = reinterpret_cast<const double *>(out + kOutHeaderWords);
+    WalkLattice wl;
+    wl.center[0] = c.center[0]; wl.center[1] = c.center[1]; wl.off_x = c.off_x; wl.off_y = c.off_y;
+    wl.nx = c.nx; wl.ny = c.ny; wl.x_poses = c.geo->x_poses.data(); wl.y_poses = c.geo->y_poses.data();
     WalkGeometry wg;
     std::copy(c.center, c.center + 3, wg.center);
     wg.off_x = c.off_x; wg.off_y = c.off_y; wg.res_x = c.res_x; wg.res_y = c.res_y; wg.ang_res = c.ang_res;
-    const int prc = positional_covariance(m, c, lattice, wg, avg, best, q.cov);
+    const int prc = positional_covariance(m->side, m->resolution, wl, lattice, wg, avg, best, q.cov);
     if (prc != KH_OK) {q.status = prc; return KH_OK;}
-    s.last_coarse = c; s.last_lattice.swap(lattice); s.has_last_coarse = true;     // m_pSearchSpaceProbs of this matcher slot
+    // m_pSearchSpaceProbs of this matcher slot
+    s.last_coarse = wl; s.last_coarse_geo = c.geo; s.last_lattice.assign(lattice, lattice + plane); s.has_last_coarse = true;
   } else {
     // ComputeAngularCovariance, Mapper.cpp:977-1025
     const double bestAngle = normalize_angle_difference(avg[2], c.center[2]);
@@ -781,7 +766,7 @@ int finalize_job(kh_matcher * m, CorrReq & q, CorrHost & c, const ResultView & v
   }
   q.mean[0] = avg[0]; q.mean[1] = avg[1]; q.mean[2] = avg[2];
   q.response = best > 1.0 ? 1.0 : best;
-  s.last = c; s.has_last = true;
+  s.last.P = c.P; s.last.nx = c.nx; s.last.ny = c.ny; s.last.na = c.na; s.last.denom = c.denom; s.has_last = true;
   return KH_OK;
 }
 
@@ -826,7 +811,10 @@ static int enqueue_chunk(kh_matcher * m, CorrReq * reqs, size_t n, CorrBatch & B
     q.status = KH_OK;
     rc = init_ctx(q, c);
     if (rc) {return rc;}
-    B.lay[i] = stage_layout(c.P, c.nx, c.ny, c.na, q.penalize);
+    // (a chunk's jobs share their geometry: after the first this is a look-up)
+    rc = attach_table(m, q, c, q.penalize);
+    if (rc) {return rc;}
+    B.lay[i] = stage_layout(c.P, c.nx, c.ny, c.na, false);
     B.stride = std::max(B.stride, B.lay[i].total);
     B.out_words = std::max(B.out_words, kOutHeaderWords + static_cast<size_t>(c.nx) * c.ny);
     max_na = std::max(max_na, c.na);
@@ -1033,6 +1021,7 @@ int correlate_batch(kh_matcher * m, std::vector<CorrReq> & reqs)
 {
   const size_t n = reqs.size();
   if (n == 0) {return KH_OK;}
+  trim_tables(m);
   // Large batches go through in chunks of kChunk jobs on the two staging sets of the handle: while the kernels of
   // chunk i run, the host prepares chunk i + 1 and finalises chunk i - 1 (the exact host half costs ~5 us per match
   // on the worker pool, the scoring kernel ~13 us).  Chunks of 64 keep the scoring launches at full efficiency;
@@ -1293,6 +1282,7 @@ void kh_matcher_destroy(kh_matcher * m)
     if (b.kdone) {hipEventDestroy(b.kdone);}
     if (b.side) {hipStreamSynchronize(b.side); hipStreamDestroy(b.side);}
   }
+  for (auto & t : m->tables) {hipFree(t->d_dist_pen); t->d_dist_pen = nullptr;}
   hipFree(m->d_arena); hipFree(m->d_meta);
   if (m->h_arena) {hipHostFree(m->h_arena);}
   if (m->h_meta) {hipHostFree(m->h_meta);}
@@ -1578,7 +1568,7 @@ int kh_matcher_read_volume(kh_matcher * m, int32_t slot, int32_t * nx, int32_t *
   Slot & s = m->slots[slot];
   if (!s.has_last) {return KH_ERR_NOT_FOUND;}
   if (s.volume_stale) {set_error("the last search re-scored an off-lattice best pose: its volume was not kept"); return KH_ERR_NOT_FOUND;}
-  const CorrHost & c = s.last;
+  const auto & c = s.last;
   *nx = c.nx; *ny = c.ny; *na = c.na;
   if (!out_sums && !out_responses) {return KH_OK;}
   KH_HIP(hipSetDevice(m->device));
@@ -1616,7 +1606,7 @@ int kh_matcher_positional_covariance(kh_matcher * m, int32_t slot, const double 
   std::copy(center, center + 3, wg.center);
   wg.off_x = search_offset[0]; wg.off_y = search_offset[1]; wg.res_x = search_resolution[0]; wg.res_y = search_resolution[1];
   wg.ang_res = angle_resolution;
-  return positional_covariance(m, s.last_coarse, s.last_lattice, wg, best_pose, best_response, cov);
+  return positional_covariance(m->side, m->resolution, s.last_coarse, s.last_lattice.data(), wg, best_pose, best_response, cov);
 }
 
 // ScanMatcher::ComputeAngularCovariance (Mapper.cpp:977-1025): GetResponse of every search angle at the best pose's cell

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -23,6 +24,7 @@
 #include "../../include/karto_hip.h"
 #include "kh_internal.hpp"
 #include "host_pool.hpp"
+#include "covariance_walk.hpp"
 
 namespace kh
 {
@@ -39,31 +41,18 @@ void set_error(const std::string & s);
     }                                                                                        \
   } while (0)
 
-// ---- exact scalar helpers (Math.h) ----------------------------------------------------------
+// ---- exact scalar helpers (Math.h); the ones the covariance walk shares are in covariance_walk.hpp ------
 // cos and sin of ONE angle, the way the reference's Release build computes them: GCC (-O1 and up) merges a cos(a) / sin(a)
 // pair into one sincos(a) call, and glibc's sincos is NOT bit-identical to its cos and sin everywhere (a = 0.11462314399891493:
 // cos(a) = 0.9934379567501339, sincos(a) gives 0.993437956750134).  Every place where the reference takes both of the same
 // angle goes through here, so that the library does not depend on whether ITS compiler merges the pair (clang does not).
 inline void ref_sincos(double a, double * s, double * c) {::sincos(a, s, c);}
-constexpr double kTolerance = 1e-06;                 // Math.h:41
 constexpr double kPi = 3.14159265358979323846;       // Math.h:31
 constexpr double k2Pi = 6.28318530717958647692;      // Math.h:32
 constexpr double kPi180 = 0.01745329251994329577;    // Math.h:34
-constexpr double kMaxVariance = 500.0;               // Mapper.cpp:52
 constexpr double kDistanceGain = 0.2;                // Mapper.cpp:53
 constexpr double kAngleGain = 0.2;                   // Mapper.cpp:54
 
-inline double round_half_away(double v) {return v >= 0.0 ? std::floor(v + 0.5) : std::ceil(v - 0.5);}
-inline int32_t to_int32(double v)
-{
-  if (!(v > -2147483649.0 && v < 2147483648.0)) {return INT32_MIN;}
-  return static_cast<int32_t>(v);
-}
-inline bool double_equal(double a, double b)
-{
-  const double delta = a - b;
-  return delta < 0.0 ? delta >= -kTolerance : delta <= kTolerance;
-}
 inline double normalize_angle(double angle)   // Math.h:181-202
 {
   while (angle < -kPi) {
@@ -80,13 +69,6 @@ inline double normalize_angle_difference(double minuend, double subtrahend)   //
   while (minuend - subtrahend > kPi) {minuend -= k2Pi;}
   return minuend;
 }
-struct Cell {int32_t x, y;};
-inline Cell world_to_grid(double scale, double ox, double oy, double wx, double wy)   // Karto.h:4421-4436
-{
-  const double gx = (wx - ox) * scale;
-  const double gy = (wy - oy) * scale;
-  return Cell{to_int32(round_half_away(gx)), to_int32(round_half_away(gy))};
-}
 inline size_t align_up(size_t v, size_t a) {return (v + a - 1) / a * a;}
 // the penalties of a pose, Mapper.cpp:671-685: of its heading `angle` in a search centred on `centre`, of its offset (x, y)
 inline double angle_penalty(const kh_match_params & mp, double angle, double centre)
@@ -102,6 +84,18 @@ inline double distance_penalty(const kh_match_params & mp, double x, double y)
   return distancePenalty > mp.minimum_distance_penalty ? distancePenalty : mp.minimum_distance_penalty;
 }
 
+// What the jobs of one search geometry share: the pose offsets of the lattice (Mapper.cpp:736-756) and their distance penalties
+// (Mapper.cpp:673-677).  Made once per (nx, ny, offsets, resolutions, the two distance-penalty parameters) and kept on the handle
+// (kh_matcher::tables); the device copy belongs to the handle's cache, which frees it when it evicts the entry.
+struct SearchTable
+{
+  uint64_t key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int32_t nx = 0, ny = 0;
+  std::vector<double> x_poses, y_poses, dist_pen;     // [nx], [ny], [ny * nx]
+  double * d_dist_pen = nullptr;                      // batches read the table from here (nullptr: not uploaded)
+  uint64_t used = 0;                                  // kh_matcher::table_clock at the last look-up
+};
+
 // ---- per-correlate host context (what finalisation needs) -----------------------------------
 struct CorrHost
 {
@@ -110,13 +104,15 @@ struct CorrHost
   double center[3] = {0, 0, 0};
   double off_x = 0, off_y = 0, res_x = 0, res_y = 0, ang_off = 0, ang_res = 0;
   bool fine = false, penalize = false;
-  std::vector<double> x_poses, y_poses, angles, dist_pen, ang_pen;
+  std::shared_ptr<const SearchTable> geo;       // attach_table
+  std::vector<double> angles, ang_pen;
   int32_t lt_alloc = 1;          // tile lists the slot's `fast` buffer was sized for
   std::vector<int32_t> bx, by;
   double denom = 1.0;
 };
 
-struct StageLayout {size_t bx, by, dist_pen, ang_pen, cos_sin, local, invalid, total;};
+// (dist_pen_bytes 0: the job reads the distance penalties from its SearchTable's device copy)
+struct StageLayout {size_t bx, by, dist_pen, dist_pen_bytes, ang_pen, cos_sin, local, invalid, total;};
 
 // Staging and bookkeeping of one in-flight chunk of CorrelateScan jobs (a handle owns two: pipelining).  enqueue_chunk fills it,
 // finish_chunk reads it back.
@@ -169,11 +165,11 @@ struct Slot
   int32_t * d_seqctl = nullptr;
   int32_t * d_work2 = nullptr; size_t cap_work2 = 0;
   // last correlate (for the introspection calls)
-  CorrHost last;
+  struct {int32_t P = 0, nx = 0, ny = 0, na = 0; double denom = 1.0;} last;
   bool has_last = false;
   bool volume_stale = false;         // the stored volume was overwritten by an off-lattice re-score (introspection reports it)
   // what ComputePositionalCovariance reads: the search-space probabilities of the last COARSE search (Mapper.cpp:726-732, 781-799)
-  CorrHost last_coarse; std::vector<double> last_lattice; bool has_last_coarse = false;
+  WalkLattice last_coarse; std::shared_ptr<const SearchTable> last_coarse_geo; std::vector<double> last_lattice; bool has_last_coarse = false;
 };
 
 }  // namespace kh
@@ -195,6 +191,10 @@ struct kh_matcher
   uint8_t * d_kernel = nullptr;
   std::vector<Slot> slots;
   CorrBatch batch[2];
+  // search geometries in use (attach_table): a mapper has three or four -- coarse, fine, the 1 x 1 of the angular covariance, the
+  // loop closure's -- for the life of its handle.  Trimmed to kMaxTables, least recently used first, at the start of a call only
+  std::vector<std::shared_ptr<SearchTable>> tables;
+  uint64_t table_clock = 0;
   // raster staging: the distinct base scans' unfiltered points (pinned mirror + device arena), the jobs' scan lists and
   // the (job, scan) work items of K0 (one int32 block), the jobs
   double * h_arena = nullptr; double * d_arena = nullptr; size_t cap_harena = 0, cap_darena = 0;
@@ -280,7 +280,6 @@ struct CorrReq
     if (center_) {std::copy(center_, center_ + 3, center);}
   }
 };
-struct WalkGeometry {double center[3], off_x, off_y, res_x, res_y, ang_res;};
 
 // internal result of the fused sequential path: "take the general path for this step" (never leaves the library)
 constexpr int kNeedGeneric = 1000;
@@ -298,9 +297,16 @@ struct ResultView
   bool device_work = true;                    // false: a finalisation that would have to touch the stream returns kNeedGeneric instead
 };
 
-StageLayout stage_layout(int32_t P, int32_t nx, int32_t ny, int32_t na, bool penalize);
+// stage_penalties: the block holds the job's distance penalties (the fused path of one match, whose tables travel with its stamps)
+StageLayout stage_layout(int32_t P, int32_t nx, int32_t ny, int32_t na, bool stage_penalties);
 int pick_ry(int32_t ny);
 int init_ctx(const CorrReq & q, CorrHost & c);
+// The search's SearchTable from the handle's cache into c.geo, made (and with on_device uploaded, by a blocking copy: every stream
+// may read it) where it is missing.  Serial: before the pool prepares the jobs.
+constexpr size_t kMaxTables = 4;
+int attach_table(kh_matcher * m, const CorrReq & q, CorrHost & c, bool on_device);
+// start of a call, nothing of the handle in flight: the cache back to kMaxTables entries
+void trim_tables(kh_matcher * m);
 // allow_copies = false: the slot is not given re-pitched copies of its grid by this call (the fused path of one match scores from
 // the grid itself; copies the slot already has are kept in step all the same)
 int ensure_slot_scratch(kh_matcher * m, const CorrReq & q, CorrHost & c, bool allow_copies = true);

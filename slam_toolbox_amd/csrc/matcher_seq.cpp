@@ -121,6 +121,7 @@ int seq_match(kh_matcher * m, const kh_scan * query, const kh_scan * base, int32
   hipStream_t st = m->stream;
   const kh_match_params & mp = m->params;
   int rc = KH_OK;
+  trim_tables(m);      // (an earlier call of this handle has returned: nothing of it is in flight)
   // ---- scratch
   const size_t npad = (static_cast<size_t>(np) + 3) & ~static_cast<size_t>(3);
   rc = ensure_device(s.d_ractive, s.cap_ractive, static_cast<size_t>(np), st); if (rc) {return rc;}
@@ -173,13 +174,18 @@ int seq_match(kh_matcher * m, const kh_scan * query, const kh_scan * base, int32
   std::copy(cov, cov + 9, q.cov);
   CorrHost c;
   rc = init_ctx(q, c); if (rc) {return rc;}
+  // (the distance penalties travel in this path's staging block with the stamps: no device copy is asked for)
+  rc = attach_table(m, q, c, false); if (rc) {return rc;}
   rc = ensure_slot_scratch(m, q, c, false); if (rc) {return rc;}
   CorrReq qf = fine_search(m, 0, query, nullptr, penalize);      // (centred on the coarse result once there is one)
   CorrHost cf;
   bool device_fine = refine;
   if (device_fine) {
     if (init_ctx(qf, cf) != KH_OK || cf.nx != 3 || cf.ny != 3 || cf.na * 9 > kSeqMaxFine) {device_fine = false;}
-    else {rc = ensure_slot_scratch(m, qf, cf, false); if (rc) {return rc;}}
+    else {
+      rc = attach_table(m, qf, cf, false); if (rc) {return rc;}
+      rc = ensure_slot_scratch(m, qf, cf, false); if (rc) {return rc;}
+    }
   }
   // ---- 1. rasteriser: everything it needs travels as kernel arguments
   // MatchScan steps 1-4, Mapper.cpp:543-569
@@ -229,8 +235,8 @@ int seq_match(kh_matcher * m, const kh_scan * query, const kh_scan * base, int32
     double * fcs = reinterpret_cast<double *>(Q.h_stage + X.fine_cs);
     double * fap = reinterpret_cast<double *>(Q.h_stage + X.fine_ap);
     double * fdp = reinterpret_cast<double *>(Q.h_stage + X.fine_dp);
-    std::copy(c.x_poses.begin(), c.x_poses.end(), xp);
-    std::copy(c.y_poses.begin(), c.y_poses.end(), yp);
+    std::copy(c.geo->x_poses.begin(), c.geo->x_poses.end(), xp);
+    std::copy(c.geo->y_poses.begin(), c.geo->y_poses.end(), yp);
     for (int32_t a = 0; a < c.na; ++a) {
       // the tie average of ONE pose (Mapper.cpp:802-829): atan2 of its heading's sine and cosine
       const double h = normalize_angle(c.angles[a]);
@@ -253,7 +259,7 @@ int seq_match(kh_matcher * m, const kh_scan * query, const kh_scan * base, int32
       }
     }
     for (int32_t yi = 0; yi < 3; ++yi) {
-      for (int32_t xi = 0; xi < 3; ++xi) {fdp[yi * 3 + xi] = device_fine ? distance_penalty(mp, cf.x_poses[xi], cf.y_poses[yi]) : 1.0;}
+      for (int32_t xi = 0; xi < 3; ++xi) {fdp[yi * 3 + xi] = device_fine ? cf.geo->dist_pen[yi * 3 + xi] : 1.0;}
     }
   }
   // ---- 3. the stamps (with the tables' way to the device in the same launch), scoring, finalisation on the device
@@ -292,7 +298,7 @@ int seq_match(kh_matcher * m, const kh_scan * query, const kh_scan * base, int32
   fa.fine_cos_sin = reinterpret_cast<const double *>(Q.d_stage + X.fine_cs);
   fa.fine_ang_pen = reinterpret_cast<const double *>(Q.d_stage + X.fine_ap);
   fa.fine_dist_pen = reinterpret_cast<const double *>(Q.d_stage + X.fine_dp);
-  for (int32_t k = 0; k < 3; ++k) {fa.fxp[k] = device_fine ? cf.x_poses[k] : 0.0; fa.fyp[k] = device_fine ? cf.y_poses[k] : 0.0;}
+  for (int32_t k = 0; k < 3; ++k) {fa.fxp[k] = device_fine ? cf.geo->x_poses[k] : 0.0; fa.fyp[k] = device_fine ? cf.geo->y_poses[k] : 0.0;}
   fa.roi_x = m->roi_x; fa.roi_y = m->roi_y;
   fa.fine_table = s.d_table; fa.fine_sums = s.d_sums;
   fa.dbg = Q.d_dbg ? Q.d_dbg + 16 : nullptr;
