@@ -340,6 +340,39 @@ KH_API int kh_spa_compute(kh_spa * s, kh_spa_summary * summary);       /* Comput
  * [7] verdict: 1 accepted, 0 rejected, -1 invalid step, 2 / 3 terminated on parameter / function tolerance.
  * Writes min(capacity, rows) rows, *n_rows = rows available. */
 KH_API int kh_spa_iteration_log(kh_spa * s, int32_t capacity, double * rows, int32_t * n_rows);
+/* ---- pose-graph covariances (no counterpart in the reference: it never asks Ceres for a Covariance).
+ * Sigma = (J^T J)^-1 over the free nodes at the CURRENT poses, in the tangent (x, y, theta) of every node; J is the linearisation
+ * Compute() itself uses, the loss function's reweighting included, undamped.  The gauge node (the first node, constant) has
+ * covariance zero; a node no constraint touches is not in the problem.  kh_spa_compute_covariances linearises, factorises
+ * (cached analysis where the topology is unchanged; legal before any Compute) and walks the factor back down the assembly tree --
+ * the selected inverse, every block of the inverse on the pattern of the factor, at about the cost of one more factorisation --
+ * and keeps the blocks on the pattern of H resident on the device: every node's 3 x 3 marginal and the cross block of every pair
+ * of nodes joined by a constraint.  The cross block of a pair WITHOUT a constraint is not on the pattern and is not available.
+ * The result is valid until the graph or a pose changes (add_* / remove_* / modify_node / compute / reset / clear / load); after
+ * that the getters answer KH_ERR_SOLVER ("stale").  KH_ERR_SOLVER also where the level pipeline does not run (fronts beyond its
+ * LDS budget, or factor kernels 1 / 2 selected by kh_spa_set_debug) and for a graph with a free component that is not tied to
+ * the gauge (non-positive pivot); nothing stays resident then.  Arguments are checked first (KH_ERR_INVALID_ARG), then the device
+ * (KH_ERR_NO_DEVICE), then the handle. */
+typedef struct kh_spa_cov_summary {
+  int32_t n_free, levels;
+  int32_t analysis;             /* as kh_spa_summary.analysis: 0 cached, 1 full, 2 incremental */
+  int32_t pad;
+  double linearize_ms, factor_ms;   /* host wall time up to the end of the linearisation / of everything behind it */
+  double inverse_ms, gather_ms;     /* GPU time of the downward pass / of the collecting kernel, from HIP events under kh_spa_set_debug bit 1, else 0 */
+  double total_ms;
+  int64_t inverse_flops;        /* sum over the fronts of the flops of G = L21 W^T, Z21 = -Z22 G and G^T Z21 */
+} kh_spa_cov_summary;
+KH_API int kh_spa_compute_covariances(kh_spa * s, kh_spa_cov_summary * summary /* may be NULL */);
+/* cov[9 k ..]: row-major 3 x 3 of node ids[k]; ids = NULL: all nodes in insertion order (n = kh_spa_num_nodes).  The gauge node:
+ * zeros.  An unknown id or a node without constraints: KH_ERR_NOT_FOUND. */
+KH_API int kh_spa_get_covariances(kh_spa * s, int32_t n, const int32_t * ids, double * cov /* 9n */);
+/* row-major 6 x 6 [[aa ab], [ba bb]] of two nodes joined by a constraint (either direction); KH_ERR_NOT_FOUND for an unknown id,
+ * a node without constraints and a pair without a constraint between them (their cross block is not on the pattern).  Rows and
+ * columns of the gauge node are zeros. */
+KH_API int kh_spa_get_joint_covariance(kh_spa * s, int32_t id_a, int32_t id_b, double cov[36]);
+/* the resident array for device consumers: n_slots blocks of 9 doubles (row-major), block-sparse rows over the free nodes on the
+ * pattern of H; owned by the solver, valid like the getters' answers */
+KH_API int kh_spa_covariance_device(kh_spa * s, const double ** cov_bsr, int64_t * n_slots);
 /* GetCorrections (ceres_solver.cpp:272): pass ids=NULL to query the count */
 KH_API int kh_spa_get_corrections(kh_spa * s, int32_t * n, int32_t * ids, double * poses /* 3n */);
 /* ---- pose-graph files.  The reference persists a Boost binary archive of the whole
@@ -673,6 +706,11 @@ KH_API int32_t kh_mapper_num_alive(const kh_mapper * m);
 KH_API int kh_mapper_get_alive(const kh_mapper * m, int32_t * ids);
 /* the solver plugin instance the mapper drives (RemoveNode / save / load ... ); owned by the mapper */
 KH_API kh_spa * kh_mapper_solver(kh_mapper * m);
+/* graph-aware covariances of scan poses (kh_spa_compute_covariances / kh_spa_get_covariances of the mapper's solver; a scan's
+ * solver node carries the scan's id): computed on the first call after the graph or a pose has changed, answered from the
+ * resident result otherwise.  scan_ids = NULL: all solver nodes in insertion order (n = kh_spa_num_nodes of the solver).
+ * summary (may be NULL): the computation this call ran, all zeros when it ran none. */
+KH_API int kh_mapper_get_covariances(kh_mapper * m, int32_t n, const int32_t * scan_ids, double * cov /* 9n */, kh_spa_cov_summary * summary);
 /* every solver call the mapper makes, one line each, in the format oracle/ref_slam_driver.cpp logs the reference
  * Mapper's calls with (N id pose, C a b z cov, X n ms, P id pose, K): the two logs of one scan queue must agree */
 KH_API int kh_mapper_set_log(kh_mapper * m, const char * path);

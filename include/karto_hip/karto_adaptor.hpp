@@ -480,6 +480,28 @@ public:
     return &m_Graph;
   }
 
+  // ---- beyond karto::ScanSolver (neither overrides a virtual of the reference): graph-aware covariances of the node poses,
+  // Sigma = (J^T J)^-1 at the current poses (kh_spa_compute_covariances).  false: nothing is resident (see kh_last_error()).
+  bool ComputeCovariances()
+  {
+    std::lock_guard<std::mutex> lock(m_Mutex);
+    return kh_spa_compute_covariances(m_pHandle, nullptr) == KH_OK;
+  }
+
+  // marginal covariance (x, y, heading) of one node; the zero matrix where the covariances are stale or the node is not in the
+  // problem (and for the gauge node, whose covariance IS zero)
+  karto::Matrix3 GetCovariance(kt_int32s id)
+  {
+    std::lock_guard<std::mutex> lock(m_Mutex);
+    karto::Matrix3 result;
+    result.Clear();
+    double cov[9];
+    const int32_t one = id;
+    if (kh_spa_get_covariances(m_pHandle, 1, &one, cov) != KH_OK) {return result;}
+    for (int r = 0; r < 3; ++r) {for (int q = 0; q < 3; ++q) {result(r, q) = cov[3 * r + q];}}
+    return result;
+  }
+
 private:
   kh_spa * m_pHandle;
   std::mutex m_Mutex;

@@ -62,6 +62,12 @@ class KhSpaSummary(C.Structure):
                 ("worst_linear_residual", C.c_double), ("analysis", C.c_int32), ("analysis_pad", C.c_int32)]
 
 
+class KhSpaCovSummary(C.Structure):
+    _fields_ = [("n_free", C.c_int32), ("levels", C.c_int32), ("analysis", C.c_int32), ("pad", C.c_int32),
+                ("linearize_ms", C.c_double), ("factor_ms", C.c_double), ("inverse_ms", C.c_double),
+                ("gather_ms", C.c_double), ("total_ms", C.c_double), ("inverse_flops", C.c_int64)]
+
+
 # every symbol include/karto_hip.h declares (tests check that the built library exports all of them)
 SYMBOLS = [
     "kh_last_error", "kh_device_count", "kh_version", "kh_scan_points", "kh_match_params_default",
@@ -104,6 +110,8 @@ SYMBOLS = [
     "kh_map_feed_stats",
     "kh_graph_relocalize_candidates", "kh_graph_last_relocalize_kernel_ms", "kh_relocalize_params_default", "kh_mapper_relocalize", "kh_mapper_get_params",
     "kh_merge_fit", "kh_merge_fit_stats", "kh_merge_align_params_default", "kh_merge_align",
+    "kh_spa_compute_covariances", "kh_spa_get_covariances", "kh_spa_get_joint_covariance", "kh_spa_covariance_device",
+    "kh_mapper_get_covariances",
 ]
 
 
@@ -303,6 +311,10 @@ def lib():
         L.kh_spa_get_node_at.argtypes = [vp, i32, C.POINTER(i32), dptr]
         L.kh_spa_get_nodes.argtypes = [vp, vp, vp]
         L.kh_spa_get_constraint.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), dptr, dptr]
+        L.kh_spa_compute_covariances.argtypes = [vp, C.POINTER(KhSpaCovSummary)]
+        L.kh_spa_get_covariances.argtypes = [vp, i32, vp, vp]
+        L.kh_spa_get_joint_covariance.argtypes = [vp, i32, i32, vp]
+        L.kh_spa_covariance_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
     if hasattr(L, "kh_comm_create"):
         L.kh_comm_unique_id.argtypes = [bptr]
         L.kh_comm_create.argtypes = [i32, i32, i32, bptr, C.POINTER(vp)]
@@ -353,6 +365,7 @@ def lib():
         L.kh_mapper_get_stats.argtypes = [vp, C.POINTER(KhMapperStats)]
         L.kh_mapper_solver.argtypes = [vp]
         L.kh_mapper_solver.restype = vp
+        L.kh_mapper_get_covariances.argtypes = [vp, i32, vp, vp, C.POINTER(KhSpaCovSummary)]
         L.kh_mapper_set_log.argtypes = [vp, C.c_char_p]
         L.kh_mapper_remove_node.argtypes = [vp, i32]
         L.kh_mapper_set_lifelong.argtypes = [vp, C.POINTER(KhDecayParams)]

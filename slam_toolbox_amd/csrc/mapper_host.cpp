@@ -48,6 +48,7 @@ void set_pending_query_hook(std::function<void()> fn);       // matcher_seq.cpp 
 void run_pending_query_hook();
 void spa_export_session_state(kh_spa * s, int64_t words[7], std::vector<int32_t> & sn_ptr, std::vector<int32_t> & sn_ids);
 void spa_import_session_state(kh_spa * s, const int64_t words[7], const std::vector<int32_t> & sn_ptr, const std::vector<int32_t> & sn_ids);
+bool spa_covariances_valid(const kh_spa * s);
 int graph_swap(kh_graph * g, int32_t n_scans, std::vector<double> & ref_xy, std::vector<int32_t> & adj_ptr, std::vector<int32_t> & adj_idx,
   std::vector<double> & pose_xy);   // graph.hip
 int graph_relocalize_candidates(kh_graph * g, double seed_spacing, double base_radius, int32_t max_base, const double * center_xy, double radius,
@@ -858,6 +859,21 @@ int kh_mapper_set_log(kh_mapper * m, const char * path)
 }
 
 kh_spa * kh_mapper_solver(kh_mapper * m) {return m ? m->solver : nullptr;}
+
+int kh_mapper_get_covariances(kh_mapper * m, int32_t n, const int32_t * scan_ids, double * cov, kh_spa_cov_summary * summary)
+{
+  if (summary) {std::memset(summary, 0, sizeof(*summary));}
+  if (n < 0 || (n > 0 && !cov)) {return KH_ERR_INVALID_ARG;}
+  if (kh::require_device(0) != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!m) {return KH_ERR_INVALID_ARG;}
+  // (a scan's solver node carries the scan's id; every change of the graph or of a pose goes through the solver, which keeps
+  // track of whether its resident covariances still hold)
+  if (!kh::spa_covariances_valid(m->solver)) {
+    const int rc = kh_spa_compute_covariances(m->solver, summary);
+    if (rc) {return rc;}
+  }
+  return kh_spa_get_covariances(m->solver, n, scan_ids, cov);
+}
 
 }  // extern "C"
 namespace kh

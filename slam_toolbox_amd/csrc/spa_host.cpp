@@ -177,6 +177,14 @@ struct kh_spa
   hipEvent_t ev_lin[2 * kMaxTimed + 2][2] = {};
   double last_symbolic_ms = 0.0;
   int32_t debug_flags = 0;                     // kh_spa_set_debug
+  // covariances (kh_spa_compute_covariances): the selected inverse over the fronts' layout, allocated on first use, and the blocks
+  // of the inverse on H's pattern; cov_valid falls with every change of the graph or of a pose.  The host copies (the array
+  // and the pattern it is addressed by) are fetched by the first getter behind a computation.
+  DevBuf<double> d_zbuf, d_cov;
+  bool cov_valid = false, cov_on_host = false;
+  std::vector<double> h_cov;
+  std::vector<int32_t> h_cov_row_ptr, h_cov_col, h_cov_diag;
+  hipEvent_t ev_cov[3] = {};
 };
 
 // drops the tombstones; positions in `nodes` / `cons` and both maps are final again afterwards.  Every entry point that
@@ -204,6 +212,7 @@ static void bury_constraint(kh_spa * s, int32_t k)
 {
   Constraint & c = s->cons[k];
   if (c.dead) {return;}
+  s->cov_valid = false;
   auto range = s->con_of.equal_range(kh_spa::edge_key(c.a, c.b));
   for (auto it = range.first; it != range.second; ++it) {
     if (it->second == k) {s->con_of.erase(it); break;}
@@ -755,6 +764,7 @@ int kh_spa_create(int32_t device, kh_spa ** out)
   }
   for (auto & row : s->ev_phase) {for (auto & e : row) {KS_HIP(hipEventCreate(&e));}}
   for (auto & row : s->ev_lin) {for (auto & e : row) {KS_HIP(hipEventCreate(&e));}}
+  for (auto & e : s->ev_cov) {KS_HIP(hipEventCreate(&e));}
   *out = s;
   return KH_OK;
 }
@@ -774,8 +784,10 @@ void kh_spa_destroy(kh_spa * s)
   s->d_edge_lin.release(); s->d_edge_cost.release(); s->d_Hg.release(); s->d_fronts.release(); s->d_fronts_b.release(); s->d_deferred.release(); s->d_pack.release();
   s->d_x.release(); s->d_cand.release(); s->d_scale.release(); s->d_diag.release(); s->d_rhs.release();
   s->d_step.release(); s->d_delta.release(); s->d_scal.release(); s->d_upd.release(); s->d_fsb.release(); s->d_partial.release(); s->d_Hg_alt.release(); s->d_best.release();
+  s->d_zbuf.release(); s->d_cov.release();
   for (auto & row : s->ev_phase) {for (auto & e : row) {if (e) {(void)hipEventDestroy(e);}}}
   for (auto & row : s->ev_lin) {for (auto & e : row) {if (e) {(void)hipEventDestroy(e);}}}
+  for (auto & e : s->ev_cov) {if (e) {(void)hipEventDestroy(e);}}
   if (s->h_scal) {(void)hipHostFree(s->h_scal);}
   if (s->h_res) {(void)hipHostFree(s->h_res);}
   if (s->h_upload) {(void)hipHostFree(s->h_upload);}
@@ -821,6 +833,7 @@ int kh_spa_set_debug(kh_spa * s, int32_t flags)
 int kh_spa_reset(kh_spa * s)     // ceres_solver.cpp:279-314
 {
   if (!s) {return KH_ERR_INVALID_ARG;}
+  s->cov_valid = false;
   s->nodes.clear(); s->index_of.clear(); s->cons.clear(); s->con_of.clear(); s->incident.clear(); s->n_dead = 0; s->n_dead_nodes = 0;
   s->corr_ids.clear(); s->corr_poses.clear();
   s->has_first = false; s->was_constant_set = false; s->topology_dirty = true; s->fixed_index = -1;
@@ -831,6 +844,7 @@ int kh_spa_reset(kh_spa * s)     // ceres_solver.cpp:279-314
 int kh_spa_clear(kh_spa * s)     // ceres_solver.cpp:272-276
 {
   if (!s) {return KH_ERR_INVALID_ARG;}
+  s->cov_valid = false;
   s->corr_ids.clear(); s->corr_poses.clear();
   return KH_OK;
 }
@@ -839,6 +853,7 @@ int kh_spa_add_node(kh_spa * s, int32_t id, const double pose[3])    // ceres_so
 {
   if (!s || !pose) {return KH_ERR_INVALID_ARG;}
   if (s->index_of.count(id)) {return KH_OK;}       // unordered_map::insert keeps the existing entry
+  s->cov_valid = false;
   Node n; n.id = id; std::copy(pose, pose + 3, n.pose);
   s->index_of[id] = static_cast<int32_t>(s->nodes.size());
   s->nodes.push_back(n);
@@ -867,6 +882,7 @@ static int add_constraint_information(kh_spa * s, int32_t id_a, int32_t id_b, co
   s->incident[id_a].push_back(static_cast<int32_t>(s->cons.size()));
   s->incident[id_b].push_back(static_cast<int32_t>(s->cons.size()));
   s->cons.push_back(c);
+  s->cov_valid = false;
   s->topology_dirty = true;
   return KH_OK;
 }
@@ -1129,6 +1145,7 @@ int kh_spa_remove_node(kh_spa * s, int32_t id)     // ceres_solver.cpp:395-427 (
   if (!s) {return KH_ERR_INVALID_ARG;}
   auto it = s->index_of.find(id);
   if (it == s->index_of.end()) {set_error("RemoveNode: Failed to find node matching id"); return KH_ERR_NOT_FOUND;}
+  s->cov_valid = false;
   auto inc = s->incident.find(id);                     // O(degree): the node's own constraint list
   if (inc != s->incident.end()) {
     for (int32_t k : inc->second) {bury_constraint(s, k);}
@@ -1163,6 +1180,7 @@ int kh_spa_modify_node(kh_spa * s, int32_t id, const double pose[3])    // ceres
   if (it == s->index_of.end()) {return KH_ERR_NOT_FOUND;}
   Node & n = s->nodes[it->second];
   const double yaw_init = n.pose[2];
+  s->cov_valid = false;
   n.pose[0] = pose[0]; n.pose[1] = pose[1]; n.pose[2] = pose[2];
   n.pose[2] += yaw_init;
   return KH_OK;
@@ -1235,11 +1253,108 @@ int kh_link_info(const double pose1[3], const double pose2[3], const double cov[
   return KH_OK;
 }
 
+}  // extern "C"
+
+// ---- pieces Compute() and the covariance pass share -------------------------------------------------------------------
+namespace
+{
+// H || g of this rank's edge block -> sums over all ranks; also with one rank of a communicator (identity)
+int allreduce_normal_equations(kh_spa * s, const SpaDev & into)
+{
+  const int64_t hg_count = static_cast<int64_t>(s->n_slots) * 9 + static_cast<int64_t>(into.n_free) * 3;
+  if (s->comm) {
+    // on the solver's stream (RCCL over xGMI)
+    const int arc = kh_comm_allreduce_sum_f64(s->comm, into.H, hg_count, s->stream);
+    if (arc) {return arc;}
+  } else if (s->shard_world > 1) {
+    if (!s->allreduce) {set_error("kh_spa: sharding enabled without a communicator or an all-reduce callback"); return KH_ERR_INVALID_ARG;}
+    if (s->allreduce(s->allreduce_user, into.H, hg_count, s->stream) != 0) {set_error("kh_spa: all-reduce callback failed"); return KH_ERR_SOLVER;}
+  }
+  return KH_OK;
+}
+
+// cost, H and g at the poses `at` (this rank's edge block [e_lo, e_hi), then the all-reduce); ev: an event pair around the
+// kernels, or nullptr
+int linearize_normal_equations(kh_spa * s, const SpaDev & into, const double * at, double * cost_slot, int32_t e_lo, int32_t e_hi, hipEvent_t * ev)
+{
+  if (ev) {KS_HIP(hipEventRecord(ev[0], s->stream));}
+  spa_launch_linearize(into, at, cost_slot, e_lo, e_hi, s->stream);
+  if (ev) {KS_HIP(hipEventRecord(ev[1], s->stream));}
+  return allreduce_normal_equations(s, into);
+}
+
+// The fronts (and buffer B) start every factorisation as zeros: 2 x 190 MB on the 10k-node graph, 27 us each at the head of
+// the critical stream.  In scatter mode the fronts are SELF-CLEANING instead: every entry has exactly one last reader in a
+// factorisation (k_potrf the pivot block, k_trsm buffer B under L21, k_syrk the update block, k_backward3 L21 -- behind a covariance
+// pass k_selinv_clean, which zeroes what the downward pass wrote over L21), and that reader
+// stores a zero behind itself; only the update matrices that stay in place take a (small) kernel of their own.  (Zeroing on a
+// second stream beside the step evaluation was tried first: the fill kernels take every compute unit, k_step_fused and the
+// linearisation ran 2-3 x longer and the iteration gained 10 us of the 54.)
+int zero_fronts(kh_spa * s, const SpaDev & dev)
+{
+  hipStream_t st = s->stream;
+  if (dev.scatter && s->clean_a == dev.fronts && s->clean_b == dev.fronts_b) {s->clean_a = nullptr; return KH_OK;}
+  s->clean_a = nullptr;
+  // (the WHOLE allocation: a later analysis may lay larger fronts over the same buffers, and "clean" has to mean all of them)
+  KS_HIP(hipMemsetAsync(dev.fronts, 0, sizeof(double) * (dev.scatter ? s->d_fronts.cap : static_cast<size_t>(dev.fronts_size)), st));
+  if (dev.scatter) {KS_HIP(hipMemsetAsync(dev.fronts_b, 0, sizeof(double) * s->d_fronts_b.cap, st));}
+  return KH_OK;
+}
+
+// how a front's update matrix reaches its parent (kh_spa_set_debug bits 8, 9): added in by k_syrk (default), read in place by the
+// parent, or summed in by an extend-add launch per level (rounds 3-5); returns whether the level pipeline runs
+bool select_factor_mode(const kh_spa * s, SpaDev & dev)
+{
+  const int factor_mode = ((s->debug_flags >> 4) & 15) ? ((s->debug_flags >> 4) & 15) : 3;
+  const bool pipeline = factor_mode >= 3 && spa_level_pipeline_fits(s->sym.max_m, s->sym.max_ns);
+  dev.gather = pipeline && (s->debug_flags & 256) ? 1 : 0;
+  dev.scatter = pipeline && !dev.gather && !(s->debug_flags & 512) ? 1 : 0;
+  return pipeline;
+}
+
+// numeric factorisation + forward solve of the assembled fronts, leaves to root
+int launch_factor_levels(kh_spa * s, const SpaDev & dev, bool pipeline)
+{
+  hipStream_t st = s->stream;
+  const Symbolic & sym = s->sym;
+  const int n_levels = static_cast<int>(sym.levels.size());
+  if (!pipeline) {KS_HIP(hipMemsetAsync(s->d_sync.p, 0, sizeof(int32_t) * 4 * static_cast<size_t>(sym.n_fronts), st));}
+  constexpr int32_t kNarrowLevel = 128;      // levels of at most this many fronts take the chip-wide extend-add
+  for (int l = 0; l < n_levels; ++l) {
+    const int32_t n_level = s->level_offsets[l + 1] - s->level_offsets[l];
+    const int32_t * lf = s->d_level_fronts.p + s->level_offsets[l];
+    if (pipeline) {
+      // (running the part of the extend-add that k_potrf does not read on a second stream beside the pivot chains was measured
+      // slower on the 10k / 30k graph: 14.7 ms per solve against 13.2 -- the event records and stream waits on the critical
+      // stream cost more than the overlap wins)
+      if (l > 0 && !dev.gather && !dev.scatter) {spa_launch_extend_add(dev, lf, n_level, s->level_max_m[l], st);}
+      spa_launch_potrf_level(dev, s->level_offsets[l], n_level, s->level_max_m[l], s->level_max_ns[l], s->d_fail.p, s->d_rhs.p, s->d_upd.p, st);
+      // the update of the level: the fronts that fit one workgroup's LDS whole in k_front_update (when there are enough of them), the
+      // larger ones -- the head of the level -- in k_trsm / k_syrk
+      if (s->level_max_nu[l] == 0) {continue;}                   // (the root: nothing below the pivot block)
+      const int32_t split = dev.gather ? n_level : s->level_split[l];
+      spa_launch_update_level(dev, s->level_offsets[l], split, s->level_max_m[l], s->level_max_ns[l], s->d_rhs.p, s->d_upd.p, st);
+      spa_launch_front_update(dev, s->level_offsets[l] + split, n_level - split, s->level_fused_lds[l], s->d_rhs.p, s->d_upd.p, st);
+      continue;
+    }
+    // narrow levels: the extend-add runs chip-wide in its own launch instead of on each front's single CU
+    const bool split = l > 0 && n_level <= kNarrowLevel;
+    if (split) {spa_launch_extend_add(dev, lf, n_level, s->level_max_m[l], st);}
+    spa_launch_factor_level(dev, lf, n_level, s->level_max_m[l], s->level_max_ns[l], s->d_fail.p,
+      s->d_rhs.p, s->d_upd.p, s->d_fsb.p, s->d_sync.p + 4 * s->level_offsets[l], split ? 1 : 0, st);
+  }
+  return KH_OK;
+}
+}  // namespace
+
+extern "C" {
+
 // CeresSolver::Compute, ceres_solver.cpp:214-269
 int kh_spa_compute(kh_spa * s, kh_spa_summary * summary)
 {
   settle(s);
   if (!s) {return KH_ERR_INVALID_ARG;}
+  s->cov_valid = false;
   kh_spa_summary sum;
   std::memset(&sum, 0, sizeof(sum));
   sum.usable = 1;
@@ -1297,28 +1412,14 @@ int kh_spa_compute(kh_spa * s, kh_spa_summary * summary)
   dev.loss_kind = opt.loss_function; dev.loss_b = opt.loss_scale * opt.loss_scale; dev.loss_a = opt.loss_scale;
   const int32_t e_lo = static_cast<int32_t>(static_cast<int64_t>(dev.n_edges) * s->shard_rank / s->shard_world);
   const int32_t e_hi = static_cast<int32_t>(static_cast<int64_t>(dev.n_edges) * (s->shard_rank + 1) / s->shard_world);
-  const int64_t hg_count = static_cast<int64_t>(s->n_slots) * 9 + static_cast<int64_t>(dev.n_free) * 3;
   int n_lin = 0, n_timed = 0;
   // kh_spa_set_debug bit 1: HIP events around the phases of every LM iteration (kh_spa_summary.*_gpu_ms).  Off by default: an event
   // record between two kernels is a 5-6 us bubble on the stream, three of them per iteration were 0.15 ms of a 9 ms solve.
   const bool phase_events = (s->debug_flags & 2) != 0;
-  auto allreduce_Hg = [&](const SpaDev & into) -> int {
-    if (s->comm) {
-      // H || g of this rank's edge block -> sums over all ranks, on the solver's stream (RCCL over xGMI)
-      const int arc = kh_comm_allreduce_sum_f64(s->comm, into.H, hg_count, st);
-      if (arc) {return arc;}
-    } else if (s->shard_world > 1) {
-      if (!s->allreduce) {set_error("kh_spa: sharding enabled without a communicator or an all-reduce callback"); return KH_ERR_INVALID_ARG;}
-      if (s->allreduce(s->allreduce_user, into.H, hg_count, st) != 0) {set_error("kh_spa: all-reduce callback failed"); return KH_ERR_SOLVER;}
-    }
-    return KH_OK;
-  };
+  auto allreduce_Hg = [&](const SpaDev & into) -> int {return allreduce_normal_equations(s, into);};
   auto linearize = [&](const SpaDev & into, const double * at, double * cost_slot) -> int {
     const bool timed = phase_events && n_lin < 2 * kh_spa::kMaxTimed + 2;
-    if (timed) {KS_HIP(hipEventRecord(s->ev_lin[n_lin][0], st));}
-    spa_launch_linearize(into, at, cost_slot, e_lo, e_hi, st);
-    if (timed) {KS_HIP(hipEventRecord(s->ev_lin[n_lin][1], st)); ++n_lin;}
-    return allreduce_Hg(into);
+    return linearize_normal_equations(s, into, at, cost_slot, e_lo, e_hi, timed ? s->ev_lin[n_lin++] : nullptr);
   };
   // The normal equations at the CANDIDATE point are built speculatively, into a second H || g, in the same batch of
   // launches that evaluates the candidate's cost: a step is nearly always accepted, and the iteration then needs one
@@ -1326,26 +1427,7 @@ int kh_spa_compute(kh_spa * s, kh_spa_summary * summary)
   // A rejected step simply leaves the second buffer unused.
   SpaDev alt = dev;
   alt.H = s->d_Hg_alt.p; alt.g = s->d_Hg_alt.p + static_cast<size_t>(s->n_slots) * 9;
-  // how a front's update matrix reaches its parent (kh_spa_set_debug bits 8, 9): added in by k_syrk (default), read in place by the
-  // parent, or summed in by an extend-add launch per level (rounds 3-5)
-  const int factor_mode = ((s->debug_flags >> 4) & 15) ? ((s->debug_flags >> 4) & 15) : 3;
-  const bool pipeline = factor_mode >= 3 && spa_level_pipeline_fits(sym.max_m, sym.max_ns);
-  dev.gather = pipeline && (s->debug_flags & 256) ? 1 : 0;
-  dev.scatter = pipeline && !dev.gather && !(s->debug_flags & 512) ? 1 : 0;
-  // The fronts (and buffer B) start every factorisation as zeros: 2 x 190 MB on the 10k-node graph, 27 us each at the head of
-  // the critical stream.  In scatter mode the fronts are SELF-CLEANING instead: every entry has exactly one last reader in a
-  // factorisation (k_potrf the pivot block, k_trsm buffer B under L21, k_syrk the update block, k_backward3 L21), and that reader
-  // stores a zero behind itself; only the update matrices that stay in place take a (small) kernel of their own.  (Zeroing on a
-  // second stream beside the step evaluation was tried first: the fill kernels take every compute unit, k_step_fused and the
-  // linearisation ran 2-3 x longer and the iteration gained 10 us of the 54.)
-  auto zero_fronts = [&]() -> int {
-    if (dev.scatter && s->clean_a == dev.fronts && s->clean_b == dev.fronts_b) {s->clean_a = nullptr; return KH_OK;}
-    s->clean_a = nullptr;
-    // (the WHOLE allocation: a later analysis may lay larger fronts over the same buffers, and "clean" has to mean all of them)
-    KS_HIP(hipMemsetAsync(dev.fronts, 0, sizeof(double) * (dev.scatter ? s->d_fronts.cap : static_cast<size_t>(dev.fronts_size)), st));
-    if (dev.scatter) {KS_HIP(hipMemsetAsync(dev.fronts_b, 0, sizeof(double) * s->d_fronts_b.cap, st));}
-    return KH_OK;
-  };
+  const bool pipeline = select_factor_mode(s, dev);
   rc = linearize(dev, x, scal + 0); if (rc) {return finish(rc);}
   if (opt.jacobi_scaling) {
     spa_launch_jacobi_scale(dev, s->d_scale.p, st);
@@ -1399,35 +1481,11 @@ int kh_spa_compute(kh_spa * s, kh_spa_summary * summary)
     have_diagonal = true;
     const bool timed = phase_events && n_timed < kh_spa::kMaxTimed;
     if (timed) {KS_HIP(hipEventRecord(s->ev_phase[n_timed][0], st));}
-    rc = zero_fronts(); if (rc) {return finish(rc);}
+    rc = zero_fronts(s, dev); if (rc) {return finish(rc);}
     // one launch: the scaled + damped matrix into the fronts (forming the LM diagonal on the way when a new one is due), the
     // right-hand side in elimination order (factorisation and forward solve are one kernel per level) and the fail word's reset
     spa_launch_assemble(dev, s->d_scale.p, s->d_diag.p, 1.0 / radius, new_diagonal, opt.min_lm_diagonal, opt.max_lm_diagonal, s->d_rhs.p, s->d_fail.p, st);
-    if (!pipeline) {KS_HIP(hipMemsetAsync(s->d_sync.p, 0, sizeof(int32_t) * 4 * static_cast<size_t>(sym.n_fronts), st));}
-    constexpr int32_t kNarrowLevel = 128;      // levels of at most this many fronts take the chip-wide extend-add
-    for (int l = 0; l < n_levels; ++l) {
-      const int32_t n_level = s->level_offsets[l + 1] - s->level_offsets[l];
-      const int32_t * lf = s->d_level_fronts.p + s->level_offsets[l];
-      if (pipeline) {
-        // (running the part of the extend-add that k_potrf does not read on a second stream beside the pivot chains was measured
-        // slower on the 10k / 30k graph: 14.7 ms per solve against 13.2 -- the event records and stream waits on the critical
-        // stream cost more than the overlap wins)
-        if (l > 0 && !dev.gather && !dev.scatter) {spa_launch_extend_add(dev, lf, n_level, s->level_max_m[l], st);}
-        spa_launch_potrf_level(dev, s->level_offsets[l], n_level, s->level_max_m[l], s->level_max_ns[l], s->d_fail.p, s->d_rhs.p, s->d_upd.p, st);
-        // the update of the level: the fronts that fit one workgroup's LDS whole in k_front_update (when there are enough of them), the
-        // larger ones -- the head of the level -- in k_trsm / k_syrk
-        if (s->level_max_nu[l] == 0) {continue;}                   // (the root: nothing below the pivot block)
-        const int32_t split = dev.gather ? n_level : s->level_split[l];
-        spa_launch_update_level(dev, s->level_offsets[l], split, s->level_max_m[l], s->level_max_ns[l], s->d_rhs.p, s->d_upd.p, st);
-        spa_launch_front_update(dev, s->level_offsets[l] + split, n_level - split, s->level_fused_lds[l], s->d_rhs.p, s->d_upd.p, st);
-        continue;
-      }
-      // narrow levels: the extend-add runs chip-wide in its own launch instead of on each front's single CU
-      const bool split = l > 0 && n_level <= kNarrowLevel;
-      if (split) {spa_launch_extend_add(dev, lf, n_level, s->level_max_m[l], st);}
-      spa_launch_factor_level(dev, lf, n_level, s->level_max_m[l], s->level_max_ns[l], s->d_fail.p,
-        s->d_rhs.p, s->d_upd.p, s->d_fsb.p, s->d_sync.p + 4 * s->level_offsets[l], split ? 1 : 0, st);
-    }
+    rc = launch_factor_levels(s, dev, pipeline); if (rc) {return finish(rc);}
     if (timed) {KS_HIP(hipEventRecord(s->ev_phase[n_timed][1], st));}
     for (int l = n_levels - 1; l >= 0; --l) {
       const int32_t n_level = s->level_offsets[l + 1] - s->level_offsets[l];
@@ -1596,7 +1654,260 @@ int kh_spa_compute(kh_spa * s, kh_spa_summary * summary)
   return finish(KH_OK);
 }
 
+// ---- covariances: Sigma = (J^T J)^-1 on the pattern of H, from the selected inverse of the factor ----------------------------
+static int covariance_device_check()
+{
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    (void)hipGetLastError();
+    set_error("no usable HIP device (libkartohip has no CPU fallback)");
+    return KH_ERR_NO_DEVICE;
+  }
+  return KH_OK;
+}
+
+int kh_spa_compute_covariances(kh_spa * s, kh_spa_cov_summary * summary)
+{
+  if (covariance_device_check() != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!s) {return KH_ERR_INVALID_ARG;}
+  settle(s);
+  s->cov_valid = false; s->cov_on_host = false;
+  kh_spa_cov_summary sum;
+  std::memset(&sum, 0, sizeof(sum));
+  auto finish = [&](int rc) {if (summary) {*summary = sum;} return rc;};
+  if (s->nodes.empty()) {set_error("kh_spa_compute_covariances: the graph has no nodes"); return finish(KH_ERR_NOT_FOUND);}
+  const kh_spa_options & opt = s->opt;
+  if (opt.loss_function != KH_LOSS_NONE && !(opt.loss_scale > 0.0)) {
+    set_error("kh_spa: loss_scale must be positive");
+    return finish(KH_ERR_INVALID_ARG);
+  }
+  KS_HIP(hipSetDevice(s->device));
+  const auto t_begin = std::chrono::steady_clock::now();
+  auto ms_since = [](std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+  };
+  SpaDev dev;
+  std::memset(&dev, 0, sizeof(dev));
+  bool has_work = false;
+  int rc = prepare_problem(s, dev, has_work);
+  if (rc) {return finish(rc);}
+  if (!has_work) {set_error("kh_spa_compute_covariances: no constraint touches a free node: nothing is in the problem"); return finish(KH_ERR_NOT_FOUND);}
+  const Symbolic & sym = s->sym;
+  hipStream_t st = s->stream;
+  const int n_levels = static_cast<int>(sym.levels.size());
+  sum.n_free = dev.n_free; sum.levels = n_levels;
+  sum.analysis = s->last_symbolic_ms > 0.0 ? (s->last_analysis_incremental ? 2 : 1) : 0;
+  if (!select_factor_mode(s, dev)) {
+    // (the downward pass needs W = L11^-T of every front, which only the level pipeline leaves behind)
+    set_error("kh_spa_compute_covariances: needs the level pipeline (a front exceeds its LDS budget, or factor kernels 1 / 2 are selected)");
+    return finish(KH_ERR_SOLVER);
+  }
+  {
+    // Every free node must reach the gauge node through constraints, or J^T J is singular.  Checked on the graph itself: the
+    // last pivot of a floating component is zero only up to rounding, so the fail word of the factorisation (checked below as
+    // well) sees it only when the rounding falls that way.
+    const int32_t nf = dev.n_free;
+    std::vector<int32_t> root(nf);
+    for (int32_t f = 0; f < nf; ++f) {root[f] = f;}
+    auto find = [&](int32_t f) {while (root[f] != f) {root[f] = root[root[f]]; f = root[f];} return f;};
+    std::vector<uint8_t> tied(nf, 0);
+    for (size_t e = 0; e < s->cached_ea.size(); ++e) {
+      const int32_t fa = s->free_of_node[s->cached_ea[e]], fb = s->free_of_node[s->cached_eb[e]];
+      if (fa >= 0 && fb >= 0) {root[find(fa)] = find(fb);}
+    }
+    for (size_t e = 0; e < s->cached_ea.size(); ++e) {
+      const int32_t pa = s->cached_ea[e], pb = s->cached_eb[e];
+      if (pa == s->fixed_index && s->free_of_node[pb] >= 0) {tied[find(s->free_of_node[pb])] = 1;}
+      if (pb == s->fixed_index && s->free_of_node[pa] >= 0) {tied[find(s->free_of_node[pa])] = 1;}
+    }
+    for (int32_t f = 0; f < nf; ++f) {
+      if (!tied[find(f)]) {
+        set_error("kh_spa_compute_covariances: node " + std::to_string(s->nodes[s->node_of_free[f]].id) +
+          " belongs to a free component of the graph that is not tied to the gauge node: J^T J is singular");
+        return finish(KH_ERR_SOLVER);
+      }
+    }
+  }
+  for (int32_t k = 0; k < sym.n_fronts; ++k) {
+    const int64_t ns = sym.front_ns[k], nu = sym.front_m[k] - ns;
+    sum.inverse_flops += nu * ns * ns + 2 * nu * nu * ns + 2 * ns * ns * nu;
+  }
+  if (s->d_zbuf.ensure(static_cast<size_t>(sym.fronts_size) + 16) || s->d_cov.ensure(static_cast<size_t>(s->n_slots) * 9 + 16)) {return finish(KH_ERR_HIP);}
+  dev.loss_kind = opt.loss_function; dev.loss_b = opt.loss_scale * opt.loss_scale; dev.loss_a = opt.loss_scale;
+  const int32_t e_lo = static_cast<int32_t>(static_cast<int64_t>(dev.n_edges) * s->shard_rank / s->shard_world);
+  const int32_t e_hi = static_cast<int32_t>(static_cast<int64_t>(dev.n_edges) * (s->shard_rank + 1) / s->shard_world);
+  rc = linearize_normal_equations(s, dev, s->d_x.p, s->d_scal.p, e_lo, e_hi, nullptr); if (rc) {return finish(rc);}
+  if (opt.jacobi_scaling) {
+    spa_launch_jacobi_scale(dev, s->d_scale.p, st);
+  } else {
+    std::vector<double> ones(static_cast<size_t>(dev.n_free) * 3, 1.0);
+    KS_HIP(hipMemcpyAsync(s->d_scale.p, ones.data(), ones.size() * 8, hipMemcpyHostToDevice, st));
+    KS_HIP(hipStreamSynchronize(st));
+  }
+  KS_HIP(hipStreamSynchronize(st));
+  sum.linearize_ms = ms_since(t_begin);
+  const auto t_factor = std::chrono::steady_clock::now();
+  rc = zero_fronts(s, dev); if (rc) {return finish(rc);}
+  // undamped: inv_radius = 0.  The LM diagonal is formed on the way into a scratch vector (d_delta: every iteration of a Compute
+  // overwrites it), so that 0 * diagonal is 0 whatever d_diag holds -- it may never have been formed
+  spa_launch_assemble(dev, s->d_scale.p, s->d_delta.p, 0.0, true, opt.min_lm_diagonal, opt.max_lm_diagonal, s->d_rhs.p, s->d_fail.p, st);
+  rc = launch_factor_levels(s, dev, true); if (rc) {return finish(rc);}
+  const bool events = (s->debug_flags & 2) != 0;
+  if (events) {KS_HIP(hipEventRecord(s->ev_cov[0], st));}
+  for (int l = n_levels - 1; l >= 0; --l) {
+    spa_launch_selinv_level(dev, s->level_offsets[l], s->level_offsets[l + 1] - s->level_offsets[l], s->level_max_m[l], s->level_max_ns[l], s->d_zbuf.p, st);
+  }
+  if (events) {KS_HIP(hipEventRecord(s->ev_cov[1], st));}
+  spa_launch_cov_gather(dev, s->d_zbuf.p, s->d_scale.p, s->d_cov.p, st);
+  if (events) {KS_HIP(hipEventRecord(s->ev_cov[2], st));}
+  if (dev.scatter) {
+    // the pass stands where the backward sweep stands in a solve: the last reader of what the factorisation left in the fronts
+    spa_launch_selinv_clean(dev, st);
+    spa_launch_zero_update_blocks(dev, s->d_deferred.p, s->n_deferred_fronts, s->deferred_max_m, st);
+  }
+  KS_HIP(hipMemcpyAsync(s->h_fail, s->d_fail.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  KS_HIP(hipGetLastError());
+  KS_HIP(hipStreamSynchronize(st));
+  if (s->h_fail[0] != 0) {
+    // (a failed front has handed NaNs up the tree: the fronts are not trusted to be clean, the next factorisation memsets)
+    set_error("kh_spa_compute_covariances: non-positive pivot: a free component of the graph is not tied to the gauge node");
+    return finish(KH_ERR_SOLVER);
+  }
+  if (dev.scatter) {
+    s->clean_a = dev.fronts; s->clean_b = dev.fronts_b;
+    if (s->debug_flags & 1) {
+      // the self-cleaning fronts must be all zeros now, as behind a Compute()
+      KS_HIP(hipMemsetAsync(s->d_fail.p, 0, sizeof(int32_t), st));
+      spa_launch_count_nonzero(dev.fronts, dev.fronts_size, s->d_fail.p, st);
+      spa_launch_count_nonzero(dev.fronts_b, dev.fronts_size, s->d_fail.p, st);
+      KS_HIP(hipMemcpyAsync(s->h_fail, s->d_fail.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      KS_HIP(hipStreamSynchronize(st));
+      if (s->h_fail[0] != 0) {
+        s->clean_a = nullptr;
+        set_error("kh_spa: " + std::to_string(s->h_fail[0]) + " entries of the self-cleaning fronts were left behind by the covariance pass");
+        return finish(KH_ERR_SOLVER);
+      }
+    }
+  }
+  if (events) {
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, s->ev_cov[0], s->ev_cov[1]) == hipSuccess) {sum.inverse_ms = ms;}
+    if (hipEventElapsedTime(&ms, s->ev_cov[1], s->ev_cov[2]) == hipSuccess) {sum.gather_ms = ms;}
+  }
+  s->cov_valid = true;
+  sum.factor_ms = ms_since(t_factor);
+  sum.total_ms = ms_since(t_begin);
+  return finish(KH_OK);
+}
+
+// the array and the pattern it is addressed by, on the host (first getter behind a computation)
+static int fetch_covariances(kh_spa * s)
+{
+  if (!s->cov_valid) {
+    set_error("kh_spa: the covariances are stale (the graph or a pose has changed since kh_spa_compute_covariances, or it never ran)");
+    return KH_ERR_SOLVER;
+  }
+  if (s->cov_on_host) {return KH_OK;}
+  const size_t nf = s->node_of_free.size(), nslots = static_cast<size_t>(s->n_slots);
+  s->h_cov.resize(nslots * 9); s->h_cov_row_ptr.resize(nf + 1); s->h_cov_col.resize(nslots); s->h_cov_diag.resize(nf);
+  KS_HIP(hipSetDevice(s->device));
+  KS_HIP(hipMemcpyAsync(s->h_cov.data(), s->d_cov.p, nslots * 9 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  KS_HIP(hipMemcpyAsync(s->h_cov_row_ptr.data(), s->d_bsr_row_ptr.p, (nf + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+  KS_HIP(hipMemcpyAsync(s->h_cov_col.data(), s->d_bsr_col.p, nslots * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+  KS_HIP(hipMemcpyAsync(s->h_cov_diag.data(), s->d_bsr_diag.p, nf * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+  KS_HIP(hipStreamSynchronize(s->stream));
+  s->cov_on_host = true;
+  return KH_OK;
+}
+
+// free index of node `id`: -1 the gauge node; KH_ERR_NOT_FOUND (through rc) for an unknown id or a node without constraints
+static int covariance_index(kh_spa * s, int32_t id, int32_t & free_index)
+{
+  const auto it = s->index_of.find(id);
+  if (it == s->index_of.end()) {set_error("kh_spa: no node with id " + std::to_string(id)); return KH_ERR_NOT_FOUND;}
+  free_index = s->free_of_node[it->second];
+  if (free_index < 0 && it->second != s->fixed_index) {
+    set_error("kh_spa: node " + std::to_string(id) + " has no constraints: it is not in the problem");
+    return KH_ERR_NOT_FOUND;
+  }
+  return KH_OK;
+}
+
+int kh_spa_get_covariances(kh_spa * s, int32_t n, const int32_t * ids, double * cov)
+{
+  if (n < 0 || (n > 0 && !cov)) {return KH_ERR_INVALID_ARG;}
+  if (covariance_device_check() != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!s) {return KH_ERR_INVALID_ARG;}
+  int rc = fetch_covariances(s);
+  if (rc) {return rc;}
+  if (!ids && n != static_cast<int32_t>(s->nodes.size())) {
+    set_error("kh_spa_get_covariances: without ids, n must be kh_spa_num_nodes");
+    return KH_ERR_INVALID_ARG;
+  }
+  for (int32_t k = 0; k < n; ++k) {
+    int32_t f = -1;
+    rc = covariance_index(s, ids ? ids[k] : s->nodes[k].id, f);
+    if (rc) {return rc;}
+    if (f < 0) {
+      std::fill(cov + 9 * static_cast<size_t>(k), cov + 9 * static_cast<size_t>(k) + 9, 0.0);
+    } else {
+      const double * b = s->h_cov.data() + 9 * static_cast<size_t>(s->h_cov_diag[f]);
+      std::copy(b, b + 9, cov + 9 * static_cast<size_t>(k));
+    }
+  }
+  return KH_OK;
+}
+
+int kh_spa_get_joint_covariance(kh_spa * s, int32_t id_a, int32_t id_b, double cov[36])
+{
+  if (!cov) {return KH_ERR_INVALID_ARG;}
+  if (covariance_device_check() != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!s) {return KH_ERR_INVALID_ARG;}
+  int rc = fetch_covariances(s);
+  if (rc) {return rc;}
+  int32_t f[2] = {-1, -1};
+  rc = covariance_index(s, id_a, f[0]); if (rc) {return rc;}
+  rc = covariance_index(s, id_b, f[1]); if (rc) {return rc;}
+  if (s->first_constraint(id_a, id_b) < 0 && s->first_constraint(id_b, id_a) < 0) {
+    set_error("kh_spa_get_joint_covariance: no constraint joins the two nodes: their cross block is not on the pattern of the factor");
+    return KH_ERR_NOT_FOUND;
+  }
+  std::fill(cov, cov + 36, 0.0);
+  for (int p = 0; p < 2; ++p) {
+    for (int q = 0; q < 2; ++q) {
+      if (f[p] < 0 || f[q] < 0) {continue;}                    // the gauge node: zeros
+      const auto b = s->h_cov_col.begin() + s->h_cov_row_ptr[f[p]], e = s->h_cov_col.begin() + s->h_cov_row_ptr[f[p] + 1];
+      const auto it = std::lower_bound(b, e, f[q]);
+      if (it == e || *it != f[q]) {set_error("kh_spa_get_joint_covariance: block outside the pattern"); return KH_ERR_SOLVER;}
+      const double * blk = s->h_cov.data() + 9 * static_cast<size_t>(it - s->h_cov_col.begin());
+      for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) {cov[(3 * p + r) * 6 + 3 * q + c] = blk[3 * r + c];}
+      }
+    }
+  }
+  return KH_OK;
+}
+
+int kh_spa_covariance_device(kh_spa * s, const double ** cov_bsr, int64_t * n_slots)
+{
+  if (!cov_bsr || !n_slots) {return KH_ERR_INVALID_ARG;}
+  if (covariance_device_check() != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!s) {return KH_ERR_INVALID_ARG;}
+  if (!s->cov_valid) {
+    set_error("kh_spa: the covariances are stale (the graph or a pose has changed since kh_spa_compute_covariances, or it never ran)");
+    return KH_ERR_SOLVER;
+  }
+  *cov_bsr = s->d_cov.p; *n_slots = s->n_slots;
+  return KH_OK;
+}
+
 }  // extern "C"
+
+namespace kh
+{
+// whether the resident covariances still belong to the graph (the mapper recomputes lazily)
+bool spa_covariances_valid(const kh_spa * s) {return s && s->cov_valid;}
+}  // namespace kh
 
 // ---- the part of the solver's state a mapping session file carries besides nodes and constraints (mapper_host.cpp) ----
 // The gauge bookkeeping (first_node_ and whether it was set constant) and the analysis cache that makes the next Compute()

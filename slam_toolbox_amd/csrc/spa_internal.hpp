@@ -123,6 +123,15 @@ void spa_launch_update_level(const SpaDev & d, int32_t first_front, int32_t n, i
 size_t spa_front_update_lds(int32_t m, int32_t ns);
 void spa_launch_front_update(const SpaDev & d, int32_t first_front, int32_t n, size_t lds_bytes, const double * rhs, double * upd, void * stream);
 void spa_launch_backward3_level(const SpaDev & d, int32_t first_front, int32_t n, int32_t max_m, int32_t max_ns, double * rhs, void * stream);
+// Selected inverse of the factor, Z = (L L^T)^-1 on the pattern of L: one level of the walk back down the tree (call it for the
+// root level first, then level by level to the leaves, after the level pipeline has factorised: it needs L21 in the fronts and
+// W in winv).  zbuf: fronts_size doubles with the fronts' own offsets; a front's m x m block of Z is stored in full.  G = L21 W^T
+// is left where L21 was.
+void spa_launch_selinv_level(const SpaDev & d, int32_t first_front, int32_t n, int32_t max_m, int32_t max_ns, double * zbuf, void * stream);
+// self-cleaning fronts (scatter mode): zeroes what spa_launch_selinv_level left under the pivot blocks, as the backward sweep does
+void spa_launch_selinv_clean(const SpaDev & d, void * stream);
+// cov (n_slots * 9 doubles, addressed like H): block (i, j) of the pattern = s_i Z_ij s_j, with s = scale
+void spa_launch_cov_gather(const SpaDev & d, const double * zbuf, const double * scale, double * cov, void * stream);
 // self-cleaning fronts (scatter mode): zero the update matrices of the fronts in `list` (children read in place by their parents)
 void spa_launch_zero_update_blocks(const SpaDev & d, const int32_t * list, int32_t n, int32_t max_m, void * stream);
 // debugging aid: *count += entries of p[0..n) whose bit pattern is not zero

@@ -254,6 +254,23 @@ class Mapper:
         capi.check(capi.lib().kh_mapper_get_alive(self._h, ids), "kh_mapper_get_alive")
         return ids[:capi.lib().kh_mapper_num_alive(self._h)]
 
+    def covariances(self, ids=None) -> np.ndarray:
+        """(n, 3, 3): graph-aware covariance of the listed scans' poses (None: every solver node, insertion order); computed by
+        the solver on the first call after the graph or a pose has changed.  `cov_summary` holds the summary of the computation
+        this call ran (all zeros when it ran none)."""
+        L = capi.lib()
+        if ids is None:
+            n, idp = L.kh_spa_num_nodes(L.kh_mapper_solver(self._h)), None
+        else:
+            idv = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+            n, idp = idv.size, idv.ctypes.data_as(C.c_void_p)
+        out = np.zeros((max(n, 1), 3, 3))
+        s = capi.KhSpaCovSummary()
+        rc = L.kh_mapper_get_covariances(self._h, n, idp, out.ctypes.data_as(C.c_void_p), C.byref(s))
+        self.cov_summary = {k: getattr(s, k) for k, _ in capi.KhSpaCovSummary._fields_ if k != "pad"}
+        capi.check(rc, "kh_mapper_get_covariances")
+        return out[:n]
+
     def stats(self) -> dict:
         st = capi.KhMapperStats()
         capi.check(capi.lib().kh_mapper_get_stats(self._h, C.byref(st)), "kh_mapper_get_stats")

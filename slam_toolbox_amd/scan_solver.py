@@ -27,6 +27,24 @@ def link_info(pose1, pose2, covariance):
     return diff, cov.reshape(3, 3)
 
 
+def relative_covariance(pose_a, pose_b, joint):
+    """First-order covariance (3, 3) of b's pose expressed in a's frame, d = R(-theta_a) (t_b - t_a), theta_b - theta_a, from the
+    joint (6, 6) covariance of (a, b) that HipSpaSolver.JointCovariance returns: J joint J^T with J = [dd/da  dd/db]."""
+    pa, pb = _d(pose_a), _d(pose_b)
+    c, s = np.cos(pa[2]), np.sin(pa[2])
+    dx, dy = pb[0] - pa[0], pb[1] - pa[1]
+    rt = np.array([[c, s], [-s, c]])
+    ja, jb = np.zeros((3, 3)), np.zeros((3, 3))
+    ja[:2, :2] = -rt
+    ja[0, 2] = -s * dx + c * dy
+    ja[1, 2] = -c * dx - s * dy
+    ja[2, 2] = -1.0
+    jb[:2, :2] = rt
+    jb[2, 2] = 1.0
+    j = np.hstack([ja, jb])
+    return j @ _d(joint).reshape(6, 6) @ j.T
+
+
 class HipSpaSolver:
     """solver_plugins::HipSpaSolver : karto::ScanSolver"""
 
@@ -100,6 +118,38 @@ class HipSpaSolver:
             return self.summary
         capi.check(rc, "kh_spa_compute")
         return self.summary
+
+    # ---- covariances (no counterpart in the reference) ---------------------------------------------------------
+    def ComputeCovariances(self):
+        """kh_spa_compute_covariances: Sigma = (J^T J)^-1 at the current poses, every block on the pattern of H, resident on the
+        device until the graph or a pose changes.  Returns the summary dict; failures raise KartoHipError."""
+        s = capi.KhSpaCovSummary()
+        rc = capi.lib().kh_spa_compute_covariances(self._h, C.byref(s))
+        self.cov_summary = {k: getattr(s, k) for k, _ in capi.KhSpaCovSummary._fields_ if k != "pad"}
+        capi.check(rc, "kh_spa_compute_covariances")
+        return self.cov_summary
+
+    def Covariances(self, ids=None):
+        """(n, 3, 3): the marginal covariance of every listed node (None: all nodes, insertion order); zeros for the gauge node."""
+        L = capi.lib()
+        if ids is None:
+            n, idp = L.kh_spa_num_nodes(self._h), None
+        else:
+            idv = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+            n, idp = idv.size, idv.ctypes.data_as(C.c_void_p)
+        out = np.zeros((max(n, 1), 3, 3))
+        capi.check(L.kh_spa_get_covariances(self._h, n, idp, out.ctypes.data_as(C.c_void_p)), "kh_spa_get_covariances")
+        return out[:n]
+
+    def Covariance(self, unique_id: int):
+        return self.Covariances([int(unique_id)])[0]
+
+    def JointCovariance(self, id_a: int, id_b: int):
+        """(6, 6) [[aa ab], [ba bb]] of two nodes joined by a constraint."""
+        out = np.zeros((6, 6))
+        capi.check(capi.lib().kh_spa_get_joint_covariance(self._h, int(id_a), int(id_b), out.ctypes.data_as(C.c_void_p)),
+                   "kh_spa_get_joint_covariance")
+        return out
 
     def iteration_log(self):
         """(n, 8) array: the trust-region iterations of the last Compute() (kh_spa_iteration_log: iteration, cost, candidate cost,
