@@ -373,6 +373,30 @@ KH_API int kh_spa_get_joint_covariance(kh_spa * s, int32_t id_a, int32_t id_b, d
 /* the resident array for device consumers: n_slots blocks of 9 doubles (row-major), block-sparse rows over the free nodes on the
  * pattern of H; owned by the solver, valid like the getters' answers */
 KH_API int kh_spa_covariance_device(kh_spa * s, const double ** cov_bsr, int64_t * n_slots);
+/* ---- marginalizing node removal (no counterpart in the reference, whose RemoveNode drops the node's constraints and transfers
+ * nothing: a lifelong graph falls apart).  Every listed node leaves like kh_spa_remove_node, but first its constraints are composed
+ * through it into constraints among its neighbours: parallel constraints to one neighbour are fused; the
+ * neighbour whose (fused) information has the largest determinant is the hub, ties to the lowest id; for every other neighbour n
+ * the constraint hub -> n = inverse(v -> hub) (+) (v -> n) is formed, the hub's covariance weighted d - 1 (d neighbours), which
+ * keeps the d - 1 new constraints together no more informative than the exact dense marginal (exact for d = 2); it is fused into
+ * the first existing constraint between hub and n, which keeps its index and its direction, or appended.  Only constraints are
+ * read: no poses, no linearisation point.  A node with fewer than two neighbours is simply removed.
+ * The list is worked off in ROUNDS, formed greedily in list order: a node whose closed neighbourhood meets that of a listed node
+ * before it which is in the round or still waiting, waits for the next round.  One launch marginalizes a round, one wave per node
+ * and one lane per neighbour; the values equal those of the list processed one node after the other, and so does the order of the
+ * constraints when no node of the list had to wait behind a node that is not its predecessor in the list (appended constraints
+ * are in round order).  Arguments are checked first (n < 0, ids NULL: KH_ERR_INVALID_ARG), then the device (KH_ERR_NO_DEVICE),
+ * then the handle.  Before anything changes: an unknown id is KH_ERR_NOT_FOUND; a duplicate id, the gauge node (the first node:
+ * it cannot be handed on) and a node with more than 64 neighbours are KH_ERR_INVALID_ARG.  A node that only GROWS past 64
+ * neighbours through the nodes listed before it stops the call at its round with KH_ERR_INVALID_ARG; the earlier rounds stay. */
+typedef struct kh_marginalize_summary {
+  int32_t n_marginalized, n_plain;   /* nodes whose constraints were handed on / that had fewer than two neighbours */
+  int32_t n_rounds;
+  int32_t n_added, n_fused;          /* new constraints appended / fused into an existing one */
+  int32_t max_degree;
+  double pack_ms, kernel_ms, apply_ms, total_ms;   /* host: rounds + packing; upload + launch + download; edits of the graph */
+} kh_marginalize_summary;
+KH_API int kh_spa_marginalize_nodes(kh_spa * s, int32_t n, const int32_t * ids, kh_marginalize_summary * summary /* may be NULL */);
 /* GetCorrections (ceres_solver.cpp:272): pass ids=NULL to query the count */
 KH_API int kh_spa_get_corrections(kh_spa * s, int32_t * n, int32_t * ids, double * poses /* 3n */);
 /* ---- pose-graph files.  The reference persists a Boost binary archive of the whole
@@ -638,6 +662,8 @@ typedef struct kh_mapper_stats {
                                                    the device finished (kh_matcher_seq_stats of the sequential matcher) */
   int64_t decay_calls_resident, decay_calls_packed;   /* node-decay calls scored from the resident readings + filter masks / sent
                                                    down the packed form because a candidate had no device copy */
+  int64_t marginalize_fallbacks;                /* KH_REMOVE_MARGINALIZE: nodes node decay removed plainly because
+                                                   kh_spa_marginalize_nodes would have refused them */
 } kh_mapper_stats;
 /* config/mapper_params_offline.yaml:31-66 */
 KH_API void kh_mapper_params_default(kh_mapper_params * p);
@@ -701,6 +727,19 @@ KH_API int kh_mapper_set_node_score(kh_mapper * m, int32_t scan_id, double score
  * FindNearLinkedVertices within half the diagonal of the scan's bounding box, kh_lifelong_scores over them, removal of the
  * ones scoring below params->removal_score, the new score stored on the others.  params = NULL switches it off. */
 KH_API int kh_mapper_set_lifelong(kh_mapper * m, const kh_decay_params * params);
+/* kh_spa_marginalize_nodes on the mapper's solver, mirrored in the mapper: every listed scan leaves as in kh_mapper_remove_node
+ * (adjacency, edge sources, localization buffer, device copies), every NEW constraint becomes an edge whose source is the hub, a
+ * constraint fused into an existing one changes nothing in the topology.  The solver log gets the E / D lines of a removal and a
+ * C line for every added or replaced constraint (its covariance column holds the inverse of the information).  Error codes as
+ * kh_spa_marginalize_nodes; a removed or unknown scan is KH_ERR_NOT_FOUND. */
+KH_API int kh_mapper_marginalize_nodes(kh_mapper * m, int32_t n, const int32_t * scan_ids);
+/* How node decay (kh_mapper_set_lifelong) removes a scan.  KH_REMOVE_PLAIN (the default) is the reference's removal.  Under
+ * KH_REMOVE_MARGINALIZE the scans of one decay step that score below removal_score are marginalized as one list, in the order
+ * the step visits them; those the solver call would refuse (the gauge, more than 64 neighbours) are removed plainly and counted
+ * in kh_mapper_stats.marginalize_fallbacks.  The localization buffer's evictions and kh_mapper_remove_node are plain in every
+ * mode.  The mode is NOT part of a session file: a caller sets it again after kh_mapper_load. */
+enum { KH_REMOVE_PLAIN = 0, KH_REMOVE_MARGINALIZE = 1 };
+KH_API int kh_mapper_set_removal_mode(kh_mapper * m, int32_t mode);
 /* ids of the scans still in the graph, ascending (ids[kh_mapper_num_alive]) */
 KH_API int32_t kh_mapper_num_alive(const kh_mapper * m);
 KH_API int kh_mapper_get_alive(const kh_mapper * m, int32_t * ids);

@@ -480,6 +480,16 @@ public:
     return &m_Graph;
   }
 
+  // ---- beyond karto::ScanSolver: the listed nodes leave like RemoveNode, but their constraints are composed through them into
+  // constraints among their neighbours, so the graph stays connected (kh_spa_marginalize_nodes).  false: refused, the graph is
+  // untouched (unknown or duplicate id, the gauge node, more than 64 neighbours; see kh_last_error()).
+  bool MarginalizeNodes(const std::vector<kt_int32s> & ids)
+  {
+    std::lock_guard<std::mutex> lock(m_Mutex);
+    std::vector<int32_t> list(ids.begin(), ids.end());
+    return kh_spa_marginalize_nodes(m_pHandle, static_cast<int32_t>(list.size()), list.data(), nullptr) == KH_OK;
+  }
+
   // ---- beyond karto::ScanSolver (neither overrides a virtual of the reference): graph-aware covariances of the node poses,
   // Sigma = (J^T J)^-1 at the current poses (kh_spa_compute_covariances).  false: nothing is resident (see kh_last_error()).
   bool ComputeCovariances()

@@ -68,6 +68,14 @@ class KhSpaCovSummary(C.Structure):
                 ("gather_ms", C.c_double), ("total_ms", C.c_double), ("inverse_flops", C.c_int64)]
 
 
+class KhMarginalizeSummary(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_marginalized", "n_plain", "n_rounds", "n_added", "n_fused", "max_degree")] + \
+               [(k, C.c_double) for k in ("pack_ms", "kernel_ms", "apply_ms", "total_ms")]
+
+
+KH_REMOVE_PLAIN, KH_REMOVE_MARGINALIZE = 0, 1
+
+
 # every symbol include/karto_hip.h declares (tests check that the built library exports all of them)
 SYMBOLS = [
     "kh_last_error", "kh_device_count", "kh_version", "kh_scan_points", "kh_match_params_default",
@@ -112,6 +120,7 @@ SYMBOLS = [
     "kh_merge_fit", "kh_merge_fit_stats", "kh_merge_align_params_default", "kh_merge_align",
     "kh_spa_compute_covariances", "kh_spa_get_covariances", "kh_spa_get_joint_covariance", "kh_spa_covariance_device",
     "kh_mapper_get_covariances",
+    "kh_spa_marginalize_nodes", "kh_mapper_marginalize_nodes", "kh_mapper_set_removal_mode",
 ]
 
 
@@ -151,7 +160,7 @@ class KhMapperStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("scans_processed", "matches", "loop_candidates", "loop_closures", "speculation_discarded", "nodes_removed")] + \
                [(k, C.c_double) for k in ("process_ms", "match_ms", "solver_ms", "update_ms", "lifelong_ms")] + \
                [(k, C.c_int64) for k in ("fused_declined", "fused_declined_reason", "fused_matches", "fused_fine_passes",
-                                           "decay_calls_resident", "decay_calls_packed")]
+                                           "decay_calls_resident", "decay_calls_packed", "marginalize_fallbacks")]
 
 
 class KhSessionInfo(C.Structure):
@@ -315,6 +324,10 @@ def lib():
         L.kh_spa_get_covariances.argtypes = [vp, i32, vp, vp]
         L.kh_spa_get_joint_covariance.argtypes = [vp, i32, i32, vp]
         L.kh_spa_covariance_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
+    if hasattr(L, "kh_spa_marginalize_nodes"):
+        L.kh_spa_marginalize_nodes.argtypes = [vp, i32, vp, C.POINTER(KhMarginalizeSummary)]
+        L.kh_mapper_marginalize_nodes.argtypes = [vp, i32, vp]
+        L.kh_mapper_set_removal_mode.argtypes = [vp, i32]
     if hasattr(L, "kh_comm_create"):
         L.kh_comm_unique_id.argtypes = [bptr]
         L.kh_comm_create.argtypes = [i32, i32, i32, bptr, C.POINTER(vp)]

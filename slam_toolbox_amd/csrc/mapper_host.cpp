@@ -37,6 +37,7 @@
 
 #include "../../include/karto_hip.h"
 #include "mapper_internal.hpp"
+#include "marginalize.hpp"
 
 namespace kh
 {
@@ -49,6 +50,8 @@ void run_pending_query_hook();
 void spa_export_session_state(kh_spa * s, int64_t words[7], std::vector<int32_t> & sn_ptr, std::vector<int32_t> & sn_ids);
 void spa_import_session_state(kh_spa * s, const int64_t words[7], const std::vector<int32_t> & sn_ptr, const std::vector<int32_t> & sn_ids);
 bool spa_covariances_valid(const kh_spa * s);
+const std::vector<MargEdit> & spa_marginalize_edits(const kh_spa * s);       // spa_host.cpp (MargEdit: marginalize.hpp)
+bool spa_marginalize_refuses(const kh_spa * s, int32_t id);
 int graph_swap(kh_graph * g, int32_t n_scans, std::vector<double> & ref_xy, std::vector<int32_t> & adj_ptr, std::vector<int32_t> & adj_idx,
   std::vector<double> & pose_xy);   // graph.hip
 int graph_relocalize_candidates(kh_graph * g, double seed_spacing, double base_radius, int32_t max_base, const double * center_xy, double radius,
@@ -273,6 +276,7 @@ struct kh_mapper
   std::vector<std::vector<int32_t>> out_edges;           // targets of the edges whose SOURCE is the vertex (AddEdge's duplicate test)
   int64_t n_edges = 0;
   bool graph_dirty = true;
+  int32_t removal_mode = KH_REMOVE_PLAIN;                // kh_mapper_set_removal_mode (not part of a session file)
   FILE * log = nullptr;
   kh_mapper_stats stats;
   // device copies of the scans' readings: slots of 2 * laser.n doubles carved from slabs of 256 (one hipMalloc per 256
@@ -639,7 +643,8 @@ int try_close_loop(kh_mapper * m, int32_t scan_id, bool & closed)
 }
 
 // Mapper::RemoveNodeFromGraph (Mapper.cpp:2964-3021) + MapperSensorManager::RemoveScan (:208-218)
-int remove_node(kh_mapper * m, int32_t id)
+// in_solver = false: the solver has already let the node and its constraints go (kh_spa_marginalize_nodes); the log lines stay
+int remove_node(kh_mapper * m, int32_t id, bool in_solver = true)
 {
   ProfScope prof(m, 4);
   if (id < 0 || id >= static_cast<int32_t>(m->scans.size()) || !m->scans[id]) {
@@ -656,13 +661,13 @@ int remove_node(kh_mapper * m, int32_t id)
     auto out = std::find(m->out_edges[a].begin(), m->out_edges[a].end(), id);
     if (out != m->out_edges[a].end()) {source = a; target = id; m->out_edges[a].erase(out);}
     if (m->log) {std::fprintf(m->log, "E %d %d\n", source, target);}
-    const int rc = kh_spa_remove_constraint(m->solver, source, target);
+    const int rc = in_solver ? kh_spa_remove_constraint(m->solver, source, target) : KH_OK;
     if (rc != KH_OK && rc != KH_ERR_NOT_FOUND) {return rc;}
     --m->n_edges;
   }
   // 2) the vertex leaves the optimizer, 3) the graph and the scan map
   if (m->log) {std::fprintf(m->log, "D %d\n", id);}
-  const int rc = kh_spa_remove_node(m->solver, id);
+  const int rc = in_solver ? kh_spa_remove_node(m->solver, id) : KH_OK;
   if (rc != KH_OK && rc != KH_ERR_NOT_FOUND) {return rc;}
   m->adj[id].clear(); m->out_edges[id].clear();
   for (int q = 0; q < m->n_slots; ++q) {
@@ -675,6 +680,45 @@ int remove_node(kh_mapper * m, int32_t id)
   m->graph_dirty = true;
   m->stats.nodes_removed += 1;
   return KH_OK;
+}
+
+// kh_spa_marginalize_nodes on the mapper's solver, then the same edits in the mapper's own topology, in the order they were made
+int marginalize_nodes(kh_mapper * m, int32_t n, const int32_t * ids)
+{
+  for (int32_t k = 0; k < n; ++k) {
+    if (ids[k] < 0 || ids[k] >= static_cast<int32_t>(m->scans.size()) || !m->scans[ids[k]]) {
+      set_error("MarginalizeNodes: Failed to find node matching id");
+      return KH_ERR_NOT_FOUND;
+    }
+  }
+  const int rc = kh_spa_marginalize_nodes(m->solver, n, ids, nullptr);
+  // (a call that stopped at a later round has made the edits of the earlier ones: they are mirrored whatever it answered)
+  for (const MargEdit & e : spa_marginalize_edits(m->solver)) {
+    if (e.kind == 2) {
+      const int rr = remove_node(m, e.via, false);
+      if (rr) {return rr;}
+      continue;
+    }
+    if (m->log) {
+      // (a C line carries a covariance: the inverse of the information the constraint now has)
+      const double o[9] = {e.omega[0], e.omega[1], e.omega[2], e.omega[1], e.omega[3], e.omega[4], e.omega[2], e.omega[4], e.omega[5]};
+      const double c00 = o[4] * o[8] - o[5] * o[7], c01 = o[2] * o[7] - o[1] * o[8], c02 = o[1] * o[5] - o[2] * o[4];
+      const double c11 = o[0] * o[8] - o[2] * o[6], c12 = o[2] * o[3] - o[0] * o[5], c22 = o[0] * o[4] - o[1] * o[3];
+      const double r = 1.0 / (o[0] * c00 + o[1] * c01 + o[2] * c02);
+      const double cov[9] = {c00 * r, c01 * r, c02 * r, c01 * r, c11 * r, c12 * r, c02 * r, c12 * r, c22 * r};
+      std::fprintf(m->log, "C %d %d %.17g %.17g %.17g", e.a, e.b, e.z[0], e.z[1], e.z[2]);
+      for (int k = 0; k < 9; ++k) {std::fprintf(m->log, " %.17g", cov[k]);}
+      std::fprintf(m->log, "\n");
+    }
+    if (e.kind == 0) {                       // a new edge, the hub its source; a fused constraint changes nothing here
+      m->out_edges[e.a].push_back(e.b);
+      m->adj[e.a].push_back(e.b);
+      m->adj[e.b].push_back(e.a);
+      ++m->n_edges;
+      m->graph_dirty = true;
+    }
+  }
+  return rc;
 }
 
 kh_scan_box box_of(const kh_mapper * m, const MScan & s)
@@ -738,13 +782,27 @@ int lifelong_step(kh_mapper * m, int32_t id)
   }
   if (rc) {return rc;}
   (all_resident ? m->stats.decay_calls_resident : m->stats.decay_calls_packed) += 1;
+  std::vector<int32_t> leaving;                  // KH_REMOVE_MARGINALIZE: the step's removals as one list, in `near` order
   for (size_t k = 0; k < near.size(); ++k) {
     if (!kept[k]) {continue;}
     if (scores[k] < m->decay.removal_score) {
+      if (m->removal_mode == KH_REMOVE_MARGINALIZE && !spa_marginalize_refuses(m->solver, near[k])) {leaving.push_back(near[k]); continue;}
+      if (m->removal_mode == KH_REMOVE_MARGINALIZE) {m->stats.marginalize_fallbacks += 1;}
       rc = remove_node(m, near[k]);
       if (rc) {return rc;}
     } else {
       m->scans[near[k]]->score = scores[k];
+    }
+  }
+  if (!leaving.empty()) {
+    rc = marginalize_nodes(m, static_cast<int32_t>(leaving.size()), leaving.data());
+    if (rc != KH_OK && rc != KH_ERR_INVALID_ARG) {return rc;}
+    // (a node that grew past 64 neighbours through the ones before it stopped the call: it and the rest leave plainly)
+    for (int32_t id : leaving) {
+      if (!m->scans[id]) {continue;}
+      m->stats.marginalize_fallbacks += 1;
+      rc = remove_node(m, id);
+      if (rc) {return rc;}
     }
   }
   m->stats.lifelong_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1226,6 +1284,27 @@ int kh_mapper_remove_node(kh_mapper * m, int32_t scan_id)
     return KH_ERR_INVALID_ARG;
   }
   return kh::remove_node(m, scan_id);
+}
+
+int kh_mapper_marginalize_nodes(kh_mapper * m, int32_t n, const int32_t * scan_ids)
+{
+  if (n < 0 || (n > 0 && !scan_ids)) {return KH_ERR_INVALID_ARG;}
+  if (kh::require_device(0) != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!m) {return KH_ERR_INVALID_ARG;}
+  for (int32_t k = 0; k < n; ++k) {                     // as kh_mapper_remove_node: the next Process() reads these scans
+    if (scan_ids[k] == m->last || std::find(m->running.begin(), m->running.end(), scan_ids[k]) != m->running.end()) {
+      kh::set_error("MarginalizeNodes: a scan is the last scan or in the running-scan window");
+      return KH_ERR_INVALID_ARG;
+    }
+  }
+  return kh::marginalize_nodes(m, n, scan_ids);
+}
+
+int kh_mapper_set_removal_mode(kh_mapper * m, int32_t mode)
+{
+  if (!m || (mode != KH_REMOVE_PLAIN && mode != KH_REMOVE_MARGINALIZE)) {return KH_ERR_INVALID_ARG;}
+  m->removal_mode = mode;
+  return KH_OK;
 }
 
 int kh_mapper_set_lifelong(kh_mapper * m, const kh_decay_params * params)

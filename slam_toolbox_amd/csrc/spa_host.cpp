@@ -31,10 +31,12 @@
 #include <string>
 #include <thread>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/karto_hip.h"
 #include "host_wait.hpp"
+#include "marginalize.hpp"
 #include "spa_internal.hpp"
 #include "spa_symbolic.hpp"
 
@@ -185,6 +187,10 @@ struct kh_spa
   std::vector<double> h_cov;
   std::vector<int32_t> h_cov_row_ptr, h_cov_col, h_cov_diag;
   hipEvent_t ev_cov[3] = {};
+  // marginalizing removal (kh_spa_marginalize_nodes): a round's upload and download, and what the last call did to the graph
+  // (the mapper mirrors it: spa_marginalize_edits)
+  DevBuf<char> d_marg_in, d_marg_out;
+  std::vector<MargEdit> marg_edits;
 };
 
 // drops the tombstones; positions in `nodes` / `cons` and both maps are final again afterwards.  Every entry point that
@@ -784,7 +790,7 @@ void kh_spa_destroy(kh_spa * s)
   s->d_edge_lin.release(); s->d_edge_cost.release(); s->d_Hg.release(); s->d_fronts.release(); s->d_fronts_b.release(); s->d_deferred.release(); s->d_pack.release();
   s->d_x.release(); s->d_cand.release(); s->d_scale.release(); s->d_diag.release(); s->d_rhs.release();
   s->d_step.release(); s->d_delta.release(); s->d_scal.release(); s->d_upd.release(); s->d_fsb.release(); s->d_partial.release(); s->d_Hg_alt.release(); s->d_best.release();
-  s->d_zbuf.release(); s->d_cov.release();
+  s->d_zbuf.release(); s->d_cov.release(); s->d_marg_in.release(); s->d_marg_out.release();
   for (auto & row : s->ev_phase) {for (auto & e : row) {if (e) {(void)hipEventDestroy(e);}}}
   for (auto & row : s->ev_lin) {for (auto & e : row) {if (e) {(void)hipEventDestroy(e);}}}
   for (auto & e : s->ev_cov) {if (e) {(void)hipEventDestroy(e);}}
@@ -1140,11 +1146,22 @@ int kh_spa_load(kh_spa * s, const char * path)
   return KH_OK;
 }
 
+static void remove_found_node(kh_spa * s, std::unordered_map<int32_t, int32_t>::iterator it);
+
 int kh_spa_remove_node(kh_spa * s, int32_t id)     // ceres_solver.cpp:395-427 (RemoveParameterBlock drops its residuals)
 {
   if (!s) {return KH_ERR_INVALID_ARG;}
   auto it = s->index_of.find(id);
   if (it == s->index_of.end()) {set_error("RemoveNode: Failed to find node matching id"); return KH_ERR_NOT_FOUND;}
+  remove_found_node(s, it);
+  return KH_OK;
+}
+
+}  // extern "C"
+
+static void remove_found_node(kh_spa * s, std::unordered_map<int32_t, int32_t>::iterator it)
+{
+  const int32_t id = it->first;
   s->cov_valid = false;
   auto inc = s->incident.find(id);                     // O(degree): the node's own constraint list
   if (inc != s->incident.end()) {
@@ -1160,8 +1177,9 @@ int kh_spa_remove_node(kh_spa * s, int32_t id)     // ceres_solver.cpp:395-427 (
   if (s->has_first && id == s->first_id) {s->has_first = false;}
   s->index_of.erase(it);
   s->topology_dirty = true;
-  return KH_OK;
 }
+
+extern "C" {
 
 int kh_spa_remove_constraint(kh_spa * s, int32_t id_a, int32_t id_b)    // ceres_solver.cpp:430-448
 {
@@ -1902,6 +1920,256 @@ int kh_spa_covariance_device(kh_spa * s, const double ** cov_bsr, int64_t * n_sl
 }
 
 }  // extern "C"
+
+// ---- marginalizing node removal: the constraints of a leaving node composed through it, a round of nodes per launch ------------
+namespace
+{
+// the live constraints of node v, grouped by neighbour in the order of v's first constraint to each: nb[i] and, flat,
+// ks[kp[i] .. kp[i + 1]).  Returns the number of neighbours, or cap + 1 as soon as there are more than cap.
+int32_t neighbour_entries(const kh_spa * s, int32_t v, int32_t cap, std::vector<int32_t> & nb, std::vector<int32_t> & kp, std::vector<int32_t> & ks)
+{
+  nb.clear(); kp.assign(1, 0); ks.clear();
+  auto inc = s->incident.find(v);
+  if (inc == s->incident.end()) {return 0;}
+  // (two passes over a short list: the neighbours first, then each one's constraints, so that ks comes out grouped)
+  for (int32_t k : inc->second) {
+    const Constraint & c = s->cons[k];
+    if (c.dead) {continue;}
+    const int32_t o = c.a == v ? c.b : c.a;
+    if (std::find(nb.begin(), nb.end(), o) == nb.end()) {
+      if (static_cast<int32_t>(nb.size()) == cap) {return cap + 1;}
+      nb.push_back(o);
+    }
+  }
+  for (int32_t o : nb) {
+    for (int32_t k : inc->second) {
+      const Constraint & c = s->cons[k];
+      if (!c.dead && (c.a == v ? c.b : c.a) == o) {ks.push_back(k);}
+    }
+    kp.push_back(static_cast<int32_t>(ks.size()));
+  }
+  return static_cast<int32_t>(nb.size());
+}
+}  // namespace
+
+extern "C" int kh_spa_marginalize_nodes(kh_spa * s, int32_t n, const int32_t * ids, kh_marginalize_summary * summary)
+{
+  if (s) {s->marg_edits.clear();}                        // (whatever the call answers, the edits on record are its own)
+  if (n < 0 || (n > 0 && !ids)) {return KH_ERR_INVALID_ARG;}
+  if (covariance_device_check() != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!s) {return KH_ERR_INVALID_ARG;}
+  kh_marginalize_summary sum;
+  std::memset(&sum, 0, sizeof(sum));
+  const auto t_begin = std::chrono::steady_clock::now();
+  auto ms_since = [](std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+  };
+  auto finish = [&](int rc) {sum.total_ms = ms_since(t_begin); if (summary) {*summary = sum;} return rc;};
+  std::vector<int32_t> nb, kp, ks;
+  {
+    // everything that can be refused is refused on the graph as it stands, before the first edit
+    std::unordered_set<int32_t> seen;
+    for (int32_t i = 0; i < n; ++i) {
+      const int32_t id = ids[i];
+      if (!s->index_of.count(id)) {set_error("kh_spa_marginalize_nodes: no node " + std::to_string(id)); return finish(KH_ERR_NOT_FOUND);}
+      if (!seen.insert(id).second) {set_error("kh_spa_marginalize_nodes: node " + std::to_string(id) + " is listed twice"); return finish(KH_ERR_INVALID_ARG);}
+      if (s->has_first && id == s->first_id) {
+        set_error("kh_spa_marginalize_nodes: node " + std::to_string(id) + " is the gauge node, which cannot be handed on");
+        return finish(KH_ERR_INVALID_ARG);
+      }
+      if (neighbour_entries(s, id, kMargMaxDegree, nb, kp, ks) > kMargMaxDegree) {
+        set_error("kh_spa_marginalize_nodes: node " + std::to_string(id) + " has more than 64 neighbours");
+        return finish(KH_ERR_INVALID_ARG);
+      }
+    }
+  }
+  KS_HIP(hipSetDevice(s->device));
+  hipStream_t st = s->stream;
+  std::vector<int32_t> pending(ids, ids + n), waiting;
+  // a round, packed: per member (list order) its id and, for those that go to the device, their number there (-1: plain removal)
+  std::vector<int32_t> member, member_dev;
+  std::vector<int32_t> ent_ptr, ent_id, con_ptr, con_dir, pair_ptr, pair_ent, pair_con, out_ptr, ints;
+  std::vector<double> dbl;
+  std::vector<char> blob, result;
+  std::unordered_set<int32_t> blocked;
+  auto put9 = [&](const Constraint & c) {
+    dbl.insert(dbl.end(), c.z, c.z + 3);
+    dbl.insert(dbl.end(), c.omega, c.omega + 6);
+  };
+  while (!pending.empty()) {
+    const auto t_pack = std::chrono::steady_clock::now();
+    ++sum.n_rounds;
+    member.clear(); member_dev.clear(); waiting.clear(); blocked.clear();
+    ent_ptr.assign(1, 0); ent_id.clear(); con_ptr.assign(1, 0); con_dir.clear(); pair_ptr.assign(1, 0); pair_ent.clear(); pair_con.clear();
+    out_ptr.assign(1, 0); dbl.clear();
+    std::vector<double> pair_dbl;
+    for (int32_t v : pending) {
+      const int32_t d = neighbour_entries(s, v, kMargMaxDegree, nb, kp, ks);
+      if (d > kMargMaxDegree) {
+        set_error("kh_spa_marginalize_nodes: node " + std::to_string(v) + " has grown past 64 neighbours through the nodes listed before it");
+        return finish(KH_ERR_INVALID_ARG);
+      }
+      // the node waits when its closed neighbourhood meets that of an earlier node of this pass, in the round or waiting itself
+      bool meets = blocked.count(v) != 0;
+      for (int32_t o : nb) {meets = meets || blocked.count(o) != 0;}
+      blocked.insert(v);
+      blocked.insert(nb.begin(), nb.end());
+      if (meets) {waiting.push_back(v); continue;}
+      sum.max_degree = std::max(sum.max_degree, d);
+      member.push_back(v);
+      if (d < 2) {member_dev.push_back(-1); continue;}
+      member_dev.push_back(static_cast<int32_t>(ent_ptr.size()) - 1);
+      for (int32_t i = 0; i < d; ++i) {
+        ent_id.push_back(nb[i]);
+        for (int32_t q = kp[i]; q < kp[i + 1]; ++q) {
+          const Constraint & c = s->cons[ks[q]];
+          con_dir.push_back(c.a == v ? 0 : 1);
+          put9(c);
+        }
+        con_ptr.push_back(static_cast<int32_t>(con_dir.size()));
+      }
+      // the first existing constraint of every pair of neighbours (the host knows the topology, not the hub)
+      const size_t pair_begin = pair_ent.size();
+      for (int32_t i = 0; i < d; ++i) {
+        auto inc = s->incident.find(nb[i]);
+        if (inc == s->incident.end()) {continue;}
+        for (int32_t k : inc->second) {
+          const Constraint & c = s->cons[k];
+          if (c.dead) {continue;}
+          const int32_t o = c.a == nb[i] ? c.b : c.a;
+          if (o == v) {continue;}
+          const int32_t j = static_cast<int32_t>(std::find(nb.begin(), nb.end(), o) - nb.begin());
+          if (j >= d || j <= i) {continue;}
+          const int32_t key = i | (j << 8);
+          bool known = false;
+          for (size_t p = pair_begin; p < pair_ent.size(); ++p) {known = known || (pair_ent[p] & 0xffff) == key;}
+          if (known) {continue;}
+          pair_ent.push_back(key | ((c.a == nb[i] ? 0 : 1) << 16));
+          pair_con.push_back(k);
+          pair_dbl.insert(pair_dbl.end(), c.z, c.z + 3);
+          pair_dbl.insert(pair_dbl.end(), c.omega, c.omega + 6);
+        }
+      }
+      ent_ptr.push_back(static_cast<int32_t>(ent_id.size()));
+      pair_ptr.push_back(static_cast<int32_t>(pair_ent.size()));
+      out_ptr.push_back(out_ptr.back() + d - 1);
+    }
+    const int32_t n_dev = static_cast<int32_t>(ent_ptr.size()) - 1;
+    const int32_t n_out = out_ptr.back();
+    const size_t n_con = con_dir.size(), n_pair = pair_ent.size(), n_ent = ent_id.size();
+    if (n_dev > 0) {
+      // one upload: the doubles (incident constraints, then pairs), then the index arrays
+      dbl.insert(dbl.end(), pair_dbl.begin(), pair_dbl.end());
+      ints.clear();
+      const size_t o_ent_ptr = 0, o_out_ptr = o_ent_ptr + n_dev + 1, o_pair_ptr = o_out_ptr + n_dev + 1, o_ent_id = o_pair_ptr + n_dev + 1,
+        o_con_ptr = o_ent_id + n_ent, o_con_dir = o_con_ptr + n_ent + 1, o_pair_ent = o_con_dir + n_con;
+      ints.insert(ints.end(), ent_ptr.begin(), ent_ptr.end());
+      ints.insert(ints.end(), out_ptr.begin(), out_ptr.end());
+      ints.insert(ints.end(), pair_ptr.begin(), pair_ptr.end());
+      ints.insert(ints.end(), ent_id.begin(), ent_id.end());
+      ints.insert(ints.end(), con_ptr.begin(), con_ptr.end());
+      ints.insert(ints.end(), con_dir.begin(), con_dir.end());
+      ints.insert(ints.end(), pair_ent.begin(), pair_ent.end());
+      const size_t dbl_bytes = dbl.size() * sizeof(double), int_bytes = ints.size() * sizeof(int32_t);
+      blob.resize(dbl_bytes + int_bytes);
+      std::memcpy(blob.data(), dbl.data(), dbl_bytes);
+      std::memcpy(blob.data() + dbl_bytes, ints.data(), int_bytes);
+      const size_t out_dbl_bytes = static_cast<size_t>(n_out) * 9 * sizeof(double), out_bytes = out_dbl_bytes + static_cast<size_t>(n_out) * 2 * sizeof(int32_t);
+      sum.pack_ms += ms_since(t_pack);
+      const auto t_kernel = std::chrono::steady_clock::now();
+      int rc = s->d_marg_in.ensure(blob.size());
+      if (rc) {return finish(rc);}
+      rc = s->d_marg_out.ensure(out_bytes);
+      if (rc) {return finish(rc);}
+      KS_HIP(hipMemcpyAsync(s->d_marg_in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+      const double * dd = reinterpret_cast<const double *>(s->d_marg_in.p);
+      const int32_t * di = reinterpret_cast<const int32_t *>(s->d_marg_in.p + dbl_bytes);
+      MargDev g;
+      g.n_nodes = n_dev;
+      g.ent_ptr = di + o_ent_ptr; g.out_ptr = di + o_out_ptr; g.pair_ptr = di + o_pair_ptr; g.ent_id = di + o_ent_id;
+      g.con_ptr = di + o_con_ptr; g.con_dir = di + o_con_dir; g.pair_ent = di + o_pair_ent;
+      g.con_d = dd; g.pair_d = dd + 9 * n_con;
+      g.out_d = reinterpret_cast<double *>(s->d_marg_out.p);
+      g.out_i = reinterpret_cast<int32_t *>(s->d_marg_out.p + out_dbl_bytes);
+      marginalize_launch_round(g, st);
+      KS_HIP(hipGetLastError());
+      result.resize(out_bytes);
+      KS_HIP(hipMemcpyAsync(result.data(), s->d_marg_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+      KS_HIP(hipStreamSynchronize(st));
+      sum.kernel_ms += ms_since(t_kernel);
+    } else {
+      sum.pack_ms += ms_since(t_pack);
+    }
+    const auto t_apply = std::chrono::steady_clock::now();
+    const double * out_d = reinterpret_cast<const double *>(result.data());
+    const int32_t * out_i = reinterpret_cast<const int32_t *>(result.data() + static_cast<size_t>(n_out) * 9 * sizeof(double));
+    // nothing of the round is applied unless all of it can be: every result finite, every information positive definite
+    for (int32_t q = 0; q < (n_dev > 0 ? n_out : 0); ++q) {
+      double u[9];
+      sqrt_information(out_d + 9 * q + 3, u);
+      bool ok = u[0] > 0.0 && u[4] > 0.0 && u[8] > 0.0;
+      for (int k = 0; k < 3; ++k) {ok = ok && std::isfinite(out_d[9 * q + k]);}
+      if (!ok) {
+        set_error("kh_spa_marginalize_nodes: a composed constraint is not finite or its information is not positive definite");
+        return finish(KH_ERR_SOLVER);
+      }
+    }
+    for (size_t w = 0; w < member.size(); ++w) {
+      const int32_t v = member[w], dev = member_dev[w];
+      MargEdit ed;
+      std::memset(&ed, 0, sizeof(ed));
+      ed.via = v;
+      if (dev >= 0) {
+        const int32_t d = ent_ptr[dev + 1] - ent_ptr[dev];
+        for (int32_t r = 0; r < d - 1; ++r) {
+          const int32_t q = out_ptr[dev] + r;
+          const int32_t h = out_i[2 * q], p = out_i[2 * q + 1];
+          if (h < 0 || h >= d || p < -1 || p >= static_cast<int32_t>(n_pair)) {set_error("kh_spa_marginalize_nodes: the device returned an index out of range"); return finish(KH_ERR_SOLVER);}
+          const int32_t i = r < h ? r : r + 1;
+          const double * z = out_d + 9 * q; const double * omega = z + 3;
+          std::copy(z, z + 3, ed.z); std::copy(omega, omega + 6, ed.omega);
+          if (p >= 0) {
+            Constraint & c = s->cons[pair_con[p]];
+            std::copy(z, z + 3, c.z); std::copy(omega, omega + 6, c.omega);
+            sqrt_information(c.omega, c.u);
+            ed.kind = 1; ed.a = c.a; ed.b = c.b;
+            ++sum.n_fused;
+          } else {
+            ed.kind = 0; ed.a = ent_id[ent_ptr[dev] + h]; ed.b = ent_id[ent_ptr[dev] + i];
+            const int rc = add_constraint_information(s, ed.a, ed.b, z, omega);
+            if (rc) {return finish(rc);}
+            ++sum.n_added;
+          }
+          s->marg_edits.push_back(ed);
+        }
+        ++sum.n_marginalized;
+      } else {
+        ++sum.n_plain;
+      }
+      ed.kind = 2; ed.a = ed.b = v;
+      s->marg_edits.push_back(ed);
+      remove_found_node(s, s->index_of.find(v));
+    }
+    s->cov_valid = false;
+    s->topology_dirty = true;
+    sum.apply_ms += ms_since(t_apply);
+    pending.swap(waiting);
+  }
+  return finish(KH_OK);
+}
+
+namespace kh
+{
+// what the last kh_spa_marginalize_nodes did, edit by edit (the mapper mirrors it in its own topology)
+const std::vector<MargEdit> & spa_marginalize_edits(const kh_spa * s) {return s->marg_edits;}
+// whether kh_spa_marginalize_nodes would refuse the node on the graph as it stands (unknown, the gauge, more than 64 neighbours)
+bool spa_marginalize_refuses(const kh_spa * s, int32_t id)
+{
+  if (!s->index_of.count(id) || (s->has_first && id == s->first_id)) {return true;}
+  std::vector<int32_t> nb, kp, ks;
+  return neighbour_entries(s, id, kMargMaxDegree, nb, kp, ks) > kMargMaxDegree;
+}
+}  // namespace kh
 
 namespace kh
 {

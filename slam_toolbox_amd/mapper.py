@@ -236,6 +236,18 @@ class Mapper:
         """Mapper::RemoveNodeFromGraph + MapperSensorManager::RemoveScan (what lifelong mode does to a decayed node)"""
         capi.check(capi.lib().kh_mapper_remove_node(self._h, int(scan_id)), "kh_mapper_remove_node")
 
+    def MarginalizeNodes(self, scan_ids):
+        """kh_mapper_marginalize_nodes: the scans leave like RemoveNode, but their constraints are handed on to their neighbours
+        (HipSpaSolver.MarginalizeNodes on the mapper's solver, mirrored in the mapper's edges)"""
+        idv = np.ascontiguousarray(scan_ids, dtype=np.int32).reshape(-1)
+        capi.check(capi.lib().kh_mapper_marginalize_nodes(self._h, idv.size, idv.ctypes.data_as(C.c_void_p)), "kh_mapper_marginalize_nodes")
+
+    def SetRemovalMode(self, marginalize: bool):
+        """how node decay removes a scan: False the reference's plain removal (default), True marginalizing removal.  Not stored
+        in a session: set it again after load."""
+        mode = capi.KH_REMOVE_MARGINALIZE if marginalize else capi.KH_REMOVE_PLAIN
+        capi.check(capi.lib().kh_mapper_set_removal_mode(self._h, mode), "kh_mapper_set_removal_mode")
+
     def SetLifelong(self, enabled: bool = True, **decay):
         """LifelongSlamToolbox::evaluateNodeDepreciation after every accepted scan; decay = kh_decay_params overrides"""
         if not enabled:

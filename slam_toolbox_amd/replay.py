@@ -49,12 +49,14 @@ class LapQueue:
 
 def run(n_scans: int, lifelong: bool = True, mode: str = "sync", period_s: float = 0.025, device: int = 0,
         max_candidates: int = 32, map_resolution: float = 0.05, progress=None, devices=None, queue=None, save_session=None,
-        save_at=None, load_session=None, **mapper_params):
+        save_at=None, load_session=None, marginalize: bool = False, **mapper_params):
     """Replays the queue; returns a dict with the throughput, the mapper's own statistics and the map agreement.
     save_session: the mapper is saved there (Mapper.save) behind queue scan `save_at` (default: the last one), with the replay's
     own bookkeeping -- how far the queue got, which queue scan every scan id came from -- beside it in <path>.replay.json;
     load_session: the run starts from such a pair instead of an empty mapper and continues with the rest of the SAME queue
-    (same n_scans; the session carries its own parameters and lifelong switch)."""
+    (same n_scans; the session carries its own parameters and lifelong switch).
+    marginalize: node decay hands a leaving scan's constraints on to its neighbours (Mapper.SetRemovalMode; not part of a session,
+    so it is set again on a loaded mapper)."""
     import json
     from .mapper import Mapper
     from .occupancy_grid import OccupancyGrid
@@ -71,6 +73,8 @@ def run(n_scans: int, lifelong: bool = True, mode: str = "sync", period_s: float
         m = Mapper(q.laser, device=device, max_candidates=max_candidates, devices=devices, **mapper_params)
         if lifelong:
             m.SetLifelong(True)
+    if marginalize:
+        m.SetRemovalMode(True)
     # the queue is made up front so that the timed region holds the mapper, not the ray casting
     all_ranges = [q.ranges(i) for i in range(n_scans)]
     t0 = time.perf_counter()

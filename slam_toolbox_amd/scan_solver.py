@@ -119,6 +119,19 @@ class HipSpaSolver:
         capi.check(rc, "kh_spa_compute")
         return self.summary
 
+    # ---- marginalizing removal (no counterpart in the reference) -------------------------------------------------
+    def MarginalizeNodes(self, ids):
+        """kh_spa_marginalize_nodes: the listed nodes leave, their constraints composed through them into constraints among
+        their neighbours (one launch per round of nodes with disjoint closed neighbourhoods).  Returns the summary dict, also
+        kept as `marginalize_summary`; refusals (unknown, duplicate, gauge, more than 64 neighbours) raise KartoHipError with
+        the graph untouched."""
+        idv = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        s = capi.KhMarginalizeSummary()
+        rc = capi.lib().kh_spa_marginalize_nodes(self._h, idv.size, idv.ctypes.data_as(C.c_void_p), C.byref(s))
+        self.marginalize_summary = {k: getattr(s, k) for k, _ in capi.KhMarginalizeSummary._fields_}
+        capi.check(rc, "kh_spa_marginalize_nodes")
+        return self.marginalize_summary
+
     # ---- covariances (no counterpart in the reference) ---------------------------------------------------------
     def ComputeCovariances(self):
         """kh_spa_compute_covariances: Sigma = (J^T J)^-1 at the current poses, every block on the pattern of H, resident on the
