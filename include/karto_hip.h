@@ -373,6 +373,37 @@ KH_API int kh_spa_get_joint_covariance(kh_spa * s, int32_t id_a, int32_t id_b, d
 /* the resident array for device consumers: n_slots blocks of 9 doubles (row-major), block-sparse rows over the free nodes on the
  * pattern of H; owned by the solver, valid like the getters' answers */
 KH_API int kh_spa_covariance_device(kh_spa * s, const double ** cov_bsr, int64_t * n_slots);
+/* ---- covariance columns: the cross-covariance of ANY two nodes, joined by a constraint or not (a loop-closure candidate, a pose
+ * against the dock or the first scan).  kh_spa_compute_covariance_columns is kh_spa_compute_covariances -- the same pass, the same
+ * marginals, the same refusals -- and, while the factor is still in the fronts, solves A X = E_q for the listed query nodes through
+ * it (a forward sweep up the assembly tree over the fronts between a query and the root, a backward sweep over all of them): the
+ * block column Sigma(:, q) of every query, every row at once, resident on the device as n_queries x n_free blocks of 9 doubles and
+ * valid exactly as long as the marginals are.  At most KH_SPA_MAX_COV_COLUMNS queries per call; the gauge node is a legal query
+ * (its column is zeros).  n < 1, n > KH_SPA_MAX_COV_COLUMNS, ids = NULL or an id listed twice: KH_ERR_INVALID_ARG, before a device
+ * is looked for (then KH_ERR_NO_DEVICE, then the handle); an unknown id or a node without constraints: KH_ERR_NOT_FOUND.  A call
+ * replaces the columns of the call before it; kh_spa_compute_covariances leaves none. */
+#define KH_SPA_MAX_COV_COLUMNS 64
+typedef struct kh_spa_cov_columns_summary {
+  kh_spa_cov_summary cov;           /* the pass the columns rode on */
+  int32_t n_queries;
+  int32_t path_fronts;              /* fronts the forward sweep visited: the union of the paths from a query's front to its root */
+  double forward_ms, backward_ms;   /* GPU time of the two sweeps, from HIP events under kh_spa_set_debug bit 1, else 0 */
+  double total_ms;
+  int64_t column_flops;             /* flops of the two sweeps over the padded right-hand sides */
+} kh_spa_cov_columns_summary;
+KH_API int kh_spa_compute_covariance_columns(kh_spa * s, int32_t n, const int32_t * ids, kh_spa_cov_columns_summary * summary /* may be NULL */);
+/* out[9 k ..]: row-major 3 x 3 Sigma(ids[k], id_q); ids = NULL: all nodes in insertion order (n = kh_spa_num_nodes).  The gauge
+ * node as a row or as the query: zeros.  id_q not among the queries of the last column pass: KH_ERR_NOT_FOUND; stale: KH_ERR_SOLVER. */
+KH_API int kh_spa_get_covariance_column(kh_spa * s, int32_t id_q, int32_t n, const int32_t * ids, double * out /* 9n */);
+/* kh_spa_get_joint_covariance for a pair with or without a constraint: one of the two must be a query of the last column pass
+ * (id_b's column is used when both are).  The diagonal blocks are the marginals of kh_spa_get_covariances, the cross block comes
+ * from the column and its transpose fills the other corner: the 6 x 6 is bit-wise symmetric. */
+KH_API int kh_spa_get_joint_covariance_any(kh_spa * s, int32_t id_a, int32_t id_b, double cov[36]);
+/* out[9 k ..]: first-order covariance of node ids[k]'s pose expressed in the frame of id_ref (a query of the last column pass),
+ * d = R(-theta_ref) (t_k - t_ref), theta_k - theta_ref at the solver's current poses: J [[S_rr S_rk], [S_kr S_kk]] J^T with
+ * J = [dd/dref dd/dk], one thread per listed node (k_cov_relative).  ids = NULL: all nodes in insertion order.  ids[k] = id_ref:
+ * exact zeros. */
+KH_API int kh_spa_get_relative_covariances(kh_spa * s, int32_t id_ref, int32_t n, const int32_t * ids, double * out /* 9n */);
 /* ---- marginalizing node removal (no counterpart in the reference, whose RemoveNode drops the node's constraints and transfers
  * nothing: a lifelong graph falls apart).  Every listed node leaves like kh_spa_remove_node, but first its constraints are composed
  * through it into constraints among its neighbours: parallel constraints to one neighbour are fused; the
@@ -750,6 +781,11 @@ KH_API kh_spa * kh_mapper_solver(kh_mapper * m);
  * resident result otherwise.  scan_ids = NULL: all solver nodes in insertion order (n = kh_spa_num_nodes of the solver).
  * summary (may be NULL): the computation this call ran, all zeros when it ran none. */
 KH_API int kh_mapper_get_covariances(kh_mapper * m, int32_t n, const int32_t * scan_ids, double * cov /* 9n */, kh_spa_cov_summary * summary);
+/* kh_spa_get_relative_covariances of the mapper's solver, lazy in the same way: the column of ref_scan is computed
+ * (kh_spa_compute_covariance_columns with that one query) only when it is not resident or is stale.  summary (may be NULL): the
+ * computation this call ran, all zeros when it ran none. */
+KH_API int kh_mapper_get_relative_covariances(kh_mapper * m, int32_t ref_scan, int32_t n, const int32_t * scan_ids, double * out /* 9n */,
+                                              kh_spa_cov_columns_summary * summary);
 /* every solver call the mapper makes, one line each, in the format oracle/ref_slam_driver.cpp logs the reference
  * Mapper's calls with (N id pose, C a b z cov, X n ms, P id pose, K): the two logs of one scan queue must agree */
 KH_API int kh_mapper_set_log(kh_mapper * m, const char * path);

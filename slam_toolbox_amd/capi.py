@@ -68,6 +68,14 @@ class KhSpaCovSummary(C.Structure):
                 ("gather_ms", C.c_double), ("total_ms", C.c_double), ("inverse_flops", C.c_int64)]
 
 
+class KhSpaCovColumnsSummary(C.Structure):
+    _fields_ = [("cov", KhSpaCovSummary), ("n_queries", C.c_int32), ("path_fronts", C.c_int32),
+                ("forward_ms", C.c_double), ("backward_ms", C.c_double), ("total_ms", C.c_double), ("column_flops", C.c_int64)]
+
+
+KH_SPA_MAX_COV_COLUMNS = 64
+
+
 class KhMarginalizeSummary(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("n_marginalized", "n_plain", "n_rounds", "n_added", "n_fused", "max_degree")] + \
                [(k, C.c_double) for k in ("pack_ms", "kernel_ms", "apply_ms", "total_ms")]
@@ -120,6 +128,8 @@ SYMBOLS = [
     "kh_merge_fit", "kh_merge_fit_stats", "kh_merge_align_params_default", "kh_merge_align",
     "kh_spa_compute_covariances", "kh_spa_get_covariances", "kh_spa_get_joint_covariance", "kh_spa_covariance_device",
     "kh_mapper_get_covariances",
+    "kh_spa_compute_covariance_columns", "kh_spa_get_covariance_column", "kh_spa_get_joint_covariance_any", "kh_spa_get_relative_covariances",
+    "kh_mapper_get_relative_covariances",
     "kh_spa_marginalize_nodes", "kh_mapper_marginalize_nodes", "kh_mapper_set_removal_mode",
 ]
 
@@ -324,6 +334,11 @@ def lib():
         L.kh_spa_get_covariances.argtypes = [vp, i32, vp, vp]
         L.kh_spa_get_joint_covariance.argtypes = [vp, i32, i32, vp]
         L.kh_spa_covariance_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
+    if hasattr(L, "kh_spa_compute_covariance_columns"):
+        L.kh_spa_compute_covariance_columns.argtypes = [vp, i32, vp, C.POINTER(KhSpaCovColumnsSummary)]
+        L.kh_spa_get_covariance_column.argtypes = [vp, i32, i32, vp, vp]
+        L.kh_spa_get_joint_covariance_any.argtypes = [vp, i32, i32, vp]
+        L.kh_spa_get_relative_covariances.argtypes = [vp, i32, i32, vp, vp]
     if hasattr(L, "kh_spa_marginalize_nodes"):
         L.kh_spa_marginalize_nodes.argtypes = [vp, i32, vp, C.POINTER(KhMarginalizeSummary)]
         L.kh_mapper_marginalize_nodes.argtypes = [vp, i32, vp]
@@ -379,6 +394,8 @@ def lib():
         L.kh_mapper_solver.argtypes = [vp]
         L.kh_mapper_solver.restype = vp
         L.kh_mapper_get_covariances.argtypes = [vp, i32, vp, vp, C.POINTER(KhSpaCovSummary)]
+        if hasattr(L, "kh_mapper_get_relative_covariances"):
+            L.kh_mapper_get_relative_covariances.argtypes = [vp, i32, i32, vp, vp, C.POINTER(KhSpaCovColumnsSummary)]
         L.kh_mapper_set_log.argtypes = [vp, C.c_char_p]
         L.kh_mapper_remove_node.argtypes = [vp, i32]
         L.kh_mapper_set_lifelong.argtypes = [vp, C.POINTER(KhDecayParams)]

@@ -50,6 +50,7 @@ void run_pending_query_hook();
 void spa_export_session_state(kh_spa * s, int64_t words[7], std::vector<int32_t> & sn_ptr, std::vector<int32_t> & sn_ids);
 void spa_import_session_state(kh_spa * s, const int64_t words[7], const std::vector<int32_t> & sn_ptr, const std::vector<int32_t> & sn_ids);
 bool spa_covariances_valid(const kh_spa * s);
+bool spa_covariance_column_resident(const kh_spa * s, int32_t id);
 const std::vector<MargEdit> & spa_marginalize_edits(const kh_spa * s);       // spa_host.cpp (MargEdit: marginalize.hpp)
 bool spa_marginalize_refuses(const kh_spa * s, int32_t id);
 int graph_swap(kh_graph * g, int32_t n_scans, std::vector<double> & ref_xy, std::vector<int32_t> & adj_ptr, std::vector<int32_t> & adj_idx,
@@ -931,6 +932,20 @@ int kh_mapper_get_covariances(kh_mapper * m, int32_t n, const int32_t * scan_ids
     if (rc) {return rc;}
   }
   return kh_spa_get_covariances(m->solver, n, scan_ids, cov);
+}
+
+int kh_mapper_get_relative_covariances(kh_mapper * m, int32_t ref_scan, int32_t n, const int32_t * scan_ids, double * out, kh_spa_cov_columns_summary * summary)
+{
+  if (summary) {std::memset(summary, 0, sizeof(*summary));}
+  if (n < 0 || (n > 0 && !out)) {return KH_ERR_INVALID_ARG;}
+  if (kh::require_device(0) != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!m) {return KH_ERR_INVALID_ARG;}
+  // (the solver keeps track of whether the column of ref_scan is resident and still belongs to the graph)
+  if (!kh::spa_covariance_column_resident(m->solver, ref_scan)) {
+    const int rc = kh_spa_compute_covariance_columns(m->solver, 1, &ref_scan, summary);
+    if (rc) {return rc;}
+  }
+  return kh_spa_get_relative_covariances(m->solver, ref_scan, n, scan_ids, out);
 }
 
 }  // extern "C"

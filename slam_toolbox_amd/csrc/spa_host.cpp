@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/karto_hip.h"
+#include "covariance_columns_plan.hpp"
 #include "host_wait.hpp"
 #include "marginalize.hpp"
 #include "spa_internal.hpp"
@@ -187,6 +188,17 @@ struct kh_spa
   std::vector<double> h_cov;
   std::vector<int32_t> h_cov_row_ptr, h_cov_col, h_cov_diag;
   hipEvent_t ev_cov[3] = {};
+  // covariance columns (kh_spa_compute_covariance_columns): the right-hand sides of the sweeps, the block columns they leave
+  // (n_queries x n_free blocks, valid with cov_valid), the plan's lists on the device, and who the queries of the last pass were
+  // (free index -1: the gauge node).  A column comes to the host when a getter first asks for it.
+  DevBuf<double> d_col_rhs, d_columns, d_rel;
+  DevBuf<int32_t> d_col_lists;
+  DevBuf<uint64_t> d_col_masks;
+  DevBuf<char> d_rel_in;
+  std::vector<int32_t> col_ids, col_free, h_col_lists;
+  std::vector<std::vector<double>> h_columns;
+  CovColumnsPlan col_plan;
+  hipEvent_t ev_col[3] = {};
   // marginalizing removal (kh_spa_marginalize_nodes): a round's upload and download, and what the last call did to the graph
   // (the mapper mirrors it: spa_marginalize_edits)
   DevBuf<char> d_marg_in, d_marg_out;
@@ -771,6 +783,7 @@ int kh_spa_create(int32_t device, kh_spa ** out)
   for (auto & row : s->ev_phase) {for (auto & e : row) {KS_HIP(hipEventCreate(&e));}}
   for (auto & row : s->ev_lin) {for (auto & e : row) {KS_HIP(hipEventCreate(&e));}}
   for (auto & e : s->ev_cov) {KS_HIP(hipEventCreate(&e));}
+  for (auto & e : s->ev_col) {KS_HIP(hipEventCreate(&e));}
   *out = s;
   return KH_OK;
 }
@@ -791,9 +804,11 @@ void kh_spa_destroy(kh_spa * s)
   s->d_x.release(); s->d_cand.release(); s->d_scale.release(); s->d_diag.release(); s->d_rhs.release();
   s->d_step.release(); s->d_delta.release(); s->d_scal.release(); s->d_upd.release(); s->d_fsb.release(); s->d_partial.release(); s->d_Hg_alt.release(); s->d_best.release();
   s->d_zbuf.release(); s->d_cov.release(); s->d_marg_in.release(); s->d_marg_out.release();
+  s->d_col_rhs.release(); s->d_columns.release(); s->d_rel.release(); s->d_col_lists.release(); s->d_col_masks.release(); s->d_rel_in.release();
   for (auto & row : s->ev_phase) {for (auto & e : row) {if (e) {(void)hipEventDestroy(e);}}}
   for (auto & row : s->ev_lin) {for (auto & e : row) {if (e) {(void)hipEventDestroy(e);}}}
   for (auto & e : s->ev_cov) {if (e) {(void)hipEventDestroy(e);}}
+  for (auto & e : s->ev_col) {if (e) {(void)hipEventDestroy(e);}}
   if (s->h_scal) {(void)hipHostFree(s->h_scal);}
   if (s->h_res) {(void)hipHostFree(s->h_res);}
   if (s->h_upload) {(void)hipHostFree(s->h_upload);}
@@ -840,6 +855,13 @@ int kh_spa_reset(kh_spa * s)     // ceres_solver.cpp:279-314
 {
   if (!s) {return KH_ERR_INVALID_ARG;}
   s->cov_valid = false;
+  if (s->d_col_rhs.p || s->d_columns.p) {
+    // (the columns' buffers are the large ones of the handle: 46 MB at 10 000 nodes and 64 queries)
+    (void)hipSetDevice(s->device);
+    if (s->stream) {(void)hipStreamSynchronize(s->stream);}
+    s->d_col_rhs.release(); s->d_columns.release();
+  }
+  s->col_ids.clear(); s->col_free.clear(); s->h_columns.clear();
   s->nodes.clear(); s->index_of.clear(); s->cons.clear(); s->con_of.clear(); s->incident.clear(); s->n_dead = 0; s->n_dead_nodes = 0;
   s->corr_ids.clear(); s->corr_poses.clear();
   s->has_first = false; s->was_constant_set = false; s->topology_dirty = true; s->fixed_index = -1;
@@ -1684,16 +1706,27 @@ static int covariance_device_check()
   return KH_OK;
 }
 
-int kh_spa_compute_covariances(kh_spa * s, kh_spa_cov_summary * summary)
+static int covariance_index(kh_spa * s, int32_t id, int32_t & free_index);
+
+// The covariance pass.  query_ids (possibly none): the nodes whose block columns of Sigma are solved for while the factor is
+// still in the fronts; without queries the launches are the selected inverse's alone, in their order.
+static int covariance_pass(kh_spa * s, kh_spa_cov_summary * summary, const std::vector<int32_t> & query_ids, kh_spa_cov_columns_summary * col_summary,
+                           const char * caller)
 {
-  if (covariance_device_check() != KH_OK) {return KH_ERR_NO_DEVICE;}
-  if (!s) {return KH_ERR_INVALID_ARG;}
+  const std::string who = caller;
   settle(s);
   s->cov_valid = false; s->cov_on_host = false;
+  s->col_ids.clear(); s->col_free.clear(); s->h_columns.clear();
   kh_spa_cov_summary sum;
   std::memset(&sum, 0, sizeof(sum));
-  auto finish = [&](int rc) {if (summary) {*summary = sum;} return rc;};
-  if (s->nodes.empty()) {set_error("kh_spa_compute_covariances: the graph has no nodes"); return finish(KH_ERR_NOT_FOUND);}
+  kh_spa_cov_columns_summary csum;
+  std::memset(&csum, 0, sizeof(csum));
+  auto finish = [&](int rc) {
+    if (summary) {*summary = sum;}
+    if (col_summary) {csum.cov = sum; *col_summary = csum;}
+    return rc;
+  };
+  if (s->nodes.empty()) {set_error(who + ": the graph has no nodes"); return finish(KH_ERR_NOT_FOUND);}
   const kh_spa_options & opt = s->opt;
   if (opt.loss_function != KH_LOSS_NONE && !(opt.loss_scale > 0.0)) {
     set_error("kh_spa: loss_scale must be positive");
@@ -1709,15 +1742,21 @@ int kh_spa_compute_covariances(kh_spa * s, kh_spa_cov_summary * summary)
   bool has_work = false;
   int rc = prepare_problem(s, dev, has_work);
   if (rc) {return finish(rc);}
-  if (!has_work) {set_error("kh_spa_compute_covariances: no constraint touches a free node: nothing is in the problem"); return finish(KH_ERR_NOT_FOUND);}
+  if (!has_work) {set_error(who + ": no constraint touches a free node: nothing is in the problem"); return finish(KH_ERR_NOT_FOUND);}
   const Symbolic & sym = s->sym;
   hipStream_t st = s->stream;
   const int n_levels = static_cast<int>(sym.levels.size());
+  const int32_t n_queries = static_cast<int32_t>(query_ids.size());
+  std::vector<int32_t> query_free(query_ids.size(), -1);
+  for (int32_t k = 0; k < n_queries; ++k) {
+    rc = covariance_index(s, query_ids[k], query_free[k]);
+    if (rc) {return finish(rc);}
+  }
   sum.n_free = dev.n_free; sum.levels = n_levels;
   sum.analysis = s->last_symbolic_ms > 0.0 ? (s->last_analysis_incremental ? 2 : 1) : 0;
   if (!select_factor_mode(s, dev)) {
     // (the downward pass needs W = L11^-T of every front, which only the level pipeline leaves behind)
-    set_error("kh_spa_compute_covariances: needs the level pipeline (a front exceeds its LDS budget, or factor kernels 1 / 2 are selected)");
+    set_error(who + ": needs the level pipeline (a front exceeds its LDS budget, or factor kernels 1 / 2 are selected)");
     return finish(KH_ERR_SOLVER);
   }
   {
@@ -1740,7 +1779,7 @@ int kh_spa_compute_covariances(kh_spa * s, kh_spa_cov_summary * summary)
     }
     for (int32_t f = 0; f < nf; ++f) {
       if (!tied[find(f)]) {
-        set_error("kh_spa_compute_covariances: node " + std::to_string(s->nodes[s->node_of_free[f]].id) +
+        set_error(who + ": node " + std::to_string(s->nodes[s->node_of_free[f]].id) +
           " belongs to a free component of the graph that is not tied to the gauge node: J^T J is singular");
         return finish(KH_ERR_SOLVER);
       }
@@ -1751,6 +1790,31 @@ int kh_spa_compute_covariances(kh_spa * s, kh_spa_cov_summary * summary)
     sum.inverse_flops += nu * ns * ns + 2 * nu * nu * ns + 2 * ns * ns * nu;
   }
   if (s->d_zbuf.ensure(static_cast<size_t>(sym.fronts_size) + 16) || s->d_cov.ensure(static_cast<size_t>(s->n_slots) * 9 + 16)) {return finish(KH_ERR_HIP);}
+  // the columns' plan: the fronts of every level on the union of the paths from a query's front to its root, and which queries
+  // each carries; [query -> elimination position | the levels' lists] go to the device in one piece
+  const int32_t R = (3 * n_queries + 15) & ~15;
+  std::vector<int32_t> col_level_off(n_levels + 1, n_queries);
+  if (n_queries > 0) {
+    if (!plan_covariance_columns(sym.parent, sym.level, n_levels, sym.sn_of_elim, sym.elim_of_free, query_free, s->col_plan)) {
+      set_error(who + ": the queries do not fit the analysis");
+      return finish(KH_ERR_SOLVER);
+    }
+    const CovColumnsPlan & plan = s->col_plan;
+    s->h_col_lists.clear();
+    for (int32_t k = 0; k < n_queries; ++k) {s->h_col_lists.push_back(query_free[k] < 0 ? -1 : sym.elim_of_free[query_free[k]]);}
+    for (int l = 0; l < n_levels; ++l) {
+      col_level_off[l] = static_cast<int32_t>(s->h_col_lists.size());
+      s->h_col_lists.insert(s->h_col_lists.end(), plan.level_fronts[l].begin(), plan.level_fronts[l].end());
+    }
+    col_level_off[n_levels] = static_cast<int32_t>(s->h_col_lists.size());
+    csum.n_queries = n_queries; csum.path_fronts = plan.n_path_fronts;
+    for (int32_t k = 0; k < sym.n_fronts; ++k) {
+      const int64_t ns = sym.front_ns[k], nu = sym.front_m[k] - ns;
+      csum.column_flops += (ns * ns + 2 * nu * ns) * R * (plan.front_mask[k] ? 2 : 1);
+    }
+    if (s->d_col_rhs.ensure(3 * static_cast<size_t>(dev.n_free) * R + 16) || s->d_columns.ensure(9 * static_cast<size_t>(dev.n_free) * n_queries + 16) ||
+        s->d_col_lists.upload(s->h_col_lists, st) || s->d_col_masks.upload(plan.front_mask, st)) {return finish(KH_ERR_HIP);}
+  }
   dev.loss_kind = opt.loss_function; dev.loss_b = opt.loss_scale * opt.loss_scale; dev.loss_a = opt.loss_scale;
   const int32_t e_lo = static_cast<int32_t>(static_cast<int64_t>(dev.n_edges) * s->shard_rank / s->shard_world);
   const int32_t e_hi = static_cast<int32_t>(static_cast<int64_t>(dev.n_edges) * (s->shard_rank + 1) / s->shard_world);
@@ -1778,6 +1842,20 @@ int kh_spa_compute_covariances(kh_spa * s, kh_spa_cov_summary * summary)
   if (events) {KS_HIP(hipEventRecord(s->ev_cov[1], st));}
   spa_launch_cov_gather(dev, s->d_zbuf.p, s->d_scale.p, s->d_cov.p, st);
   if (events) {KS_HIP(hipEventRecord(s->ev_cov[2], st));}
+  if (n_queries > 0) {
+    // the fronts still hold G where L21 was, winv holds W: forward up the paths, backward over every front, then the blocks
+    if (events) {KS_HIP(hipEventRecord(s->ev_col[0], st));}
+    spa_launch_cov_columns_init(dev, s->d_col_lists.p, n_queries, R, s->d_scale.p, s->d_col_rhs.p, st);
+    for (int l = 0; l < n_levels; ++l) {
+      spa_launch_cov_columns_forward(dev, s->d_col_lists.p + col_level_off[l], col_level_off[l + 1] - col_level_off[l], s->d_col_masks.p, R, s->d_col_rhs.p, st);
+    }
+    if (events) {KS_HIP(hipEventRecord(s->ev_col[1], st));}
+    for (int l = n_levels - 1; l >= 0; --l) {
+      spa_launch_cov_columns_backward(dev, s->level_offsets[l], s->level_offsets[l + 1] - s->level_offsets[l], R, s->d_col_rhs.p, st);
+    }
+    if (events) {KS_HIP(hipEventRecord(s->ev_col[2], st));}
+    spa_launch_cov_columns_gather(dev, n_queries, R, s->d_scale.p, s->d_col_rhs.p, s->d_columns.p, st);
+  }
   if (dev.scatter) {
     // the pass stands where the backward sweep stands in a solve: the last reader of what the factorisation left in the fronts
     spa_launch_selinv_clean(dev, st);
@@ -1788,7 +1866,7 @@ int kh_spa_compute_covariances(kh_spa * s, kh_spa_cov_summary * summary)
   KS_HIP(hipStreamSynchronize(st));
   if (s->h_fail[0] != 0) {
     // (a failed front has handed NaNs up the tree: the fronts are not trusted to be clean, the next factorisation memsets)
-    set_error("kh_spa_compute_covariances: non-positive pivot: a free component of the graph is not tied to the gauge node");
+    set_error(who + ": non-positive pivot: a free component of the graph is not tied to the gauge node");
     return finish(KH_ERR_SOLVER);
   }
   if (dev.scatter) {
@@ -1811,12 +1889,47 @@ int kh_spa_compute_covariances(kh_spa * s, kh_spa_cov_summary * summary)
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, s->ev_cov[0], s->ev_cov[1]) == hipSuccess) {sum.inverse_ms = ms;}
     if (hipEventElapsedTime(&ms, s->ev_cov[1], s->ev_cov[2]) == hipSuccess) {sum.gather_ms = ms;}
+    if (n_queries > 0) {
+      if (hipEventElapsedTime(&ms, s->ev_col[0], s->ev_col[1]) == hipSuccess) {csum.forward_ms = ms;}
+      if (hipEventElapsedTime(&ms, s->ev_col[1], s->ev_col[2]) == hipSuccess) {csum.backward_ms = ms;}
+    }
   }
   s->cov_valid = true;
+  s->col_ids = query_ids; s->col_free = query_free; s->h_columns.assign(query_ids.size(), {});
   sum.factor_ms = ms_since(t_factor);
   sum.total_ms = ms_since(t_begin);
+  csum.total_ms = sum.total_ms;
   return finish(KH_OK);
 }
+
+int kh_spa_compute_covariances(kh_spa * s, kh_spa_cov_summary * summary)
+{
+  if (covariance_device_check() != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!s) {return KH_ERR_INVALID_ARG;}
+  return covariance_pass(s, summary, {}, nullptr, "kh_spa_compute_covariances");
+}
+
+int kh_spa_compute_covariance_columns(kh_spa * s, int32_t n, const int32_t * ids, kh_spa_cov_columns_summary * summary)
+{
+  if (summary) {std::memset(summary, 0, sizeof(*summary));}
+  if (n < 1 || n > KH_SPA_MAX_COV_COLUMNS || !ids) {
+    set_error("kh_spa_compute_covariance_columns: between 1 and " + std::to_string(KH_SPA_MAX_COV_COLUMNS) + " query nodes are listed");
+    return KH_ERR_INVALID_ARG;
+  }
+  std::vector<int32_t> query_ids(ids, ids + n);
+  {
+    std::vector<int32_t> sorted = query_ids;
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) {
+      set_error("kh_spa_compute_covariance_columns: a query node is listed twice");
+      return KH_ERR_INVALID_ARG;
+    }
+  }
+  if (covariance_device_check() != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!s) {return KH_ERR_INVALID_ARG;}
+  return covariance_pass(s, nullptr, query_ids, summary, "kh_spa_compute_covariance_columns");
+}
+
 
 // the array and the pattern it is addressed by, on the host (first getter behind a computation)
 static int fetch_covariances(kh_spa * s)
@@ -1916,6 +2029,147 @@ int kh_spa_covariance_device(kh_spa * s, const double ** cov_bsr, int64_t * n_sl
     return KH_ERR_SOLVER;
   }
   *cov_bsr = s->d_cov.p; *n_slots = s->n_slots;
+  return KH_OK;
+}
+
+// ---- covariance columns: the getters --------------------------------------------------------------------------------------
+// position of `id` among the queries of the last column pass; KH_ERR_SOLVER when stale, KH_ERR_NOT_FOUND when the node was no query
+static int column_of_query(kh_spa * s, int32_t id, int32_t & k)
+{
+  if (!s->cov_valid) {
+    set_error("kh_spa: the covariances are stale (the graph or a pose has changed since kh_spa_compute_covariance_columns, or it never ran)");
+    return KH_ERR_SOLVER;
+  }
+  const auto it = std::find(s->col_ids.begin(), s->col_ids.end(), id);
+  if (it == s->col_ids.end()) {
+    set_error("kh_spa: node " + std::to_string(id) + " was not a query of the last kh_spa_compute_covariance_columns: its column is not resident");
+    return KH_ERR_NOT_FOUND;
+  }
+  k = static_cast<int32_t>(it - s->col_ids.begin());
+  return KH_OK;
+}
+
+// the column of query k on the host (the first getter that asks for it brings it)
+static int fetch_column(kh_spa * s, int32_t k)
+{
+  const size_t len = 9 * s->node_of_free.size();
+  if (s->h_columns[k].size() == len) {return KH_OK;}
+  s->h_columns[k].resize(len);
+  KS_HIP(hipSetDevice(s->device));
+  KS_HIP(hipMemcpyAsync(s->h_columns[k].data(), s->d_columns.p + len * static_cast<size_t>(k), len * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  KS_HIP(hipStreamSynchronize(s->stream));
+  return KH_OK;
+}
+
+int kh_spa_get_covariance_column(kh_spa * s, int32_t id_q, int32_t n, const int32_t * ids, double * out)
+{
+  if (n < 0 || (n > 0 && !out)) {return KH_ERR_INVALID_ARG;}
+  if (covariance_device_check() != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!s) {return KH_ERR_INVALID_ARG;}
+  int32_t k = -1;
+  int rc = column_of_query(s, id_q, k);
+  if (rc) {return rc;}
+  if (!ids && n != static_cast<int32_t>(s->nodes.size())) {
+    set_error("kh_spa_get_covariance_column: without ids, n must be kh_spa_num_nodes");
+    return KH_ERR_INVALID_ARG;
+  }
+  rc = fetch_column(s, k);
+  if (rc) {return rc;}
+  for (int32_t t = 0; t < n; ++t) {
+    int32_t f = -1;
+    rc = covariance_index(s, ids ? ids[t] : s->nodes[t].id, f);
+    if (rc) {return rc;}
+    double * o = out + 9 * static_cast<size_t>(t);
+    if (f < 0 || s->col_free[k] < 0) {
+      std::fill(o, o + 9, 0.0);                                    // the gauge node, as a row or as the query
+    } else {
+      std::copy(s->h_columns[k].begin() + 9 * static_cast<size_t>(f), s->h_columns[k].begin() + 9 * static_cast<size_t>(f) + 9, o);
+    }
+  }
+  return KH_OK;
+}
+
+int kh_spa_get_joint_covariance_any(kh_spa * s, int32_t id_a, int32_t id_b, double cov[36])
+{
+  if (!cov) {return KH_ERR_INVALID_ARG;}
+  if (covariance_device_check() != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!s) {return KH_ERR_INVALID_ARG;}
+  int rc = fetch_covariances(s);
+  if (rc) {return rc;}
+  int32_t f[2] = {-1, -1};
+  rc = covariance_index(s, id_a, f[0]); if (rc) {return rc;}
+  rc = covariance_index(s, id_b, f[1]); if (rc) {return rc;}
+  // the column of id_b where it is resident, else that of id_a; `row` is the other node: its block of the column is Sigma(row, query)
+  int32_t k = -1, row = 0;
+  if (std::find(s->col_ids.begin(), s->col_ids.end(), id_b) != s->col_ids.end()) {
+    rc = column_of_query(s, id_b, k); row = 0;
+  } else {
+    rc = column_of_query(s, id_a, k); row = 1;
+  }
+  if (rc) {return rc;}
+  rc = fetch_column(s, k);
+  if (rc) {return rc;}
+  std::fill(cov, cov + 36, 0.0);
+  for (int p = 0; p < 2; ++p) {
+    if (f[p] < 0) {continue;}                                       // the gauge node: zeros
+    const double * blk = s->h_cov.data() + 9 * static_cast<size_t>(s->h_cov_diag[f[p]]);
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) {cov[(3 * p + r) * 6 + 3 * p + c] = blk[3 * r + c];}
+    }
+  }
+  if (f[0] >= 0 && f[1] >= 0) {
+    const double * blk = s->h_columns[k].data() + 9 * static_cast<size_t>(f[row]);
+    const int q = 1 - row;                                          // block (row, q) of the 6 x 6, and its transpose at (q, row)
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) {
+        cov[(3 * row + r) * 6 + 3 * q + c] = blk[3 * r + c];
+        cov[(3 * q + c) * 6 + 3 * row + r] = blk[3 * r + c];
+      }
+    }
+  }
+  return KH_OK;
+}
+
+int kh_spa_get_relative_covariances(kh_spa * s, int32_t id_ref, int32_t n, const int32_t * ids, double * out)
+{
+  if (n < 0 || (n > 0 && !out)) {return KH_ERR_INVALID_ARG;}
+  if (covariance_device_check() != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!s) {return KH_ERR_INVALID_ARG;}
+  int32_t k = -1;
+  int rc = column_of_query(s, id_ref, k);
+  if (rc) {return rc;}
+  if (!ids && n != static_cast<int32_t>(s->nodes.size())) {
+    set_error("kh_spa_get_relative_covariances: without ids, n must be kh_spa_num_nodes");
+    return KH_ERR_INVALID_ARG;
+  }
+  if (n == 0) {return KH_OK;}
+  // [poses of the listed nodes, then the reference's | their free indices] go up, nine doubles per node come back
+  const size_t nn = static_cast<size_t>(n);
+  std::vector<char> in((3 * nn + 3) * sizeof(double) + nn * sizeof(int32_t));
+  double * poses = reinterpret_cast<double *>(in.data());
+  int32_t * free_idx = reinterpret_cast<int32_t *>(in.data() + (3 * nn + 3) * sizeof(double));
+  for (int32_t t = 0; t < n; ++t) {
+    const int32_t id = ids ? ids[t] : s->nodes[t].id;
+    rc = covariance_index(s, id, free_idx[t]);
+    if (rc) {return rc;}
+    const double * pose = s->nodes[s->index_of[id]].pose;
+    std::copy(pose, pose + 3, poses + 3 * static_cast<size_t>(t));
+  }
+  const double * ref_pose = s->nodes[s->index_of[id_ref]].pose;
+  std::copy(ref_pose, ref_pose + 3, poses + 3 * nn);
+  KS_HIP(hipSetDevice(s->device));
+  if (s->d_rel_in.ensure(in.size()) || s->d_rel.ensure(9 * nn)) {return KH_ERR_HIP;}
+  KS_HIP(hipMemcpyAsync(s->d_rel_in.p, in.data(), in.size(), hipMemcpyHostToDevice, s->stream));
+  SpaDev dev;
+  std::memset(&dev, 0, sizeof(dev));
+  dev.n_free = static_cast<int32_t>(s->node_of_free.size());
+  dev.bsr_diag_slot = s->d_bsr_diag.p;
+  const double * d_poses = reinterpret_cast<const double *>(s->d_rel_in.p);
+  spa_launch_cov_relative(dev, s->d_cov.p, s->d_columns.p + 9 * static_cast<size_t>(dev.n_free) * k, s->col_free[k], d_poses + 3 * nn,
+    reinterpret_cast<const int32_t *>(s->d_rel_in.p + (3 * nn + 3) * sizeof(double)), d_poses, n, s->d_rel.p, s->stream);
+  KS_HIP(hipGetLastError());
+  KS_HIP(hipMemcpyAsync(out, s->d_rel.p, 9 * nn * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  KS_HIP(hipStreamSynchronize(s->stream));
   return KH_OK;
 }
 
@@ -2175,6 +2429,11 @@ namespace kh
 {
 // whether the resident covariances still belong to the graph (the mapper recomputes lazily)
 bool spa_covariances_valid(const kh_spa * s) {return s && s->cov_valid;}
+// ... and whether the block column of node `id` is resident with them
+bool spa_covariance_column_resident(const kh_spa * s, int32_t id)
+{
+  return s && s->cov_valid && std::find(s->col_ids.begin(), s->col_ids.end(), id) != s->col_ids.end();
+}
 }  // namespace kh
 
 // ---- the part of the solver's state a mapping session file carries besides nodes and constraints (mapper_host.cpp) ----

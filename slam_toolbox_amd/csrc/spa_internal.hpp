@@ -132,6 +132,23 @@ void spa_launch_selinv_level(const SpaDev & d, int32_t first_front, int32_t n, i
 void spa_launch_selinv_clean(const SpaDev & d, void * stream);
 // cov (n_slots * 9 doubles, addressed like H): block (i, j) of the pattern = s_i Z_ij s_j, with s = scale
 void spa_launch_cov_gather(const SpaDev & d, const double * zbuf, const double * scale, double * cov, void * stream);
+// Covariance columns: A X = E_q through the factor for a handful of query nodes, between spa_launch_cov_gather and the clean (the
+// fronts hold G = L21 W^T where L21 was, winv holds W).  B: the right-hand sides, 3 * n_free rows in elimination order (the rows of
+// `rhs`) x R columns, row-major, R a multiple of 16, column 3 k + c = component c of query k.
+// init: B <- 0, then B[3 * query_elim[k] + c][3 k + c] <- scale of that row (query_elim[k] < 0: the gauge node, a column of zeros)
+void spa_launch_cov_columns_init(const SpaDev & d, const int32_t * query_elim, int32_t n_queries, int32_t R, const double * scale, double * B, void * stream);
+// one level of the forward sweep (leaves first): the fronts list[0 .. n) of that level, each touching only the columns of the
+// queries in front_mask[front] (bit k = query k): Y1 = W^T B1 in place of B1, B[struct rows] -= G B1
+void spa_launch_cov_columns_forward(const SpaDev & d, const int32_t * list, int32_t n, const uint64_t * front_mask, int32_t R, double * B, void * stream);
+// one level of the backward sweep (root level first), every front first_front .. + n - 1 and every column: X1 = W Y1 - G^T X2
+void spa_launch_cov_columns_backward(const SpaDev & d, int32_t first_front, int32_t n, int32_t R, double * B, void * stream);
+// columns (n_queries x n_free blocks of 9 doubles, row-major): block (k, i) = Sigma(free node i, query k) = s_i X_ik
+void spa_launch_cov_columns_gather(const SpaDev & d, int32_t n_queries, int32_t R, const double * scale, const double * B, double * columns, void * stream);
+// out[9 t ..] = first-order covariance of node t's pose in the frame of the reference node: free_idx[t] / ref_free = free indices
+// (-1: the gauge node, whose blocks are zeros), poses[3 t ..] / ref_pose the poses, cov = the resident marginals (spa_launch_cov_gather),
+// column = the reference's block column (n_free blocks)
+void spa_launch_cov_relative(const SpaDev & d, const double * cov, const double * column, int32_t ref_free, const double * ref_pose,
+                             const int32_t * free_idx, const double * poses, int32_t n, double * out, void * stream);
 // self-cleaning fronts (scatter mode): zero the update matrices of the fronts in `list` (children read in place by their parents)
 void spa_launch_zero_update_blocks(const SpaDev & d, const int32_t * list, int32_t n, int32_t max_m, void * stream);
 // debugging aid: *count += entries of p[0..n) whose bit pattern is not zero

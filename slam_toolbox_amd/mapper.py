@@ -283,6 +283,25 @@ class Mapper:
         capi.check(rc, "kh_mapper_get_covariances")
         return out[:n]
 
+    def relative_covariances(self, ref, ids=None) -> np.ndarray:
+        """(n, 3, 3): covariance of the listed scans' poses expressed in the frame of scan `ref` (None: every solver node,
+        insertion order), from the graph as a whole: kh_mapper_get_relative_covariances.  The column of `ref` is computed only
+        when it is not resident or is stale; `cov_columns_summary` holds the summary of the computation this call ran (all zeros
+        when it ran none)."""
+        L = capi.lib()
+        if ids is None:
+            n, idp = L.kh_spa_num_nodes(L.kh_mapper_solver(self._h)), None
+        else:
+            idv = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+            n, idp = idv.size, idv.ctypes.data_as(C.c_void_p)
+        out = np.zeros((max(n, 1), 3, 3))
+        s = capi.KhSpaCovColumnsSummary()
+        rc = L.kh_mapper_get_relative_covariances(self._h, int(ref), n, idp, out.ctypes.data_as(C.c_void_p), C.byref(s))
+        self.cov_columns_summary = {k: getattr(s, k) for k, _ in capi.KhSpaCovColumnsSummary._fields_ if k != "cov"}
+        self.cov_columns_summary["cov"] = {k: getattr(s.cov, k) for k, _ in capi.KhSpaCovSummary._fields_ if k != "pad"}
+        capi.check(rc, "kh_mapper_get_relative_covariances")
+        return out[:n]
+
     def stats(self) -> dict:
         st = capi.KhMapperStats()
         capi.check(capi.lib().kh_mapper_get_stats(self._h, C.byref(st)), "kh_mapper_get_stats")

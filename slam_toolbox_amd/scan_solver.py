@@ -164,6 +164,55 @@ class HipSpaSolver:
                    "kh_spa_get_joint_covariance")
         return out
 
+    # ---- covariance columns: any pair of nodes, joined by a constraint or not ---------------------------------------
+    @staticmethod
+    def _columns_summary(s):
+        out = {k: getattr(s, k) for k, _ in capi.KhSpaCovColumnsSummary._fields_ if k != "cov"}
+        out["cov"] = {k: getattr(s.cov, k) for k, _ in capi.KhSpaCovSummary._fields_ if k != "pad"}
+        return out
+
+    def _id_list(self, ids):
+        """(n, pointer, keep-alive) of a list of ids; None: all nodes in insertion order"""
+        if ids is None:
+            return capi.lib().kh_spa_num_nodes(self._h), None, None
+        idv = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        return idv.size, idv.ctypes.data_as(C.c_void_p), idv
+
+    def ComputeCovarianceColumns(self, ids):
+        """kh_spa_compute_covariance_columns: ComputeCovariances(), and the block columns Sigma(:, q) of the listed query nodes
+        (at most capi.KH_SPA_MAX_COV_COLUMNS) solved for through the factor while the pass has it.  Returns the summary dict
+        (`cov`: the embedded summary of the pass); failures raise KartoHipError."""
+        n, idp, _keep = self._id_list(list(ids))
+        s = capi.KhSpaCovColumnsSummary()
+        rc = capi.lib().kh_spa_compute_covariance_columns(self._h, n, idp, C.byref(s))
+        self.cov_columns_summary = self._columns_summary(s)
+        self.cov_summary = self.cov_columns_summary["cov"]
+        capi.check(rc, "kh_spa_compute_covariance_columns")
+        return self.cov_columns_summary
+
+    def CovarianceColumn(self, q: int, ids=None):
+        """(n, 3, 3): Sigma(ids[k], q) for a query q of the last ComputeCovarianceColumns (None: all nodes, insertion order)"""
+        n, idp, _keep = self._id_list(ids)
+        out = np.zeros((max(n, 1), 3, 3))
+        capi.check(capi.lib().kh_spa_get_covariance_column(self._h, int(q), n, idp, out.ctypes.data_as(C.c_void_p)), "kh_spa_get_covariance_column")
+        return out[:n]
+
+    def JointCovarianceAny(self, id_a: int, id_b: int):
+        """(6, 6) [[aa ab], [ba bb]] of any two nodes of which one was a query of the last ComputeCovarianceColumns"""
+        out = np.zeros((6, 6))
+        capi.check(capi.lib().kh_spa_get_joint_covariance_any(self._h, int(id_a), int(id_b), out.ctypes.data_as(C.c_void_p)),
+                   "kh_spa_get_joint_covariance_any")
+        return out
+
+    def RelativeCovariances(self, ref: int, ids=None):
+        """(n, 3, 3): covariance of every listed node's pose expressed in the frame of `ref` (a query of the last
+        ComputeCovarianceColumns), on the device; what relative_covariance(pose_ref, pose_i, JointCovarianceAny(ref, i)) gives"""
+        n, idp, _keep = self._id_list(ids)
+        out = np.zeros((max(n, 1), 3, 3))
+        capi.check(capi.lib().kh_spa_get_relative_covariances(self._h, int(ref), n, idp, out.ctypes.data_as(C.c_void_p)),
+                   "kh_spa_get_relative_covariances")
+        return out[:n]
+
     def iteration_log(self):
         """(n, 8) array: the trust-region iterations of the last Compute() (kh_spa_iteration_log: iteration, cost, candidate cost,
         model cost change, radius used, radius after, step norm, verdict)."""
