@@ -607,7 +607,7 @@ void prepare_job(kh_matcher * m, const CorrReq & q, CorrHost & c, const StageLay
   const int px = dec ? kTileSpan : score_tile_poses(this_sx);
   job->tiles_x = (c.nx + px - 1) / px;
   job->ry = this_ry; job->tile_px = px; job->dec = dec ? 1 : 0;
-  shape.sx = dec ? 1 : this_sx; shape.ry = this_ry; shape.tiles = job->tiles_x * job->tiles_y;
+  shape.sx = dec ? 1 : this_sx; shape.lds_sx = this_sx; shape.ry = this_ry; shape.tiles = job->tiles_x * job->tiles_y;
   // LDS-staged scoring: linear lattice whose window fits 64 bytes x 64 rows
   // ... and a launch of at least two workgroups (angle pairs) per compute unit: one config-2 search alone is 41 workgroups that
   // walk their 25 chunks one after the other -- 0.26 ms against the windowed kernel's 0.14
@@ -856,9 +856,13 @@ static int enqueue_chunk(kh_matcher * m, CorrReq * reqs, size_t n, CorrBatch & B
   }
   // one scoring launch for the chunk if every job takes the same kernel instance
   int32_t max_tiles = 0, sx_variant = shapes[0].sx, ry = shapes[0].ry;
+  // (the LDS-staged kernels score the grid itself with the lattice's own step: a two-cell search on a slot that holds column-decimated
+  // copies is a one-cell search for the windowed kernel only)
+  const int32_t lds_sx = shapes[0].lds_sx;
   bool uniform_kernel = true, all_lds = true;
   for (size_t i = 0; i < n; ++i) {
     if (sx_variant != shapes[i].sx || ry != shapes[i].ry) {uniform_kernel = false;}
+    all_lds = all_lds && shapes[i].lds_sx == lds_sx;
     max_tiles = std::max(max_tiles, shapes[i].tiles);
     all_lds = all_lds && shapes[i].lds != 0;
   }
@@ -895,7 +899,7 @@ static int enqueue_chunk(kh_matcher * m, CorrReq * reqs, size_t n, CorrBatch & B
   if (B.use_lds) {
     bool full_rows = true;
     for (size_t i = 0; i < n; ++i) {full_rows = full_rows && lds_row_waves(B.ctx[i].ny) == 4;}
-    launch_score_lds(B.d_stage, stride, static_cast<int32_t>(n), max_na, sx_variant, full_rows, cs);
+    launch_score_lds(B.d_stage, stride, static_cast<int32_t>(n), max_na, lds_sx, full_rows, cs);
   } else if (uniform_kernel) {
     launch_score(B.d_stage, stride, static_cast<int32_t>(n), max_tiles, max_na, sx_variant, ry, cs);
   } else {

@@ -285,7 +285,9 @@ struct CorrReq
 constexpr int kNeedGeneric = 1000;
 
 // shape of one prepared job: what picks the scoring kernel instance of a launch
-struct JobShape {int32_t sx = 1, ry = 1, tiles = 1, lds = 0;};
+// sx: the windowed kernel's instance (1 for a two-cell search read from the column-decimated copies); lds_sx: the lattice's own step in
+// cells, which is what the LDS-staged kernels score with (they read the grid itself, never the copies)
+struct JobShape {int32_t sx = 1, ry = 1, tiles = 1, lds = 0, lds_sx = 1;};
 // where a finished job's results lie (host memory)
 struct ResultView
 {
