@@ -404,6 +404,12 @@ KH_API int kh_spa_get_joint_covariance_any(kh_spa * s, int32_t id_a, int32_t id_
  * J = [dd/dref dd/dk], one thread per listed node (k_cov_relative).  ids = NULL: all nodes in insertion order.  ids[k] = id_ref:
  * exact zeros. */
 KH_API int kh_spa_get_relative_covariances(kh_spa * s, int32_t id_ref, int32_t n, const int32_t * ids, double * out /* 9n */);
+/* out[9 k ..]: row-major covariance of x_k - x_ref in the WORLD frame, D = S_kk + S_rr - S_kr - S_kr^T (k_cov_difference, one
+ * thread per listed node): no pose enters and nothing is rotated, which is what a gate over world positions wants (section 7h).
+ * id_ref must be a query of the last column pass.  The upper triangle is computed and mirrored: bit-wise symmetric.  The gauge
+ * node's blocks are zeros, as k or as the reference; ids[k] = id_ref: exact zeros.  Argument checks, ids = NULL and staleness as
+ * kh_spa_get_relative_covariances. */
+KH_API int kh_spa_get_difference_covariances(kh_spa * s, int32_t id_ref, int32_t n, const int32_t * ids, double * out /* 9n */);
 /* ---- marginalizing node removal (no counterpart in the reference, whose RemoveNode drops the node's constraints and transfers
  * nothing: a lifelong graph falls apart).  Every listed node leaves like kh_spa_remove_node, but first its constraints are composed
  * through it into constraints among its neighbours: parallel constraints to one neighbour are fused; the
@@ -519,6 +525,21 @@ KH_API int kh_graph_find_loop_candidates_from(kh_graph * g, int32_t n_queries, c
                                               const int32_t * start_scans, double loop_search_maximum_distance,
                                               int32_t loop_match_minimum_chain_size, int32_t * chain_begin, int32_t * chains,
                                               int32_t cap_chains, int32_t * n_chains);
+/* kh_graph_find_loop_candidates_from with the distance test widened by the uncertainty of every scan's displacement from the
+ * query: gate holds, per query, n_scans rows of 9 doubles in list order -- the row-major 3 x 3 world-frame
+ * covariance D of x_i - x_query (kh_spa_get_difference_covariances), of which Dxx, Dxy, Dyy = [0], [1], [4] are read.  With
+ * r = loop_search_maximum_distance and s = chi2 / (r * r), every operation rounded on its own:
+ *   a = 1 + s Dxx, c = 1 + s Dyy, b = s Dxy, det = a c - b b, q = ((c (dx dx) - 2 b (dx dy)) + a (dy dy)) / det
+ * -- q = delta^T (I + s D)^-1 delta, so q < r^2 is the ellipse delta^T (r^2 I + chi2 D)^-1 delta < 1 -- and q replaces the squared
+ * distance in BOTH tests (candidate: q < r^2 + KT_TOLERANCE; visitable by the breadth-first "linked" walk: q <= r^2 - KT_TOLERANCE).
+ * A row with det <= 0, a < 1, c < 1 or a quotient that is not finite is tested with the plain squared distance.  D = 0 or chi2 = 0
+ * gives q = dx dx + dy dy exactly: the chains of kh_graph_find_loop_candidates_from, bit for bit.  gate = NULL, chi2 < 0 or NaN:
+ * KH_ERR_INVALID_ARG; everything else as kh_graph_find_loop_candidates_from. */
+KH_API int kh_graph_find_loop_candidates_gated(kh_graph * g, int32_t n_queries, const int32_t * query_scans,
+                                               const int32_t * start_scans /* may be NULL */, double loop_search_maximum_distance,
+                                               int32_t loop_match_minimum_chain_size, double chi2,
+                                               const double * gate /* n_queries x 9 n_scans, host */, int32_t * chain_begin,
+                                               int32_t * chains, int32_t cap_chains, int32_t * n_chains);
 KH_API double kh_graph_last_kernel_ms(kh_graph * g);
 /* After scans were removed (lifelong mode) the reference's candidate walks stop at the SIZE of its scan map, which has
  * fallen behind the largest scan id (Mapper.cpp:1974-1976, 1751-1756): only the first n_visit scans of the list are
@@ -786,6 +807,50 @@ KH_API int kh_mapper_get_covariances(kh_mapper * m, int32_t n, const int32_t * s
  * computation this call ran, all zeros when it ran none. */
 KH_API int kh_mapper_get_relative_covariances(kh_mapper * m, int32_t ref_scan, int32_t n, const int32_t * scan_ids, double * out /* 9n */,
                                               kh_spa_cov_columns_summary * summary);
+/* kh_spa_get_difference_covariances of the mapper's solver (world-frame covariance of x_k - x_ref), lazy as above */
+KH_API int kh_mapper_get_difference_covariances(kh_mapper * m, int32_t ref_scan, int32_t n, const int32_t * scan_ids, double * out /* 9n */,
+                                                kh_spa_cov_columns_summary * summary);
+/* ---- the covariance gate of the loop search (no counterpart in the reference, whose TryCloseLoop looks within a fixed radius;
+ * DESIGN.md section 7h).  Enabled, TryCloseLoop enumerates with kh_graph_find_loop_candidates_gated: the search disk of
+ * loop_search_maximum_distance widened, per scan, by the chi2_position ellipse of covariance_scale * D, D the world-frame covariance
+ * of the scan's displacement from the current scan (kh_spa_get_difference_covariances).
+ *   refresh  D is refreshed -- one column pass with the current scan as the query, then k_cov_difference over the scans alive --
+ *            when refresh_scans TryCloseLoop calls have passed since the last refresh, and always after a closure moved the poses.
+ *            In between the last D is reused; a scan appended since, and a scan the solver does not know, has D = 0.  A pass the
+ *            solver refuses (KH_ERR_SOLVER: a component not tied to the gauge, fronts beyond the LDS budget) leaves that scan's
+ *            search ungated and is counted; any other error is returned.
+ *   reach    where s (Gxx + Gyy) > (max_reach / r)^2 - 1 (G = covariance_scale D, r the search distance, s = chi2_position / r^2)
+ *            G is scaled down to meet it: no semi-axis of the widened ellipse exceeds max_reach.
+ *   jump     (chi2_jump > 0) a chain whose fine match passes is still not accepted when the correction it asks for,
+ *            e = fine mean - current sensor pose (angle normalised), has e^T (covariance_scale D3 + C_fine)^-1 e > chi2_jump or that
+ *            3 x 3 is not positive definite; D3 = the full D of the chain's scan LinkChainToScan would link to, C_fine the fine
+ *            match's covariance.  Consumption goes on to the next passing chain.
+ * With enabled = 0 the mapper is the reference's; enabled with covariance_scale = 0, or with chi2_position = 0 and chi2_jump <= 0,
+ * runs no column pass and is the same run bit for bit.  The gate is NOT part of a session file: after kh_mapper_load it is off.
+ * Localization mode, kh_mapper_relocalize and sessions are untouched. */
+typedef struct kh_loop_gate_params {
+  int32_t enabled;
+  int32_t refresh_scans;        /* >= 1 */
+  double chi2_position;         /* >= 0; 5.991 = 95 % of chi-square, 2 degrees of freedom */
+  double chi2_jump;             /* <= 0: no jump test; 7.815 = 95 %, 3 degrees of freedom */
+  double covariance_scale;      /* >= 0: how far the solver's covariances are trusted */
+  double max_reach;             /* > 0, metres; default loop_search_maximum_distance + loop_search_space_dimension / 2: the coarse
+                                   matcher cannot pull a scan further than half its window */
+} kh_loop_gate_params;
+typedef struct kh_loop_gate_stats {
+  int64_t column_passes;        /* refreshes that ran */
+  int64_t ungated_searches;     /* scans whose search ran ungated because the solver refused the pass */
+  int64_t jump_rejected;        /* chains the jump test kept from being accepted */
+  double column_ms;             /* wall time of the refreshes (pass + k_cov_difference + download) */
+  double max_semi_axis;         /* metres: the largest semi-axis sqrt(r^2 + chi2_position lambda_max(G)) of a prepared row */
+} kh_loop_gate_stats;
+/* params = NULL: kh_mapper_params_default's distances */
+KH_API void kh_loop_gate_params_default(const kh_mapper_params * params, kh_loop_gate_params * gate);
+/* refresh_scans < 1, chi2_position < 0, covariance_scale < 0, max_reach <= 0, a NaN or an infinite value (chi2_jump may be
+ * infinite): KH_ERR_INVALID_ARG, before the device is looked for; then KH_ERR_NO_DEVICE, then the handle */
+KH_API int kh_mapper_set_loop_gate(kh_mapper * m, const kh_loop_gate_params * gate);
+KH_API int kh_mapper_get_loop_gate(const kh_mapper * m, kh_loop_gate_params * gate);
+KH_API int kh_mapper_get_loop_gate_stats(const kh_mapper * m, kh_loop_gate_stats * out);
 /* every solver call the mapper makes, one line each, in the format oracle/ref_slam_driver.cpp logs the reference
  * Mapper's calls with (N id pose, C a b z cov, X n ms, P id pose, K): the two logs of one scan queue must agree */
 KH_API int kh_mapper_set_log(kh_mapper * m, const char * path);

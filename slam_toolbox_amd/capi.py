@@ -131,6 +131,8 @@ SYMBOLS = [
     "kh_spa_compute_covariance_columns", "kh_spa_get_covariance_column", "kh_spa_get_joint_covariance_any", "kh_spa_get_relative_covariances",
     "kh_mapper_get_relative_covariances",
     "kh_spa_marginalize_nodes", "kh_mapper_marginalize_nodes", "kh_mapper_set_removal_mode",
+    "kh_spa_get_difference_covariances", "kh_mapper_get_difference_covariances", "kh_graph_find_loop_candidates_gated",
+    "kh_loop_gate_params_default", "kh_mapper_set_loop_gate", "kh_mapper_get_loop_gate", "kh_mapper_get_loop_gate_stats",
 ]
 
 
@@ -171,6 +173,16 @@ class KhMapperStats(C.Structure):
                [(k, C.c_double) for k in ("process_ms", "match_ms", "solver_ms", "update_ms", "lifelong_ms")] + \
                [(k, C.c_int64) for k in ("fused_declined", "fused_declined_reason", "fused_matches", "fused_fine_passes",
                                            "decay_calls_resident", "decay_calls_packed", "marginalize_fallbacks")]
+
+
+class KhLoopGateParams(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("refresh_scans", C.c_int32), ("chi2_position", C.c_double), ("chi2_jump", C.c_double),
+                ("covariance_scale", C.c_double), ("max_reach", C.c_double)]
+
+
+class KhLoopGateStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("column_passes", "ungated_searches", "jump_rejected")] + \
+               [(k, C.c_double) for k in ("column_ms", "max_semi_axis")]
 
 
 class KhSessionInfo(C.Structure):
@@ -339,6 +351,15 @@ def lib():
         L.kh_spa_get_covariance_column.argtypes = [vp, i32, i32, vp, vp]
         L.kh_spa_get_joint_covariance_any.argtypes = [vp, i32, i32, vp]
         L.kh_spa_get_relative_covariances.argtypes = [vp, i32, i32, vp, vp]
+    if hasattr(L, "kh_graph_find_loop_candidates_gated"):
+        L.kh_spa_get_difference_covariances.argtypes = [vp, i32, i32, vp, vp]
+        L.kh_mapper_get_difference_covariances.argtypes = [vp, i32, i32, vp, vp, C.POINTER(KhSpaCovColumnsSummary)]
+        L.kh_graph_find_loop_candidates_gated.argtypes = [vp, i32, vp, vp, dbl, i32, dbl, vp, vp, vp, i32, C.POINTER(i32)]
+        L.kh_loop_gate_params_default.argtypes = [C.POINTER(KhMapperParams), C.POINTER(KhLoopGateParams)]
+        L.kh_loop_gate_params_default.restype = None
+        L.kh_mapper_set_loop_gate.argtypes = [vp, C.POINTER(KhLoopGateParams)]
+        L.kh_mapper_get_loop_gate.argtypes = [vp, C.POINTER(KhLoopGateParams)]
+        L.kh_mapper_get_loop_gate_stats.argtypes = [vp, C.POINTER(KhLoopGateStats)]
     if hasattr(L, "kh_spa_marginalize_nodes"):
         L.kh_spa_marginalize_nodes.argtypes = [vp, i32, vp, C.POINTER(KhMarginalizeSummary)]
         L.kh_mapper_marginalize_nodes.argtypes = [vp, i32, vp]

@@ -44,9 +44,29 @@ struct GraphDev
   const int32_t * adj_idx;
 };
 
+// The gated squared distance: delta^T (I + s D)^-1 delta with s = chi2 / r^2 and D = [[dxx dxy], [dxy dyy]]
+// the covariance of the displacement, so that `q < r^2` is the ellipse delta^T (r^2 I + chi2 D)^-1 delta < 1 -- the search disk
+// widened by the chi2 ellipse.  Every operation is rounded on its own, on the device and on the host alike.  D = 0 or s = 0 gives
+// a = c = det = 1, b = 0 and q = dx * dx + dy * dy to the bit; a row that is not a covariance (negative diagonal, det <= 0, NaN,
+// infinity) or a quotient that is not finite falls back to that plain distance.
+__host__ __device__ __forceinline__ double gated_dist_sq(double dx, double dy, double s, double dxx, double dxy, double dyy)
+{
+#pragma clang fp contract(off)
+  const double a = 1.0 + s * dxx, c = 1.0 + s * dyy, b = s * dxy;
+  const double det = a * c - b * b;
+  const double num = (c * (dx * dx) - 2.0 * b * (dx * dy)) + a * (dy * dy);
+  const double q = num / det;
+  const bool plain = !(det > 0.0) || !(a >= 1.0) || !(c >= 1.0) || !__builtin_isfinite(q);
+  return plain ? dx * dx + dy * dy : q;
+}
+
+// kGated: stage (1) tests gated_dist_sq instead of the plain squared distance; `gate` holds, per query, three planes of n doubles
+// (dxx, dxy, dyy of every scan: lane i reads gate[.. + i], a wave 512 bytes in a row per plane).  Stages (2) and (3) are shared.
+template <bool kGated>
 __global__ __launch_bounds__(256) void k_loop_candidates(
   GraphDev g, const int32_t * __restrict__ queries, const int32_t * __restrict__ starts, double max_sq_plus, double max_sq_minus,
-  int32_t min_chain, int32_t n_visit, uint8_t * flags_all, int32_t * frontier_all, int32_t * chain_count, int32_t * chains, int32_t cap_per_query)
+  int32_t min_chain, int32_t n_visit, uint8_t * flags_all, int32_t * frontier_all, int32_t * chain_count, int32_t * chains, int32_t cap_per_query,
+  const double * __restrict__ gate, double gate_s)
 {
   const int qi = blockIdx.x;
   const int q = queries[qi];
@@ -60,9 +80,15 @@ __global__ __launch_bounds__(256) void k_loop_candidates(
   __shared__ int32_t s_cur_n, s_nxt_n, s_out_n, s_stop;
   const double qx = g.xy[2 * q], qy = g.xy[2 * q + 1];
   // (1) distance flags
+  const double * gxx = kGated ? gate + (size_t)qi * 3 * n : nullptr;
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
     const double dx = g.xy[2 * i] - qx, dy = g.xy[2 * i + 1] - qy;
-    const double d2 = dx * dx + dy * dy;
+    double d2;
+    if constexpr (kGated) {
+      d2 = gated_dist_sq(dx, dy, gate_s, gxx[i], gxx[(size_t)n + i], gxx[2 * (size_t)n + i]);
+    } else {
+      d2 = dx * dx + dy * dy;
+    }
     uint8_t f = 0;
     if (d2 < max_sq_plus) {f |= kInRange;}
     if (d2 <= max_sq_minus) {f |= kVisitable;}
@@ -362,6 +388,8 @@ struct kh_graph
   int32_t * d_frontier = nullptr; size_t cap_frontier = 0;
   int32_t * d_count = nullptr; size_t cap_count = 0;
   int32_t * d_chains = nullptr; size_t cap_chains = 0;
+  double * d_gate = nullptr; size_t cap_gate = 0;      // kh_graph_find_loop_candidates_gated: per query the planes dxx | dxy | dyy (3n)
+  std::vector<double> h_gate;                          // ... as packed for the upload
   double last_ms = 0.0;
   hipEvent_t ev[2] = {nullptr, nullptr};
   // host copy of the store: the neighbourhood walks of FindNearChains touch tens of vertices (no kernel)
@@ -421,7 +449,7 @@ void kh_graph_destroy(kh_graph * g)
   (void)hipFree(g->d_flags); (void)hipFree(g->d_frontier); (void)hipFree(g->d_count); (void)hipFree(g->d_chains);
   (void)hipFree(g->d_pose); (void)hipFree(g->d_nb_query); (void)hipFree(g->d_nb_idx); (void)hipFree(g->d_nb_d2);
   (void)hipFree(g->d_rl_flag); (void)hipFree(g->d_rl_prefix); (void)hipFree(g->d_rl_seeds); (void)hipFree(g->d_rl_count);
-  (void)hipFree(g->d_rl_begin); (void)hipFree(g->d_rl_idx);
+  (void)hipFree(g->d_rl_begin); (void)hipFree(g->d_rl_idx); (void)hipFree(g->d_gate);
   if (g->ev[0]) {(void)hipEventDestroy(g->ev[0]);}
   if (g->ev[1]) {(void)hipEventDestroy(g->ev[1]);}
   if (g->stream) {(void)hipStreamDestroy(g->stream);}
@@ -549,12 +577,15 @@ int kh_graph_find_loop_candidates(
            cap_chains, n_chains);
 }
 
+}  // extern "C"
 // One query, answered from the host copy of the store: the same three steps as k_loop_candidates -- the same IEEE
 // operations for the two distance tests, the breadth-first marking of the linked scans, the run rule per scan -- in ~20 us
 // for an 18 000-scan store, where the device round trip (upload of the edited store, launch, two downloads, a stream drain)
 // is ~150 us.  A mapper asks exactly one such question per processed scan; batches of queries go to the kernel.
+// kGated: gate = the query's row as the caller gave it (9 doubles per scan), gate_s = chi2 / r^2 (see gated_dist_sq)
+template <bool kGated>
 static void loop_candidates_host(const kh_graph * g, int32_t q, int32_t start, double max_sq_plus, double max_sq_minus, int32_t min_chain,
-                                 std::vector<std::pair<int32_t, int32_t>> & out)
+                                 std::vector<std::pair<int32_t, int32_t>> & out, const double * gate = nullptr, double gate_s = 0.0)
 {
   const int32_t n = g->n, n_visit = g->n_visit;
   static thread_local std::vector<uint8_t> flags;
@@ -564,7 +595,13 @@ static void loop_candidates_host(const kh_graph * g, int32_t q, int32_t start, d
   const double qx = xy[2 * q], qy = xy[2 * q + 1];
   for (int32_t i = 0; i < n; ++i) {
     const double dx = xy[2 * i] - qx, dy = xy[2 * i + 1] - qy;
-    const double d2 = dx * dx + dy * dy;
+    double d2;
+    if constexpr (kGated) {
+      const double * row = gate + 9 * static_cast<size_t>(i);
+      d2 = gated_dist_sq(dx, dy, gate_s, row[0], row[1], row[4]);
+    } else {
+      d2 = dx * dx + dy * dy;
+    }
     uint8_t f = 0;
     if (d2 < max_sq_plus) {f |= kInRange;}
     if (d2 <= max_sq_minus) {f |= kVisitable;}
@@ -605,9 +642,10 @@ static void loop_candidates_host(const kh_graph * g, int32_t q, int32_t start, d
   }
 }
 
-int kh_graph_find_loop_candidates_from(
+// kh_graph_find_loop_candidates_from (gate = NULL) and kh_graph_find_loop_candidates_gated (gate = n_queries rows of 9 n_scans doubles)
+static int find_loop_candidates(
   kh_graph * g, int32_t n_queries, const int32_t * query_scans, const int32_t * start_scans, double max_distance,
-  int32_t min_chain_size, int32_t * chain_begin, int32_t * chains, int32_t cap_chains, int32_t * n_chains)
+  int32_t min_chain_size, const double * gate, double chi2, int32_t * chain_begin, int32_t * chains, int32_t cap_chains, int32_t * n_chains)
 {
   if (!g || n_queries < 0 || !chain_begin || !n_chains || (n_queries > 0 && !query_scans) || cap_chains < 0 || (cap_chains > 0 && !chains)) {
     return KH_ERR_INVALID_ARG;
@@ -623,7 +661,11 @@ int kh_graph_find_loop_candidates_from(
     if (start_scans && start_scans[0] < 0) {set_error("kh_graph_find_loop_candidates_from: negative start"); return KH_ERR_INVALID_ARG;}
     const double sq1 = max_distance * max_distance;
     std::vector<std::pair<int32_t, int32_t>> v;
-    loop_candidates_host(g, query_scans[0], start_scans ? start_scans[0] : 0, sq1 + kTol, sq1 - kTol, min_chain_size, v);
+    if (gate) {
+      loop_candidates_host<true>(g, query_scans[0], start_scans ? start_scans[0] : 0, sq1 + kTol, sq1 - kTol, min_chain_size, v, gate, chi2 / sq1);
+    } else {
+      loop_candidates_host<false>(g, query_scans[0], start_scans ? start_scans[0] : 0, sq1 + kTol, sq1 - kTol, min_chain_size, v);
+    }
     int32_t total1 = 0;
     for (const auto & ch : v) {                            // already in scan order
       if (total1 < cap_chains) {chains[2 * total1] = ch.first; chains[2 * total1 + 1] = ch.second;}
@@ -665,10 +707,29 @@ int kh_graph_find_loop_candidates_from(
   }
   // Mapper.cpp:1988-1990 and 1326-1327: Square(maxDistance) +/- KT_TOLERANCE
   const double sq = max_distance * max_distance;
+  if (gate) {
+    // the three doubles of a row the test reads, as planes of n per query (dxx | dxy | dyy): a third of the bytes goes up, and lane i
+    // of the kernel reads plane[i] -- consecutive lanes, consecutive addresses -- instead of three loads at a stride of 72 bytes
+    g->h_gate.resize(3 * nq * n);
+    for (size_t qi = 0; qi < nq; ++qi) {
+      const double * row = gate + 9 * n * qi;
+      double * plane = g->h_gate.data() + 3 * n * qi;
+      for (size_t i = 0; i < n; ++i) {plane[i] = row[9 * i]; plane[n + i] = row[9 * i + 1]; plane[2 * n + i] = row[9 * i + 4];}
+    }
+    rc = ensure(g->d_gate, g->cap_gate, 3 * nq * n); if (rc) {return rc;}
+    if (hipMemcpyAsync(g->d_gate, g->h_gate.data(), 3 * nq * n * sizeof(double), hipMemcpyHostToDevice, g->stream) != hipSuccess) {return KH_ERR_HIP;}
+  }
   GraphDev dev{g->n, g->d_xy, g->d_adj_ptr, g->d_adj_idx};
   (void)hipEventRecord(g->ev[0], g->stream);
-  hipLaunchKernelGGL(k_loop_candidates, dim3(static_cast<unsigned>(nq)), dim3(256), 0, g->stream, dev, g->d_queries,
-    start_scans ? g->d_queries + nq : nullptr, sq + kTol, sq - kTol, min_chain_size, g->n_visit, g->d_flags, g->d_frontier, g->d_count, g->d_chains, per_query);
+  if (gate) {
+    hipLaunchKernelGGL(k_loop_candidates<true>, dim3(static_cast<unsigned>(nq)), dim3(256), 0, g->stream, dev, g->d_queries,
+      start_scans ? g->d_queries + nq : nullptr, sq + kTol, sq - kTol, min_chain_size, g->n_visit, g->d_flags, g->d_frontier, g->d_count, g->d_chains, per_query,
+      g->d_gate, chi2 / sq);
+  } else {
+    hipLaunchKernelGGL(k_loop_candidates<false>, dim3(static_cast<unsigned>(nq)), dim3(256), 0, g->stream, dev, g->d_queries,
+      start_scans ? g->d_queries + nq : nullptr, sq + kTol, sq - kTol, min_chain_size, g->n_visit, g->d_flags, g->d_frontier, g->d_count, g->d_chains, per_query,
+      nullptr, 0.0);
+  }
   (void)hipEventRecord(g->ev[1], g->stream);
   std::vector<int32_t> counts(nq), all(nq * per_query * 2);
   if (hipMemcpyAsync(counts.data(), g->d_count, nq * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
@@ -695,6 +756,24 @@ int kh_graph_find_loop_candidates_from(
   }
   *n_chains = total;
   return KH_OK;
+}
+extern "C" {
+
+int kh_graph_find_loop_candidates_from(
+  kh_graph * g, int32_t n_queries, const int32_t * query_scans, const int32_t * start_scans, double max_distance,
+  int32_t min_chain_size, int32_t * chain_begin, int32_t * chains, int32_t cap_chains, int32_t * n_chains)
+{
+  return find_loop_candidates(g, n_queries, query_scans, start_scans, max_distance, min_chain_size, nullptr, 0.0, chain_begin, chains, cap_chains,
+           n_chains);
+}
+
+int kh_graph_find_loop_candidates_gated(
+  kh_graph * g, int32_t n_queries, const int32_t * query_scans, const int32_t * start_scans, double max_distance,
+  int32_t min_chain_size, double chi2, const double * gate, int32_t * chain_begin, int32_t * chains, int32_t cap_chains, int32_t * n_chains)
+{
+  if (!gate || !(chi2 >= 0.0)) {return KH_ERR_INVALID_ARG;}          // (chi2 = NaN fails the comparison)
+  return find_loop_candidates(g, n_queries, query_scans, start_scans, max_distance, min_chain_size, gate, chi2, chain_begin, chains, cap_chains,
+           n_chains);
 }
 
 double kh_graph_last_kernel_ms(kh_graph * g) {return g ? g->last_ms : 0.0;}

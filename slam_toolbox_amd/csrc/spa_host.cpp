@@ -683,8 +683,12 @@ static int prepare_problem(kh_spa * s, SpaDev & dev, bool & has_work)
     // H and g share one buffer so that a sharded run sums them across ranks with ONE all-reduce
     r2 |= s->d_Hg.ensure(static_cast<size_t>(n_slots) * 9 + static_cast<size_t>(nf) * 3 + 8);
     r2 |= s->d_Hg_alt.ensure(static_cast<size_t>(n_slots) * 9 + static_cast<size_t>(nf) * 3 + 8);
+    // (a buffer that grows is a NEW allocation, and the allocator may hand the old address back: "clean" is a fact about the
+    // contents, so it ends with the allocation -- a mapper that asks for a covariance pass per scan grows the fronts between passes)
+    const size_t fronts_cap = s->d_fronts.cap, fronts_b_cap = s->d_fronts_b.cap;
     r2 |= s->d_fronts.ensure(static_cast<size_t>(sym.fronts_size) + 16);
     r2 |= s->d_fronts_b.ensure(static_cast<size_t>(sym.fronts_size) + 16);
+    if (s->d_fronts.cap != fronts_cap || s->d_fronts_b.cap != fronts_b_cap) {s->clean_a = nullptr;}
     r2 |= s->d_scale.ensure(3 * nf); r2 |= s->d_diag.ensure(3 * nf); r2 |= s->d_rhs.ensure(3 * nf);
     r2 |= s->d_step.ensure(3 * nf); r2 |= s->d_delta.ensure(3 * nf);
     r2 |= s->d_fail.ensure(4);
@@ -2173,6 +2177,41 @@ int kh_spa_get_relative_covariances(kh_spa * s, int32_t id_ref, int32_t n, const
   return KH_OK;
 }
 
+int kh_spa_get_difference_covariances(kh_spa * s, int32_t id_ref, int32_t n, const int32_t * ids, double * out)
+{
+  if (n < 0 || (n > 0 && !out)) {return KH_ERR_INVALID_ARG;}
+  if (covariance_device_check() != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!s) {return KH_ERR_INVALID_ARG;}
+  int32_t k = -1;
+  int rc = column_of_query(s, id_ref, k);
+  if (rc) {return rc;}
+  if (!ids && n != static_cast<int32_t>(s->nodes.size())) {
+    set_error("kh_spa_get_difference_covariances: without ids, n must be kh_spa_num_nodes");
+    return KH_ERR_INVALID_ARG;
+  }
+  if (n == 0) {return KH_OK;}
+  // the free indices of the listed nodes go up (no poses: the difference is taken in the world frame), nine doubles per node come back
+  const size_t nn = static_cast<size_t>(n);
+  std::vector<int32_t> free_idx(nn);
+  for (int32_t t = 0; t < n; ++t) {
+    rc = covariance_index(s, ids ? ids[t] : s->nodes[t].id, free_idx[t]);
+    if (rc) {return rc;}
+  }
+  KS_HIP(hipSetDevice(s->device));
+  if (s->d_rel_in.ensure(nn * sizeof(int32_t)) || s->d_rel.ensure(9 * nn)) {return KH_ERR_HIP;}
+  KS_HIP(hipMemcpyAsync(s->d_rel_in.p, free_idx.data(), nn * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+  SpaDev dev;
+  std::memset(&dev, 0, sizeof(dev));
+  dev.n_free = static_cast<int32_t>(s->node_of_free.size());
+  dev.bsr_diag_slot = s->d_bsr_diag.p;
+  spa_launch_cov_difference(dev, s->d_cov.p, s->d_columns.p + 9 * static_cast<size_t>(dev.n_free) * k, s->col_free[k],
+    reinterpret_cast<const int32_t *>(s->d_rel_in.p), n, s->d_rel.p, s->stream);
+  KS_HIP(hipGetLastError());
+  KS_HIP(hipMemcpyAsync(out, s->d_rel.p, 9 * nn * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  KS_HIP(hipStreamSynchronize(s->stream));
+  return KH_OK;
+}
+
 }  // extern "C"
 
 // ---- marginalizing node removal: the constraints of a leaving node composed through it, a round of nodes per launch ------------
@@ -2433,6 +2472,15 @@ bool spa_covariances_valid(const kh_spa * s) {return s && s->cov_valid;}
 bool spa_covariance_column_resident(const kh_spa * s, int32_t id)
 {
   return s && s->cov_valid && std::find(s->col_ids.begin(), s->col_ids.end(), id) != s->col_ids.end();
+}
+// ... and whether node `id` is in the problem of the last covariance pass (the gauge node or a node with constraints): the
+// nodes the covariance getters answer for
+bool spa_covariance_has_node(const kh_spa * s, int32_t id)
+{
+  if (!s || !s->cov_valid) {return false;}
+  const auto it = s->index_of.find(id);
+  if (it == s->index_of.end() || static_cast<size_t>(it->second) >= s->free_of_node.size()) {return false;}
+  return s->free_of_node[it->second] >= 0 || it->second == s->fixed_index;
 }
 }  // namespace kh
 

@@ -149,6 +149,9 @@ void spa_launch_cov_columns_gather(const SpaDev & d, int32_t n_queries, int32_t 
 // column = the reference's block column (n_free blocks)
 void spa_launch_cov_relative(const SpaDev & d, const double * cov, const double * column, int32_t ref_free, const double * ref_pose,
                              const int32_t * free_idx, const double * poses, int32_t n, double * out, void * stream);
+// out[9 t ..] = world-frame covariance of x_t - x_ref, S_tt + S_rr - S_tr - S_tr^T, bit-wise symmetric; arguments as above
+void spa_launch_cov_difference(const SpaDev & d, const double * cov, const double * column, int32_t ref_free, const int32_t * free_idx, int32_t n,
+                               double * out, void * stream);
 // self-cleaning fronts (scatter mode): zero the update matrices of the fronts in `list` (children read in place by their parents)
 void spa_launch_zero_update_blocks(const SpaDev & d, const int32_t * list, int32_t n, int32_t max_m, void * stream);
 // debugging aid: *count += entries of p[0..n) whose bit pattern is not zero

@@ -2886,4 +2886,40 @@ void spa_launch_cov_relative(const SpaDev & d, const double * cov, const double 
   hipLaunchKernelGGL(k_cov_relative, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d, cov, column, ref_free, ref_pose, free_idx, poses, n, out);
 }
 
+// Difference covariances: the covariance of x_i - x_r in the WORLD frame, D = S_ii + S_rr - S_ir - S_ir^T, no pose and no rotation
+// (what a gate over the store's world positions wants).  One thread per listed node; the upper triangle is computed --
+// ((S_ii + S_rr) - S_ir) - S_ri, entry by entry, each operation rounded on its own -- and mirrored, so D is bit-wise symmetric
+// whatever the marginals are.  The gauge node's blocks are zeros; i = r is exact zeros by construction, not by cancellation.
+__global__ __launch_bounds__(256) void k_cov_difference(SpaDev d, const double * __restrict__ cov, const double * __restrict__ column, int ref_free,
+                                                        const int32_t * __restrict__ free_idx, int n, double * out)
+{
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= n) {return;}
+  const int fi = free_idx[t];
+  double srr[9], sii[9], sir[9], o[9];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    srr[q] = ref_free >= 0 ? cov[9 * (int64_t)d.bsr_diag_slot[ref_free] + q] : 0.0;
+    sii[q] = fi >= 0 ? cov[9 * (int64_t)d.bsr_diag_slot[fi] + q] : 0.0;
+    sir[q] = fi >= 0 && ref_free >= 0 ? column[9 * (int64_t)fi + q] : 0.0;
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int c = r; c < 3; ++c) {
+      const double v = fi == ref_free ? 0.0 : ((sii[3 * r + c] + srr[3 * r + c]) - sir[3 * r + c]) - sir[3 * c + r];
+      o[3 * r + c] = v; o[3 * c + r] = v;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {out[9 * (int64_t)t + q] = o[q];}
+}
+void spa_launch_cov_difference(const SpaDev & d, const double * cov, const double * column, int32_t ref_free, const int32_t * free_idx, int32_t n,
+                               double * out, void * stream)
+{
+  if (n <= 0) {return;}
+  hipLaunchKernelGGL(k_cov_difference, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d, cov, column, ref_free, free_idx, n, out);
+}
+
 }  // namespace kh

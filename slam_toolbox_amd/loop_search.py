@@ -72,6 +72,38 @@ class MapperGraphSearch:
         chains = chains.reshape(-1, 2)
         return [[(int(a), int(b)) for a, b in chains[begin[i]: begin[i + 1]]] for i in range(q.size)]
 
+    def find_loop_candidates(self, query_scans, loop_search_maximum_distance, loop_match_minimum_chain_size, starts=None, gate=None,
+                             chi2: float = 0.0):
+        """FindPossibleLoopClosures with the covariance gate (kh_graph_find_loop_candidates_gated): gate is
+        (n_queries, n_scans, 3, 3) -- per query and scan, in list order, the world-frame covariance of the scan's displacement from
+        the query -- and chi2 the size of the ellipse the search disk is widened by.  gate=None is the ungated call."""
+        if gate is None:
+            return self.FindPossibleLoopClosures(query_scans, loop_search_maximum_distance, loop_match_minimum_chain_size, starts)
+        q = np.ascontiguousarray(query_scans, dtype=np.int32)
+        gate = np.ascontiguousarray(gate, dtype=np.float64)
+        if gate.size != q.size * self.n * 9:
+            raise ValueError("gate must hold 9 doubles per query and scan")
+        startp = None
+        if starts is not None:
+            starts = np.ascontiguousarray(starts, dtype=np.int32)
+            if starts.shape != q.shape:
+                raise ValueError("one start per query")
+            startp = starts.ctypes.data_as(C.c_void_p)
+        begin = np.zeros(q.size + 1, dtype=np.int32)
+        cap = max(16, 4 * q.size)
+        total = C.c_int32(0)
+        while True:
+            chains = np.zeros(2 * cap, dtype=np.int32)
+            capi.check(capi.lib().kh_graph_find_loop_candidates_gated(
+                self._h, q.size, q.ctypes.data_as(C.c_void_p), startp, float(loop_search_maximum_distance), int(loop_match_minimum_chain_size),
+                float(chi2), gate.ctypes.data_as(C.c_void_p), begin.ctypes.data_as(C.c_void_p), chains.ctypes.data_as(C.c_void_p), cap,
+                C.byref(total)), "kh_graph_find_loop_candidates_gated")
+            if total.value <= cap:
+                break
+            cap = total.value
+        chains = chains.reshape(-1, 2)
+        return [[(int(a), int(b)) for a, b in chains[begin[i]: begin[i + 1]]] for i in range(q.size)]
+
     def FindNearChains(self, query_scan, link_scan_maximum_distance):
         """MapperGraph::FindNearChains (Mapper.cpp:1683-1793) -> [(first, last), ...] in the reference's order."""
         cap = 64

@@ -302,6 +302,48 @@ class Mapper:
         capi.check(rc, "kh_mapper_get_relative_covariances")
         return out[:n]
 
+    def difference_covariances(self, ref, ids=None) -> np.ndarray:
+        """(n, 3, 3): world-frame covariance of x_i - x_ref for the listed scans (None: every solver node, insertion order):
+        kh_mapper_get_difference_covariances, lazy like relative_covariances."""
+        L = capi.lib()
+        if ids is None:
+            n, idp = L.kh_spa_num_nodes(L.kh_mapper_solver(self._h)), None
+        else:
+            idv = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+            n, idp = idv.size, idv.ctypes.data_as(C.c_void_p)
+        out = np.zeros((max(n, 1), 3, 3))
+        s = capi.KhSpaCovColumnsSummary()
+        rc = L.kh_mapper_get_difference_covariances(self._h, int(ref), n, idp, out.ctypes.data_as(C.c_void_p), C.byref(s))
+        self.cov_columns_summary = {k: getattr(s, k) for k, _ in capi.KhSpaCovColumnsSummary._fields_ if k != "cov"}
+        self.cov_columns_summary["cov"] = {k: getattr(s.cov, k) for k, _ in capi.KhSpaCovSummary._fields_ if k != "pad"}
+        capi.check(rc, "kh_mapper_get_difference_covariances")
+        return out[:n]
+
+    def SetLoopGate(self, enabled: bool = True, **params):
+        """kh_mapper_set_loop_gate: the loop search gated by the pose graph's covariances.  params: fields of
+        kh_loop_gate_params (refresh_scans, chi2_position, chi2_jump, covariance_scale, max_reach) over the defaults of this
+        mapper's parameters.  Not stored in a session: set it again after load."""
+        g = capi.KhLoopGateParams()
+        capi.lib().kh_loop_gate_params_default(C.byref(self.params()), C.byref(g))
+        for k, v in params.items():
+            if k == "enabled" or not hasattr(g, k):
+                raise KeyError(k)
+            setattr(g, k, v)
+        g.enabled = 1 if enabled else 0
+        capi.check(capi.lib().kh_mapper_set_loop_gate(self._h, C.byref(g)), "kh_mapper_set_loop_gate")
+
+    def loop_gate(self) -> dict:
+        g = capi.KhLoopGateParams()
+        capi.check(capi.lib().kh_mapper_get_loop_gate(self._h, C.byref(g)), "kh_mapper_get_loop_gate")
+        return {k: getattr(g, k) for k, _ in capi.KhLoopGateParams._fields_}
+
+    def loop_gate_stats(self) -> dict:
+        """column passes run for the gate and their wall time, searches left ungated, chains the jump test rejected, the largest
+        semi-axis (m) a prepared row had"""
+        st = capi.KhLoopGateStats()
+        capi.check(capi.lib().kh_mapper_get_loop_gate_stats(self._h, C.byref(st)), "kh_mapper_get_loop_gate_stats")
+        return {k: getattr(st, k) for k, _ in capi.KhLoopGateStats._fields_}
+
     def stats(self) -> dict:
         st = capi.KhMapperStats()
         capi.check(capi.lib().kh_mapper_get_stats(self._h, C.byref(st)), "kh_mapper_get_stats")

@@ -49,14 +49,16 @@ class LapQueue:
 
 def run(n_scans: int, lifelong: bool = True, mode: str = "sync", period_s: float = 0.025, device: int = 0,
         max_candidates: int = 32, map_resolution: float = 0.05, progress=None, devices=None, queue=None, save_session=None,
-        save_at=None, load_session=None, marginalize: bool = False, **mapper_params):
+        save_at=None, load_session=None, marginalize: bool = False, loop_gate: dict = None, **mapper_params):
     """Replays the queue; returns a dict with the throughput, the mapper's own statistics and the map agreement.
     save_session: the mapper is saved there (Mapper.save) behind queue scan `save_at` (default: the last one), with the replay's
     own bookkeeping -- how far the queue got, which queue scan every scan id came from -- beside it in <path>.replay.json;
     load_session: the run starts from such a pair instead of an empty mapper and continues with the rest of the SAME queue
     (same n_scans; the session carries its own parameters and lifelong switch).
     marginalize: node decay hands a leaving scan's constraints on to its neighbours (Mapper.SetRemovalMode; not part of a session,
-    so it is set again on a loaded mapper)."""
+    so it is set again on a loaded mapper).
+    loop_gate: parameters of Mapper.SetLoopGate (an empty dict: its defaults); the result then carries "loop_gate_stats".  Not
+    part of a session either."""
     import json
     from .mapper import Mapper
     from .occupancy_grid import OccupancyGrid
@@ -75,6 +77,8 @@ def run(n_scans: int, lifelong: bool = True, mode: str = "sync", period_s: float
             m.SetLifelong(True)
     if marginalize:
         m.SetRemovalMode(True)
+    if loop_gate is not None:
+        m.SetLoopGate(True, **loop_gate)
     # the queue is made up front so that the timed region holds the mapper, not the ray casting
     all_ranges = [q.ranges(i) for i in range(n_scans)]
     t0 = time.perf_counter()
@@ -114,6 +118,7 @@ def run(n_scans: int, lifelong: bool = True, mode: str = "sync", period_s: float
                   f"{time.perf_counter() - t0:.1f} s", flush=True)
     wall = time.perf_counter() - t0
     st = m.stats()
+    gate_st = m.loop_gate_stats() if loop_gate is not None else None
     alive = m.alive()
     # connected components of the pose graph that is left (node decay removes vertices with their edges: nothing in
     # LifelongSlamToolbox::evaluateNodeDepreciation keeps the graph connected)
@@ -199,6 +204,8 @@ def run(n_scans: int, lifelong: bool = True, mode: str = "sync", period_s: float
     out["ms_split"] = {"match": st["match_ms"], "solver": st["solver_ms"], "pose_updates": st["update_ms"], "node_decay": st["lifelong_ms"],
                        "other_in_process": st["process_ms"] - known, "process_total": st["process_ms"],
                        "outside_process_python_ctypes": (wall - waited_s) * 1e3 - st["process_ms"], "wall": (wall - waited_s) * 1e3}
+    if gate_st is not None:
+        out["loop_gate_stats"] = gate_st
     out["poses"] = poses
     out["alive_queue_index"] = [queue_index[k] for k in alive]
     ref_grid.close()

@@ -213,6 +213,15 @@ class HipSpaSolver:
                    "kh_spa_get_relative_covariances")
         return out[:n]
 
+    def DifferenceCovariances(self, ref: int, ids=None):
+        """(n, 3, 3): world-frame covariance of x_i - x_ref for every listed node, S_ii + S_rr - S_ir - S_ir^T, on the device
+        (kh_spa_get_difference_covariances); `ref` must be a query of the last ComputeCovarianceColumns.  Bit-wise symmetric."""
+        n, idp, _keep = self._id_list(ids)
+        out = np.zeros((max(n, 1), 3, 3))
+        capi.check(capi.lib().kh_spa_get_difference_covariances(self._h, int(ref), n, idp, out.ctypes.data_as(C.c_void_p)),
+                   "kh_spa_get_difference_covariances")
+        return out[:n]
+
     def iteration_log(self):
         """(n, 8) array: the trust-region iterations of the last Compute() (kh_spa_iteration_log: iteration, cost, candidate cost,
         model cost change, radius used, radius after, step norm, verdict)."""
