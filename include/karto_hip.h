@@ -410,6 +410,30 @@ KH_API int kh_spa_get_relative_covariances(kh_spa * s, int32_t id_ref, int32_t n
  * node's blocks are zeros, as k or as the reference; ids[k] = id_ref: exact zeros.  Argument checks, ids = NULL and staleness as
  * kh_spa_get_relative_covariances. */
 KH_API int kh_spa_get_difference_covariances(kh_spa * s, int32_t id_ref, int32_t n, const int32_t * ids, double * out /* 9n */);
+/* ---- constraint audit (no counterpart in the reference, whose only remedy for a false loop closure is a person dragging nodes;
+ * DESIGN.md section 7i): the leave-one-out test of every constraint that is already in the graph, from the resident selected
+ * inverse.  For constraint e between a and b, with r (3) the whitened, loss-weighted residual and A = [Ja Jb] (3 x 6) of the
+ * linearisation at the current poses, and Sigma(ab, ab) the joint covariance of the two poses (a gauge end: no Jacobian, zeros):
+ *   chi2        r^T r: what the constraint costs now
+ *   redundancy  trace(M), M = I - A Sigma(ab, ab) A^T, in [0, 3]: how much of the constraint the rest of the graph checks
+ *   min_pivot   the smallest pivot of the lower Cholesky factorisation of M in the order 0, 1, 2, which stops at the first pivot
+ *               that is not > min_redundancy (a NaN is not); the failing pivot is included
+ *   verifiable  1 when all three pivots are > min_redundancy.  0: a bridge, or the only constraint that fixes some direction --
+ *               nothing else in the graph has an opinion on it, and removing it would cut the graph or leave it underdetermined
+ *   chi2_loo    r^T M^-1 r, chi-square (3 degrees of freedom) of the constraint against the graph WITHOUT it (the linear
+ *               leave-one-out identity e_loo = M^-1 e, cov = M^-1); -1 when not verifiable
+ * k_edge_audit, one thread per constraint; an edge's figures do not depend on which other edges are audited with it.  Under a
+ * robust loss r and A carry the loss weights: a down-weighted outlier looks milder, which is the loss at work. */
+typedef struct kh_spa_audit_t { int32_t index, id_a, id_b, verifiable; double chi2, redundancy, min_pivot, chi2_loo; } kh_spa_audit_t;
+typedef struct kh_spa_audit_summary { kh_spa_cov_summary cov; /* the pass this call ran, zeros when it rode on a resident one */
+  int32_t n_constraints, n_verifiable; double kernel_ms /* HIP events under debug bit 1, else 0 */, total_ms; } kh_spa_audit_summary;
+/* out: kh_spa_num_constraints records in constraint insertion order (index = the index of kh_spa_get_constraint).  Runs
+ * kh_spa_compute_covariances itself when no valid marginals are resident -- its refusals (KH_ERR_SOLVER) are this call's -- and
+ * leaves them resident; otherwise it rides on them.  The linearisation of the audit covers all edges, on a sharded solver too,
+ * in a buffer of its own: the call is bit-neutral for every kh_spa_compute and covariance getter around it.  min_redundancy
+ * must be finite and in (0, 1) (1e-6 is a good value), out not NULL: KH_ERR_INVALID_ARG before a device is looked for; then
+ * KH_ERR_NO_DEVICE, then the handle.  A graph without constraints: KH_OK and no records.  summary may be NULL. */
+KH_API int kh_spa_audit_constraints(kh_spa * s, double min_redundancy, kh_spa_audit_t * out /* kh_spa_num_constraints */, kh_spa_audit_summary * summary);
 /* ---- marginalizing node removal (no counterpart in the reference, whose RemoveNode drops the node's constraints and transfers
  * nothing: a lifelong graph falls apart).  Every listed node leaves like kh_spa_remove_node, but first its constraints are composed
  * through it into constraints among its neighbours: parallel constraints to one neighbour are fused; the
@@ -851,6 +875,50 @@ KH_API void kh_loop_gate_params_default(const kh_mapper_params * params, kh_loop
 KH_API int kh_mapper_set_loop_gate(kh_mapper * m, const kh_loop_gate_params * gate);
 KH_API int kh_mapper_get_loop_gate(const kh_mapper * m, kh_loop_gate_params * gate);
 KH_API int kh_mapper_get_loop_gate_stats(const kh_mapper * m, kh_loop_gate_stats * out);
+/* ---- single-edge edits, the constraint audit and outlier rejection (no counterpart in the reference).
+ * kh_mapper_add_edge + kh_mapper_correct_poses are the interactive node's "manual loop closure".
+ * kh_mapper_add_edge: MapperGraph::LinkScans made public.  mean_sensor_pose = the SENSOR pose of `to` the constraint asserts, as
+ *   LinkChainToScan passes it, cov its covariance; the duplicate test of AddEdge (an edge from -> to exists: nothing is attached,
+ *   KH_OK) and the `C` log line are LinkScans'.  correct != 0: kh_mapper_correct_poses afterwards.  A dead or unknown scan, or
+ *   from == to: KH_ERR_NOT_FOUND; a NULL or non-finite mean or cov: KH_ERR_INVALID_ARG before the device is looked for.
+ * kh_mapper_remove_edge: the edge with that source and target leaves the adjacency of both scans, the edge list and the solver
+ *   (kh_spa_remove_constraint), with the `E from to` log line of a node removal.  KH_ERR_NOT_FOUND (nothing changed) when there is
+ *   no such edge -- the direction counts.
+ * kh_mapper_correct_poses: MapperGraph::CorrectPoses -- solve, every scan re-posed and re-projected.
+ * kh_mapper_audit: kh_spa_audit_constraints on the mapper's solver (node ids are scan ids); *n = the number of constraints, which
+ *   cap must hold (KH_ERR_INVALID_ARG otherwise, *n still set). */
+KH_API int kh_mapper_add_edge(kh_mapper * m, int32_t from, int32_t to, const double mean_sensor_pose[3], const double cov[9], int32_t correct);
+KH_API int kh_mapper_remove_edge(kh_mapper * m, int32_t from, int32_t to);
+KH_API int kh_mapper_correct_poses(kh_mapper * m);
+KH_API int kh_mapper_audit(kh_mapper * m, double min_redundancy, kh_spa_audit_t * out, int32_t cap, int32_t * n, kh_spa_audit_summary * summary);
+/* Outlier rejection.  Each round: kh_mapper_correct_poses, then the audit; the candidates are the verifiable constraints with
+ * |id_a - id_b| >= min_id_gap (odometry is exempt: on a cycle that only a false closure closes every edge of the cycle has the
+ * same chi2_loo); top = their largest chi2_loo; top <= chi2 ends the loop; otherwise, among the candidates with
+ * chi2_loo >= (1 - tie) top, the one with the highest constraint index -- the constraint added last is the one the graph was
+ * consistent without -- leaves through kh_mapper_remove_edge, and the next round begins.  When the rounds run out behind a
+ * removal a final kh_mapper_correct_poses follows, so the poses are always those of a solve after the last removal.  An
+ * unverifiable constraint is never removed: the number of connected components cannot grow and the solver never loses a pinned
+ * direction.  removed[k]: the record of the k-th removal as audited in the round that removed it; more removals than cap:
+ * KH_ERR_INVALID_ARG (the graph keeps the removals made).  The loop gate, when on, refreshes at the next scan. */
+typedef struct kh_reject_params {
+  double chi2;                  /* >= 0; 16.266 = 99.9 % of chi-square, 3 degrees of freedom */
+  double min_redundancy;        /* in (0, 1); 1e-6 */
+  double tie;                   /* in [0, 1); 1e-6: candidates within this relative distance of the top are tied */
+  int32_t min_id_gap;           /* >= 1; 2: consecutive scans (odometry) are no candidates */
+  int32_t max_rounds;           /* >= 1; 8 */
+} kh_reject_params;
+typedef struct kh_reject_summary {
+  int32_t rounds;               /* audits run */
+  int32_t n_removed;
+  double max_chi2_loo;          /* the largest chi2_loo among the candidates of the last audit (0: no candidate) */
+  double solve_ms, audit_ms;    /* wall time of the kh_mapper_correct_poses calls / of the audits (covariance pass included) */
+  double total_ms;
+} kh_reject_summary;
+KH_API void kh_reject_params_default(kh_reject_params * params);
+/* params = NULL: the defaults.  min_id_gap < 1, max_rounds < 1, tie outside [0, 1), min_redundancy outside (0, 1), chi2 < 0, a
+ * non-finite parameter, cap < 0 or removed = NULL with cap > 0: KH_ERR_INVALID_ARG before the device is looked for; then
+ * KH_ERR_NO_DEVICE, then the handle. */
+KH_API int kh_mapper_reject_outliers(kh_mapper * m, const kh_reject_params * params, kh_spa_audit_t * removed, int32_t cap, kh_reject_summary * summary);
 /* every solver call the mapper makes, one line each, in the format oracle/ref_slam_driver.cpp logs the reference
  * Mapper's calls with (N id pose, C a b z cov, X n ms, P id pose, K): the two logs of one scan queue must agree */
 KH_API int kh_mapper_set_log(kh_mapper * m, const char * path);

@@ -73,6 +73,30 @@ class KhSpaCovColumnsSummary(C.Structure):
                 ("forward_ms", C.c_double), ("backward_ms", C.c_double), ("total_ms", C.c_double), ("column_flops", C.c_int64)]
 
 
+class KhSpaAudit(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("index", "id_a", "id_b", "verifiable")] + \
+               [(k, C.c_double) for k in ("chi2", "redundancy", "min_pivot", "chi2_loo")]
+
+
+# the records of kh_spa_audit_constraints as a structured array (same layout as KhSpaAudit)
+AUDIT_DTYPE = np.dtype([(k, np.int32) for k in ("index", "id_a", "id_b", "verifiable")] +
+                       [(k, np.float64) for k in ("chi2", "redundancy", "min_pivot", "chi2_loo")])
+
+
+class KhSpaAuditSummary(C.Structure):
+    _fields_ = [("cov", KhSpaCovSummary), ("n_constraints", C.c_int32), ("n_verifiable", C.c_int32),
+                ("kernel_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+class KhRejectParams(C.Structure):
+    _fields_ = [("chi2", C.c_double), ("min_redundancy", C.c_double), ("tie", C.c_double), ("min_id_gap", C.c_int32), ("max_rounds", C.c_int32)]
+
+
+class KhRejectSummary(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("n_removed", C.c_int32), ("max_chi2_loo", C.c_double), ("solve_ms", C.c_double),
+                ("audit_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 KH_SPA_MAX_COV_COLUMNS = 64
 
 
@@ -133,6 +157,8 @@ SYMBOLS = [
     "kh_spa_marginalize_nodes", "kh_mapper_marginalize_nodes", "kh_mapper_set_removal_mode",
     "kh_spa_get_difference_covariances", "kh_mapper_get_difference_covariances", "kh_graph_find_loop_candidates_gated",
     "kh_loop_gate_params_default", "kh_mapper_set_loop_gate", "kh_mapper_get_loop_gate", "kh_mapper_get_loop_gate_stats",
+    "kh_spa_audit_constraints", "kh_mapper_add_edge", "kh_mapper_remove_edge", "kh_mapper_correct_poses", "kh_mapper_audit",
+    "kh_reject_params_default", "kh_mapper_reject_outliers",
 ]
 
 
@@ -360,6 +386,15 @@ def lib():
         L.kh_mapper_set_loop_gate.argtypes = [vp, C.POINTER(KhLoopGateParams)]
         L.kh_mapper_get_loop_gate.argtypes = [vp, C.POINTER(KhLoopGateParams)]
         L.kh_mapper_get_loop_gate_stats.argtypes = [vp, C.POINTER(KhLoopGateStats)]
+    if hasattr(L, "kh_spa_audit_constraints"):
+        L.kh_spa_audit_constraints.argtypes = [vp, dbl, vp, C.POINTER(KhSpaAuditSummary)]
+        L.kh_mapper_add_edge.argtypes = [vp, i32, i32, vp, vp, i32]
+        L.kh_mapper_remove_edge.argtypes = [vp, i32, i32]
+        L.kh_mapper_correct_poses.argtypes = [vp]
+        L.kh_mapper_audit.argtypes = [vp, dbl, vp, i32, C.POINTER(i32), C.POINTER(KhSpaAuditSummary)]
+        L.kh_reject_params_default.argtypes = [C.POINTER(KhRejectParams)]
+        L.kh_reject_params_default.restype = None
+        L.kh_mapper_reject_outliers.argtypes = [vp, C.POINTER(KhRejectParams), vp, i32, C.POINTER(KhRejectSummary)]
     if hasattr(L, "kh_spa_marginalize_nodes"):
         L.kh_spa_marginalize_nodes.argtypes = [vp, i32, vp, C.POINTER(KhMarginalizeSummary)]
         L.kh_mapper_marginalize_nodes.argtypes = [vp, i32, vp]
@@ -517,6 +552,12 @@ def lib():
         L.kh_occupancy_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(dbl), C.POINTER(C.c_int64)]
     _lib = L
     return L
+
+
+def audit_summary_dict(s):
+    out = {k: getattr(s, k) for k, _ in KhSpaAuditSummary._fields_ if k != "cov"}
+    out["cov"] = {k: getattr(s.cov, k) for k, _ in KhSpaCovSummary._fields_ if k != "pad"}
+    return out
 
 
 def check(code, where):

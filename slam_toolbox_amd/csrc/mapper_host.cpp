@@ -1479,6 +1479,144 @@ int kh_mapper_set_removal_mode(kh_mapper * m, int32_t mode)
   return KH_OK;
 }
 
+// ---- single-edge edits, the constraint audit and the rejection loop ----
+static bool scan_alive(const kh_mapper * m, int32_t id) {return id >= 0 && id < static_cast<int32_t>(m->scans.size()) && m->scans[id];}
+
+int kh_mapper_correct_poses(kh_mapper * m)
+{
+  if (kh::require_device(0) != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!m) {return KH_ERR_INVALID_ARG;}
+  const int rc = kh::correct_poses(m);
+  m->gate_due = true;                                // the poses may have moved: the gate's covariances are no longer theirs
+  return rc;
+}
+
+int kh_mapper_add_edge(kh_mapper * m, int32_t from, int32_t to, const double mean_sensor_pose[3], const double cov[9], int32_t correct)
+{
+  if (!mean_sensor_pose || !cov) {return KH_ERR_INVALID_ARG;}
+  for (int k = 0; k < 3; ++k) {if (!std::isfinite(mean_sensor_pose[k])) {return KH_ERR_INVALID_ARG;}}
+  for (int k = 0; k < 9; ++k) {if (!std::isfinite(cov[k])) {return KH_ERR_INVALID_ARG;}}
+  if (kh::require_device(0) != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!m) {return KH_ERR_INVALID_ARG;}
+  if (!scan_alive(m, from) || !scan_alive(m, to) || from == to) {
+    kh::set_error("AddEdge: Failed to find the two scans");
+    return KH_ERR_NOT_FOUND;
+  }
+  int rc = kh::link_scans(m, from, to, mean_sensor_pose, cov);
+  if (rc) {return rc;}
+  m->gate_due = true;
+  return correct ? kh_mapper_correct_poses(m) : KH_OK;
+}
+
+int kh_mapper_remove_edge(kh_mapper * m, int32_t from, int32_t to)
+{
+  if (kh::require_device(0) != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!m) {return KH_ERR_INVALID_ARG;}
+  if (!scan_alive(m, from) || !scan_alive(m, to)) {kh::set_error("RemoveEdge: Failed to find the two scans"); return KH_ERR_NOT_FOUND;}
+  const auto out = std::find(m->out_edges[from].begin(), m->out_edges[from].end(), to);
+  const auto af = std::find(m->adj[from].begin(), m->adj[from].end(), to);
+  const auto at = std::find(m->adj[to].begin(), m->adj[to].end(), from);
+  if (out == m->out_edges[from].end() || af == m->adj[from].end() || at == m->adj[to].end()) {
+    kh::set_error("RemoveEdge: no edge with that source and target");
+    return KH_ERR_NOT_FOUND;
+  }
+  m->out_edges[from].erase(out); m->adj[from].erase(af); m->adj[to].erase(at);
+  --m->n_edges;
+  m->graph_dirty = true;
+  m->gate_due = true;
+  if (m->log) {std::fprintf(m->log, "E %d %d\n", from, to);}
+  const int rc = kh_spa_remove_constraint(m->solver, from, to);
+  return (rc == KH_OK || rc == KH_ERR_NOT_FOUND) ? KH_OK : rc;
+}
+
+int kh_mapper_audit(kh_mapper * m, double min_redundancy, kh_spa_audit_t * out, int32_t cap, int32_t * n, kh_spa_audit_summary * summary)
+{
+  if (summary) {std::memset(summary, 0, sizeof(*summary));}
+  if (n) {*n = 0;}
+  if (!std::isfinite(min_redundancy) || !(min_redundancy > 0.0) || !(min_redundancy < 1.0) || !out || !n || cap < 0) {return KH_ERR_INVALID_ARG;}
+  if (kh::require_device(0) != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!m) {return KH_ERR_INVALID_ARG;}
+  const int32_t nc = kh_spa_num_constraints(m->solver);
+  *n = nc;
+  if (nc > cap) {kh::set_error("kh_mapper_audit: the capacity is below the number of constraints"); return KH_ERR_INVALID_ARG;}
+  return kh_spa_audit_constraints(m->solver, min_redundancy, out, summary);
+}
+
+void kh_reject_params_default(kh_reject_params * p)
+{
+  if (!p) {return;}
+  p->chi2 = 16.266;                                  // 99.9 % of chi-square with 3 degrees of freedom
+  p->min_redundancy = 1e-6; p->tie = 1e-6;
+  p->min_id_gap = 2; p->max_rounds = 8;
+}
+
+int kh_mapper_reject_outliers(kh_mapper * m, const kh_reject_params * params, kh_spa_audit_t * removed, int32_t cap, kh_reject_summary * summary)
+{
+  if (summary) {std::memset(summary, 0, sizeof(*summary));}
+  kh_reject_params p;
+  kh_reject_params_default(&p);
+  if (params) {p = *params;}
+  if (!std::isfinite(p.chi2) || !std::isfinite(p.min_redundancy) || !std::isfinite(p.tie) || !(p.chi2 >= 0.0) || !(p.min_redundancy > 0.0) ||
+    !(p.min_redundancy < 1.0) || !(p.tie >= 0.0) || !(p.tie < 1.0) || p.min_id_gap < 1 || p.max_rounds < 1 || cap < 0 || (cap > 0 && !removed)) {
+    return KH_ERR_INVALID_ARG;
+  }
+  if (kh::require_device(0) != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!m) {return KH_ERR_INVALID_ARG;}
+  const auto t_begin = std::chrono::steady_clock::now();
+  auto ms_since = [](std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+  };
+  kh_reject_summary sum;
+  std::memset(&sum, 0, sizeof(sum));
+  auto finish = [&](int rc) {sum.total_ms = ms_since(t_begin); if (summary) {*summary = sum;} return rc;};
+  std::vector<kh_spa_audit_t> rec;
+  bool solved = true;                                // whether correct_poses has run since the last removal
+  for (int32_t round = 0; round < p.max_rounds; ++round) {
+    ++sum.rounds;
+    auto t0 = std::chrono::steady_clock::now();
+    int rc = kh_mapper_correct_poses(m);
+    sum.solve_ms += ms_since(t0);
+    if (rc) {return finish(rc);}
+    solved = true;
+    rec.resize(static_cast<size_t>(std::max(1, kh_spa_num_constraints(m->solver))));
+    kh_spa_audit_summary as;
+    t0 = std::chrono::steady_clock::now();
+    rc = kh_spa_audit_constraints(m->solver, p.min_redundancy, rec.data(), &as);
+    sum.audit_ms += ms_since(t0);
+    if (rc) {return finish(rc);}
+    // the candidates: verifiable (never a bridge, never the only constraint that pins a direction) and not odometry
+    double top = -1.0;
+    for (int32_t e = 0; e < as.n_constraints; ++e) {
+      const int64_t gap = std::llabs(static_cast<int64_t>(rec[e].id_a) - rec[e].id_b);
+      if (rec[e].verifiable && gap >= p.min_id_gap && rec[e].chi2_loo > top) {top = rec[e].chi2_loo;}
+    }
+    sum.max_chi2_loo = top < 0.0 ? 0.0 : top;
+    if (!(top > p.chi2)) {break;}
+    // near-ties go to the newest constraint: the graph was consistent without the one added last
+    int32_t pick = -1;
+    for (int32_t e = 0; e < as.n_constraints; ++e) {
+      const int64_t gap = std::llabs(static_cast<int64_t>(rec[e].id_a) - rec[e].id_b);
+      if (rec[e].verifiable && gap >= p.min_id_gap && rec[e].chi2_loo >= (1.0 - p.tie) * top) {pick = e;}
+    }
+    if (sum.n_removed >= cap) {
+      kh::set_error("kh_mapper_reject_outliers: more removals than `removed` holds");
+      return finish(KH_ERR_INVALID_ARG);
+    }
+    rc = kh_mapper_remove_edge(m, rec[pick].id_a, rec[pick].id_b);
+    if (rc) {return finish(rc);}
+    removed[sum.n_removed++] = rec[pick];
+    solved = false;
+  }
+  if (!solved) {
+    // the rounds ran out behind a removal: max_chi2_loo is the figure of the audit BEFORE it
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = kh_mapper_correct_poses(m);
+    sum.solve_ms += ms_since(t0);
+    if (rc) {return finish(rc);}
+  }
+  return finish(KH_OK);
+}
+
 void kh_loop_gate_params_default(const kh_mapper_params * params, kh_loop_gate_params * g)
 {
   if (!g) {return;}

@@ -195,6 +195,11 @@ struct kh_spa
   DevBuf<int32_t> d_col_lists;
   DevBuf<uint64_t> d_col_masks;
   DevBuf<char> d_rel_in;
+  // constraint audit (kh_spa_audit_constraints): the audit's own linearisation of all edges and cost slots, what k_edge_audit
+  // leaves (4 doubles and a flag per constraint)
+  DevBuf<double> d_audit_lin, d_audit_cost, d_audit_out;
+  DevBuf<int32_t> d_audit_flag;
+  hipEvent_t ev_audit[2] = {};
   std::vector<int32_t> col_ids, col_free, h_col_lists;
   std::vector<std::vector<double>> h_columns;
   CovColumnsPlan col_plan;
@@ -788,6 +793,7 @@ int kh_spa_create(int32_t device, kh_spa ** out)
   for (auto & row : s->ev_lin) {for (auto & e : row) {KS_HIP(hipEventCreate(&e));}}
   for (auto & e : s->ev_cov) {KS_HIP(hipEventCreate(&e));}
   for (auto & e : s->ev_col) {KS_HIP(hipEventCreate(&e));}
+  for (auto & e : s->ev_audit) {KS_HIP(hipEventCreate(&e));}
   *out = s;
   return KH_OK;
 }
@@ -809,10 +815,12 @@ void kh_spa_destroy(kh_spa * s)
   s->d_step.release(); s->d_delta.release(); s->d_scal.release(); s->d_upd.release(); s->d_fsb.release(); s->d_partial.release(); s->d_Hg_alt.release(); s->d_best.release();
   s->d_zbuf.release(); s->d_cov.release(); s->d_marg_in.release(); s->d_marg_out.release();
   s->d_col_rhs.release(); s->d_columns.release(); s->d_rel.release(); s->d_col_lists.release(); s->d_col_masks.release(); s->d_rel_in.release();
+  s->d_audit_lin.release(); s->d_audit_cost.release(); s->d_audit_out.release(); s->d_audit_flag.release();
   for (auto & row : s->ev_phase) {for (auto & e : row) {if (e) {(void)hipEventDestroy(e);}}}
   for (auto & row : s->ev_lin) {for (auto & e : row) {if (e) {(void)hipEventDestroy(e);}}}
   for (auto & e : s->ev_cov) {if (e) {(void)hipEventDestroy(e);}}
   for (auto & e : s->ev_col) {if (e) {(void)hipEventDestroy(e);}}
+  for (auto & e : s->ev_audit) {if (e) {(void)hipEventDestroy(e);}}
   if (s->h_scal) {(void)hipHostFree(s->h_scal);}
   if (s->h_res) {(void)hipHostFree(s->h_res);}
   if (s->h_upload) {(void)hipHostFree(s->h_upload);}
@@ -2210,6 +2218,69 @@ int kh_spa_get_difference_covariances(kh_spa * s, int32_t id_ref, int32_t n, con
   KS_HIP(hipMemcpyAsync(out, s->d_rel.p, 9 * nn * sizeof(double), hipMemcpyDeviceToHost, s->stream));
   KS_HIP(hipStreamSynchronize(s->stream));
   return KH_OK;
+}
+
+// ---- constraint audit: the leave-one-out test of every constraint from the resident selected inverse ----
+int kh_spa_audit_constraints(kh_spa * s, double min_redundancy, kh_spa_audit_t * out, kh_spa_audit_summary * summary)
+{
+  if (summary) {std::memset(summary, 0, sizeof(*summary));}
+  if (!std::isfinite(min_redundancy) || !(min_redundancy > 0.0) || !(min_redundancy < 1.0) || !out) {
+    set_error("kh_spa_audit_constraints: min_redundancy must lie in (0, 1) and out must not be NULL");
+    return KH_ERR_INVALID_ARG;
+  }
+  if (covariance_device_check() != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!s) {return KH_ERR_INVALID_ARG;}
+  settle(s);
+  const auto t_begin = std::chrono::steady_clock::now();
+  kh_spa_audit_summary sum;
+  std::memset(&sum, 0, sizeof(sum));
+  auto finish = [&](int rc) {
+    sum.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    if (summary) {*summary = sum;}
+    return rc;
+  };
+  const int32_t E = static_cast<int32_t>(s->cons.size());
+  if (E == 0) {return finish(KH_OK);}
+  if (!s->cov_valid) {
+    const int rc = covariance_pass(s, &sum.cov, {}, nullptr, "kh_spa_audit_constraints");
+    if (rc) {return finish(rc);}
+  }
+  // the resident pass left the analysis, the edge arrays and the poses it linearised at (d_x) on the device: cov_valid falls with
+  // every change of the graph or of a pose.  Only what k_edge_lin and k_edge_audit read is filled in.
+  KS_HIP(hipSetDevice(s->device));
+  const size_t ne = static_cast<size_t>(E);
+  if (s->d_audit_lin.ensure(21 * ne) || s->d_audit_cost.ensure(ne) || s->d_audit_out.ensure(4 * ne) || s->d_audit_flag.ensure(ne)) {return finish(KH_ERR_HIP);}
+  SpaDev dev;
+  std::memset(&dev, 0, sizeof(dev));
+  dev.n_nodes = static_cast<int32_t>(s->nodes.size()); dev.n_free = static_cast<int32_t>(s->node_of_free.size()); dev.n_edges = E;
+  dev.edge_a = s->d_edge_a.p; dev.edge_b = s->d_edge_b.p; dev.edge_z = s->d_edge_z.p; dev.edge_u = s->d_edge_u.p;
+  dev.free_of_node = s->d_free_of_node.p; dev.node_of_free = s->d_node_of_free.p;
+  dev.edge_lin = s->d_audit_lin.p; dev.edge_cost = s->d_audit_cost.p;
+  dev.loss_kind = s->opt.loss_function; dev.loss_b = s->opt.loss_scale * s->opt.loss_scale; dev.loss_a = s->opt.loss_scale;
+  dev.n_slots = s->n_slots; dev.bsr_row_ptr = s->d_bsr_row_ptr.p; dev.bsr_col = s->d_bsr_col.p; dev.bsr_diag_slot = s->d_bsr_diag.p;
+  const bool events = (s->debug_flags & 2) != 0;
+  if (events) {KS_HIP(hipEventRecord(s->ev_audit[0], s->stream));}
+  spa_launch_edge_audit(dev, s->d_x.p, s->d_cov.p, min_redundancy, s->d_audit_out.p, s->d_audit_flag.p, s->stream);
+  if (events) {KS_HIP(hipEventRecord(s->ev_audit[1], s->stream));}
+  KS_HIP(hipGetLastError());
+  std::vector<double> h_out(4 * ne);
+  std::vector<int32_t> h_flag(ne);
+  KS_HIP(hipMemcpyAsync(h_out.data(), s->d_audit_out.p, 4 * ne * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  KS_HIP(hipMemcpyAsync(h_flag.data(), s->d_audit_flag.p, ne * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+  KS_HIP(hipStreamSynchronize(s->stream));
+  if (events) {
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, s->ev_audit[0], s->ev_audit[1]) == hipSuccess) {sum.kernel_ms = ms;}
+  }
+  for (int32_t e = 0; e < E; ++e) {
+    kh_spa_audit_t & o = out[e];
+    o.index = e; o.id_a = s->cons[e].a; o.id_b = s->cons[e].b; o.verifiable = h_flag[e];
+    o.chi2 = h_out[4 * static_cast<size_t>(e)]; o.redundancy = h_out[4 * static_cast<size_t>(e) + 1];
+    o.min_pivot = h_out[4 * static_cast<size_t>(e) + 2]; o.chi2_loo = h_out[4 * static_cast<size_t>(e) + 3];
+    sum.n_verifiable += h_flag[e] ? 1 : 0;
+  }
+  sum.n_constraints = E;
+  return finish(KH_OK);
 }
 
 }  // extern "C"

@@ -152,6 +152,11 @@ void spa_launch_cov_relative(const SpaDev & d, const double * cov, const double 
 // out[9 t ..] = world-frame covariance of x_t - x_ref, S_tt + S_rr - S_tr - S_tr^T, bit-wise symmetric; arguments as above
 void spa_launch_cov_difference(const SpaDev & d, const double * cov, const double * column, int32_t ref_free, const int32_t * free_idx, int32_t n,
                                double * out, void * stream);
+// Constraint audit: linearises ALL edges at x into audit.edge_lin / audit.edge_cost (buffers of the audit's own: the solver's are
+// not touched), then k_edge_audit, one thread per constraint, against the resident blocks `cov` of Sigma (spa_launch_cov_gather):
+// out[4 e ..] = chi2, redundancy, min_pivot, chi2_loo; flag[e] = verifiable.  Needs n_edges, the edge arrays, free_of_node, the
+// BSR pattern and the loss of `audit`.
+void spa_launch_edge_audit(const SpaDev & audit, const double * x, const double * cov, double min_redundancy, double * out, int32_t * flag, void * stream);
 // self-cleaning fronts (scatter mode): zero the update matrices of the fronts in `list` (children read in place by their parents)
 void spa_launch_zero_update_blocks(const SpaDev & d, const int32_t * list, int32_t n, int32_t max_m, void * stream);
 // debugging aid: *count += entries of p[0..n) whose bit pattern is not zero

@@ -344,6 +344,50 @@ class Mapper:
         capi.check(capi.lib().kh_mapper_get_loop_gate_stats(self._h, C.byref(st)), "kh_mapper_get_loop_gate_stats")
         return {k: getattr(st, k) for k, _ in capi.KhLoopGateStats._fields_}
 
+    # ---- single-edge edits, constraint audit, outlier rejection ----
+    def AddEdge(self, from_scan: int, to_scan: int, mean_sensor_pose, covariance, correct: bool = True):
+        """kh_mapper_add_edge: a manual loop closure.  mean_sensor_pose: the sensor pose of `to_scan` the constraint asserts."""
+        mean = np.ascontiguousarray(mean_sensor_pose, dtype=np.float64).reshape(3)
+        cov = np.ascontiguousarray(covariance, dtype=np.float64).reshape(9)
+        capi.check(capi.lib().kh_mapper_add_edge(self._h, int(from_scan), int(to_scan), mean.ctypes.data_as(C.c_void_p),
+                                                 cov.ctypes.data_as(C.c_void_p), 1 if correct else 0), "kh_mapper_add_edge")
+
+    def RemoveEdge(self, from_scan: int, to_scan: int):
+        """kh_mapper_remove_edge: KartoHipError (KH_ERR_NOT_FOUND) when there is no edge with that source and target"""
+        capi.check(capi.lib().kh_mapper_remove_edge(self._h, int(from_scan), int(to_scan)), "kh_mapper_remove_edge")
+
+    def CorrectPoses(self):
+        capi.check(capi.lib().kh_mapper_correct_poses(self._h), "kh_mapper_correct_poses")
+
+    def audit(self, min_redundancy: float = 1e-6) -> np.ndarray:
+        """kh_mapper_audit: the leave-one-out test of every constraint of the graph (capi.AUDIT_DTYPE, ids are scan ids)"""
+        L = capi.lib()
+        cap = max(L.kh_spa_num_constraints(L.kh_mapper_solver(self._h)), 1)
+        out = np.zeros(cap, dtype=capi.AUDIT_DTYPE)
+        n, s = C.c_int32(0), capi.KhSpaAuditSummary()
+        rc = L.kh_mapper_audit(self._h, float(min_redundancy), out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(s))
+        self.audit_summary = capi.audit_summary_dict(s)
+        capi.check(rc, "kh_mapper_audit")
+        return out[:n.value]
+
+    def RejectOutliers(self, cap: int = 64, **params) -> np.ndarray:
+        """kh_mapper_reject_outliers: rounds of solve + audit, each removing the newest of the verifiable non-odometry constraints
+        tied for the largest chi2_loo while that exceeds `chi2`.  params: fields of kh_reject_params over its defaults.  Returns
+        the records of the removed constraints as audited in the round that removed them; the summary is kept as `reject_summary`."""
+        L = capi.lib()
+        p = capi.KhRejectParams()
+        L.kh_reject_params_default(C.byref(p))
+        for k, v in params.items():
+            if not hasattr(p, k):
+                raise KeyError(k)
+            setattr(p, k, v)
+        out = np.zeros(max(int(cap), 1), dtype=capi.AUDIT_DTYPE)
+        s = capi.KhRejectSummary()
+        rc = L.kh_mapper_reject_outliers(self._h, C.byref(p), out.ctypes.data_as(C.c_void_p), int(cap), C.byref(s))
+        self.reject_summary = {k: getattr(s, k) for k, _ in capi.KhRejectSummary._fields_}
+        capi.check(rc, "kh_mapper_reject_outliers")
+        return out[:s.n_removed]
+
     def stats(self) -> dict:
         st = capi.KhMapperStats()
         capi.check(capi.lib().kh_mapper_get_stats(self._h, C.byref(st)), "kh_mapper_get_stats")

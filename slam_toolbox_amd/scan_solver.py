@@ -222,6 +222,20 @@ class HipSpaSolver:
                    "kh_spa_get_difference_covariances")
         return out[:n]
 
+    # ---- constraint audit (no counterpart in the reference) ---------------------------------------------------------
+    def AuditConstraints(self, min_redundancy: float = 1e-6):
+        """kh_spa_audit_constraints: the leave-one-out test of every constraint, in insertion order, as a structured array
+        (capi.AUDIT_DTYPE: index, id_a, id_b, verifiable, chi2, redundancy, min_pivot, chi2_loo; chi2_loo = -1 where the rest of the
+        graph has no opinion on the constraint).  Runs the covariance pass itself when no valid marginals are resident.  The
+        summary is kept as `audit_summary`."""
+        L = capi.lib()
+        out = np.zeros(max(L.kh_spa_num_constraints(self._h), 1), dtype=capi.AUDIT_DTYPE)
+        s = capi.KhSpaAuditSummary()
+        rc = L.kh_spa_audit_constraints(self._h, float(min_redundancy), out.ctypes.data_as(C.c_void_p), C.byref(s))
+        self.audit_summary = capi.audit_summary_dict(s)
+        capi.check(rc, "kh_spa_audit_constraints")
+        return out[:s.n_constraints]
+
     def iteration_log(self):
         """(n, 8) array: the trust-region iterations of the last Compute() (kh_spa_iteration_log: iteration, cost, candidate cost,
         model cost change, radius used, radius after, step norm, verdict)."""
