@@ -202,6 +202,10 @@ KH_API int kh_matcher_read_lookup(kh_matcher * m, int32_t slot, int32_t * n_angl
  * raw integer sums (GetResponse numerator, Mapper.cpp:1200) and the penalised responses */
 KH_API int kh_matcher_read_volume(kh_matcher * m, int32_t slot, int32_t * nx, int32_t * ny,
                                   int32_t * na, int32_t * out_sums, double * out_responses);
+/* search-space probabilities (m_pSearchSpaceProbs, Mapper.cpp:781-799) of the last COARSE CorrelateScan of `slot`: for every
+ * cell of its lattice the best response over the search angles, ny rows of nx doubles; pass out=NULL to query sizes.
+ * KH_ERR_NOT_FOUND when the slot has run no coarse search.  Host-side state: no GPU work. */
+KH_API int kh_matcher_read_search_probabilities(kh_matcher * m, int32_t slot, int32_t * nx, int32_t * ny, double * out);
 /* bit 0: keep the penalised response volume of every CorrelateScan on the device so that
  * kh_matcher_read_volume can return it (parity tests); bit 1: score EVERY search the LDS-staged kernels can take through
  * them (by default only the large ones: windows of at most 61 bytes x 64 rows with >= 1e8 lookups per search, where they

@@ -115,7 +115,7 @@ SYMBOLS = [
     "kh_matcher_match_batch", "kh_matcher_add_scans", "kh_matcher_correlate", "kh_matcher_correlate_batch",
     "kh_matcher_grid_info", "kh_matcher_read_grid", "kh_matcher_read_kernel", "kh_matcher_read_lookup",
     "kh_matcher_positional_covariance", "kh_matcher_angular_covariance",
-    "kh_matcher_read_volume", "kh_matcher_set_debug", "kh_matcher_stream", "kh_matcher_profile", "kh_matcher_score_loads", "kh_matcher_seq_stats", "kh_matcher_profile_side",
+    "kh_matcher_read_volume", "kh_matcher_read_search_probabilities", "kh_matcher_set_debug", "kh_matcher_stream", "kh_matcher_profile", "kh_matcher_score_loads", "kh_matcher_seq_stats", "kh_matcher_profile_side",
     "kh_matcher_group_create", "kh_matcher_group_destroy", "kh_matcher_group_set_params", "kh_matcher_group_size", "kh_matcher_group_member",
     "kh_matcher_group_device", "kh_matcher_group_match_batch", "kh_loop_closure_batch",
     "kh_spa_options_default", "kh_spa_create", "kh_spa_set_debug", "kh_spa_destroy", "kh_spa_set_options", "kh_spa_reset",
@@ -333,6 +333,8 @@ def lib():
     L.kh_matcher_read_kernel.argtypes = [vp, bptr]
     L.kh_matcher_read_lookup.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), vp]
     L.kh_matcher_read_volume.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp, vp]
+    if hasattr(L, "kh_matcher_read_search_probabilities"):      # (KH_LIBRARY may name a build from before the call existed: A/B runs)
+        L.kh_matcher_read_search_probabilities.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), vp]
     L.kh_matcher_set_debug.argtypes = [vp, i32]
     L.kh_matcher_stream.argtypes = [vp]
     L.kh_matcher_stream.restype = vp

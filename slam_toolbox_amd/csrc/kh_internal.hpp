@@ -119,6 +119,8 @@ struct CorrJob
   int32_t do_penalize;
   int32_t coarse;            // !doingFineMatch: maintain probs (max over angle per (x, y))
   int32_t write_resp;        // also store the penalised response volume (parity tests)
+  int32_t cells_in_score;    // LDS-staged path: K3' keeps probs itself (an atomic maximum per cell and workgroup in its epilogue); K4 is
+                             // the tie scan alone (k_ties_only) and never reads the sums volume back for them
   double denom;              // P * 100 (Mapper.cpp:1204)
   double grid_off_x, grid_off_y, scale;
   // inputs staged by the host (exact libm / reference arithmetic)
@@ -206,6 +208,7 @@ void launch_offsets_lds(const uint8_t * d_jobs, size_t stride, int32_t n_jobs, i
 // full_rows: every job's lattice has more than 32 rows (lds_row_waves = 4)
 void launch_score_lds(const uint8_t * d_jobs, size_t stride, int32_t n_jobs, int32_t max_na, int32_t sx_variant, bool full_rows, void * stream);
 void launch_gather_small(const uint8_t * d_jobs, size_t stride, int32_t n_jobs, int32_t * d_out, int32_t small_stride, void * stream);
-void launch_ties(const uint8_t * d_jobs, size_t stride, int32_t n_jobs, int32_t max_poses, int32_t tile_pairs, void * stream);
+// cells_in_score: every job of the launch has CorrJob::cells_in_score set (one scoring tile per angle): the tie scan alone
+void launch_ties(const uint8_t * d_jobs, size_t stride, int32_t n_jobs, int32_t max_poses, int32_t tile_pairs, bool cells_in_score, void * stream);
 
 }  // namespace kh

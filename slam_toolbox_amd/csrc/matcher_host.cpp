@@ -873,6 +873,8 @@ static int enqueue_chunk(kh_matcher * m, CorrReq * reqs, size_t n, CorrBatch & B
     if (B.use_lds) {
       // the LDS-staged kernel scores an angle's whole lattice in one workgroup: one scoring tile per angle for K4
       job->tiles_x = 1; job->tiles_y = 1; job->ry = 16; job->tile_px = kTileSpan;
+      // ... and keeps the search-space probabilities in its epilogue: K4 is the tie scan alone
+      job->cells_in_score = 1;
     }
     tile_pairs = std::max(tile_pairs, job->na * job->tiles_x * job->tiles_y);
   }
@@ -910,7 +912,7 @@ static int enqueue_chunk(kh_matcher * m, CorrReq * reqs, size_t n, CorrBatch & B
     }
   }
   if (m->profiling) {KH_HIP(hipEventRecord(B.ev[1], cs)); KH_HIP(hipEventRecord(B.evs[2], cs));}
-  launch_ties(B.d_stage, stride, static_cast<int32_t>(n), max_poses, tile_pairs, cs);
+  launch_ties(B.d_stage, stride, static_cast<int32_t>(n), max_poses, tile_pairs, B.use_lds, cs);
   if (m->profiling) {KH_HIP(hipEventRecord(B.evs[3], cs));}
   KH_HIP(hipGetLastError());
   KH_HIP(hipMemcpyAsync(B.h_out, B.d_out, out_words * 8 * n, hipMemcpyDeviceToHost, cs));
@@ -1593,6 +1595,18 @@ int kh_matcher_read_volume(kh_matcher * m, int32_t slot, int32_t * nx, int32_t *
       for (size_t p = 0; p < plane; ++p) {out_responses[p * c.na + a] = tmp[static_cast<size_t>(a) * plane + p];}
     }
   }
+  return KH_OK;
+}
+
+// m_pSearchSpaceProbs as the last COARSE CorrelateScan of `slot` left it: the lattice's cells only (ny rows of nx), from the host's
+// copy -- no GPU work
+int kh_matcher_read_search_probabilities(kh_matcher * m, int32_t slot, int32_t * nx, int32_t * ny, double * out)
+{
+  if (!m || slot < 0 || slot >= m->max_batch || !nx || !ny) {return KH_ERR_INVALID_ARG;}
+  const Slot & s = m->slots[slot];
+  if (!s.has_last_coarse) {set_error("no coarse search has run in this slot"); return KH_ERR_NOT_FOUND;}
+  *nx = s.last_coarse.nx; *ny = s.last_coarse.ny;
+  if (out) {std::copy(s.last_lattice.begin(), s.last_lattice.end(), out);}
   return KH_OK;
 }
 

@@ -3,7 +3,8 @@
 //   k_raster_* K1  AddScans/AddScan/SmearPoint      Mapper.cpp:1032-1105, Mapper.h:1152-1183 (clear, bin, scan, fill, tile)
 //   k_offsets  K2  GridIndexLookup::ComputeOffsets  Karto.h:6844-6894 (+ per-lattice compaction, empty-window skipping)
 //   k_score    K3  operator()(y) + GetResponse      Mapper.cpp:641-694, 1172-1208
-//   k_ties     K4  best-response tie collection     Mapper.cpp:802-817
+//   k_ties     K4  best-response tie collection     Mapper.cpp:802-817 (+ the search-space probabilities, :781-799; behind the
+//                  LDS-staged K3' the tie scan alone, k_ties_only: K3' keeps the probabilities in its epilogue)
 //
 // Build with -ffp-contract=off: the grid-index roundings and the penalty product must see the
 // same IEEE operations, unfused, as the reference's generic x86-64 build.
@@ -1326,7 +1327,9 @@ __global__ __launch_bounds__(256) void k_ties(const uint8_t * jobs, size_t strid
   uint32_t * tie_idx = reinterpret_cast<uint32_t *>(job.out + 2);
   if (job.coarse) {
     // search-space probabilities (Mapper.cpp:781-799): one plain store per cell instead of one atomic maximum per POSE in the
-    // scoring kernel's epilogue (301 401 of them per config-2 match, all on the same 30 KB)
+    // scoring kernel's epilogue (301 401 of them per config-2 match, all on the same 30 KB).  The windowed k_score, mixed chunks and
+    // the fused path keep this pass; the LDS-staged k_score_lds folds its angles per cell first and raises a cell at most once per
+    // workgroup, which pays: its launches end in k_ties_only
     (void)cell_maxima(job, (int)blockIdx.x, (int)gridDim.x, nullptr);
   }
   auto consider = [&](int a, int yi, int xi) {
@@ -1384,9 +1387,59 @@ void launch_gather_small(const uint8_t * d_jobs, size_t stride, int32_t n_jobs, 
   hipLaunchKernelGGL(k_gather_small, dim3(n_jobs), dim3(256), 0, (hipStream_t)stream, d_jobs, stride, d_out, (int)small_stride);
 }
 
-void launch_ties(const uint8_t * d_jobs, size_t stride, int32_t n_jobs, int32_t max_poses, int32_t tile_pairs, void * stream)
+// K4 of the LDS-staged path (CorrJob::cells_in_score: K3' kept the search-space probabilities itself, one scoring tile per angle): the
+// tie scan alone.  Every workgroup reads the job's tile_best -- one double per angle, 81 of them on the config-2 search, 256 at a time
+// (lane = angle) -- and scans its share of the lattice at the few angles whose best ties with the job's; the sums volume is read at those
+// angles only.  Made to sit beside two workgroups of K3' on a compute unit: at most 64 VGPRs (eight waves per SIMD), four words of LDS.
+__global__ __launch_bounds__(256, 8) void k_ties_only(const uint8_t * jobs, size_t stride)
+{
+  const CorrJob & job = *reinterpret_cast<const CorrJob *>(jobs + (size_t)blockIdx.y * stride);
+  const int nx = job.nx, na = job.na;
+  const int plane = nx * job.ny;
+  const double best = __longlong_as_double((long long)job.out[0]);
+  const double * const tile_best = job.tile_best;
+  uint32_t * const tie_idx = reinterpret_cast<uint32_t *>(job.out + 2);
+  __shared__ unsigned long long s_mask[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int a_base = 0; a_base < na; a_base += 256) {
+    const int at = a_base + (int)threadIdx.x;
+    bool tying = false;
+    if (at < na) {
+      const double delta = tile_best[at] - best;
+      tying = delta < 0.0 ? delta >= -1e-06 : delta <= 1e-06;
+    }
+    const unsigned long long mine = __ballot(tying);
+    if (lane == 0) {s_mask[wave] = mine;}
+    __syncthreads();
+    for (int w = 0; w < 4; ++w) {
+      unsigned long long mask = s_mask[w];
+      while (mask) {
+        const int a = a_base + 64 * w + __builtin_ctzll(mask);
+        mask &= mask - 1;
+        for (int p = blockIdx.x * 256 + threadIdx.x; p < plane; p += gridDim.x * 256) {
+          const int yi = p / nx, xi = p - yi * nx;
+          const double response = pose_response(job, job.sums[(size_t)a * plane + p], a, yi, xi);
+          const double delta = response - best;
+          const bool tie = delta < 0.0 ? delta >= -1e-06 : delta <= 1e-06;
+          if (tie) {
+            const unsigned long long slot = atomicAdd(&job.out[1], 1ull);
+            if (slot < (unsigned long long)kTieCap) {tie_idx[slot] = (uint32_t)((size_t)p * na + a);}
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+void launch_ties(const uint8_t * d_jobs, size_t stride, int32_t n_jobs, int32_t max_poses, int32_t tile_pairs, bool cells_in_score, void * stream)
 {
   if (n_jobs <= 0 || max_poses <= 0) {return;}
+  if (cells_in_score) {
+    // a tying angle's lattice (at most 61 x 64 poses) in quarters when jobs are many, in sixteenths when they are few
+    hipLaunchKernelGGL(k_ties_only, dim3(n_jobs >= 16 ? 4 : 16, n_jobs), dim3(256), 0, (hipStream_t)stream, d_jobs, stride);
+    return;
+  }
   int blocks = (max_poses + 255) / 256;
   // every job of the launch has tile bests: pairs per job are few.  A batch: 16 workgroups per job, each taking four of the lattice's 64-cell
   // groups in turn -- the job's fields and the angle penalties fetched once per four groups (64 per job: k_ties 0.095 -> 0.081 ms per launch
@@ -1421,6 +1474,11 @@ void launch_ties(const uint8_t * d_jobs, size_t stride, int32_t n_jobs, int32_t 
 //                      dwords it loaded into accumulator b -- one MFMA per 1 KB read, no unpacking, no VALU in the loop
 //                      besides the four window addresses.  The alignment class (window start & 3) only decides which of a
 //                      wave's four accumulator sets a beam adds to; the sets are merged with their shifts in the epilogue.
+//                      The epilogue forms every pose's exact response (sums, tile_best, out[0] as the windowed kernel writes them)
+//                      and, for coarse searches, keeps the search-space probabilities: the workgroup's two angles folded per
+//                      cell through LDS, the cell read first, one no-return atomic maximum where the fold is larger.
+//   K4  k_ties_only    the tie scan alone: 81 tile_best doubles per job, the lattice of the few angles that tie.  No second
+//                      pass over the sums volume (1.2 MB per config-2 match); 28 registers, 32 bytes of LDS.
 //
 // LDS staging alone (round 1: ds_read_b32 + 4 VALU per dword) lost to the vector ALU, the matrix-core sums alone (round 3)
 // to the L1; together neither is on the critical path.  What is: the waves' own instruction streams (a wave issues one instruction
@@ -1705,6 +1763,12 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 #define KH_PRIO 1
 #endif
 constexpr int kScoreLdsBlocksPerCu = (160 * 1024 - 4096) / (2 * kLdsRegionBytes);      // two regions per workgroup
+// the epilogue's use of the two regions, the chunk loop done: the angles' sums (s_tile, an int32 per pose and angle), and behind them
+// the responses the angle teams hand each other for the per-cell maxima (a double per pose from every team but the cell's owner)
+constexpr int kTilePoses = 64 * kTileSpan;
+static_assert(kGroupAngles * kTilePoses * 4 + (kGroupAngles - 1) * kTilePoses * 8 <= 2 * kLdsRegionBytes,
+  "the sums and the exchanged responses of kGroupAngles angles must fit the workgroup's two LDS regions");
+static_assert((kGroupAngles * kTilePoses * 4) % 8 == 0, "the exchanged responses are doubles");
 static_assert(kScoreLdsBlocksPerCu >= 1 && kScoreLdsBlocksPerCu * kGroupAngles * 4 <= 16, "four waves per SIMD");
 // (__launch_bounds__' second argument: the waves per SIMD the kernel must fit -- four: two workgroups of eight waves per compute unit)
 template <int S, int NW, bool kFull>
@@ -1958,44 +2022,85 @@ __global__ __launch_bounds__(64 * kGroupAngles * NW, 4) void k_score_lds(const u
   const int32_t * const jbx = job.bx, * const jby = job.by;
   const uint8_t * const jgrid = job.grid;
   const int64_t data_size = job.data_size;
+  // Search-space probabilities (Mapper.cpp:781-799; coarse searches): per lattice cell the best response over the angles.  The
+  // responses are all here, so the workgroup folds its kGroupAngles angles cell by cell and raises the cell in the job's result block
+  // with ONE 64-bit unsigned atomic maximum (responses are >= 0: the bits order like the value; K2' stored the zero; the maximum is
+  // order-free, so the cell is the same bits whatever the arrival order) -- and K4 no longer reads the sums volume back to derive
+  // them again.  The angle teams handle the same poses with the same ta, a ROUND of kThreadsPerAngle poses at a time: team q OWNS
+  // the rounds k with k % kGroupAngles == q (a dead second angle still owns its share and contributes zeros), the other teams hand it
+  // their responses through the staged regions, which are free behind s_tile.  The owner reads the cell first, all of its reads in
+  // flight together behind the pose loop (in front of it, beside the penalties, the kernel does not fit its registers): within the
+  // launch a cell only grows, so what the read returns is a lower bound however stale -- an owner whose maximum does not exceed it has
+  // nothing to add, a stale value costs an atomic and never a wrong maximum.  (41 workgroups of a config-2 search meet on the same
+  // 3721 cells.)
+  constexpr int kOwned = (kPosesPerThread + kGroupAngles - 1) / kGroupAngles;
+  constexpr int kRounds = kOwned * kGroupAngles;     // >= kPosesPerThread: the rounds beyond hold no pose (yi >= 64)
+  const bool cells = job.coarse != 0 && job.cells_in_score != 0;
+  typedef __attribute__((address_space(1))) unsigned long long gu64;     // (global_load / global_atomic: vmcnt only)
+  gu64 * const probs = (gu64 *)(job.out + kOutHeaderWords);
+  double * const s_xch = reinterpret_cast<double *>(reinterpret_cast<int32_t *>(s_region) + kGroupAngles * kTilePoses);
+  // slab of s_xch team q writes the response of a round of team `owner` to (the owner reads all kGroupAngles - 1)
+  auto slab_of = [&](int owner) -> int {return kGroupAngles == 2 ? 0 : (q - owner + kGroupAngles) % kGroupAngles - 1;};
   // the distance penalties of this thread's poses first, all in flight together
-  double dpen[kPosesPerThread];
+  double dpen[kRounds];
   const double apen = (live && penal) ? job.ang_pen[a] : 1.0;
 #pragma unroll
-  for (int k = 0; k < kPosesPerThread; ++k) {
+  for (int k = 0; k < kRounds; ++k) {
     const int p = ta + kThreadsPerAngle * k;
     const int yi = p / PX, xi = p % PX;
     dpen[k] = (live && penal && xi < nx && yi < ny) ? job.dist_pen[yi * nx + xi] : 1.0;
   }
+  double mine[kOwned];
+#pragma unroll
+  for (int j = 0; j < kOwned; ++j) {mine[j] = 0.0;}
   __syncthreads();
   const int n_slow = live ? job.counts[kCountsPerAngle * a + kClasses] : 0;
   const int32_t * slow = job.slow + (size_t)(live ? a : 0) * P;
   double best = 0.0;
 #pragma unroll
-  for (int k = 0; k < kPosesPerThread; ++k) {
+  for (int k = 0; k < kRounds; ++k) {
     const int p = ta + kThreadsPerAngle * k;
     const int yi = p / PX, xi = p % PX;
-    if (!live || xi >= nx || yi >= ny) {continue;}
-    int32_t sum = s_tile[p];
-    if (n_slow > 0) {
-      // per-pose range check exactly as GetResponse does it (Mapper.cpp:1192-1197)
-      const int64_t pose = (int64_t)jbx[xi] + (int64_t)jby[yi];
-      for (int j = 0; j < n_slow; ++j) {
-        const int64_t idx = pose + slow[j];
-        if (idx >= 0 && idx < data_size) {sum += jgrid[idx];}
+    if (xi >= nx || yi >= ny) {continue;}
+    const bool owned = k % kGroupAngles == q;
+    double response = 0.0;
+    if (live) {
+      int32_t sum = s_tile[p];
+      if (n_slow > 0) {
+        // per-pose range check exactly as GetResponse does it (Mapper.cpp:1192-1197)
+        const int64_t pose = (int64_t)jbx[xi] + (int64_t)jby[yi];
+        for (int j = 0; j < n_slow; ++j) {
+          const int64_t idx = pose + slow[j];
+          if (idx >= 0 && idx < data_size) {sum += jgrid[idx];}
+        }
       }
+      const size_t o = (size_t)yi * nx + xi;
+      sums_out[o] = sum;
+      // pose_response with the penalties at hand (same operations: Mapper.cpp:1204, 671-685)
+      response = (double)sum / denom;
+      if (penal) {
+        const double delta = response - 0.0;
+        const bool is_zero = delta < 0.0 ? delta >= -1e-06 : delta <= 1e-06;
+        if (!is_zero) {response *= (dpen[k] * apen);}
+      }
+      if (wr_resp) {resp_out[o] = response;}
+      best = response > best ? response : best;
     }
-    const size_t o = (size_t)yi * nx + xi;
-    sums_out[o] = sum;
-    // pose_response with the penalties at hand (same operations: Mapper.cpp:1204, 671-685)
-    double response = (double)sum / denom;
-    if (penal) {
-      const double delta = response - 0.0;
-      const bool is_zero = delta < 0.0 ? delta >= -1e-06 : delta <= 1e-06;
-      if (!is_zero) {response *= (dpen[k] * apen);}
+    if (cells) {
+      if (owned) {mine[k / kGroupAngles] = response;} else {s_xch[slab_of(k % kGroupAngles) * kTilePoses + p] = response;}
     }
-    if (wr_resp) {resp_out[o] = response;}
-    best = response > best ? response : best;
+  }
+  // (the cells of this thread's own rounds as they stand now)
+  unsigned long long seen[kOwned];
+  uint32_t cell[kOwned];                             // kNoCell: the round's pose is none of the lattice's
+  constexpr uint32_t kNoCell = 0xffffffffu;
+#pragma unroll
+  for (int j = 0; j < kOwned; ++j) {
+    const int p = ta + kThreadsPerAngle * (kGroupAngles * j + q);
+    const int yi = p / PX, xi = p % PX;
+    cell[j] = (cells && xi < nx && yi < ny) ? (uint32_t)(yi * nx + xi) : kNoCell;
+    __builtin_assume(cell[j] == kNoCell || cell[j] < 64u * kTileSpan);
+    seen[j] = cell[j] != kNoCell ? __hip_atomic_load(probs + cell[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
   }
 #pragma unroll
   for (int sft = 32; sft > 0; sft >>= 1) {
@@ -2013,6 +2118,31 @@ __global__ __launch_bounds__(64 * kGroupAngles * NW, 4) void k_score_lds(const u
     for (int t = 1; t < NW; ++t) {b = wb[t] > b ? wb[t] : b;}
     if (job.tile_best) {job.tile_best[a] = b;}
     if (b > 0.0) {atomicMax(&job.out[0], (unsigned long long)__double_as_longlong(b));}
+  }
+  if (cells) {
+    // (behind the barrier above: the other teams' responses of this team's rounds are in s_xch.  All the comparisons first, then the
+    // atomics back to back: one wait for the reads above, none between the atomics.  Compare and atomic pose by pose, the compiler
+    // puts a vmcnt(0) in front of every comparison, i.e. a wait for the previous atomic: that form needs 108 registers against 122
+    // and measured 116.3 - 117.5 k matches/s where this one gave 118.6 - 119.4 k, same box, same session)
+    bool raise[kOwned];
+#pragma unroll
+    for (int j = 0; j < kOwned; ++j) {
+      const int p = ta + kThreadsPerAngle * (kGroupAngles * j + q);
+      raise[j] = false;
+      if (cell[j] == kNoCell) {continue;}
+#pragma unroll
+      for (int t = 0; t < kGroupAngles - 1; ++t) {
+        const double o = s_xch[t * kTilePoses + p];
+        mine[j] = o > mine[j] ? o : mine[j];
+      }
+      raise[j] = (unsigned long long)__double_as_longlong(mine[j]) > seen[j];
+    }
+#pragma unroll
+    for (int j = 0; j < kOwned; ++j) {
+      if (raise[j]) {
+        (void)__hip_atomic_fetch_max(probs + cell[j], (unsigned long long)__double_as_longlong(mine[j]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
   }
 }
 

@@ -287,6 +287,18 @@ class ScanMatcher:
                    "read_volume")
         return sums, resp
 
+    def search_probabilities(self, slot=0):
+        """the search-space probabilities of the slot's last COARSE CorrelateScan: per lattice cell the best response over the
+        angles, (ny, nx) doubles (what the positional covariance is computed from)"""
+        nx, ny = C.c_int32(), C.c_int32()
+        capi.check(capi.lib().kh_matcher_read_search_probabilities(self._h, slot, C.byref(nx), C.byref(ny), None),
+                   "read_search_probabilities")
+        out = np.zeros((ny.value, nx.value))
+        capi.check(capi.lib().kh_matcher_read_search_probabilities(self._h, slot, C.byref(nx), C.byref(ny),
+                                                                   out.ctypes.data_as(C.c_void_p)),
+                   "read_search_probabilities")
+        return out
+
     def seq_stats(self):
         """counters of the fused path of ONE MatchScan (kh_matcher_seq_stats)"""
         out = (C.c_int64 * 8)()
