@@ -146,7 +146,7 @@ struct kh_spa
   DevBuf<int32_t> d_edge_a, d_edge_b, d_free_of_node, d_node_of_free, d_slot_contrib_ptr, d_slot_contrib,
     d_bsr_row_ptr, d_bsr_col, d_bsr_diag, d_node_contrib_ptr, d_node_contrib, d_front_m, d_front_ns,
     d_front_first, d_rows_ptr, d_rows, d_child_ptr, d_child_list, d_relpos_ptr, d_relpos, d_slot_ld,
-    d_elim_of_free, d_free_of_elim, d_level_fronts, d_fail, d_sync;
+    d_elim_of_free, d_free_of_elim, d_level_fronts, d_fail;
   DevBuf<int64_t> d_front_off, d_slot_dest, d_winv_off;
   DevBuf<double> d_winv;                       // L11^-T of every front (level pipeline, round 3)
   DevBuf<FrontDesc> d_desc;
@@ -168,7 +168,7 @@ struct kh_spa
   std::vector<int32_t> level_split; std::vector<size_t> level_fused_lds;
   // per level: the most rows any of its fronts has below the pivot block (0: the root -- no update launches)
   std::vector<int32_t> level_max_nu;
-  DevBuf<double> d_upd, d_fsb, d_partial;
+  DevBuf<double> d_upd, d_partial;
   DevBuf<double> d_Hg_alt, d_best;          // normal equations at the candidate point (speculative); minimum-cost iterate
   // multi-GPU: edge-block sharded linearisation, H and g summed by the caller's collective
   int32_t shard_rank = 0, shard_world = 1;
@@ -697,10 +697,8 @@ static int prepare_problem(kh_spa * s, SpaDev & dev, bool & has_work)
     r2 |= s->d_scale.ensure(3 * nf); r2 |= s->d_diag.ensure(3 * nf); r2 |= s->d_rhs.ensure(3 * nf);
     r2 |= s->d_step.ensure(3 * nf); r2 |= s->d_delta.ensure(3 * nf);
     r2 |= s->d_fail.ensure(4);
-    r2 |= s->d_sync.ensure(4 * static_cast<size_t>(sym.n_fronts) + 4);
     r2 |= s->d_upd.ensure(static_cast<size_t>(3) * sym.rows_ptr[sym.n_fronts] + 16);
     r2 |= s->d_partial.ensure(static_cast<size_t>(5) * ((4 * nf + 255) / 256) + (E + 255) / 256 + static_cast<size_t>(2) * ((3 * nf + 255) / 256) + 32);
-    r2 |= s->d_fsb.ensure(static_cast<size_t>(3) * (static_cast<size_t>(nf) + sym.rows_ptr[sym.n_fronts]) + 16);
     if (r2) {(void)hipStreamSynchronize(st); return KH_ERR_HIP;}
     // the uploads above read pageable host vectors of this block: they must have landed before the block ends
     KS_HIP(hipStreamSynchronize(st));
@@ -809,10 +807,10 @@ void kh_spa_destroy(kh_spa * s)
   s->d_front_ns.release(); s->d_front_first.release(); s->d_rows_ptr.release(); s->d_rows.release();
   s->d_child_ptr.release(); s->d_child_list.release(); s->d_relpos_ptr.release(); s->d_relpos.release();
   s->d_slot_ld.release(); s->d_elim_of_free.release(); s->d_free_of_elim.release(); s->d_level_fronts.release();
-  s->d_fail.release(); s->d_sync.release(); s->d_front_off.release(); s->d_slot_dest.release(); s->d_winv_off.release(); s->d_winv.release(); s->d_desc.release(); s->d_cinv.release(); s->d_edge_z.release(); s->d_edge_u.release();
+  s->d_fail.release(); s->d_front_off.release(); s->d_slot_dest.release(); s->d_winv_off.release(); s->d_winv.release(); s->d_desc.release(); s->d_cinv.release(); s->d_edge_z.release(); s->d_edge_u.release();
   s->d_edge_lin.release(); s->d_edge_cost.release(); s->d_Hg.release(); s->d_fronts.release(); s->d_fronts_b.release(); s->d_deferred.release(); s->d_pack.release();
   s->d_x.release(); s->d_cand.release(); s->d_scale.release(); s->d_diag.release(); s->d_rhs.release();
-  s->d_step.release(); s->d_delta.release(); s->d_scal.release(); s->d_upd.release(); s->d_fsb.release(); s->d_partial.release(); s->d_Hg_alt.release(); s->d_best.release();
+  s->d_step.release(); s->d_delta.release(); s->d_scal.release(); s->d_upd.release(); s->d_partial.release(); s->d_Hg_alt.release(); s->d_best.release();
   s->d_zbuf.release(); s->d_cov.release(); s->d_marg_in.release(); s->d_marg_out.release();
   s->d_col_rhs.release(); s->d_columns.release(); s->d_rel.release(); s->d_col_lists.release(); s->d_col_masks.release(); s->d_rel_in.release();
   s->d_audit_lin.release(); s->d_audit_cost.release(); s->d_audit_out.release(); s->d_audit_flag.release();
@@ -1370,7 +1368,6 @@ int launch_factor_levels(kh_spa * s, const SpaDev & dev, bool pipeline)
   hipStream_t st = s->stream;
   const Symbolic & sym = s->sym;
   const int n_levels = static_cast<int>(sym.levels.size());
-  if (!pipeline) {KS_HIP(hipMemsetAsync(s->d_sync.p, 0, sizeof(int32_t) * 4 * static_cast<size_t>(sym.n_fronts), st));}
   constexpr int32_t kNarrowLevel = 128;      // levels of at most this many fronts take the chip-wide extend-add
   for (int l = 0; l < n_levels; ++l) {
     const int32_t n_level = s->level_offsets[l + 1] - s->level_offsets[l];
@@ -1392,8 +1389,43 @@ int launch_factor_levels(kh_spa * s, const SpaDev & dev, bool pipeline)
     // narrow levels: the extend-add runs chip-wide in its own launch instead of on each front's single CU
     const bool split = l > 0 && n_level <= kNarrowLevel;
     if (split) {spa_launch_extend_add(dev, lf, n_level, s->level_max_m[l], st);}
-    spa_launch_factor_level(dev, lf, n_level, s->level_max_m[l], s->level_max_ns[l], s->d_fail.p,
-      s->d_rhs.p, s->d_upd.p, s->d_fsb.p, s->d_sync.p + 4 * s->level_offsets[l], split ? 1 : 0, st);
+    spa_launch_factor_level(dev, lf, n_level, s->level_max_m[l], s->d_fail.p, s->d_rhs.p, s->d_upd.p, split ? 1 : 0, st);
+  }
+  return KH_OK;
+}
+
+// the loss of the options into dev; returns the edge block [first, second) that this rank linearises (dev.n_edges is set)
+std::pair<int32_t, int32_t> set_loss_and_shard(const kh_spa * s, SpaDev & dev)
+{
+  dev.loss_kind = s->opt.loss_function; dev.loss_b = s->opt.loss_scale * s->opt.loss_scale; dev.loss_a = s->opt.loss_scale;
+  return {static_cast<int32_t>(static_cast<int64_t>(dev.n_edges) * s->shard_rank / s->shard_world),
+          static_cast<int32_t>(static_cast<int64_t>(dev.n_edges) * (s->shard_rank + 1) / s->shard_world)};
+}
+
+// d_scale: the Jacobi scaling of the linearised H, or ones (a pageable upload: it has landed when this returns)
+int make_scale(kh_spa * s, const SpaDev & dev)
+{
+  if (s->opt.jacobi_scaling) {spa_launch_jacobi_scale(dev, s->d_scale.p, s->stream); return KH_OK;}
+  std::vector<double> ones(static_cast<size_t>(dev.n_free) * 3, 1.0);
+  KS_HIP(hipMemcpyAsync(s->d_scale.p, ones.data(), ones.size() * 8, hipMemcpyHostToDevice, s->stream));
+  KS_HIP(hipStreamSynchronize(s->stream));
+  return KH_OK;
+}
+
+// kh_spa_set_debug bit 0 (every test that checks its linear solves checks this): the self-cleaning fronts must be all zeros
+// behind their last reader; `left_by` ends the message
+int check_fronts_clean(kh_spa * s, const SpaDev & dev, const char * left_by)
+{
+  hipStream_t st = s->stream;
+  KS_HIP(hipMemsetAsync(s->d_fail.p, 0, sizeof(int32_t), st));
+  spa_launch_count_nonzero(dev.fronts, dev.fronts_size, s->d_fail.p, st);
+  spa_launch_count_nonzero(dev.fronts_b, dev.fronts_size, s->d_fail.p, st);
+  KS_HIP(hipMemcpyAsync(s->h_fail, s->d_fail.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  KS_HIP(hipStreamSynchronize(st));
+  if (s->h_fail[0] != 0) {
+    s->clean_a = nullptr;
+    set_error("kh_spa: " + std::to_string(s->h_fail[0]) + " entries of the self-cleaning fronts were left behind by " + left_by);
+    return KH_ERR_SOLVER;
   }
   return KH_OK;
 }
@@ -1461,9 +1493,8 @@ int kh_spa_compute(kh_spa * s, kh_spa_summary * summary)
     set_error("kh_spa: loss_scale must be positive");
     return finish(KH_ERR_INVALID_ARG);
   }
-  dev.loss_kind = opt.loss_function; dev.loss_b = opt.loss_scale * opt.loss_scale; dev.loss_a = opt.loss_scale;
-  const int32_t e_lo = static_cast<int32_t>(static_cast<int64_t>(dev.n_edges) * s->shard_rank / s->shard_world);
-  const int32_t e_hi = static_cast<int32_t>(static_cast<int64_t>(dev.n_edges) * (s->shard_rank + 1) / s->shard_world);
+  const std::pair<int32_t, int32_t> shard = set_loss_and_shard(s, dev);
+  const int32_t e_lo = shard.first, e_hi = shard.second;
   int n_lin = 0, n_timed = 0;
   // kh_spa_set_debug bit 1: HIP events around the phases of every LM iteration (kh_spa_summary.*_gpu_ms).  Off by default: an event
   // record between two kernels is a 5-6 us bubble on the stream, three of them per iteration were 0.15 ms of a 9 ms solve.
@@ -1481,13 +1512,7 @@ int kh_spa_compute(kh_spa * s, kh_spa_summary * summary)
   alt.H = s->d_Hg_alt.p; alt.g = s->d_Hg_alt.p + static_cast<size_t>(s->n_slots) * 9;
   const bool pipeline = select_factor_mode(s, dev);
   rc = linearize(dev, x, scal + 0); if (rc) {return finish(rc);}
-  if (opt.jacobi_scaling) {
-    spa_launch_jacobi_scale(dev, s->d_scale.p, st);
-  } else {
-    std::vector<double> ones(static_cast<size_t>(dev.n_free) * 3, 1.0);
-    KS_HIP(hipMemcpyAsync(s->d_scale.p, ones.data(), ones.size() * 8, hipMemcpyHostToDevice, st));
-    KS_HIP(hipStreamSynchronize(st));
-  }
+  rc = make_scale(s, dev); if (rc) {return finish(rc);}
   spa_launch_grad_norms(dev, x, scal + 1, st);
   KS_HIP(hipMemsetAsync(s->d_fail.p, 0, sizeof(int32_t), st));
   rc = fetch(); if (rc) {return finish(rc);}
@@ -1662,17 +1687,7 @@ int kh_spa_compute(kh_spa * s, kh_spa_summary * summary)
   }
 
   if ((s->debug_flags & 1) && dev.scatter && s->clean_a == dev.fronts && iteration > 0) {
-    // the self-cleaning fronts must be all zeros now (kh_spa_set_debug bit 0: every test that checks its linear solves checks this)
-    KS_HIP(hipMemsetAsync(s->d_fail.p, 0, sizeof(int32_t), st));
-    spa_launch_count_nonzero(dev.fronts, dev.fronts_size, s->d_fail.p, st);
-    spa_launch_count_nonzero(dev.fronts_b, dev.fronts_size, s->d_fail.p, st);
-    KS_HIP(hipMemcpyAsync(s->h_fail, s->d_fail.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    KS_HIP(hipStreamSynchronize(st));
-    if (s->h_fail[0] != 0) {
-      s->clean_a = nullptr;
-      set_error("kh_spa: " + std::to_string(s->h_fail[0]) + " entries of the self-cleaning fronts were left behind by the last factorisation");
-      return finish(KH_ERR_SOLVER);
-    }
+    rc = check_fronts_clean(s, dev, "the last factorisation"); if (rc) {return finish(rc);}
   }
   sum.iterations = iteration;
   sum.final_cost = minimum_cost;
@@ -1827,17 +1842,9 @@ static int covariance_pass(kh_spa * s, kh_spa_cov_summary * summary, const std::
     if (s->d_col_rhs.ensure(3 * static_cast<size_t>(dev.n_free) * R + 16) || s->d_columns.ensure(9 * static_cast<size_t>(dev.n_free) * n_queries + 16) ||
         s->d_col_lists.upload(s->h_col_lists, st) || s->d_col_masks.upload(plan.front_mask, st)) {return finish(KH_ERR_HIP);}
   }
-  dev.loss_kind = opt.loss_function; dev.loss_b = opt.loss_scale * opt.loss_scale; dev.loss_a = opt.loss_scale;
-  const int32_t e_lo = static_cast<int32_t>(static_cast<int64_t>(dev.n_edges) * s->shard_rank / s->shard_world);
-  const int32_t e_hi = static_cast<int32_t>(static_cast<int64_t>(dev.n_edges) * (s->shard_rank + 1) / s->shard_world);
-  rc = linearize_normal_equations(s, dev, s->d_x.p, s->d_scal.p, e_lo, e_hi, nullptr); if (rc) {return finish(rc);}
-  if (opt.jacobi_scaling) {
-    spa_launch_jacobi_scale(dev, s->d_scale.p, st);
-  } else {
-    std::vector<double> ones(static_cast<size_t>(dev.n_free) * 3, 1.0);
-    KS_HIP(hipMemcpyAsync(s->d_scale.p, ones.data(), ones.size() * 8, hipMemcpyHostToDevice, st));
-    KS_HIP(hipStreamSynchronize(st));
-  }
+  const std::pair<int32_t, int32_t> shard = set_loss_and_shard(s, dev);
+  rc = linearize_normal_equations(s, dev, s->d_x.p, s->d_scal.p, shard.first, shard.second, nullptr); if (rc) {return finish(rc);}
+  rc = make_scale(s, dev); if (rc) {return finish(rc);}
   KS_HIP(hipStreamSynchronize(st));
   sum.linearize_ms = ms_since(t_begin);
   const auto t_factor = std::chrono::steady_clock::now();
@@ -1883,19 +1890,8 @@ static int covariance_pass(kh_spa * s, kh_spa_cov_summary * summary, const std::
   }
   if (dev.scatter) {
     s->clean_a = dev.fronts; s->clean_b = dev.fronts_b;
-    if (s->debug_flags & 1) {
-      // the self-cleaning fronts must be all zeros now, as behind a Compute()
-      KS_HIP(hipMemsetAsync(s->d_fail.p, 0, sizeof(int32_t), st));
-      spa_launch_count_nonzero(dev.fronts, dev.fronts_size, s->d_fail.p, st);
-      spa_launch_count_nonzero(dev.fronts_b, dev.fronts_size, s->d_fail.p, st);
-      KS_HIP(hipMemcpyAsync(s->h_fail, s->d_fail.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      KS_HIP(hipStreamSynchronize(st));
-      if (s->h_fail[0] != 0) {
-        s->clean_a = nullptr;
-        set_error("kh_spa: " + std::to_string(s->h_fail[0]) + " entries of the self-cleaning fronts were left behind by the covariance pass");
-        return finish(KH_ERR_SOLVER);
-      }
-    }
+    // (as behind a Compute())
+    if (s->debug_flags & 1) {rc = check_fronts_clean(s, dev, "the covariance pass"); if (rc) {return finish(rc);}}
   }
   if (events) {
     float ms = 0.0f;
@@ -2256,7 +2252,7 @@ int kh_spa_audit_constraints(kh_spa * s, double min_redundancy, kh_spa_audit_t *
   dev.edge_a = s->d_edge_a.p; dev.edge_b = s->d_edge_b.p; dev.edge_z = s->d_edge_z.p; dev.edge_u = s->d_edge_u.p;
   dev.free_of_node = s->d_free_of_node.p; dev.node_of_free = s->d_node_of_free.p;
   dev.edge_lin = s->d_audit_lin.p; dev.edge_cost = s->d_audit_cost.p;
-  dev.loss_kind = s->opt.loss_function; dev.loss_b = s->opt.loss_scale * s->opt.loss_scale; dev.loss_a = s->opt.loss_scale;
+  (void)set_loss_and_shard(s, dev);          // the audit walks every edge: only the loss
   dev.n_slots = s->n_slots; dev.bsr_row_ptr = s->d_bsr_row_ptr.p; dev.bsr_col = s->d_bsr_col.p; dev.bsr_diag_slot = s->d_bsr_diag.p;
   const bool events = (s->debug_flags & 2) != 0;
   if (events) {KS_HIP(hipEventRecord(s->ev_audit[0], s->stream));}

@@ -774,51 +774,15 @@ void spa_launch_extend_add(const SpaDev & d, const int32_t * level_fronts, int32
   hipLaunchKernelGGL(k_extend_add, dim3(n, (max_m + 15) / 16), dim3(threads), 0, (hipStream_t)stream, d, level_fronts);
 }
 
-// ---- workgroup-level hand-offs between the workgroups that share one front (agent scope: the L1 of a CU is never
-// refreshed by another CU's stores, MI355X_MICROARCH.md "inter-workgroup visibility") ----
-// publish: everything this workgroup has stored becomes visible, then the word moves
-__device__ __forceinline__ void wg_publish_add(int * word, int value)
+// The any-size factorisation of one level: one workgroup per front (blockIdx.x = the front's slot in level_fronts), no
+// hand-offs between workgroups.  The workgroup extend-adds the children (their forward-solve contributions always, their
+// update matrices unless k_extend_add has done that: matrix_added), then runs the blocked right-looking partial Cholesky
+// of the front's ns pivot columns with the forward solve fused in.  Fronts of up to kMaxLdsRows rows keep the solved
+// panel pair in LDS (lds_rows rows of XS doubles); larger ones read it back from the front itself.
+__global__ __launch_bounds__(1024) void k_factor(SpaDev d, const int32_t * __restrict__ level_fronts, int32_t * fail_flag,
+              double * rhs, double * upd, int lds_rows, int matrix_added)
 {
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __hip_atomic_fetch_add(word, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-// wait until *word >= value, then make the publishers' stores visible to every thread of this workgroup.  The spin is
-// bounded: a hand-off that never comes (it cannot, all workgroups of a launch are resident) must not hang the device.
-__device__ __forceinline__ bool wg_wait_ge(int * word, int value)
-{
-  __shared__ int s_ok;
-  if (threadIdx.x == 0) {
-    int ok = 0;
-    for (int spin = 0; spin < (1 << 26); ++spin) {
-      if (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= value) {ok = 1; break;}
-      __builtin_amdgcn_s_sleep(2);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    s_ok = ok;
-  }
-  __syncthreads();
-  return s_ok != 0;
-}
-
-// G workgroups per front (G = 1 on the wide levels).  Workgroup 0 of a front is its LEADER and runs the factorisation
-// as before; on the narrow upper levels, where a handful of large fronts would leave most of the chip idle, G - 1 helper
-// workgroups take destination-column slices of the extend-add and tile slices of every K = 32 trailing update (the bulk
-// of the flops), reading the solved panel from the front itself.  Hand-offs: sync[4 * slot + 0] extend-add arrivals,
-// + 1 panel pairs published by the leader, + 2 helper completions (zeroed by the host before every factorisation).
-__global__ __launch_bounds__(1024) void k_factor(SpaDev d, const int32_t * __restrict__ level_fronts, int32_t * fail_flag, long long * tbuf,
-              double * rhs, double * upd, int lds_rows, int G, int * sync, int matrix_added)
-{
-  // KH_SPA_TIMING=1: stage timestamps (100 MHz wall clock) of the level's largest front, printed by the host
-  int tcount = 0;
-#define TSTAMP() do { if (tbuf && blockIdx.x == 0 && threadIdx.x == 0 && tcount < 60) {tbuf[1 + tcount++] = wall_clock64();} } while (0)
-  TSTAMP();
-  const int slot = (int)blockIdx.x / G, g = (int)blockIdx.x - slot * G;
-  int * sy = sync + 4 * slot;
-  const int k = level_fronts[slot];
+  const int k = level_fronts[blockIdx.x];
   const int m = d.front_m[k], ns = d.front_ns[k];
   double * F = d.fronts + d.front_off[k];
   const int tid = threadIdx.x, nthreads = blockDim.x;
@@ -849,10 +813,8 @@ __global__ __launch_bounds__(1024) void k_factor(SpaDev d, const int32_t * __res
     const int32_t * rp = d.relpos + d.relpos_ptr[c];
     for (int a = tid; a < nuc; a += nthreads) {pos[a] = 3 * rp[a / 3] + a % 3;}
     __syncthreads();
-    if (g == 0) {
-      const double * uc = upd + 3 * (int64_t)d.front_rows_ptr[c];      // the child's forward-solve contribution
-      for (int a = tid; a < nuc; a += nthreads) {sb[pos[a]] += uc[a];}
-    }
+    const double * uc = upd + 3 * (int64_t)d.front_rows_ptr[c];        // the child's forward-solve contribution
+    for (int a = tid; a < nuc; a += nthreads) {sb[pos[a]] += uc[a];}
     constexpr int CB = 8;
     // matrix_added: k_extend_add has already summed the children's update matrices into the front, chip-wide
     for (int b0 = wave * CB; b0 < nuc && !matrix_added; b0 += nwaves * CB) {
@@ -865,9 +827,7 @@ __global__ __launch_bounds__(1024) void k_factor(SpaDev d, const int32_t * __res
 #pragma unroll
         for (int q = 0; q < CB; ++q) {
           const int b = b0 + q;
-          // with several workgroups on the front, a DESTINATION column (block of 16) has one owner: whatever the child,
-          // all additions into an entry come from the same workgroup, children in turn
-          on[q] = a < nuc && b < nuc && a >= b && (G == 1 || ((pos[b] >> 4) % G) == g);
+          on[q] = a < nuc && b < nuc && a >= b;
           dst[q] = F + pa + (int64_t)(on[q] ? pos[b] : 0) * m;
           u[q] = on[q] ? Uc[a + (int64_t)b * mc] : 0.0;
           f[q] = on[q] ? *dst[q] : 0.0;
@@ -879,41 +839,7 @@ __global__ __launch_bounds__(1024) void k_factor(SpaDev d, const int32_t * __res
     __syncthreads();
   }
 
-  TSTAMP();
-  if (G > 1) {
-    wg_publish_add(&sy[0], 1);
-    if (g > 0) {
-      // helper: the same walk over the panels as the leader's below, taking part in the K = 32 updates only
-      int pairs = 0;
-      for (int jb = 0; jb < ns; ) {
-        const int nb_a = min(NB, ns - jb);
-        const int rb = jb + nb_a;
-        const int nrows = m - rb;
-        const int nrows_pad = (nrows + 15) & ~15;
-        if (jb + 2 * NB > ns) {jb += NB; continue;}
-        ++pairs;
-        if (!wg_wait_ge(&sy[1], pairs)) {if (tid == 0) {atomicExch(fail_flag, 1);} return;}
-        if (use_lds) {
-          // the solved panel pair into this workgroup's LDS (rows relative to rb; the second panel has no rows 0..15),
-          // coalesced along the rows, then the same LDS-operand MFMA path as the leader's
-          for (int t = tid; t < nrows_pad * 2 * NB; t += nthreads) {
-            const int c = t / nrows_pad, row = t - c * nrows_pad;
-            Xs[row * XS + c] = (row < nrows && (c < NB || row >= NB)) ? F[(rb + row) + (int64_t)(jb + c) * m] : 0.0;
-          }
-          __syncthreads();
-          trailing_update<true, 32>(F, Xs, m, rb, jb, nb_a, NB, nrows, nrows_pad, false, false, lane, g * nwaves + wave, G * nwaves);
-        } else {
-          trailing_update<false, 32>(F, nullptr, m, rb, jb, nb_a, NB, nrows, nrows_pad, false, false, lane, g * nwaves + wave, G * nwaves);
-        }
-        wg_publish_add(&sy[2], 1);
-        jb += 2 * NB;
-      }
-      return;
-    }
-    if (!wg_wait_ge(&sy[0], G)) {if (tid == 0) {atomicExch(fail_flag, 1);} return;}
-  }
   // 2. blocked right-looking partial Cholesky of the first ns columns
-  int pairs_published = 0;
   if (tid == 0) {s_fail = 0;}
   __syncthreads();
   // Panels are taken in pairs with a delayed update: after panel A only the next 16 columns of the trailing
@@ -925,7 +851,6 @@ __global__ __launch_bounds__(1024) void k_factor(SpaDev d, const int32_t * __res
       if (factor_diag_block(F, m, jb, nb, lane, &Ld[0][0], sb + jb)) {s_fail = 1;}
     }
     __syncthreads();
-    TSTAMP();
     // (b) panel: X = F[rows, jb:jb+nb] * Ld^{-T}, rows below the diagonal block; one thread per row (out of
     //     line, see panel_row_solve); fronts too large for the LDS panel solve in place in the front instead
     const int r0 = jb + nb;
@@ -953,7 +878,6 @@ __global__ __launch_bounds__(1024) void k_factor(SpaDev d, const int32_t * __res
       }
     }
     __syncthreads();
-    TSTAMP();
   };
   for (int jb = 0; jb < ns; ) {
     const int nb_a = min(NB, ns - jb);
@@ -975,7 +899,6 @@ __global__ __launch_bounds__(1024) void k_factor(SpaDev d, const int32_t * __res
         trailing_update<false, 16>(F, Xs, m, rb, jb, nb_a, 0, nrows, nrows_pad, false, true, lane, wave, nwaves);
       }
       __syncthreads();
-      TSTAMP();
       jb += NB;
       continue;
     }
@@ -987,17 +910,12 @@ __global__ __launch_bounds__(1024) void k_factor(SpaDev d, const int32_t * __res
     __syncthreads();
     const int nb_b = NB;
     panel(jb + NB, nb_b, rb, Xs + NB);
-    if (G > 1) {wg_publish_add(&sy[1], 1); ++pairs_published;}      // both panels are in the front: the helpers may start
     if (use_lds) {
-      trailing_update<true, 32>(F, Xs, m, rb, jb, nb_a, nb_b, nrows, nrows_pad, false, false, lane, wave, G * nwaves);
+      trailing_update<true, 32>(F, Xs, m, rb, jb, nb_a, nb_b, nrows, nrows_pad, false, false, lane, wave, nwaves);
     } else {
-      trailing_update<false, 32>(F, Xs, m, rb, jb, nb_a, nb_b, nrows, nrows_pad, false, false, lane, wave, G * nwaves);
-    }
-    if (G > 1) {
-      if (!wg_wait_ge(&sy[2], (G - 1) * pairs_published)) {if (tid == 0) {atomicExch(fail_flag, 1);} return;}
+      trailing_update<false, 32>(F, Xs, m, rb, jb, nb_a, nb_b, nrows, nrows_pad, false, false, lane, wave, nwaves);
     }
     __syncthreads();
-    TSTAMP();
     jb += 2 * NB;
   }
   // forward-solve results: y of the pivots back to rhs, the struct rows' partial sums to this front's slot
@@ -1006,7 +924,6 @@ __global__ __launch_bounds__(1024) void k_factor(SpaDev d, const int32_t * __res
     double * uk = upd + 3 * (int64_t)d.front_rows_ptr[k];
     for (int q = tid; q < m - ns; q += nthreads) {uk[q] = sb[ns + q];}
   }
-  if (tbuf && blockIdx.x == 0 && threadIdx.x == 0) {tbuf[0] = tcount; tbuf[63] = ((long long)m << 32) | ns;}
   if (tid == 0 && s_fail) {atomicExch(fail_flag, 1);}
 }
 
@@ -1033,20 +950,14 @@ __device__ __forceinline__ double row_bcast(double v, int n)      // n is a cons
 }
 
 
-void spa_launch_factor_level(const SpaDev & d, const int32_t * level_fronts, int32_t n, int32_t max_m, int32_t max_ns, int32_t * fail_flag,
-                             double * rhs, double * upd, double * fsb, int32_t * sync, int32_t matrix_added, void * stream)
+void spa_launch_factor_level(const SpaDev & d, const int32_t * level_fronts, int32_t n, int32_t max_m, int32_t * fail_flag,
+                             double * rhs, double * upd, int32_t matrix_added, void * stream)
 {
   // The any-size form: what factorises a level whose fronts do not fit the level pipeline's LDS (spa_level_pipeline_fits: more
-  // than ~2700 rows), and what `kh_spa_set_debug` factor mode 1 / 2 selects so that the tests can lay an independent
-  // factorisation beside the pipeline's.  One workgroup per front (the round-2 panel-pair kernels, a subset of the pipeline's
-  // domain, are gone).
-  (void)max_ns; (void)fsb;
+  // than ~2700 rows), and what `kh_spa_set_debug` factor modes 1 and 2 (the same thing) select so that the tests can lay an
+  // independent factorisation beside the pipeline's.  One workgroup per front.
   if (n <= 0) {return;}
-  const int G = 1;
   const int threads = max_m <= 96 ? 256 : (max_m <= 192 ? 512 : 1024);
-  static long long * tbuf = nullptr;
-  static const bool timing = std::getenv("KH_SPA_TIMING") != nullptr;
-  if (timing && !tbuf) {(void)hipHostMalloc(reinterpret_cast<void **>(&tbuf), 64 * sizeof(long long), hipHostMallocDefault);}
   const int lds_rows = ((max_m < kMaxLdsRows ? max_m : kMaxLdsRows) + 15) & ~15;
   // panel + the front's right-hand side behind it; fronts beyond the LDS panel keep only the rhs (+ the
   // extend-add position table) in LDS
@@ -1054,14 +965,8 @@ void spa_launch_factor_level(const SpaDev & d, const int32_t * level_fronts, int
   const size_t lds = sizeof(double) * std::max((size_t)lds_rows * XS + small_m, (size_t)max_m + (max_m + 1) / 2 + 8);
   static std::atomic<unsigned long long> attr_done{0};
   allow_dynamic_lds(reinterpret_cast<const void *>(k_factor), (int)(sizeof(double) * ((size_t)kMaxLdsRows * XS + kMaxLdsRows + 16)), attr_done);
-  hipLaunchKernelGGL(k_factor, dim3(n * G), dim3(threads), lds, (hipStream_t)stream, d, level_fronts, fail_flag, timing ? tbuf : nullptr, rhs, upd,
-                     lds_rows, G, sync, (int)matrix_added);
-  if (timing) {
-    (void)hipStreamSynchronize((hipStream_t)stream);
-    std::fprintf(stderr, "[k_factor] n=%d max_m=%d front0 m=%lld ns=%lld stamps(x10ns):", n, max_m, tbuf[63] >> 32, tbuf[63] & 0xffffffff);
-    for (int i = 1; i < (int)tbuf[0]; ++i) {std::fprintf(stderr, " %lld", tbuf[1 + i] - tbuf[i]);}
-    std::fprintf(stderr, "\n");
-  }
+  hipLaunchKernelGGL(k_factor, dim3(n), dim3(threads), lds, (hipStream_t)stream, d, level_fronts, fail_flag, rhs, upd, lds_rows,
+                     (int)matrix_added);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1744,13 +1649,13 @@ __global__ __launch_bounds__(kPotrfThreads) void k_potrf(SpaDev d, int first_fro
 }
 
 // rows [prow0, prow0 + R) x columns [0, nsp) of the panel columns of a front -> LDS rows of stride LD (zeros outside
-// nr rows / ns columns), sixteen loads in flight per thread; with kids, the children's update matrices are added (the
-// same thread handles the same entry in every pass: no barrier in between)
-template <int R>
-__device__ __forceinline__ void stage_rows(double * S, int LD, const SpaDev & d, const FrontDesc & fd, int prow0, int nr, int ns, int nsp, int nkids,
+// nr rows / ns columns), LU loads in flight per thread; with kids, the children's update matrices are added (the
+// same thread handles the same entry in every pass: no barrier in between).  R is a constant for the slab kernels and
+// the front's whole padded F21 (column by column) for k_front_update.
+template <int LU>
+__device__ __forceinline__ void stage_rows(double * S, int LD, int R, const SpaDev & d, const FrontDesc & fd, int prow0, int nr, int ns, int nsp, int nkids,
                                            const double * Bfront, int tid, int nthreads)
 {
-  constexpr int LU = 16;
   const int m = fd.m, mp = m / 3;
   const double * Fcol0 = d.fronts + fd.off + prow0;
   const double * Bcol0 = Bfront ? Bfront + prow0 : nullptr;
@@ -1790,7 +1695,7 @@ __device__ __forceinline__ void stage_rows(double * S, int LD, const SpaDev & d,
     for (int u = 0; u < LU; ++u) {
       const int idx = base + u * nthreads + tid;
       const int c = idx / R, i = idx - c * R;
-      if (idx < R * nsp) {S[i * LD + c] = (i < nr && c < ns) ? v[u] : 0.0;}
+      if (idx < R * nsp) {S[(size_t)i * LD + c] = (i < nr && c < ns) ? v[u] : 0.0;}
     }
   }
 }
@@ -1823,7 +1728,7 @@ __global__ __launch_bounds__(512) void k_trsm(SpaDev d, int first_front, const d
   const double uold = tid < nr ? uk[r0 + tid] : 0.0;
   for (int j = tid; j < nsp; j += nthreads) {yv[j] = j < ns ? rhs[first + j] : 0.0;}
   for (int j = tid; j < 8 * R; j += nthreads) {red[j] = 0.0;}
-  stage_rows<R>(S, LD, d, fd, ns + r0, nr, ns, nsp, front_nkids(d, fd), front_b(d, fd), tid, nthreads);
+  stage_rows<16>(S, LD, R, d, fd, ns + r0, nr, ns, nsp, front_nkids(d, fd), front_b(d, fd), tid, nthreads);
   __syncthreads();
   double part[RT];
 #pragma unroll
@@ -1970,8 +1875,8 @@ __global__ __launch_bounds__(TS * 8) void k_syrk(SpaDev d, int first_front, int 
       }
     }
   }
-  stage_rows<TS>(XA, LD, d, fd, ns + TS * I, min(TS, nu - TS * I), ns, nsp, 0, nullptr, tid, nthreads);      // L21 is final: no children
-  if (I != J) {stage_rows<TS>(XB, LD, d, fd, ns + TS * J, min(TS, nu - TS * J), ns, nsp, 0, nullptr, tid, nthreads);}
+  stage_rows<16>(XA, LD, TS, d, fd, ns + TS * I, min(TS, nu - TS * I), ns, nsp, 0, nullptr, tid, nthreads);      // L21 is final: no children
+  if (I != J) {stage_rows<16>(XB, LD, TS, d, fd, ns + TS * J, min(TS, nu - TS * J), ns, nsp, 0, nullptr, tid, nthreads);}
   __syncthreads();
   if (live[0]) {
     const double * xb = XA + (NB * si + lr) * LD + 4 * lk;
@@ -2026,55 +1931,6 @@ __global__ __launch_bounds__(TS * 8) void k_syrk(SpaDev d, int first_front, int 
 // so F21, W and F22 are read once and L21 is written once.  The host sends the fronts of a level that fit (front_update_fits)
 // here when there are enough of them to fill the chip; the larger ones (the head of the level: fronts are sorted by size) keep
 // k_trsm / k_syrk.
-// stage_rows with the number of rows known at run time (the whole F21 of a front at once, column by column)
-__device__ __forceinline__ void stage_rows_rt(double * S, int LD, int R, const SpaDev & d, const FrontDesc & fd, int prow0, int nr, int ns, int nsp, int nkids,
-                                              const double * Bfront, int tid, int nthreads)
-{
-  constexpr int LU = 8;
-  const int m = fd.m, mp = m / 3;
-  const double * Fcol0 = d.fronts + fd.off + prow0;
-  const double * Bcol0 = Bfront ? Bfront + prow0 : nullptr;
-  for (int base = 0; base < R * nsp; base += LU * nthreads) {
-    double v[LU];
-#pragma unroll
-    for (int u = 0; u < LU; ++u) {
-      const int idx = base + u * nthreads + tid;
-      const int c = idx / R, i = idx - c * R;
-      const bool want = idx < R * nsp && i < nr && c < ns;
-      v[u] = *(want ? Fcol0 + i + (int64_t)c * m : Fcol0);
-    }
-    if (Bcol0) {
-#pragma unroll
-      for (int u = 0; u < LU; ++u) {
-        const int idx = base + u * nthreads + tid;
-        const int c = idx / R, i = idx - c * R;
-        const bool want = idx < R * nsp && i < nr && c < ns;
-        const double * bp = want ? Bcol0 + i + (int64_t)c * m : Bcol0;
-        v[u] += *bp;
-        if (want) {*const_cast<double *>(bp) = 0.0;}          // self-cleaning (buffer A's entries become L21)
-      }
-    }
-    for (int s = 0; s < nkids; ++s) {
-      const ChildInfo ci = child_info(d, fd, s);
-      const int32_t * inv = d.cinv + fd.cinv_ptr + s * mp;
-#pragma unroll
-      for (int u = 0; u < LU; ++u) {
-        const int idx = base + u * nthreads + tid;
-        const int c = idx / R, i = idx - c * R;
-        const bool want = idx < R * nsp && i < nr && c < ns;
-        const double g = gather_entry(d.fronts, ci, inv, want ? prow0 + i : 0, want ? c : 0);
-        v[u] += want ? g : 0.0;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < LU; ++u) {
-      const int idx = base + u * nthreads + tid;
-      const int c = idx / R, i = idx - c * R;
-      if (idx < R * nsp) {S[(size_t)i * LD + c] = (i < nr && c < ns) ? v[u] : 0.0;}
-    }
-  }
-}
-
 constexpr int kFuThreads = 1024, kFuWaves = kFuThreads / 64;
 constexpr int kFuMaxNt = 5;          // pivot blocks of up to 80 columns (the leaves of the dissection: 24 nodes = 72): one accumulator per column
                                      // block in the trsm phase, and 1024 threads leave a lane 128 registers
@@ -2123,7 +1979,7 @@ __device__ __forceinline__ void front_update_body(const SpaDev & d, const FrontD
     const int k = idx / nsp, j = idx - k * nsp;
     Wl[k * LDW + j] = j >= (k & ~(NB - 1)) ? W[j + (int64_t)k * nsp] : 0.0;      // (left of the diagonal block W holds nothing)
   }
-  stage_rows_rt(S, LD, nup, d, fd, ns, nu, ns, nsp, nkids, Bf, tid, nthreads);
+  stage_rows<8>(S, LD, nup, d, fd, ns, nu, ns, nsp, nkids, Bf, tid, nthreads);
   __syncthreads();
   // ---- trsm ----
   double * uk = upd + 3 * (int64_t)fd.rows_ptr;

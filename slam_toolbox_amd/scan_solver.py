@@ -99,7 +99,8 @@ class HipSpaSolver:
 
     def set_debug(self, check_linear_solves: bool = False, factor_kernels: int = 0, gather_children: bool = False,
                   extend_add_pass: bool = False, phase_timing: bool = False):
-        """kh_spa_set_debug: residual check of every linear solve; numeric kernels 0 default, 3 level pipeline, 2 panel pairs;
+        """kh_spa_set_debug: residual check of every linear solve; numeric kernels 0 default, 3 level pipeline,
+        1 or 2 (the same) the any-size kernel k_factor, one workgroup per front;
         level pipeline reading ALL the children's update matrices in place / summing them in with an extend-add launch per level
         (default: k_syrk adds a front's update matrix straight into its parent); HIP events around the phases of an iteration
         (the *_gpu_ms fields of the summary)"""

@@ -228,11 +228,12 @@ def _solve(g, **kw):
 
 
 @pytest.mark.parametrize("n_clique,n_chain", [(2, 0), (4, 3), (6, 9), (11, 0), (12, 2), (17, 30), (22, 1), (23, 5), (33, 7), (43, 2), (44, 40), (70, 40),
-                                              (86, 1), (127, 3), (150, 3)])
+                                              (86, 1), (127, 3), (150, 3), (190, 0), (191, 0)])
 def test_linear_solves_of_dense_fronts(kartohip_lib, n_clique, n_chain):
-    """Every tail shape of the pivot block (3 * (n_clique - 1) pivots: 3 ... 447; above 126 the supernode is a chain of
+    """Every tail shape of the pivot block (3 * (n_clique - 1) pivots: 3 ... 570; above 126 the supernode is a chain of
     fronts) through the level pipeline: the residual of EVERY linear solve of the run, evaluated from the block-sparse
-    matrix, and the same poses as the panel-pair kernels."""
+    matrix, and the same poses as k_factor (route 2).  The last two cliques straddle k_factor's LDS panel: the largest front
+    has 567 rows (the last size whose panel stays in LDS) and 570 (the first that reads the panel back from the front)."""
     g = _clique_graph(n_clique, n_chain, seed=100 + n_clique)
     s3, x3 = _solve(g, check_linear_solves=True, factor_kernels=3)
     s2, x2 = _solve(g, check_linear_solves=True, factor_kernels=2)
