@@ -666,6 +666,28 @@ KH_API int kh_occupancy_info(kh_occupancy * g, int32_t * width, int32_t * height
 /* the grid's offset (world position of cell 0, 0) and 1 / scale; either pointer may be NULL */
 KH_API int kh_occupancy_geometry(kh_occupancy * g, double offset[2], double * resolution);
 
+/* A device view of a map: what the matcher's map entry points (kh_matcher_add_map / _match_map*, below) read.  The world point of
+ * cell (i, j) is anchor + (o + i) / scale, in float64 with the integer sum first: CoordinateConverter::GridToWorld without flip,
+ * and the inverse of the live map's round((x - ax) * scale).
+ * A view is a BORROWED pointer: it is valid until its source is next updated, grown, cleared or destroyed (kh_occupancy_add_scans /
+ * _update / _clear / _write_nav / _destroy; kh_live_map_update / _destroy), and the cells must not be written while a call that
+ * was handed the view runs.  A caller may also fill a view by hand over any device buffer it owns (kh_device_malloc /
+ * kh_device_upload). */
+typedef struct kh_map_view {
+  const uint8_t * device_cells;   /* karto cell states (0 unknown, 100 occupied, 255 free), row stride width_step */
+  int32_t device;
+  int32_t width, height, width_step;
+  int32_t ox, oy;                 /* lattice index of column 0 / row 0 (0 for a kh_occupancy; the window origin of a live map) */
+  double anchor[2];               /* kh_occupancy: its offset; live map: its anchor */
+  double scale;                   /* the source's stored 1 / resolution, not recomputed */
+} kh_map_view;
+KH_API int kh_occupancy_view(kh_occupancy * g, kh_map_view * out);
+/* The inverse of kh_occupancy_read_nav: nav holds width * height values without row padding, -1 -> 0 (unknown), 100 -> 100
+ * (occupied), 0 -> 255 (free); any other value is refused with KH_ERR_INVALID_ARG and the grid stays as it was.  The row padding
+ * of the cells is zeroed, and so are the pass / hit counters: a later kh_occupancy_update recomputes the cells from the counters,
+ * i.e. wipes what was written here.  This is how a map that arrives as an image or a nav_msgs/OccupancyGrid gets onto the device. */
+KH_API int kh_occupancy_write_nav(kh_occupancy * g, const int8_t * nav);
+
 /* ---------------------------------------------------------------- lifelong node-decay scoring (next row f-4) */
 /* LifelongSlamToolbox::computeScores (src/experimental/slam_toolbox_lifelong.cpp:295-329) with the metrics
  * of :373-478 and the objective of :199-250.  A kh_scan_box is what the scoring reads from a scan / vertex:
@@ -1185,6 +1207,9 @@ KH_API int kh_live_map_info(const kh_live_map * g, kh_live_map_info_t * out);
 /* layout of kh_occupancy_read over the window: width_step * height entries each; any pointer may be NULL */
 KH_API int kh_live_map_read(kh_live_map * g, uint8_t * cells, uint32_t * pass, uint32_t * hits);
 KH_API int kh_live_map_stats(const kh_live_map * g, kh_live_map_stats_t * out);
+/* the window's cell states as a kh_map_view (borrowed: valid until the next kh_live_map_update); KH_ERR_NOT_FOUND before the
+ * first scan gave the map a window */
+KH_API int kh_live_map_view(kh_live_map * g, kh_map_view * out);
 
 /* ---- the map feed: the live map's way out, for a costmap, a viewer, a map_msgs/OccupancyGridUpdate publisher.  A feed hands its
  * consumer, as nav_msgs/OccupancyGrid values (-1 unknown, 100 occupied, 0 free: vis_utils::toNavMap), the 16 x 16 TILES whose
@@ -1232,6 +1257,30 @@ KH_API int kh_map_feed_tiles(const kh_map_feed * f, int32_t * tile_xy, int8_t * 
  * update rectangle.  Cells outside the feed's window read -1; any x, y and any w, h >= 0 whose product fits an int32 are legal. */
 KH_API int kh_map_feed_read(kh_map_feed * f, int32_t x, int32_t y, int32_t w, int32_t h, int8_t * out);
 KH_API int kh_map_feed_stats(const kh_map_feed * f, kh_map_feed_stats_t * out);
+
+/* ---------------------------------------------------------------- matching a scan against a map
+ * The correlation grid of a slot rasterised from a MAP instead of base scans: centred on the query's sensor pose (MatchScan steps
+ * 1-4), cleared, then ScanMatcher::AddScan's point loop (Mapper.cpp:1082-1104: WorldToGrid, region-of-interest test, "cell
+ * already 100 -> skip", SmearPoint) over the world points of the map's cells whose state is exactly 100, visited in row-major
+ * order (row j outer, column i inner).  There is no FindValidPoints: a map has no viewpoint-facing side.  Everything behind the
+ * rasterisation is what the scan-sourced entry points run.
+ * KH_ERR_INVALID_ARG: a NULL or malformed view (non-positive sizes, width_step < width, a scale that is not finite or <= 0, NULL
+ * cells), a view on another device than the matcher's, a bad slot, n > max_batch.  A map with no occupied cell in reach is not an
+ * error: the grid is empty, and the match is what MatchScan gives on an empty grid. */
+/* kh_matcher_add_scans with the map in the place of the base scans; kh_matcher_correlate*, _read_grid and the covariance calls
+ * then work on the slot as usual */
+KH_API int kh_matcher_add_map(kh_matcher * m, int32_t slot, const kh_scan * query, const kh_map_view * map);
+/* kh_matcher_match_batch with the rasterisation swapped: n <= max_batch independent MatchScans against ONE map (empty queries,
+ * response expansion, fine pass and per-match status as there); kh_matcher_match_map is the batch of one */
+KH_API int kh_matcher_match_map(kh_matcher * m, const kh_scan * query, const kh_map_view * map,
+                                int32_t do_penalize, int32_t do_refine, double mean[3], double cov[9], double * response);
+KH_API int kh_matcher_match_map_batch(kh_matcher * m, int32_t n, const kh_scan * queries, const kh_map_view * map,
+                                      int32_t do_penalize, int32_t do_refine, double * means, double * covs,
+                                      double * responses, int32_t * status);
+/* a profiling aid, like kh_matcher_profile_side: while kh_matcher_profile is on, the GPU ms (device events) of the map-collect
+ * kernels -- count + scan, and fill; the download of the counts and the host's wait between them are NOT included -- and the number
+ * of map rasterisations, since the last call; reading resets them */
+KH_API int kh_matcher_profile_map(kh_matcher * m, double * collect_ms, int64_t * collects);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,12 @@ class KhGridInfo(C.Structure):
                [(k, C.c_double) for k in ("offset_x", "offset_y", "scale")]
 
 
+class KhMapView(C.Structure):
+    """kh_map_view: a borrowed device view of a map's cell states (valid until its source is next updated, grown, cleared or destroyed)"""
+    _fields_ = [("device_cells", C.c_void_p), ("device", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("width_step", C.c_int32), ("ox", C.c_int32), ("oy", C.c_int32), ("anchor", C.c_double * 2), ("scale", C.c_double)]
+
+
 KH_LOSS_NONE, KH_LOSS_HUBER, KH_LOSS_CAUCHY = 0, 1, 2
 
 
@@ -159,6 +165,8 @@ SYMBOLS = [
     "kh_loop_gate_params_default", "kh_mapper_set_loop_gate", "kh_mapper_get_loop_gate", "kh_mapper_get_loop_gate_stats",
     "kh_spa_audit_constraints", "kh_mapper_add_edge", "kh_mapper_remove_edge", "kh_mapper_correct_poses", "kh_mapper_audit",
     "kh_reject_params_default", "kh_mapper_reject_outliers",
+    "kh_occupancy_view", "kh_occupancy_write_nav", "kh_live_map_view",
+    "kh_matcher_add_map", "kh_matcher_match_map", "kh_matcher_match_map_batch", "kh_matcher_profile_map",
 ]
 
 
@@ -342,6 +350,14 @@ def lib():
     L.kh_matcher_score_loads.argtypes = [vp, C.POINTER(C.c_int64), i32]
     L.kh_matcher_seq_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     L.kh_matcher_profile_side.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(L, "kh_matcher_add_map"):      # (KH_LIBRARY may name a build from before the map entry points existed)
+        L.kh_occupancy_view.argtypes = [vp, C.POINTER(KhMapView)]
+        L.kh_occupancy_write_nav.argtypes = [vp, vp]
+        L.kh_live_map_view.argtypes = [vp, C.POINTER(KhMapView)]
+        L.kh_matcher_add_map.argtypes = [vp, i32, C.POINTER(KhScan), C.POINTER(KhMapView)]
+        L.kh_matcher_match_map.argtypes = [vp, C.POINTER(KhScan), C.POINTER(KhMapView), i32, i32, dptr, dptr, C.POINTER(dbl)]
+        L.kh_matcher_match_map_batch.argtypes = [vp, i32, C.POINTER(KhScan), C.POINTER(KhMapView), i32, i32, dptr, dptr, dptr, iptr]
+        L.kh_matcher_profile_map.argtypes = [vp, C.POINTER(dbl), C.POINTER(C.c_int64)]
     if hasattr(L, "kh_spa_create"):
         L.kh_spa_options_default.argtypes = [C.POINTER(KhSpaOptions)]
         L.kh_spa_create.argtypes = [i32, C.POINTER(vp)]

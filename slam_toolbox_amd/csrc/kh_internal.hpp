@@ -103,6 +103,26 @@ struct RasterJob
 };
 constexpr int32_t kRasterTile = 64;
 
+// One map-collect job (kh_matcher_add_map / _match_map*) -- device visible: the occupied cells of the clip
+// rectangle [i0, i0 + cw) x [j0, j0 + ch) of a map view whose world point passes AddScan's region-of-interest test become the
+// points of the slot's ONE pseudo-scan, in row-major order.  A UNIT is 64 consecutive cells of one row of the rectangle (one
+// wave's ballot); units in row-major order are cells in row-major order.
+struct MapJob
+{
+  const uint8_t * cells;     // the view's cell states, row stride width_step
+  int32_t width_step;
+  int32_t i0, j0, cw, ch;    // the clip rectangle, inside the view (the host's conservative bound; roi_cell is the judge)
+  int32_t ox, oy;            // lattice index of the view's column 0 / row 0
+  double ax, ay, map_scale;  // world point of cell (i, j): a + (o + i) / map_scale
+  double off_x, off_y, scale;   // the slot's CoordinateConverter, as in RasterJob (what roi_cell reads)
+  int32_t roi_w, roi_h;
+  int32_t units_per_row, n_units;
+  int32_t * unit;            // n_units + 1: the units' counts (count phase), then their exclusive prefix and the total (scan phase)
+  int32_t * total;           // the job's total, where the host reads the batch's from
+  double * points;           // 2 * total: the collected world points (fill phase)
+  uint8_t * active;          // total: RasterJob::active, 1 for every collected point (fill phase)
+};
+
 // One CorrelateScan job (Mapper.cpp:712-862) -- device visible.  All pointers are device pointers.
 struct CorrJob
 {
@@ -194,6 +214,10 @@ void launch_active_set(const RasterJob * d_jobs, int32_t n_jobs, int32_t max_poi
 void launch_raster(const RasterJob * d_jobs, int32_t n_jobs, int32_t max_points, int32_t max_tiles, const uint8_t * d_kernel, int32_t kernel_size,
   void * stream);
 void launch_raster_clear(const RasterJob * d_jobs, int32_t n_jobs, void * stream);
+// k_map_collect: the count and scan phases (the jobs' totals land in MapJob::total), then -- once the host has sized the point
+// arrays from the totals -- the fill phase.  max_units: the largest MapJob::n_units of the batch.
+void launch_map_count(const MapJob * d_jobs, int32_t n_jobs, int32_t max_units, void * stream);
+void launch_map_fill(const MapJob * d_jobs, int32_t n_jobs, int32_t max_units, void * stream);
 void launch_repitch(const RasterJob * d_jobs, int32_t n_jobs, int32_t max_tiles, void * stream, bool any_copies);          // after launch_raster
 void launch_repitch_full(const RasterJob * d_job, int32_t rows, void * stream);                             // one job: whole grid
 void launch_offsets(const uint8_t * d_jobs, size_t stride, int32_t n_jobs, int32_t max_na, void * stream);

@@ -409,6 +409,17 @@ int kh_live_map_stats(const kh_live_map * g, kh_live_map_stats_t * out)
   return KH_OK;
 }
 
+int kh_live_map_view(kh_live_map * g, kh_map_view * out)
+{
+  if (!g || !out) {return KH_ERR_INVALID_ARG;}
+  if (!g->win.cells || g->win.width <= 0 || g->win.height <= 0) {set_error("kh_live_map_view: the map has no window yet"); return KH_ERR_NOT_FOUND;}
+  out->device_cells = g->win.cells; out->device = g->device;
+  out->width = g->win.width; out->height = g->win.height; out->width_step = g->win.ws;
+  out->ox = g->win.ox; out->oy = g->win.oy;
+  out->anchor[0] = g->lat.ax; out->anchor[1] = g->lat.ay; out->scale = g->lat.scale;
+  return KH_OK;
+}
+
 // ---------------------------------------------------------------- the map feed
 
 namespace

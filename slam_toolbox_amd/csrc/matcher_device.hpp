@@ -32,8 +32,9 @@ __device__ __forceinline__ double2 job_point(const RasterJob & job, int p)
   }
   return reinterpret_cast<const double2 *>(job.scan_ptr[lo])[p - job.scan_prefix[lo]];
 }
-// CoordinateConverter::WorldToGrid (Karto.h:4421-4436) + the ROI test of AddScan (Mapper.cpp:1083-1088)
-__device__ __forceinline__ bool roi_cell(const RasterJob & job, double2 w, int32_t & gx, int32_t & gy)
+// CoordinateConverter::WorldToGrid (Karto.h:4421-4436) + the ROI test of AddScan (Mapper.cpp:1083-1088); Job: RasterJob or MapJob
+template <class Job>
+__device__ __forceinline__ bool roi_cell(const Job & job, double2 w, int32_t & gx, int32_t & gy)
 {
   const double gxd = (w.x - job.off_x) * job.scale;
   const double gyd = (w.y - job.off_y) * job.scale;

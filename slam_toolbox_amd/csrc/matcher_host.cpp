@@ -108,12 +108,178 @@ TablePlan plan_table_raster(const kh_matcher * m, int64_t most_points, int32_t m
   return p;
 }
 
+// AddScan's "cell already occupied -> skip" (Mapper.cpp:1093-1096) is order dependent as soon as the smear kernel writes 100
+// off-centre: the slot's cell table for k_cell_first / k_active_set, sized for a job of np points, into the job
+static int ensure_cell_table(kh_matcher * m, Slot & s, size_t np, RasterJob & j, int32_t & max_cap)
+{
+  size_t cap = 1024;
+  while (cap < 2 * std::max<size_t>(np, 1)) {cap <<= 1;}
+  int rc = ensure_device(s.d_hkeys, s.cap_hkeys, cap, m->stream); if (rc) {return rc;}
+  rc = ensure_device(s.d_hvals, s.cap_hvals, cap, m->stream); if (rc) {return rc;}
+  rc = ensure_device(s.d_hstate, s.cap_hstate, cap, m->stream); if (rc) {return rc;}
+  rc = ensure_device(s.d_hnbr, s.cap_hnbr, cap * kMaxFootprint, m->stream); if (rc) {return rc;}
+  j.hcap = static_cast<int32_t>(cap);
+  max_cap = std::max(max_cap, j.hcap);
+  j.hkeys = s.d_hkeys; j.hvals = s.d_hvals; j.hstate = s.d_hstate; j.hnbr = s.d_hnbr;
+  return KH_OK;
+}
+
+// the per-point scratch of a slot for a job of np points; returns the padded count the lists are laid out by
+static int ensure_point_scratch(kh_matcher * m, Slot & s, size_t np, size_t & npad)
+{
+  int rc = ensure_device(s.d_ractive, s.cap_ractive, std::max<size_t>(np, 1), m->stream); if (rc) {return rc;}
+  npad = (std::max<size_t>(np, 1) + 3) & ~static_cast<size_t>(3);      // the rank quadruples are read as int4
+  return ensure_device(s.d_rlists, s.cap_rlists, npad * 10, m->stream);
+}
+
+// MatchScan steps 1-4, Mapper.cpp:543-569: the slot's grid is centred on the query's sensor pose
+static void center_slot(const kh_matcher * m, Slot & s, const double * pose)
+{
+  const double res = m->grid_resolution();
+  s.off_x = pose[0] - (0.5 * (m->roi_w - 1) * res);
+  s.off_y = pose[1] - (0.5 * (m->roi_h - 1) * res);
+}
+
+// the stamping of the hash-table route (cell table and active set when the rule is order dependent, binning, tiles) and what every
+// rasterisation ends with: the re-pitched copies and the slot's tile list brought in step
+static void launch_hash_raster(kh_matcher * m, int32_t n_jobs, int32_t most_points, int32_t max_cap, bool any_copies)
+{
+  const int32_t n_foot = static_cast<int32_t>(m->footprint100.size()) - 1;
+  if (n_foot > 0) {launch_active_set(m->d_rjobs, n_jobs, most_points, max_cap, m->stream);}
+  launch_raster(m->d_rjobs, n_jobs, most_points, m->rt_w * m->rt_h, m->d_kernel, m->kernel_size, m->stream);
+  launch_repitch(m->d_rjobs, n_jobs, m->rt_w * m->rt_h, m->stream, any_copies);
+}
+
+// the rasteriser's time by events, between ev[2] and ev[3] (profiling)
+static int account_raster(kh_matcher * m)
+{
+  if (!m->profiling) {return KH_OK;}
+  KH_HIP(hipEventRecord(m->ev[3], m->stream));
+  KH_HIP(hipEventSynchronize(m->ev[3]));
+  float ms = 0;
+  KH_HIP(hipEventElapsedTime(&ms, m->ev[2], m->ev[3]));
+  m->raster_ms += ms; m->raster_launches += 1;
+  return KH_OK;
+}
+
+// ---- rasterisation of n jobs from a map view (slots[i] <- the occupied cells of the map in reach of job i) ----
+
+// Map columns (rows) [lo, lo + cnt) whose world coordinate can round into grid cells [0, roi_n) of a grid whose cell 0 lies at `off`:
+// WorldToGrid keeps x iff -0.5 <= (x - off) * gscale < roi_n - 0.5.  One cell wide of that either side (the arithmetic here is not
+// the kernel's: roi_cell stays the judge); a pose or anchor that is not finite keeps the whole axis.
+static void clip_axis(double off, int32_t roi_n, double gscale, double anchor, double mscale, int32_t o, int32_t n, int32_t & lo, int32_t & cnt)
+{
+  const double w_lo = off - 0.5 / gscale, w_hi = off + (roi_n - 0.5) / gscale;
+  double c_lo = std::floor((w_lo - anchor) * mscale) - 1.0 - o, c_hi = std::ceil((w_hi - anchor) * mscale) + 1.0 - o;
+  if (!std::isfinite(c_lo) || !std::isfinite(c_hi)) {c_lo = 0.0; c_hi = n - 1.0;}
+  c_lo = std::max(c_lo, 0.0); c_hi = std::min(c_hi, n - 1.0);
+  if (c_hi < c_lo) {lo = 0; cnt = 0; return;}
+  lo = static_cast<int32_t>(c_lo); cnt = static_cast<int32_t>(c_hi - c_lo) + 1;
+}
+
+static int raster_map_batch(kh_matcher * m, const std::vector<RasterReq> & reqs)
+{
+  const size_t n_jobs = reqs.size();
+  const int32_t nj = static_cast<int32_t>(n_jobs);
+  for (const RasterReq & r : reqs) {
+    if (!r.map) {set_error("a batch rasterises from base scans or from a map, not both"); return KH_ERR_INVALID_ARG;}
+  }
+  int rc = ensure_pinned(m->h_mapjobs, m->cap_hmapjobs, n_jobs, m->stream); if (rc) {return rc;}
+  rc = ensure_device(m->d_mapjobs, m->cap_dmapjobs, n_jobs, m->stream); if (rc) {return rc;}
+  rc = ensure_pinned(m->h_maptotal, m->cap_hmaptotal, n_jobs, m->stream); if (rc) {return rc;}
+  rc = ensure_device(m->d_maptotal, m->cap_dmaptotal, n_jobs, m->stream); if (rc) {return rc;}
+  // the pinned mirrors are reused by every call: the previous call's uploads must have left them
+  KH_HIP(hipStreamSynchronize(m->stream));
+  // 1. the jobs' clip rectangles and units
+  size_t units = 0;
+  int32_t max_units = 0;
+  std::vector<size_t> unit_at(n_jobs);
+  for (size_t r = 0; r < n_jobs; ++r) {
+    const kh_map_view & v = *reqs[r].map;
+    Slot & s = m->slots[reqs[r].slot];
+    center_slot(m, s, reqs[r].query->sensor_pose);
+    MapJob & j = m->h_mapjobs[r];
+    std::memset(&j, 0, sizeof(j));
+    j.cells = v.device_cells; j.width_step = v.width_step; j.ox = v.ox; j.oy = v.oy;
+    j.ax = v.anchor[0]; j.ay = v.anchor[1]; j.map_scale = v.scale;
+    j.off_x = s.off_x; j.off_y = s.off_y; j.scale = m->scale; j.roi_w = m->roi_w; j.roi_h = m->roi_h;
+    clip_axis(s.off_x, m->roi_w, m->scale, v.anchor[0], v.scale, v.ox, v.width, j.i0, j.cw);
+    clip_axis(s.off_y, m->roi_h, m->scale, v.anchor[1], v.scale, v.oy, v.height, j.j0, j.ch);
+    if (j.cw == 0 || j.ch == 0) {j.cw = 0; j.ch = 0;}
+    j.units_per_row = (j.cw + 63) / 64;
+    j.n_units = j.units_per_row * j.ch;        // (< 2^31 / 64 + height: the view's size was checked)
+    unit_at[r] = units;
+    units += static_cast<size_t>(j.n_units) + 1;
+    max_units = std::max(max_units, j.n_units);
+  }
+  rc = ensure_device(m->d_mapunits, m->cap_mapunits, units, m->stream); if (rc) {return rc;}
+  for (size_t r = 0; r < n_jobs; ++r) {m->h_mapjobs[r].unit = m->d_mapunits + unit_at[r]; m->h_mapjobs[r].total = m->d_maptotal + r;}
+  if (m->profiling && !m->ev_map[0]) {
+    for (auto & ev : m->ev_map) {KH_HIP(hipEventCreate(&ev));}
+  }
+  if (m->profiling) {KH_HIP(hipEventRecord(m->ev[2], m->stream));}
+  // 2. count and scan; the totals come back once per batch
+  KH_HIP(hipMemcpyAsync(m->d_mapjobs, m->h_mapjobs, sizeof(MapJob) * n_jobs, hipMemcpyHostToDevice, m->stream));
+  if (m->profiling) {KH_HIP(hipEventRecord(m->ev_map[0], m->stream));}
+  launch_map_count(m->d_mapjobs, nj, max_units, m->stream);
+  if (m->profiling) {KH_HIP(hipEventRecord(m->ev_map[1], m->stream));}
+  KH_HIP(hipMemcpyAsync(m->h_maptotal, m->d_maptotal, sizeof(int32_t) * n_jobs, hipMemcpyDeviceToHost, m->stream));
+  KH_HIP(hipStreamSynchronize(m->stream));
+  // 3. the per-point scratch from the totals; the job's one pseudo-scan = the collected points, all of them active
+  const size_t meta_words = 4 * n_jobs;              // per job: the scan pointer (two words), the prefix {0, n}
+  rc = ensure_pinned(m->h_meta, m->cap_hmeta, meta_words, m->stream); if (rc) {return rc;}
+  rc = ensure_device(m->d_meta, m->cap_dmeta, meta_words, m->stream); if (rc) {return rc;}
+  const int32_t n_foot = static_cast<int32_t>(m->footprint100.size()) - 1;
+  int32_t most_points = 0, max_cap = 0;
+  bool any_copies = false;
+  for (size_t r = 0; r < n_jobs; ++r) {
+    Slot & s = m->slots[reqs[r].slot];
+    const int32_t total = m->h_maptotal[r];
+    if (total < 0 || total > (1 << 30)) {set_error("too many occupied map cells in reach of one match"); return KH_ERR_INVALID_ARG;}
+    const size_t np = static_cast<size_t>(total);
+    most_points = std::max(most_points, total);
+    size_t npad = 0;
+    rc = ensure_point_scratch(m, s, np, npad); if (rc) {return rc;}
+    rc = ensure_device(s.d_mappts, s.cap_mappts, 2 * std::max<size_t>(np, 1), m->stream); if (rc) {return rc;}
+    m->h_mapjobs[r].points = s.d_mappts; m->h_mapjobs[r].active = s.d_ractive;
+    int32_t * meta = m->h_meta + 4 * r;
+    const double * pts = s.d_mappts;
+    std::memcpy(meta, &pts, sizeof(pts));
+    meta[2] = 0; meta[3] = total;
+    RasterJob & j = m->h_rjobs[r];
+    fill_raster_job(m, s, reqs[r].query->sensor_pose, total, npad, j);
+    j.scan_ptr = reinterpret_cast<const double * const *>(m->d_meta + 4 * r); j.scan_prefix = m->d_meta + 4 * r + 2;
+    j.n_scans = 1; j.uniform_n = total;
+    any_copies = any_copies || s.d_grid2 != nullptr;
+    if (n_foot > 0) {rc = ensure_cell_table(m, s, np, j, max_cap); if (rc) {return rc;}}
+  }
+  KH_HIP(hipMemcpyAsync(m->d_meta, m->h_meta, sizeof(int32_t) * meta_words, hipMemcpyHostToDevice, m->stream));
+  KH_HIP(hipMemcpyAsync(m->d_rjobs, m->h_rjobs, sizeof(RasterJob) * n_jobs, hipMemcpyHostToDevice, m->stream));
+  KH_HIP(hipMemcpyAsync(m->d_mapjobs, m->h_mapjobs, sizeof(MapJob) * n_jobs, hipMemcpyHostToDevice, m->stream));
+  // 4. Grid::Clear, the fill phase, and the stamping of the hash-table route as for base scans (k_find_valid* is the one stage
+  // a map job has no use for).  The first-point tables of the slots are not touched: they stay as clean as they were.
+  launch_raster_clear(m->d_rjobs, nj, m->stream);
+  if (m->profiling) {KH_HIP(hipEventRecord(m->ev_map[2], m->stream));}
+  launch_map_fill(m->d_mapjobs, nj, max_units, m->stream);
+  if (m->profiling) {KH_HIP(hipEventRecord(m->ev_map[3], m->stream));}
+  launch_hash_raster(m, nj, most_points, max_cap, any_copies);
+  KH_HIP(hipGetLastError());
+  rc = account_raster(m); if (rc) {return rc;}
+  if (m->profiling) {
+    float a = 0, b = 0;
+    KH_HIP(hipEventElapsedTime(&a, m->ev_map[0], m->ev_map[1]));
+    KH_HIP(hipEventElapsedTime(&b, m->ev_map[2], m->ev_map[3]));
+    m->map_collect_ms += a + b; m->map_collects += 1;
+  }
+  return KH_OK;
+}
+
 // ---- rasterisation of n jobs (slots[i] <- base scans of job i) ------------------------------
 
 int raster_batch(kh_matcher * m, const std::vector<RasterReq> & reqs)
 {
   if (reqs.empty()) {return KH_OK;}
-  const double res = m->grid_resolution();
+  if (reqs[0].map) {return raster_map_batch(m, reqs);}
   const size_t n_jobs = reqs.size();
   static const bool timing = std::getenv("KH_MATCH_TIMING") != nullptr;
   const auto t_enter = std::chrono::steady_clock::now();
@@ -173,9 +339,7 @@ int raster_batch(kh_matcher * m, const std::vector<RasterReq> & reqs)
     for (size_t r = 0; r < n_jobs; ++r) {
       Slot & s = m->slots[reqs[r].slot];
       const double * pose = reqs[r].query->sensor_pose;
-      // MatchScan steps 1-4, Mapper.cpp:543-569
-      s.off_x = pose[0] - (0.5 * (m->roi_w - 1) * res);
-      s.off_y = pose[1] - (0.5 * (m->roi_h - 1) * res);
+      center_slot(m, s, pose);
       const double ** scan_ptr = reinterpret_cast<const double **>(m->h_meta + meta_at[r]);
       int32_t * scan_prefix = m->h_meta + meta_at[r] + 2 * scans_of[r];
       int32_t k = 0, run = 0, uniform_n = -1;
@@ -191,9 +355,8 @@ int raster_batch(kh_matcher * m, const std::vector<RasterReq> & reqs)
       }
       scan_prefix[k] = run;
       const size_t np = static_cast<size_t>(points_of[r]);
-      int rc = ensure_device(s.d_ractive, s.cap_ractive, std::max<size_t>(np, 1), m->stream); if (rc) {return rc;}
-      const size_t npad = (std::max<size_t>(np, 1) + 3) & ~static_cast<size_t>(3);      // the rank quadruples are read as int4
-      rc = ensure_device(s.d_rlists, s.cap_rlists, npad * 10, m->stream); if (rc) {return rc;}
+      size_t npad = 0;
+      int rc = ensure_point_scratch(m, s, np, npad); if (rc) {return rc;}
       RasterJob & j = m->h_rjobs[r];
       fill_raster_job(m, s, pose, points_of[r], npad, j);
       j.scan_ptr = reinterpret_cast<const double * const *>(m->d_meta + meta_at[r]); j.scan_prefix = m->d_meta + meta_at[r] + 2 * scans_of[r];
@@ -204,17 +367,7 @@ int raster_batch(kh_matcher * m, const std::vector<RasterReq> & reqs)
         rc = ensure_seq_tables(m, s, points_of[r], j); if (rc) {return rc;}
         s.first_clean = false;                      // until this batch's stamping launch has handed the table back
       } else if (n_foot > 0) {
-        // AddScan's "cell already occupied -> skip" (Mapper.cpp:1093-1096) is order dependent as soon as the smear kernel
-        // writes 100 off-centre: cell table for k_cell_first / k_active_set
-        size_t cap = 1024;
-        while (cap < 2 * std::max<size_t>(np, 1)) {cap <<= 1;}
-        rc = ensure_device(s.d_hkeys, s.cap_hkeys, cap, m->stream); if (rc) {return rc;}
-        rc = ensure_device(s.d_hvals, s.cap_hvals, cap, m->stream); if (rc) {return rc;}
-        rc = ensure_device(s.d_hstate, s.cap_hstate, cap, m->stream); if (rc) {return rc;}
-        rc = ensure_device(s.d_hnbr, s.cap_hnbr, cap * kMaxFootprint, m->stream); if (rc) {return rc;}
-        j.hcap = static_cast<int32_t>(cap);
-        max_cap = std::max(max_cap, j.hcap);
-        j.hkeys = s.d_hkeys; j.hvals = s.d_hvals; j.hstate = s.d_hstate; j.hnbr = s.d_hnbr;
+        rc = ensure_cell_table(m, s, np, j, max_cap); if (rc) {return rc;}
       }
     }
     return KH_OK;
@@ -250,26 +403,18 @@ int raster_batch(kh_matcher * m, const std::vector<RasterReq> & reqs)
       launch_seq_stage(m->d_rjobs, nj, nullptr, m->stream);
     }
     for (size_t r = 0; r < n_jobs; ++r) {m->slots[reqs[r].slot].first_clean = true;}
+    launch_repitch(m->d_rjobs, static_cast<int32_t>(n_jobs), m->rt_w * m->rt_h, m->stream, any_copies);
   } else {
     launch_find_valid(m->d_rjobs, reinterpret_cast<const ValidItem *>(m->d_meta + items_at), static_cast<int32_t>(n_items), max_scan_n, m->stream);
-    if (n_foot > 0) {launch_active_set(m->d_rjobs, static_cast<int32_t>(n_jobs), most_points, max_cap, m->stream);}
-    launch_raster(m->d_rjobs, static_cast<int32_t>(n_jobs), most_points, m->rt_w * m->rt_h, m->d_kernel, m->kernel_size, m->stream);
+    launch_hash_raster(m, static_cast<int32_t>(n_jobs), most_points, max_cap, any_copies);
   }
-  launch_repitch(m->d_rjobs, static_cast<int32_t>(n_jobs), m->rt_w * m->rt_h, m->stream, any_copies);
   KH_HIP(hipGetLastError());
   if (timing) {
     std::fprintf(stderr, "[kh raster] host %.3f ms: %zu jobs, %zu (job, scan) items, %zu distinct scans, %.1f MB of points uploaded\n",
       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count(), n_jobs, n_items, copies.size(),
       arena_points * 16.0 / 1e6);
   }
-  if (m->profiling) {
-    KH_HIP(hipEventRecord(m->ev[3], m->stream));
-    KH_HIP(hipEventSynchronize(m->ev[3]));
-    float ms = 0;
-    KH_HIP(hipEventElapsedTime(&ms, m->ev[2], m->ev[3]));
-    m->raster_ms += ms; m->raster_launches += 1;
-  }
-  return KH_OK;
+  return account_raster(m);
 }
 
 // ---- CorrelateScan on a set of slots ---------------------------------------------------------
@@ -1259,6 +1404,9 @@ int kh_matcher_create(double search_size, double resolution, double smear, doubl
   }
   if ((e = hipHostMalloc(reinterpret_cast<void **>(&m->h_rjobs), sizeof(RasterJob) * max_batch, hipHostMallocDefault)) != hipSuccess) {return fail(e, "hipHostMalloc");}
   if ((e = hipMalloc(reinterpret_cast<void **>(&m->d_rjobs), sizeof(RasterJob) * max_batch)) != hipSuccess) {return fail(e, "hipMalloc");}
+  // (the fills above run on the null stream, which the handle's own non-blocking streams do not wait for: a rasterisation that
+  // starts with little host work in front of it -- from a map -- must not be overtaken by the zeroing of its grid)
+  if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) {return fail(e, "hipStreamSynchronize");}
   *out = m;
   return KH_OK;
 }
@@ -1274,7 +1422,7 @@ void kh_matcher_destroy(kh_matcher * m)
     hipFree(s.d_chunks); hipFree(s.d_chunk_counts);
     hipFree(s.d_sums); hipFree(s.d_resp); hipFree(s.d_ractive);
     hipFree(s.d_hkeys); hipFree(s.d_hvals); hipFree(s.d_hstate); hipFree(s.d_hnbr);
-    hipFree(s.d_first); hipFree(s.d_cand); hipFree(s.d_seqctl); hipFree(s.d_work2);
+    hipFree(s.d_first); hipFree(s.d_cand); hipFree(s.d_seqctl); hipFree(s.d_work2); hipFree(s.d_mappts);
   }
   hipFree(m->d_kernel); hipFree(m->d_rjobs); hipFree(m->d_load_counter); hipFree(m->d_tab);
   for (auto & b : m->batch) {
@@ -1290,6 +1438,10 @@ void kh_matcher_destroy(kh_matcher * m)
   }
   for (auto & t : m->tables) {hipFree(t->d_dist_pen); t->d_dist_pen = nullptr;}
   hipFree(m->d_arena); hipFree(m->d_meta);
+  hipFree(m->d_mapjobs); hipFree(m->d_maptotal); hipFree(m->d_mapunits);
+  if (m->h_mapjobs) {hipHostFree(m->h_mapjobs);}
+  if (m->h_maptotal) {hipHostFree(m->h_maptotal);}
+  for (auto & ev : m->ev_map) {if (ev) {hipEventDestroy(ev);}}
   if (m->h_arena) {hipHostFree(m->h_arena);}
   if (m->h_meta) {hipHostFree(m->h_meta);}
   if (m->h_rjobs) {hipHostFree(m->h_rjobs);}
@@ -1335,6 +1487,29 @@ int kh_matcher_add_scans(kh_matcher * m, int32_t slot, const kh_scan * query, co
   if (!m || slot < 0 || slot >= m->max_batch || !query || n_base < 0 || (n_base > 0 && !base)) {return KH_ERR_INVALID_ARG;}
   KH_HIP(hipSetDevice(m->device));
   std::vector<RasterReq> reqs{RasterReq{slot, query, base, n_base}};
+  int rc = raster_batch(m, reqs);
+  if (rc) {return rc;}
+  KH_HIP(hipStreamSynchronize(m->stream));
+  return KH_OK;
+}
+
+// a view the map entry points can read on the matcher's device
+static int check_view(const kh_matcher * m, const kh_map_view * v)
+{
+  if (!v || !v->device_cells || v->width <= 0 || v->height <= 0 || v->width_step < v->width || !std::isfinite(v->scale) || !(v->scale > 0.0)) {
+    set_error("malformed map view");
+    return KH_ERR_INVALID_ARG;
+  }
+  if (static_cast<int64_t>(v->width_step) * v->height > (1ll << 31) - 4096) {set_error("map view too large"); return KH_ERR_INVALID_ARG;}
+  if (v->device != m->device) {set_error("the map view lies on another device than the matcher"); return KH_ERR_INVALID_ARG;}
+  return KH_OK;
+}
+
+int kh_matcher_add_map(kh_matcher * m, int32_t slot, const kh_scan * query, const kh_map_view * map)
+{
+  if (!m || slot < 0 || slot >= m->max_batch || !query || check_view(m, map) != KH_OK) {return KH_ERR_INVALID_ARG;}
+  KH_HIP(hipSetDevice(m->device));
+  std::vector<RasterReq> reqs{RasterReq{slot, query, nullptr, 0, map}};
   int rc = raster_batch(m, reqs);
   if (rc) {return rc;}
   KH_HIP(hipStreamSynchronize(m->stream));
@@ -1392,12 +1567,14 @@ int kh_matcher_correlate(kh_matcher * m, int32_t slot, const kh_scan * query, co
   return KH_OK;
 }
 
-// MatchScan for n independent (query, base chain) pairs, stage by stage over the whole batch
-int kh_matcher_match_batch(kh_matcher * m, int32_t n, const kh_scan * queries, const kh_scan * base,
-  const int32_t * base_begin, int32_t do_penalize, int32_t do_refine, double * means, double * covs,
+}  // extern "C"
+
+// MatchScan for n independent queries, stage by stage over the whole batch: against (query, base chain) pairs, or -- map != nullptr,
+// base and base_begin unused -- all of them against one map view
+static int match_batch(kh_matcher * m, int32_t n, const kh_scan * queries, const kh_scan * base,
+  const int32_t * base_begin, const kh_map_view * map, int32_t do_penalize, int32_t do_refine, double * means, double * covs,
   double * responses, int32_t * status)
 {
-  if (!m || n < 0 || n > m->max_batch || !queries || !base_begin || !means || !covs || !responses) {return KH_ERR_INVALID_ARG;}
   KH_HIP(hipSetDevice(m->device));
   static const bool batch_timing = std::getenv("KH_MATCH_TIMING") != nullptr;
   const auto t_batch = std::chrono::steady_clock::now();
@@ -1417,7 +1594,7 @@ int kh_matcher_match_batch(kh_matcher * m, int32_t n, const kh_scan * queries, c
   std::vector<RasterReq> rreqs;
   for (int32_t i = 0; i < n; ++i) {
     if (check_scan(&queries[i]) != KH_OK) {return KH_ERR_INVALID_ARG;}
-    const int32_t nb = base_begin[i + 1] - base_begin[i];
+    const int32_t nb = map ? 0 : base_begin[i + 1] - base_begin[i];
     if (nb < 0 || (nb > 0 && !base)) {return KH_ERR_INVALID_ARG;}
     for (int32_t b = 0; b < nb; ++b) {
       if (check_scan(&base[base_begin[i] + b]) != KH_OK) {return KH_ERR_INVALID_ARG;}
@@ -1433,13 +1610,13 @@ int kh_matcher_match_batch(kh_matcher * m, int32_t n, const kh_scan * queries, c
       continue;
     }
     active.push_back(i);
-    rreqs.push_back(RasterReq{i, &queries[i], base ? base + base_begin[i] : nullptr, nb});
+    rreqs.push_back(RasterReq{i, &queries[i], (base && !map) ? base + base_begin[i] : nullptr, nb, map});
   }
   // ONE MatchScan -- what the reference's API issues (Mapper.cpp:2714-2717) -- takes the fused path (matcher_seq.cpp); it hands
   // back, pass by pass, whatever it could not finish
   int rc = KH_OK;
   bool coarse_done = false, fine_done = false;
-  if (n == 1 && active.size() == 1) {
+  if (n == 1 && active.size() == 1 && !map) {
     int seq_status = KH_OK;
     rc = seq_match(m, &queries[0], base ? base + base_begin[0] : nullptr, base_begin[1] - base_begin[0], do_penalize != 0, do_refine != 0,
       means, covs, responses, &seq_status, &coarse_done, &fine_done);
@@ -1513,6 +1690,42 @@ int kh_matcher_match_batch(kh_matcher * m, int32_t n, const kh_scan * queries, c
     if (st[i] != KH_OK) {worst = st[i];}
   }
   return status ? KH_OK : worst;
+}
+
+extern "C" {
+
+int kh_matcher_match_batch(kh_matcher * m, int32_t n, const kh_scan * queries, const kh_scan * base,
+  const int32_t * base_begin, int32_t do_penalize, int32_t do_refine, double * means, double * covs,
+  double * responses, int32_t * status)
+{
+  if (!m || n < 0 || n > m->max_batch || !queries || !base_begin || !means || !covs || !responses) {return KH_ERR_INVALID_ARG;}
+  return match_batch(m, n, queries, base, base_begin, nullptr, do_penalize, do_refine, means, covs, responses, status);
+}
+
+int kh_matcher_match_map_batch(kh_matcher * m, int32_t n, const kh_scan * queries, const kh_map_view * map,
+  int32_t do_penalize, int32_t do_refine, double * means, double * covs, double * responses, int32_t * status)
+{
+  if (!m || n < 0 || n > m->max_batch || !queries || !means || !covs || !responses || check_view(m, map) != KH_OK) {return KH_ERR_INVALID_ARG;}
+  return match_batch(m, n, queries, nullptr, nullptr, map, do_penalize, do_refine, means, covs, responses, status);
+}
+
+int kh_matcher_match_map(kh_matcher * m, const kh_scan * query, const kh_map_view * map, int32_t do_penalize, int32_t do_refine,
+  double mean[3], double cov[9], double * response)
+{
+  if (!m || !query || !mean || !cov || !response) {return KH_ERR_INVALID_ARG;}
+  int32_t status = KH_OK;
+  int rc = kh_matcher_match_map_batch(m, 1, query, map, do_penalize, do_refine, mean, cov, response, &status);
+  if (rc) {return rc;}
+  return status;
+}
+
+int kh_matcher_profile_map(kh_matcher * m, double * collect_ms, int64_t * collects)
+{
+  if (!m) {return KH_ERR_INVALID_ARG;}
+  if (collect_ms) {*collect_ms = m->map_collect_ms;}
+  if (collects) {*collects = m->map_collects;}
+  m->map_collect_ms = 0; m->map_collects = 0;
+  return KH_OK;
 }
 
 int kh_matcher_match(kh_matcher * m, const kh_scan * query, const kh_scan * base, int32_t n_base,

@@ -783,6 +783,93 @@ void launch_raster(const RasterJob * d_jobs, int32_t n_jobs, int32_t max_points,
   launch_raster_tiles(d_jobs, n_jobs, max_points, max_tiles, d_kernel, kernel_size, stream);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Map-sourced rasterisation (kh_matcher_add_map / _match_map*): the points of a job are the world points of the map's occupied
+// cells, in row-major order, instead of base scans' readings.  k_map_collect compacts them into the slot's point array; from
+// there the job is an ordinary rasterisation job of ONE scan whose points are all active (no FindValidPoints).
+// The order decides which point stamps when the smear kernel holds 100 off-centre, so no atomic decides a position: a wave
+// takes a unit of 64 consecutive cells of a row, its ballot's popcount is the unit's count (count phase), one workgroup per job
+// turns the counts into their exclusive prefix (k_map_collect_scan), and the fill phase repeats the ballot and writes cell
+// `lane` of unit u to prefix[u] + the set bits below the lane.  Both phases read the same cells with the same test.
+template <bool kFill>
+__global__ __launch_bounds__(256) void k_map_collect(const MapJob * jobs)
+{
+  const MapJob & job = jobs[blockIdx.y];
+  const int lane = threadIdx.x & 63;
+  const int first = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), step = (int)gridDim.x * 4;
+  for (int u = first; u < job.n_units; u += step) {
+    const int row = u / job.units_per_row, seg = u - row * job.units_per_row;
+    const int ci = 64 * seg + lane;
+    bool hit = false;
+    double2 w = make_double2(0.0, 0.0);
+    if (ci < job.cw) {
+      const int i = job.i0 + ci, j = job.j0 + row;
+      if (job.cells[(size_t)j * job.width_step + i] == (uint8_t)kOccupied) {
+        // CoordinateConverter::GridToWorld without flip (Karto.h:4443-4457), the lattice index summed in integers first
+        w.x = job.ax + (double)((long long)job.ox + i) / job.map_scale;
+        w.y = job.ay + (double)((long long)job.oy + j) / job.map_scale;
+        int32_t gx, gy;
+        hit = roi_cell(job, w, gx, gy);
+      }
+    }
+    const unsigned long long mask = __ballot(hit);
+    if (!kFill) {
+      if (lane == 0) {job.unit[u] = __builtin_popcountll(mask);}
+    } else if (hit) {
+      const int at = job.unit[u] + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
+      // (a view is borrowed: cells written between the two phases, against the contract, must not carry a write past the unit's room)
+      if (at < job.unit[u + 1]) {
+        reinterpret_cast<double2 *>(job.points)[at] = w;
+        job.active[at] = 1;
+      }
+    }
+  }
+}
+
+// counts -> exclusive prefix, in place; unit[n_units] and *total take the sum.  One workgroup per job.
+__global__ __launch_bounds__(1024) void k_map_collect_scan(const MapJob * jobs)
+{
+  const MapJob & job = jobs[blockIdx.x];
+  const int n = job.n_units;
+  const int per = (n + 1023) / 1024;
+  const int lo = min(n, (int)threadIdx.x * per), hi = min(n, lo + per);
+  __shared__ int32_t s_sum[1024];
+  int32_t sum = 0;
+  for (int u = lo; u < hi; ++u) {sum += job.unit[u];}
+  s_sum[threadIdx.x] = sum;
+  __syncthreads();
+  for (int d = 1; d < 1024; d <<= 1) {                 // Hillis-Steele inclusive scan of the per-thread totals
+    int32_t a = 0;
+    if ((int)threadIdx.x >= d) {a = s_sum[threadIdx.x - d];}
+    __syncthreads();
+    s_sum[threadIdx.x] += a;
+    __syncthreads();
+  }
+  int32_t run = s_sum[threadIdx.x] - sum;
+  for (int u = lo; u < hi; ++u) {
+    const int32_t c = job.unit[u];
+    job.unit[u] = run;
+    run += c;
+  }
+  if (threadIdx.x == 1023) {job.unit[n] = s_sum[1023]; *job.total = s_sum[1023];}
+}
+
+static int map_collect_blocks(int32_t max_units) {return std::max(1, std::min((max_units + 3) / 4, 1024));}
+
+void launch_map_count(const MapJob * d_jobs, int32_t n_jobs, int32_t max_units, void * stream)
+{
+  if (n_jobs <= 0) {return;}
+  hipStream_t s = (hipStream_t)stream;
+  if (max_units > 0) {hipLaunchKernelGGL(k_map_collect<false>, dim3(map_collect_blocks(max_units), n_jobs), dim3(256), 0, s, d_jobs);}
+  hipLaunchKernelGGL(k_map_collect_scan, dim3(n_jobs), dim3(1024), 0, s, d_jobs);
+}
+
+void launch_map_fill(const MapJob * d_jobs, int32_t n_jobs, int32_t max_units, void * stream)
+{
+  if (n_jobs <= 0 || max_units <= 0) {return;}
+  hipLaunchKernelGGL(k_map_collect<true>, dim3(map_collect_blocks(max_units), n_jobs), dim3(256), 0, (hipStream_t)stream, d_jobs);
+}
+
 // Re-pitched copies (CorrJob::grid2): the tiles the previous rasterisation touched are zeroed, the tiles this one touched
 // are copied from the grid, and this rasterisation's tile list becomes the "previous" one.  Traffic: 8 KB per touched tile.
 // column-decimated copies (RasterJob::copy_kind 2): cells x .. x + 7 (x a multiple of 8) of grid row y, as two dwords

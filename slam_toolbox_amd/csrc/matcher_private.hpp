@@ -164,6 +164,8 @@ struct Slot
   int32_t * d_cand = nullptr; size_t cap_cand = 0;
   int32_t * d_seqctl = nullptr;
   int32_t * d_work2 = nullptr; size_t cap_work2 = 0;
+  // map-sourced rasterisation: the world points k_map_collect compacted for this slot (2 doubles per point)
+  double * d_mappts = nullptr; size_t cap_mappts = 0;
   // last correlate (for the introspection calls)
   struct {int32_t P = 0, nx = 0, ny = 0, na = 0; double denom = 1.0;} last;
   bool has_last = false;
@@ -200,6 +202,13 @@ struct kh_matcher
   double * h_arena = nullptr; double * d_arena = nullptr; size_t cap_harena = 0, cap_darena = 0;
   int32_t * h_meta = nullptr; int32_t * d_meta = nullptr; size_t cap_hmeta = 0, cap_dmeta = 0;
   RasterJob * h_rjobs = nullptr; RasterJob * d_rjobs = nullptr;
+  // map-sourced rasterisation (made at its first use): the collect jobs, their totals (one int32 per job), the units' counts /
+  // prefixes of the whole batch
+  MapJob * h_mapjobs = nullptr; MapJob * d_mapjobs = nullptr; size_t cap_hmapjobs = 0, cap_dmapjobs = 0;
+  int32_t * h_maptotal = nullptr; int32_t * d_maptotal = nullptr; size_t cap_hmaptotal = 0, cap_dmaptotal = 0;
+  int32_t * d_mapunits = nullptr; size_t cap_mapunits = 0;
+  hipEvent_t ev_map[4] = {nullptr, nullptr, nullptr, nullptr};      // around count + scan and around fill (profiling)
+  double map_collect_ms = 0; int64_t map_collects = 0;
   bool keep_responses = false;
   bool force_chunks = false;       // kh_matcher_set_debug bit 3: chunk every batch of >= 128 (tests)
   bool dense_score = false;        // kh_matcher_set_debug bit 2: do not skip beams whose window is empty
@@ -259,7 +268,9 @@ int ensure_pinned(T *& p, size_t & cap, size_t need, hipStream_t stream)
 
 
 // ---- requests ------------------------------------------------------------------------------------
-struct RasterReq {int32_t slot; const kh_scan * query; const kh_scan * base; int32_t n_base;};
+// the grid of `slot`, centred on `query`, from EITHER the base scans OR (map != nullptr) the occupied cells of a map view; the
+// requests of one batch are all of one kind
+struct RasterReq {int32_t slot; const kh_scan * query; const kh_scan * base; int32_t n_base; const kh_map_view * map = nullptr;};
 struct CorrReq
 {
   int32_t slot = 0;

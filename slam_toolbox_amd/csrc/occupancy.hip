@@ -344,6 +344,25 @@ __global__ __launch_bounds__(256) void k_occ_to_nav(const uint8_t * __restrict__
   out[i] = occ_nav4(v);
 }
 
+// The inverse of k_occ_to_nav (kh_occupancy_write_nav): from a DENSE width x height array of nav values into the ws-strided cells,
+// -1 -> 0 (unknown), 100 -> 100 (occupied), 0 -> 255 (free); the host has refused every other value.  One thread per dword of the
+// cells (ws is a multiple of 8); the bytes of the row padding are written as 0.
+__global__ __launch_bounds__(256) void k_nav_to_occ(const int8_t * __restrict__ nav, int32_t width, int32_t ws, int64_t words,
+  uint32_t * __restrict__ cells)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= words) {return;}
+  const int32_t words_per_row = ws >> 2;
+  const int64_t y = i / words_per_row;
+  const int32_t x = 4 * (int32_t)(i - y * words_per_row);
+  uint32_t v = 0;
+  for (int32_t b = 0; b < 4 && x + b < width; ++b) {
+    const int32_t n = nav[y * width + x + b];
+    v |= (n == 100 ? 100u : n == 0 ? 255u : 0u) << (8 * b);
+  }
+  cells[i] = v;
+}
+
 // The map feed's compare-and-pack (kh_map_feed_poll).  One wave per STRIP of four horizontally adjacent
 // tiles, 64 cells x 16 rows: a load instruction of the wave reads four whole 64-byte row segments.  A lane owns the dword column
 // lane & 15 of the strip -- so tile (lane & 15) >> 2 -- and the rows lane >> 4, + 4, + 8, + 12.  It turns its four dwords of cell
@@ -606,7 +625,10 @@ int kh_occupancy_create(int32_t width, int32_t height, double offset_x, double o
     hipMalloc(reinterpret_cast<void **>(&g->dev.hits), size * 4) != hipSuccess ||
     hipMalloc(reinterpret_cast<void **>(&g->dev.cells), size) != hipSuccess ||
     hipMemset(g->dev.pass, 0, size * 4) != hipSuccess || hipMemset(g->dev.hits, 0, size * 4) != hipSuccess ||
-    hipMemset(g->dev.cells, 0, size) != hipSuccess)
+    hipMemset(g->dev.cells, 0, size) != hipSuccess ||
+    // (the fills may still be in flight on the null stream, and the grid's own stream does not wait for that one: a write queued
+    // there right after the create -- kh_occupancy_write_nav's small kernel -- must not be overtaken by them)
+    hipStreamSynchronize(nullptr) != hipSuccess)
   {
     set_error("kh_occupancy_create: HIP allocation failed");
     kh_occupancy_destroy(g);
@@ -737,6 +759,51 @@ int kh_occupancy_geometry(kh_occupancy * g, double offset[2], double * resolutio
   if (!g) {return KH_ERR_INVALID_ARG;}
   if (offset) {offset[0] = g->dev.off_x; offset[1] = g->dev.off_y;}
   if (resolution) {*resolution = 1.0 / g->dev.scale;}
+  return KH_OK;
+}
+
+int kh_occupancy_view(kh_occupancy * g, kh_map_view * out)
+{
+  if (!g || !out) {return KH_ERR_INVALID_ARG;}
+  out->device_cells = g->dev.cells; out->device = g->device;
+  out->width = g->dev.width; out->height = g->dev.height; out->width_step = g->dev.ws;
+  out->ox = 0; out->oy = 0;
+  out->anchor[0] = g->dev.off_x; out->anchor[1] = g->dev.off_y; out->scale = g->dev.scale;
+  return KH_OK;
+}
+
+int kh_occupancy_write_nav(kh_occupancy * g, const int8_t * nav)
+{
+  if (!g || !nav) {return KH_ERR_INVALID_ARG;}
+  const int64_t total = static_cast<int64_t>(g->dev.width) * g->dev.height;
+  for (int64_t i = 0; i < total; ++i) {
+    if (nav[i] != -1 && nav[i] != 0 && nav[i] != 100) {
+      set_error("kh_occupancy_write_nav: value " + std::to_string(nav[i]) + " at " + std::to_string(i) + " is none of -1, 0, 100");
+      return KH_ERR_INVALID_ARG;
+    }
+  }
+  if (hipSetDevice(g->device) != hipSuccess) {return KH_ERR_HIP;}
+  // (the dense values go through kh_occupancy_read_nav's buffer)
+  const size_t bytes = (static_cast<size_t>(total) + 3) & ~static_cast<size_t>(3);
+  if (!grow_device(g->stream, reinterpret_cast<void **>(&g->d_nav), &g->cap_nav, bytes, bytes)) {
+    set_error("kh_occupancy_write_nav: input allocation failed");
+    return KH_ERR_HIP;
+  }
+  const size_t size = static_cast<size_t>(g->dev.ws) * g->dev.height;
+  const int64_t words = static_cast<int64_t>(size / 4);
+  if (hipMemcpyAsync(g->d_nav, nav, static_cast<size_t>(total), hipMemcpyHostToDevice, g->stream) != hipSuccess) {
+    (void)hipStreamSynchronize(g->stream);
+    return KH_ERR_HIP;
+  }
+  hipLaunchKernelGGL(k_nav_to_occ, dim3(static_cast<unsigned>((words + 255) / 256)), dim3(256), 0, g->stream,
+    reinterpret_cast<const int8_t *>(g->d_nav), g->dev.width, g->dev.ws, words, reinterpret_cast<uint32_t *>(g->dev.cells));
+  // (the stream is drained before returning: `nav` is the caller's pageable memory)
+  if (hipMemsetAsync(g->dev.pass, 0, size * 4, g->stream) != hipSuccess || hipMemsetAsync(g->dev.hits, 0, size * 4, g->stream) != hipSuccess ||
+    hipStreamSynchronize(g->stream) != hipSuccess)
+  {
+    set_error(std::string("kh_occupancy_write_nav: ") + hipGetErrorString(hipGetLastError()));
+    return KH_ERR_HIP;
+  }
   return KH_OK;
 }
 

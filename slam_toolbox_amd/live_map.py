@@ -61,6 +61,13 @@ class LiveMap:
         capi.check(capi.lib().kh_live_map_read(self._h, None, p.ctypes.data, h.ctypes.data), "kh_live_map_read")
         return p.reshape(shape), h.reshape(shape)
 
+    def view(self) -> capi.KhMapView:
+        """kh_live_map_view: the window's cell states where they lie on the device, for ScanMatcher.AddMap / MatchScanMap*.
+        Borrowed: valid until the next update(); raises (KH_ERR_NOT_FOUND) before the first scan."""
+        v = capi.KhMapView()
+        capi.check(capi.lib().kh_live_map_view(self._h, C.byref(v)), "kh_live_map_view")
+        return v
+
     def stats(self) -> dict:
         st = capi.KhLiveMapStats()
         capi.check(capi.lib().kh_live_map_stats(self._h, C.byref(st)), "kh_live_map_stats")

@@ -86,6 +86,31 @@ class OccupancyGrid:
         capi.check(capi.lib().kh_occupancy_read_nav(self._h, out.ctypes.data), "kh_occupancy_read_nav")
         return out
 
+    def view(self) -> capi.KhMapView:
+        """kh_occupancy_view: the cell states where they lie on the device, for ScanMatcher.AddMap / MatchScanMap*.  Borrowed:
+        valid until the grid is next updated, cleared, written or closed."""
+        v = capi.KhMapView()
+        capi.check(capi.lib().kh_occupancy_view(self._h, C.byref(v)), "kh_occupancy_view")
+        return v
+
+    @staticmethod
+    def from_nav(nav, offset, resolution, device: int = 0):
+        """A grid from the data of a nav_msgs/OccupancyGrid or a map image turned into its values: nav is (height, width) int8 of
+        -1 unknown / 100 occupied / 0 free (kh_occupancy_write_nav, the inverse of nav()); any other value raises.  The counters
+        are zero: Update() would recompute the cells from them."""
+        nav = np.ascontiguousarray(nav, dtype=np.int8)
+        if nav.ndim != 2:
+            raise ValueError("nav must be (height, width)")
+        g = OccupancyGrid(nav.shape[1], nav.shape[0], offset, resolution, device)
+        g.write_nav(nav)
+        return g
+
+    def write_nav(self, nav):
+        nav = np.ascontiguousarray(nav, dtype=np.int8)
+        if nav.shape != (self.height, self.width):
+            raise ValueError("nav must be (height, width) of this grid")
+        capi.check(capi.lib().kh_occupancy_write_nav(self._h, nav.ctypes.data), "kh_occupancy_write_nav")
+
     def counters(self):
         p = np.zeros(self.width_step * self.height, dtype=np.uint32)
         h = np.zeros(self.width_step * self.height, dtype=np.uint32)

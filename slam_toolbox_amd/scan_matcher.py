@@ -116,6 +116,11 @@ def _scan_array(scans):
     return arr
 
 
+def _map_view(grid_or_view) -> capi.KhMapView:
+    """a kh_map_view from an OccupancyGrid / LiveMap (their view()) or a capi.KhMapView filled by hand"""
+    return grid_or_view if isinstance(grid_or_view, capi.KhMapView) else grid_or_view.view()
+
+
 class ScanMatcher:
     def __init__(self, handle, max_batch):
         self._h = handle
@@ -189,6 +194,33 @@ class ScanMatcher:
         cs = scan.c()
         capi.check(capi.lib().kh_matcher_add_scans(self._h, slot, C.byref(cs), _scan_array(base_scans), len(base_scans)),
                    "kh_matcher_add_scans")
+
+    def AddMap(self, scan, grid_or_view, slot=0):
+        """kh_matcher_add_map: AddScans with the occupied cells of a map (OccupancyGrid, LiveMap or a capi.KhMapView) in the place
+        of the base scans' points"""
+        cs, v = scan.c(), _map_view(grid_or_view)
+        capi.check(capi.lib().kh_matcher_add_map(self._h, slot, C.byref(cs), C.byref(v)), "kh_matcher_add_map")
+
+    def MatchScanMap(self, scan, grid_or_view, doPenalize=True, doRefineMatch=True):
+        """MatchScan against a map instead of base scans (kh_matcher_match_map)"""
+        mean, cov, resp = np.zeros(3), np.zeros(9), C.c_double(0.0)
+        cs, v = scan.c(), _map_view(grid_or_view)
+        rc = capi.lib().kh_matcher_match_map(self._h, C.byref(cs), C.byref(v), int(doPenalize), int(doRefineMatch), mean, cov, C.byref(resp))
+        if rc == capi.KH_ERR_SEARCH:
+            raise RuntimeError("Mapper FATAL ERROR - Unable to find best position")
+        capi.check(rc, "kh_matcher_match_map")
+        return resp.value, mean, cov.reshape(3, 3)
+
+    def MatchScanMapBatch(self, scans, grid_or_view, doPenalize=True, doRefineMatch=True, scan_array=None):
+        """n <= max_batch independent MatchScans against ONE map (kh_matcher_match_map_batch); scan_array: (_scan_array(scans), n),
+        reusable across calls"""
+        n = len(scans) if scan_array is None else scan_array[1]
+        arr = _scan_array(scans) if scan_array is None else scan_array[0]
+        v = _map_view(grid_or_view)
+        means, covs, resp, status = np.zeros(3 * n), np.zeros(9 * n), np.zeros(n), np.zeros(n, dtype=np.int32)
+        capi.check(capi.lib().kh_matcher_match_map_batch(self._h, n, arr, C.byref(v), int(doPenalize), int(doRefineMatch),
+                                                         means, covs, resp, status), "kh_matcher_match_map_batch")
+        return resp, means.reshape(n, 3), covs.reshape(n, 3, 3), status
 
     def CorrelateScan(self, scan, searchCenter, searchSpaceOffset, searchSpaceResolution, searchAngleOffset,
                       searchAngleResolution, doPenalize, covariance=None, doingFineMatch=False, slot=0):
@@ -321,6 +353,12 @@ class ScanMatcher:
         o, t = C.c_double(), C.c_double()
         capi.check(capi.lib().kh_matcher_profile_side(self._h, C.byref(o), C.byref(t)), "kh_matcher_profile_side")
         return {"offsets_ms": o.value, "ties_ms": t.value}
+
+    def profile_map(self):
+        """GPU ms of the map-collect kernels and the number of map rasterisations profiled since the last call"""
+        ms, n = C.c_double(), C.c_int64()
+        capi.check(capi.lib().kh_matcher_profile_map(self._h, C.byref(ms), C.byref(n)), "kh_matcher_profile_map")
+        return {"collect_ms": ms.value, "collects": n.value}
 
     def score_loads(self, reset=True):
         """wave-level dword-load instructions (256 B each) K3 issued for the searches run while profiling was on"""
