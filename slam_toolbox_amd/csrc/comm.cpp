@@ -23,11 +23,10 @@
 #include <string>
 
 #include "../../include/karto_hip.h"
+#include "host_common.hpp"
 
 namespace kh
 {
-void set_error(const std::string & s);
-
 namespace
 {
 struct RcclApi
@@ -99,6 +98,15 @@ namespace kh
 {
 // (library-internal: the mapper's host code is free of HIP) waits for everything queued on the stream
 void stream_synchronize(void * hip_stream) {(void)hipStreamSynchronize(static_cast<hipStream_t>(hip_stream));}
+
+int require_device(int32_t device)
+{
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) == hipSuccess && device >= 0 && device < ndev) {return KH_OK;}
+  (void)hipGetLastError();
+  set_error("no usable HIP device (libkartohip has no CPU fallback)");
+  return KH_ERR_NO_DEVICE;
+}
 }  // namespace kh
 
 extern "C" {

@@ -25,11 +25,11 @@
 #include <vector>
 
 #include "../../include/karto_hip.h"
+#include "graph_internal.hpp"
+#include "host_common.hpp"
 
 namespace kh
 {
-void set_error(const std::string & s);
-
 constexpr double kTol = 1e-06;      // KT_TOLERANCE, Math.h:41
 constexpr uint8_t kInRange = 1;     // squaredDistance <  maxDistance^2 + KT_TOLERANCE   (Mapper.cpp:1988-1990)
 constexpr uint8_t kVisitable = 2;   // squaredDistance <= maxDistance^2 - KT_TOLERANCE   (Mapper.cpp:1326-1327)

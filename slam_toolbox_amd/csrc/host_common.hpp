@@ -1,0 +1,20 @@
+// What every host file of libkartohip uses of the others: the last-error text, the persistent host pools and the two device calls
+// the HIP-free files make.  Needs no HIP header (spa_symbolic.cpp is also built alone on the CPU).  Not part of the public ABI
+// (include/karto_hip.h).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <functional>
+#include <string>
+
+namespace kh
+{
+void set_error(const std::string & s);                                            // matcher_host.cpp: the thread's kh_last_error text
+// the persistent host pools (host_pool.hpp, instantiated by matcher_host.cpp): fn(i) for i in [0, n), back when all are done
+void host_parallel_for(size_t n, const std::function<void(size_t)> & fn);
+void host_parallel_for_wide(size_t n, const std::function<void(size_t)> & fn);
+// comm.cpp: waits for everything queued on the HIP stream
+void stream_synchronize(void * hip_stream);
+// comm.cpp: KH_OK when `device` can be used, otherwise KH_ERR_NO_DEVICE and its text; require_device(0) asks for any device at all
+int require_device(int32_t device);
+}  // namespace kh

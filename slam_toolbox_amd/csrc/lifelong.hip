@@ -15,12 +15,12 @@
 #include <vector>
 
 #include "../../include/karto_hip.h"
+#include "host_common.hpp"
 #include "host_wait.hpp"
+#include "lifelong_internal.hpp"
 
 namespace kh
 {
-void set_error(const std::string & s);
-
 // pts: the candidate's readings (device-visible address); n_pts: how many readings count (the denominator of the reading overlap);
 // n_scan: 0 = every one of the n_pts readings at pts counts (the packed form of kh_lifelong_scores), otherwise pts holds the n_scan
 // UNFILTERED readings of the scan and bit i of the candidate's mask says whether reading i passed the range filter

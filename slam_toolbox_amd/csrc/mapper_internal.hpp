@@ -1,4 +1,4 @@
-// What mapper_host.cpp shows of a mapper to the session merger (merge.cpp) and the live map (live_map.cpp).  Not part of the public ABI (include/karto_hip.h).
+// What mapper_views.cpp shows of a mapper to the session merger (merge.cpp) and the live map (live_map.cpp).  Not part of the public ABI (include/karto_hip.h).
 #pragma once
 #include <cstdint>
 #include <vector>

@@ -21,13 +21,11 @@
 #include <vector>
 
 #include "../../include/karto_hip.h"
+#include "host_common.hpp"
+#include "query_hook.hpp"
 
 namespace kh
 {
-void set_pending_query_hook(std::function<void()> fn);       // matcher_seq.cpp (QueryHook, matcher_private.hpp)
-void run_pending_query_hook();
-void set_error(const std::string & s);
-void host_parallel_for(size_t n, const std::function<void(size_t)> & fn);
 int32_t matcher_max_batch(const kh_matcher * m);
 }
 

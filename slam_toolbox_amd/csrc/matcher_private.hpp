@@ -23,14 +23,15 @@
 
 #include "../../include/karto_hip.h"
 #include "kh_internal.hpp"
+#include "host_common.hpp"
 #include "host_pool.hpp"
 #include "covariance_walk.hpp"
+#include "query_hook.hpp"
 
 namespace kh
 {
 
 extern thread_local std::string g_last_error;
-void set_error(const std::string & s);
 
 #define KH_HIP(call)                                                                         \
   do {                                                                                       \
@@ -339,16 +340,7 @@ CorrReq fine_search(const kh_matcher * m, int32_t slot, const kh_scan * query, c
 struct TablePlan {bool ok = false; int reason = 0; size_t bin_lds = 0; bool bm_global = false;};
 TablePlan plan_table_raster(const kh_matcher * m, int64_t most_points, int32_t most_readings, int32_t n_scans);
 // matcher_seq.cpp: ONE MatchScan through the fused kernels.  *coarse_done / *fine_done say which passes it finished
-// A caller inside the library (the mapper's Process) may leave the QUERY scan's readings unfinished when it calls kh_matcher_match
-// and hand over the function that finishes them: the fused path runs it behind the rasteriser's launches -- which need the query's
-// sensor pose and nothing else of it -- so that LocalizedRangeScan::Update of the new scan (1081 sincos: 15 us) runs while the GPU
-// works; every other path runs it before it reads the query.  Per thread; consumed by the next kh_matcher_match_batch on the thread.
-struct QueryHook
-{
-  std::function<void()> fn;
-  void run() {if (fn) {std::function<void()> f; f.swap(fn); f();}}
-};
-QueryHook & pending_query_hook();
+// (the query's readings may still be owed by a QueryHook, query_hook.hpp)
 int seq_match(kh_matcher * m, const kh_scan * query, const kh_scan * base, int32_t n_base, bool penalize, bool refine,
   double mean[3], double cov[9], double * response, int * status, bool * coarse_done, bool * fine_done);
 void seq_destroy(kh_matcher * m);

@@ -81,7 +81,7 @@ QueryHook & pending_query_hook()
   return hook;
 }
 
-void set_pending_query_hook(std::function<void()> fn) {pending_query_hook().fn = std::move(fn);}     // (the mapper: it does not see matcher_private.hpp)
+void set_pending_query_hook(std::function<void()> fn) {pending_query_hook().fn = std::move(fn);}     // (query_hook.hpp: the mapper does not see matcher_private.hpp)
 void run_pending_query_hook() {pending_query_hook().run();}
 
 int seq_match(kh_matcher * m, const kh_scan * query, const kh_scan * base, int32_t n_base, bool penalize, bool refine,

@@ -21,17 +21,15 @@
 #include <vector>
 
 #include "../../include/karto_hip.h"
+#include "host_common.hpp"
 #include "mapper_internal.hpp"
 
 namespace kh
 {
-void set_error(const std::string & s);
-void stream_synchronize(void * hip_stream);      // comm.cpp
-
 namespace
 {
 // cos and sin of the correction's yaw are libm's cos() and sin(), each called on its own: a compiler that merges the pair into one
-// sincos() call would change the last bit for some angles (mapper_host.cpp, ref_sincos), hence the calls through volatile pointers
+// sincos() call would change the last bit for some angles (mapper_pose.hpp, ref_sincos), hence the calls through volatile pointers
 double (* volatile libm_cos)(double) = ::cos;
 double (* volatile libm_sin)(double) = ::sin;
 

@@ -1,5 +1,5 @@
 // What the occupancy module shares between occupancy.hip (the kernels and their launchers) and the host files that feed it:
-// mapper_host.cpp (kh_mapper_build_map), merge.cpp (kh_merge_build), live_map.cpp (kh_live_map_*).  Not part of the public ABI
+// mapper_views.cpp (kh_mapper_build_map), merge.cpp (kh_merge_build), live_map.cpp (kh_live_map_*).  Not part of the public ABI
 // (include/karto_hip.h).  The live map's lattice, window and log are stated in DESIGN.md section 7b, the map feed's tiles in 7c.
 #pragma once
 #include <cmath>
@@ -10,6 +10,7 @@
 #endif
 
 #include "../../include/karto_hip.h"
+#include "host_common.hpp"
 
 namespace kh
 {
@@ -166,19 +167,8 @@ void live_update_cells(void * stream, const LiveWindow & w, int32_t x0, int32_t 
 void nav_feed(void * stream, const NavFeedJob & job);
 
 #ifdef __HIP__
-// ---- what the module's host files do with the device the same way (absent from a build without HIP: tests/live_map_plan_check.cpp) ----
-void set_error(const std::string & s);
-
-// KH_OK when `device` can be used, otherwise KH_ERR_NO_DEVICE and its text; require_device(0) asks for any device at all
-inline int require_device(int32_t device)
-{
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) == hipSuccess && device >= 0 && device < ndev) {return KH_OK;}
-  (void)hipGetLastError();
-  set_error("no usable HIP device (libkartohip has no CPU fallback)");
-  return KH_ERR_NO_DEVICE;
-}
-
+// ---- what the module's host files do with the device the same way (absent from a build without HIP: tests/live_map_plan_check.cpp);
+// set_error and require_device: host_common.hpp ----
 // makes *buf a device buffer of at least `need` bytes once `stream` has drained: one that is too small is replaced by one of `cap`
 // bytes (what it held is not kept).  false = the allocation failed, and the buffer is gone.
 inline bool grow_device(hipStream_t stream, void ** buf, size_t * have, size_t need, size_t cap)

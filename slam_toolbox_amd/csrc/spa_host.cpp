@@ -36,6 +36,7 @@
 
 #include "../../include/karto_hip.h"
 #include "covariance_columns_plan.hpp"
+#include "host_common.hpp"
 #include "host_wait.hpp"
 #include "marginalize.hpp"
 #include "spa_internal.hpp"
@@ -43,9 +44,6 @@
 
 namespace kh
 {
-void set_error(const std::string & s);
-void host_parallel_for(size_t n, const std::function<void(size_t)> & fn);      // matcher_host.cpp: the persistent host pool
-
 #define KS_HIP(call)                                                                         \
   do {                                                                                       \
     hipError_t e_ = (call);                                                                  \
@@ -2551,7 +2549,7 @@ bool spa_covariance_has_node(const kh_spa * s, int32_t id)
 }
 }  // namespace kh
 
-// ---- the part of the solver's state a mapping session file carries besides nodes and constraints (mapper_host.cpp) ----
+// ---- the part of the solver's state a mapping session file carries besides nodes and constraints (mapper_session.cpp) ----
 // The gauge bookkeeping (first_node_ and whether it was set constant) and the analysis cache that makes the next Compute()
 // history dependent: the supernodes of the last full dissection by node id, its cost and size, and how many incremental
 // re-analyses have leaned on it since.  words: [0] has_first, [1] first_id, [2] was_constant_set, [3] cached_full_flops,

@@ -2,6 +2,10 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <vector>
+
+#include "../../include/karto_hip.h"
+#include "marginalize.hpp"
 
 namespace kh
 {
@@ -177,5 +181,18 @@ void spa_launch_lin_check(const SpaDev & d, const double * scale, const double *
                           void * stream);
 // projected-gradient norms: out[0] = max |x - Plus(x, -g)|, out[1] = |x_free|^2
 void spa_launch_grad_norms(const SpaDev & d, const double * x, double * out2, void * stream);
+
+// ---- what spa_host.cpp shows the mapper of a solver handle besides the public kh_spa_* calls ----
+// whether the resident covariances still belong to the graph (the mapper recomputes lazily), whether the block column of node
+// `id` is resident with them, and whether node `id` is in the problem of the last covariance pass
+bool spa_covariances_valid(const kh_spa * s);
+bool spa_covariance_column_resident(const kh_spa * s, int32_t id);
+bool spa_covariance_has_node(const kh_spa * s, int32_t id);
+// what the last kh_spa_marginalize_nodes did, edit by edit, and whether it would refuse the node on the graph as it stands
+const std::vector<MargEdit> & spa_marginalize_edits(const kh_spa * s);
+bool spa_marginalize_refuses(const kh_spa * s, int32_t id);
+// the part of the solver's state a mapping session file carries besides nodes and constraints (mapper_session.cpp)
+void spa_export_session_state(kh_spa * s, int64_t words[7], std::vector<int32_t> & sn_ptr, std::vector<int32_t> & sn_ids);
+void spa_import_session_state(kh_spa * s, const int64_t words[7], const std::vector<int32_t> & sn_ptr, const std::vector<int32_t> & sn_ids);
 
 }  // namespace kh

@@ -20,11 +20,10 @@
 #include <thread>
 
 #include "../../include/karto_hip.h"
+#include "host_common.hpp"
 
 namespace kh
 {
-void set_error(const std::string & s);
-
 namespace
 {
 
