@@ -1282,6 +1282,110 @@ KH_API int kh_matcher_match_map_batch(kh_matcher * m, int32_t n, const kh_scan *
  * of map rasterisations, since the last call; reading resets them */
 KH_API int kh_matcher_profile_map(kh_matcher * m, double * collect_ms, int64_t * collects);
 
+/* ---------------------------------------------------------------- localizing in a map alone
+ * Place one scan in a map without a pose guess, and carry a pose from scan to scan, with a kh_map_view as the only map: no scans,
+ * no pose graph.  The lattice cell of a world point v is round_half_away((v - anchor) * scale) (the trace kernels' WorldToGrid); the
+ * window holds lattice cells [ox, ox + width) x [oy, oy + height); columns width .. width_step - 1 are never read. */
+
+/* ---- where a robot can stand: one seed per block of `pitch` x `pitch` lattice cells, pitch = max(1, round(seed_spacing * scale)) | 1
+ * (odd: the coarse search steps by two cells, and seeds an even number of cells apart would all miss the same lattice phase).  Block
+ * (bx, by) covers lattice cells [bx pitch, (bx + 1) pitch) x [by pitch, (by + 1) pitch), floor quotients of the lattice index: a block
+ * stays where it is when a live window grows.  Its seed is its FREE cell (state 255) inside the window nearest to the block's centre,
+ * (2 i - (2 bx pitch + pitch - 1))^2 + (2 j - (2 by pitch + pitch - 1))^2 smallest, ties to the smaller j, then the smaller i; a block
+ * without a free cell has none.  Seeds come in ascending (by, bx).  The world point of a seed is anchor + (lattice index) / scale.  With
+ * center_xy and radius > 0 only the seeds with (dx * dx) + (dy * dy) < radius * radius + KT_TOLERANCE are kept.
+ * cells takes 2 int32 per seed (lattice i, j), xy 2 doubles per seed, each for the first `cap` seeds (either may be NULL); *n_seeds
+ * is the total, also beyond cap.  KH_ERR_INVALID_ARG: a malformed view, NULL n_seeds, cap < 0, a spacing that is not finite or <= 0
+ * or gives a pitch above 4096 cells, a non-finite radius or centre. */
+KH_API int kh_map_seeds(const kh_map_view * view, double seed_spacing, const double * center_xy, double radius,
+                        int32_t * cells, double * xy, int32_t cap, int32_t * n_seeds);
+
+/* ---- how well a scan at a pose agrees with the map: the ray-consistency counters of kh_merge_fit (above) for ONE scan's readings
+ * at n_poses sensor poses.  The beams of pose k are the ranges, kh_scan_points at that pose, and its (x, y); they pass AddScan's gate
+ * with the laser's range_threshold / minimum_range / maximum_range and are walked by TraceLine on the view's lattice; every visit is
+ * counted by the state of the cell it lands on, visits outside the window are dropped, a hit end cell is visited twice.  The map is
+ * only read.  KH_ERR_INVALID_ARG: a malformed view or laser, NULL ranges / sensor_poses / out, n_poses < 1, a non-finite pose, and any
+ * pose or range_threshold * scale that could make one beam walk more than 2^20 cells or leave the int32 lattice (a sensor cell beyond
+ * +-2^30). */
+KH_API int kh_map_fit(const kh_map_view * view, const kh_laser * laser, const double * ranges, int32_t n_poses,
+                      const double * sensor_poses /* 3n */, kh_merge_fit_t * out /* n */);
+
+/* ---- the localizer: a loop-preset and a sequential-preset matcher built from the same fields of kh_mapper_params as kh_mapper's,
+ * and a map view.  max_batch = hypotheses per kh_matcher_match_map_batch call. */
+typedef struct kh_map_localizer kh_map_localizer;
+KH_API int kh_map_localizer_create(const kh_mapper_params * params, const kh_laser * laser, int32_t device, int32_t max_batch,
+                                   kh_map_localizer ** out);
+KH_API void kh_map_localizer_destroy(kh_map_localizer * loc);
+/* copies the view STRUCT; the cells stay borrowed under kh_map_view's validity rule (set the map again after its source was updated).
+ * A malformed view or one on another device is KH_ERR_INVALID_ARG and the localizer keeps the map it had. */
+KH_API int kh_map_localizer_set_map(kh_map_localizer * loc, const kh_map_view * view);
+
+/* Global relocalization in the map: section 7d's scheme with kh_map_seeds in the place of the seed vertices and the map in the place
+ * of the base scans.  Hypothesis k * n_headings + h puts the robot at seed k with heading -pi + h * (2 pi / n_headings) (the sensor
+ * through the laser's offset, the readings with kh_scan_points): coarse match against the map on the loop matcher (no penalty, no
+ * refinement), the gate (response > minimum_response_coarse, cov(0,0) and cov(1,1) < maximum_variance_coarse), fine match of the
+ * readings re-posed at the coarse mean on the sequential matcher (no penalty, refined), accepted when the fine response >=
+ * minimum_response_fine.  The accepted ones are ordered by fine response (descending), coarse response (descending), index; each is
+ * fitted (kh_map_fit) at its fine mean; those with known > 0 and score < min_fit_score are dropped; then, in that order, one is
+ * dropped as a duplicate when a kept one lies within merge_distance and merge_heading of it on the fine means
+ * ((dx * dx) + (dy * dy) < merge_distance^2 and |NormalizeAngle(dh)| < merge_heading; merge_distance <= 0: no suppression). */
+typedef struct kh_map_relocalize_params {
+  double seed_spacing;      /* > 0 (default: loop_search_space_dimension / 4: a block's diagonal stays inside the half window) */
+  int32_t n_headings;       /* headings per seed; 0 = ceil(2 pi / (2 * coarse_search_angle_offset)) */
+  int32_t top_k;            /* most hypotheses returned; 0 = as many as `cap` holds (default 8) */
+  double center_xy[2];      /* with radius > 0: only the seeds within radius of this point */
+  double radius;            /* <= 0: the whole map (default) */
+  double minimum_response_coarse, maximum_variance_coarse, minimum_response_fine;   /* defaults: loop_match_* of the mapper parameters, as stored */
+  double min_fit_score;     /* default 0: drops nothing */
+  double merge_distance;    /* default loop_search_space_resolution */
+  double merge_heading;     /* default coarse_angle_resolution */
+} kh_map_relocalize_params;
+typedef struct kh_map_hyp {
+  int32_t index;            /* seed ordinal * n_headings + heading ordinal */
+  int32_t seed_cell[2];     /* lattice cell of the seed */
+  int32_t pad;
+  double heading;
+  double coarse_mean[3], coarse_cov[9], coarse_response;      /* sensor pose of the coarse match */
+  double fine_mean[3], fine_cov[9], fine_response;            /* sensor pose of the fine match */
+  double robot_pose[3];     /* GetCorrectedAt(fine_mean): what goes to kh_map_localizer_set_pose */
+  kh_merge_fit_t fit;       /* of the scan at fine_mean */
+} kh_map_hyp;
+typedef struct kh_map_relocalize_summary {
+  int32_t n_seeds, n_headings, n_hypotheses, n_passed /* the coarse gate */, n_accepted, n_rejected_fit, n_duplicates, n_returned;
+  double seed_kernel_ms, fit_kernel_ms;      /* device time of k_map_seeds and k_map_fit */
+  double coarse_ms, fine_ms, total_ms;       /* wall: the coarse batches, the fine batches, the call */
+} kh_map_relocalize_summary;
+/* defaults for parameters *mapper_params (NULL: kh_mapper_params_default's) */
+KH_API void kh_map_relocalize_params_default(const kh_mapper_params * mapper_params, kh_map_relocalize_params * p);
+/* out takes the first min(top_k, cap) kept hypotheses (top_k 0: cap), the summary the totals.  NULL ranges / params / summary, out
+ * NULL with cap > 0, cap < 0, seed_spacing not finite or <= 0, n_headings < 0 or > 4096, top_k < 0, a non-finite centre or radius or
+ * a NaN among the other parameters are KH_ERR_INVALID_ARG before a device is looked for; without a device KH_ERR_NO_DEVICE; then a
+ * NULL localizer KH_ERR_INVALID_ARG, no map set KH_ERR_NOT_FOUND, a seed pitch above 4096 cells KH_ERR_INVALID_ARG.  A map without a
+ * free cell (or a region without a seed) is KH_OK with zero everything.  The map's cells and the tracked pose are left as they were. */
+KH_API int kh_map_localizer_relocalize(kh_map_localizer * loc, const double * ranges, const kh_map_relocalize_params * params,
+                                       kh_map_hyp * out, int32_t cap, kh_map_relocalize_summary * summary);
+
+/* ---- tracking: the robot pose the localizer holds and the odometric pose it belongs to */
+KH_API int kh_map_localizer_set_pose(kh_map_localizer * loc, const double robot_pose[3], const double odometric_pose[3]);
+KH_API int kh_map_localizer_get_pose(const kh_map_localizer * loc, double robot_pose[3], double odometric_pose[3]);   /* KH_ERR_NOT_FOUND before a pose was set */
+typedef struct kh_map_track_t {
+  double predicted_pose[3]; /* robot: Transform(last odometric, last corrected).TransformPose(odometric), Mapper::Process' prediction */
+  double robot_pose[3];     /* GetCorrectedAt(sensor_pose): the pose the localizer holds from now on */
+  double sensor_pose[3];    /* MatchScan against the map on the sequential matcher, penalised and refined, from GetSensorAt(predicted) */
+  double covariance[9];
+  double response;
+  kh_merge_fit_t fit;       /* of the scan at sensor_pose */
+} kh_map_track_t;
+/* One tracking step.  The match is always adopted, as Mapper::Process adopts its own: response and fit are the caller's health
+ * signal.  NULL arguments or a non-finite odometric pose are KH_ERR_INVALID_ARG before a device is looked for; then
+ * KH_ERR_NO_DEVICE; no map or no pose set KH_ERR_NOT_FOUND.  A failure leaves the held pose as it was. */
+KH_API int kh_map_localizer_process(kh_map_localizer * loc, const double * ranges, const double odometric_pose[3], kh_map_track_t * out);
+typedef struct kh_map_localizer_stats_t {
+  int64_t relocalizations, hypotheses, steps, poses_fitted;
+  double relocalize_ms, process_ms, match_ms /* of the steps */, seed_kernel_ms, fit_kernel_ms;
+} kh_map_localizer_stats_t;
+KH_API int kh_map_localizer_stats(const kh_map_localizer * loc, kh_map_localizer_stats_t * out);
+
 #ifdef __cplusplus
 }
 #endif

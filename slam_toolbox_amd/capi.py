@@ -167,6 +167,9 @@ SYMBOLS = [
     "kh_reject_params_default", "kh_mapper_reject_outliers",
     "kh_occupancy_view", "kh_occupancy_write_nav", "kh_live_map_view",
     "kh_matcher_add_map", "kh_matcher_match_map", "kh_matcher_match_map_batch", "kh_matcher_profile_map",
+    "kh_map_seeds", "kh_map_fit", "kh_map_localizer_create", "kh_map_localizer_destroy", "kh_map_localizer_set_map",
+    "kh_map_relocalize_params_default", "kh_map_localizer_relocalize", "kh_map_localizer_set_pose", "kh_map_localizer_get_pose",
+    "kh_map_localizer_process", "kh_map_localizer_stats",
 ]
 
 
@@ -272,6 +275,36 @@ class KhMergeFit(C.Structure):
                                           "agree", "conflict", "known")] + [("score", C.c_double)]
 
 
+class KhMapRelocalizeParams(C.Structure):
+    _fields_ = [("seed_spacing", C.c_double), ("n_headings", C.c_int32), ("top_k", C.c_int32), ("center_xy", C.c_double * 2),
+                ("radius", C.c_double), ("minimum_response_coarse", C.c_double), ("maximum_variance_coarse", C.c_double),
+                ("minimum_response_fine", C.c_double), ("min_fit_score", C.c_double), ("merge_distance", C.c_double),
+                ("merge_heading", C.c_double)]
+
+
+class KhMapHyp(C.Structure):
+    _fields_ = [("index", C.c_int32), ("seed_cell", C.c_int32 * 2), ("pad", C.c_int32), ("heading", C.c_double),
+                ("coarse_mean", C.c_double * 3), ("coarse_cov", C.c_double * 9), ("coarse_response", C.c_double),
+                ("fine_mean", C.c_double * 3), ("fine_cov", C.c_double * 9), ("fine_response", C.c_double),
+                ("robot_pose", C.c_double * 3), ("fit", KhMergeFit)]
+
+
+class KhMapRelocalizeSummary(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_seeds", "n_headings", "n_hypotheses", "n_passed", "n_accepted", "n_rejected_fit", "n_duplicates",
+                                         "n_returned")] + \
+               [(k, C.c_double) for k in ("seed_kernel_ms", "fit_kernel_ms", "coarse_ms", "fine_ms", "total_ms")]
+
+
+class KhMapTrack(C.Structure):
+    _fields_ = [("predicted_pose", C.c_double * 3), ("robot_pose", C.c_double * 3), ("sensor_pose", C.c_double * 3),
+                ("covariance", C.c_double * 9), ("response", C.c_double), ("fit", KhMergeFit)]
+
+
+class KhMapLocalizerStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("relocalizations", "hypotheses", "steps", "poses_fitted")] + \
+               [(k, C.c_double) for k in ("relocalize_ms", "process_ms", "match_ms", "seed_kernel_ms", "fit_kernel_ms")]
+
+
 class KhMergeAlignParams(C.Structure):
     _fields_ = [("n_probes", C.c_int32), ("top_k", C.c_int32), ("min_known", C.c_uint64), ("min_pass_through", C.c_uint32), ("pad", C.c_uint32),
                 ("occupancy_threshold", C.c_double), ("relocalize", KhRelocalizeParams)]
@@ -358,6 +391,21 @@ def lib():
         L.kh_matcher_match_map.argtypes = [vp, C.POINTER(KhScan), C.POINTER(KhMapView), i32, i32, dptr, dptr, C.POINTER(dbl)]
         L.kh_matcher_match_map_batch.argtypes = [vp, i32, C.POINTER(KhScan), C.POINTER(KhMapView), i32, i32, dptr, dptr, dptr, iptr]
         L.kh_matcher_profile_map.argtypes = [vp, C.POINTER(dbl), C.POINTER(C.c_int64)]
+    if hasattr(L, "kh_map_localizer_create"):      # (KH_LIBRARY may name a build from before the map localizer existed)
+        L.kh_map_seeds.argtypes = [C.POINTER(KhMapView), dbl, vp, dbl, vp, vp, i32, C.POINTER(i32)]
+        L.kh_map_fit.argtypes = [C.POINTER(KhMapView), C.POINTER(KhLaser), vp, i32, vp, C.POINTER(KhMergeFit)]
+        L.kh_map_localizer_create.argtypes = [C.POINTER(KhMapperParams), C.POINTER(KhLaser), i32, i32, C.POINTER(vp)]
+        L.kh_map_localizer_destroy.argtypes = [vp]
+        L.kh_map_localizer_destroy.restype = None
+        L.kh_map_localizer_set_map.argtypes = [vp, C.POINTER(KhMapView)]
+        L.kh_map_relocalize_params_default.argtypes = [C.POINTER(KhMapperParams), C.POINTER(KhMapRelocalizeParams)]
+        L.kh_map_relocalize_params_default.restype = None
+        L.kh_map_localizer_relocalize.argtypes = [vp, vp, C.POINTER(KhMapRelocalizeParams), C.POINTER(KhMapHyp), i32,
+                                                  C.POINTER(KhMapRelocalizeSummary)]
+        L.kh_map_localizer_set_pose.argtypes = [vp, vp, vp]
+        L.kh_map_localizer_get_pose.argtypes = [vp, vp, vp]
+        L.kh_map_localizer_process.argtypes = [vp, vp, vp, C.POINTER(KhMapTrack)]
+        L.kh_map_localizer_stats.argtypes = [vp, C.POINTER(KhMapLocalizerStats)]
     if hasattr(L, "kh_spa_create"):
         L.kh_spa_options_default.argtypes = [C.POINTER(KhSpaOptions)]
         L.kh_spa_create.argtypes = [i32, C.POINTER(vp)]

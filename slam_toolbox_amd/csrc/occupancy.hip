@@ -19,6 +19,7 @@
 #include "../../include/karto_hip.h"
 #include "occupancy_device.hpp"
 #include "live_map_plan.hpp"
+#include "map_localize_plan.hpp"
 
 namespace kh
 {
@@ -235,6 +236,112 @@ __global__ __launch_bounds__(256) void k_occ_fit_merged(
     const unsigned long long v = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
     if (v) {atomicAdd(&out[(int64_t)candidate * kFitCounters + threadIdx.x], v);}
   }
+}
+
+// ---- a map view as a localizer reads it (kh_map_seeds, kh_map_fit) ----
+struct FitWindowCells            // FitCells on a window of the lattice: cell (ox, oy) is the first; WindowCells' 64-bit index and bounds guard
+{
+  const MapWindow & g;
+  uint32_t & pass_unknown, & pass_occupied, & pass_free, & hits_unknown, & hits_occupied, & hits_free;
+  __device__ __forceinline__ void add(int32_t cx, int32_t cy, bool hit) const
+  {
+    const int64_t wx = (int64_t)cx - g.ox, wy = (int64_t)cy - g.oy;
+    if (wx >= 0 && wx < g.width && wy >= 0 && wy < g.height) {
+      const uint32_t state = g.cells[wx + wy * g.ws];
+      const uint32_t unknown = state == 0u, occupied = state == 100u, is_free = state == 255u;
+      pass_unknown += unknown; pass_occupied += occupied; pass_free += is_free;
+      if (hit) {hits_unknown += unknown; hits_occupied += occupied; hits_free += is_free;}
+    }
+  }
+};
+
+// The FIT of one scan at many sensor poses against a map view (kh_map_fit): k_occ_fit_merged's layout without the scan dimension --
+// one wave per (pose, run of 64 beams), a workgroup holds waves of ONE pose (blocks_per_pose = ceil(runs / 4)) -- and its reduction:
+// six lane counters, shuffles, LDS, one 64-bit atomicAdd per non-zero counter and workgroup.  points: per pose the 2 * n_beams
+// unfiltered point readings at that pose (kh_scan_points on the host: libm stays there); sensors: 2 per pose.  The view is only read.
+// The host has refused every input whose beams could walk more than kMaxFitWalk cells or leave the int32 lattice; the test in front of
+// the walk is the same bound once more, on the cells themselves, so that no lane can spin whatever reaches the kernel.
+__global__ __launch_bounds__(256) void k_map_fit(
+  MapWindow g, const double * __restrict__ ranges, const double * __restrict__ points, const double * __restrict__ sensors, int32_t n_beams,
+  int32_t blocks_per_pose, double range_threshold, double min_range, double max_range, unsigned long long * __restrict__ out)
+{
+  __shared__ unsigned long long part[4][kFitCounters];
+  const int32_t pose = (int32_t)(blockIdx.x / (uint32_t)blocks_per_pose);
+  const int64_t wave = (int64_t)(blockIdx.x - (uint32_t)pose * (uint32_t)blocks_per_pose) * 4 + (threadIdx.x >> 6);
+  const int32_t lane = threadIdx.x & 63;
+  const int64_t i = wave * 64 + lane;
+  uint32_t n[kFitCounters] = {0u, 0u, 0u, 0u, 0u, 0u};
+  if (i < n_beams) {
+    const double sx = sensors[2 * (int64_t)pose], sy = sensors[2 * (int64_t)pose + 1];
+    const double * const p = points + 2 * ((int64_t)pose * n_beams + i);
+    const Beam b = occ_gate(ranges[i], p[0], p[1], sx, sy, range_threshold, min_range, max_range);
+    if (b.kept) {
+      const int32_t x0 = occ_cell(sx, g.ax, g.scale), y0 = occ_cell(sy, g.ay, g.scale);
+      const int32_t x1 = occ_cell(b.px, g.ax, g.scale), y1 = occ_cell(b.py, g.ay, g.scale);
+      const int64_t limit = (1ll << 30) + 2 * kMaxFitWalk;
+      const int64_t dx = (int64_t)x1 - x0, dy = (int64_t)y1 - y0;
+      const bool bounded = x0 >= -limit && x0 <= limit && y0 >= -limit && y0 <= limit && dx >= -kMaxFitWalk && dx <= kMaxFitWalk &&
+        dy >= -kMaxFitWalk && dy <= kMaxFitWalk;
+      if (bounded) {
+        occ_walk(FitWindowCells{g, n[kFitPassUnknown], n[kFitPassOccupied], n[kFitPassFree], n[kFitHitsUnknown], n[kFitHitsOccupied], n[kFitHitsFree]},
+          x0, y0, x1, y1, b.hit);
+      }
+    }
+  }
+#pragma unroll
+  for (int32_t k = 0; k < kFitCounters; ++k) {
+    unsigned long long v = n[k];
+#pragma unroll
+    for (int32_t d = 32; d >= 1; d >>= 1) {v += __shfl_xor(v, d);}
+    if (lane == 0) {part[threadIdx.x >> 6][k] = v;}
+  }
+  __syncthreads();
+  if (threadIdx.x < kFitCounters) {
+    const unsigned long long v = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+    if (v) {atomicAdd(&out[(int64_t)pose * kFitCounters + threadIdx.x], v);}
+  }
+}
+
+// Where a robot can stand (kh_map_seeds): one wave per block of pitch x pitch lattice cells; block `b` of the launch is block column
+// bx0 + b % nbx, block row by0 + b / nbx of the lattice.  The lanes stride over the block's cells inside the window, row-major, so a
+// wave reads runs of consecutive bytes of a row wherever the row segment is long enough.  Each lane keeps the minimum of a 64-bit
+// key over its free cells: the squared distance of the doubled cell index from the doubled block centre in the high half (at most
+// 2 * 4095^2), the row-major index inside the block in the low half (below 4096^2) -- so the minimum is the nearest free cell, ties
+// to the smaller row, then the smaller column.  The wave reduces by shuffles and lane 0 writes the low half, or -1 when the block
+// holds no free cell, to the block's own word: no atomic decides anything.
+__global__ __launch_bounds__(256) void k_map_seeds(MapWindow g, int32_t pitch, int64_t bx0, int64_t by0, int64_t nbx, int64_t n_blocks,
+  int32_t * __restrict__ out)
+{
+  const int64_t block = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (block >= n_blocks) {return;}                     // (the whole wave leaves)
+  const int32_t lane = threadIdx.x & 63;
+  const int64_t by = block / nbx, bx = block - by * nbx;
+  const int64_t lx0 = (bx0 + bx) * pitch, ly0 = (by0 + by) * pitch;            // the block's first lattice cell
+  // its part inside the window, in window columns and rows
+  const int64_t wx0 = lx0 - g.ox > 0 ? lx0 - g.ox : 0, wx1 = lx0 + pitch - g.ox < g.width ? lx0 + pitch - g.ox : g.width;
+  const int64_t wy0 = ly0 - g.oy > 0 ? ly0 - g.oy : 0, wy1 = ly0 + pitch - g.oy < g.height ? ly0 + pitch - g.oy : g.height;
+  const int32_t cw = (int32_t)(wx1 - wx0), ch = (int32_t)(wy1 - wy0);
+  unsigned long long key = ~0ull;
+  if (cw > 0 && ch > 0) {
+    const uint32_t total = (uint32_t)cw * (uint32_t)ch;
+    const int64_t cx2 = 2 * lx0 + pitch - 1, cy2 = 2 * ly0 + pitch - 1;        // the doubled block centre
+    for (uint32_t idx = lane; idx < total; idx += 64u) {
+      const uint32_t row = idx / (uint32_t)cw, col = idx - row * (uint32_t)cw;
+      const int64_t wx = wx0 + col, wy = wy0 + row;
+      if (g.cells[wx + wy * g.ws] == 255u) {
+        const int64_t lx = wx + g.ox, ly = wy + g.oy;
+        const int64_t dx = 2 * lx - cx2, dy = 2 * ly - cy2;
+        const unsigned long long k = ((unsigned long long)(dx * dx + dy * dy) << 32) | (unsigned long long)((ly - ly0) * pitch + (lx - lx0));
+        key = k < key ? k : key;
+      }
+    }
+  }
+#pragma unroll
+  for (int32_t d = 32; d >= 1; d >>= 1) {
+    const unsigned long long other = __shfl_xor(key, d);
+    key = other < key ? other : key;
+  }
+  if (lane == 0) {out[block] = key == ~0ull ? -1 : (int32_t)(key & 0xFFFFFFFFull);}
 }
 
 // UpdateCell (Karto.h:6240-6256) for the cell at index k of the three arrays
@@ -580,6 +687,143 @@ void nav_feed(void * stream, const NavFeedJob & job)
   hipLaunchKernelGGL(k_nav_feed, dim3(static_cast<unsigned>((n_strips + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), job, strip0,
     strips_x, n_strips);
 }
+
+struct MapWork
+{
+  int32_t device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  uint8_t * d = nullptr; size_t cap = 0;               // the launch's tables and answers (bytes)
+};
+
+MapWork * map_work_create(int32_t device)
+{
+  MapWork * w = new MapWork();
+  w->device = device;
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking) != hipSuccess ||
+    hipEventCreate(&w->ev[0]) != hipSuccess || hipEventCreate(&w->ev[1]) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    set_error("map view: HIP stream / event creation failed");
+    map_work_destroy(w);
+    return nullptr;
+  }
+  return w;
+}
+
+void map_work_destroy(MapWork * w)
+{
+  if (!w) {return;}
+  (void)hipSetDevice(w->device);
+  if (w->stream) {(void)hipStreamSynchronize(w->stream);}
+  (void)hipFree(w->d);
+  if (w->ev[0]) {(void)hipEventDestroy(w->ev[0]);}
+  if (w->ev[1]) {(void)hipEventDestroy(w->ev[1]);}
+  if (w->stream) {(void)hipStreamDestroy(w->stream);}
+  delete w;
+}
+
+int map_view_check(const kh_map_view * v)
+{
+  if (!v || !v->device_cells || v->width <= 0 || v->height <= 0 || v->width_step < v->width || !std::isfinite(v->scale) || !(v->scale > 0.0) ||
+    !std::isfinite(v->anchor[0]) || !std::isfinite(v->anchor[1]))
+  {
+    set_error("malformed map view");
+    return KH_ERR_INVALID_ARG;
+  }
+  if (static_cast<int64_t>(v->width_step) * v->height > (1ll << 31) - 4096) {set_error("map view too large"); return KH_ERR_INVALID_ARG;}
+  if (static_cast<int64_t>(v->ox) + v->width > INT32_MAX || static_cast<int64_t>(v->oy) + v->height > INT32_MAX) {
+    set_error("map view: the window leaves the int32 lattice");
+    return KH_ERR_INVALID_ARG;
+  }
+  return KH_OK;
+}
+
+namespace
+{
+MapWindow window_of(const kh_map_view & v)
+{
+  return MapWindow{v.device_cells, v.ox, v.oy, v.width, v.height, v.width_step, v.anchor[0], v.anchor[1], v.scale};
+}
+
+// the time between the work's two events, once its stream has drained; a failure is reported under `who`
+int finish_timed(MapWork * w, const char * who, double * kernel_ms)
+{
+  if (hipStreamSynchronize(w->stream) != hipSuccess) {
+    set_error(std::string(who) + ": " + hipGetErrorString(hipGetLastError()));
+    return KH_ERR_HIP;
+  }
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, w->ev[0], w->ev[1]);
+  if (kernel_ms) {*kernel_ms = ms;}
+  return KH_OK;
+}
+}  // namespace
+
+int map_seed_blocks(MapWork * w, const kh_map_view & v, int32_t pitch, int64_t bx0, int64_t by0, int64_t nbx, int64_t nby, int32_t * local,
+  double * kernel_ms)
+{
+  if (kernel_ms) {*kernel_ms = 0.0;}
+  const int64_t n_blocks = nbx * nby;
+  if (!w || pitch < 1 || nbx < 1 || nby < 1 || !local || n_blocks > (1ll << 31) - 4096) {return KH_ERR_INVALID_ARG;}
+  if (hipSetDevice(w->device) != hipSuccess) {return KH_ERR_HIP;}
+  const size_t bytes = static_cast<size_t>(n_blocks) * sizeof(int32_t);
+  if (!grow_device(w->stream, reinterpret_cast<void **>(&w->d), &w->cap, bytes, bytes)) {
+    set_error("kh_map_seeds: block table allocation failed");
+    return KH_ERR_HIP;
+  }
+  (void)hipEventRecord(w->ev[0], w->stream);
+  hipLaunchKernelGGL(k_map_seeds, dim3(static_cast<unsigned>((n_blocks + 3) / 4)), dim3(256), 0, w->stream, window_of(v), pitch, bx0, by0, nbx,
+    n_blocks, reinterpret_cast<int32_t *>(w->d));
+  (void)hipEventRecord(w->ev[1], w->stream);
+  if (hipMemcpyAsync(local, w->d, bytes, hipMemcpyDeviceToHost, w->stream) != hipSuccess) {
+    (void)hipStreamSynchronize(w->stream);
+    return KH_ERR_HIP;
+  }
+  return finish_timed(w, "kh_map_seeds", kernel_ms);
+}
+
+int map_fit_counts(MapWork * w, const kh_map_view & v, int32_t n_beams, const double * ranges, int32_t n_poses, const double * points,
+  const double * sensor_xy, double range_threshold, double min_range, double max_range, uint64_t * counts, double * kernel_ms)
+{
+  if (kernel_ms) {*kernel_ms = 0.0;}
+  if (!w || n_beams < 0 || n_poses < 1 || !counts || (n_beams > 0 && (!ranges || !points)) || !sensor_xy) {return KH_ERR_INVALID_ARG;}
+  std::fill(counts, counts + static_cast<size_t>(n_poses) * kFitCounters, uint64_t{0});
+  if (n_beams == 0) {return KH_OK;}
+  const int64_t blocks_per_pose = ((static_cast<int64_t>(n_beams) + 63) / 64 + 3) / 4;
+  if (blocks_per_pose * n_poses > INT32_MAX) {set_error("kh_map_fit: too many poses for one launch"); return KH_ERR_INVALID_ARG;}
+  if (hipSetDevice(w->device) != hipSuccess) {return KH_ERR_HIP;}
+  // the sums first, then the tables: every part a multiple of 8 bytes
+  const size_t out_bytes = static_cast<size_t>(n_poses) * kFitCounters * sizeof(unsigned long long);
+  const size_t sensor_bytes = static_cast<size_t>(n_poses) * 2 * sizeof(double);
+  const size_t range_bytes = static_cast<size_t>(n_beams) * sizeof(double);
+  const size_t point_bytes = static_cast<size_t>(n_poses) * static_cast<size_t>(n_beams) * 2 * sizeof(double);
+  const size_t bytes = out_bytes + sensor_bytes + range_bytes + point_bytes;
+  if (!grow_device(w->stream, reinterpret_cast<void **>(&w->d), &w->cap, bytes, bytes + bytes / 2)) {
+    set_error("kh_map_fit: table allocation failed");
+    return KH_ERR_HIP;
+  }
+  unsigned long long * d_out = reinterpret_cast<unsigned long long *>(w->d);
+  uint8_t * const d_sensors = w->d + out_bytes, * const d_ranges = d_sensors + sensor_bytes, * const d_points = d_ranges + range_bytes;
+  if (hipMemsetAsync(d_out, 0, out_bytes, w->stream) != hipSuccess ||
+    hipMemcpyAsync(d_sensors, sensor_xy, sensor_bytes, hipMemcpyHostToDevice, w->stream) != hipSuccess ||
+    hipMemcpyAsync(d_ranges, ranges, range_bytes, hipMemcpyHostToDevice, w->stream) != hipSuccess ||
+    hipMemcpyAsync(d_points, points, point_bytes, hipMemcpyHostToDevice, w->stream) != hipSuccess)
+  {
+    (void)hipStreamSynchronize(w->stream);
+    return KH_ERR_HIP;
+  }
+  (void)hipEventRecord(w->ev[0], w->stream);
+  hipLaunchKernelGGL(k_map_fit, dim3(static_cast<unsigned>(blocks_per_pose * n_poses)), dim3(256), 0, w->stream, window_of(v),
+    reinterpret_cast<const double *>(d_ranges), reinterpret_cast<const double *>(d_points), reinterpret_cast<const double *>(d_sensors), n_beams,
+    static_cast<int32_t>(blocks_per_pose), range_threshold, min_range, max_range, d_out);
+  (void)hipEventRecord(w->ev[1], w->stream);
+  if (hipMemcpyAsync(counts, d_out, out_bytes, hipMemcpyDeviceToHost, w->stream) != hipSuccess) {
+    (void)hipStreamSynchronize(w->stream);
+    return KH_ERR_HIP;
+  }
+  return finish_timed(w, "kh_map_fit", kernel_ms);
+}
 }  // namespace kh
 
 extern "C" {
@@ -769,6 +1013,73 @@ int kh_occupancy_view(kh_occupancy * g, kh_map_view * out)
   out->width = g->dev.width; out->height = g->dev.height; out->width_step = g->dev.ws;
   out->ox = 0; out->oy = 0;
   out->anchor[0] = g->dev.off_x; out->anchor[1] = g->dev.off_y; out->scale = g->dev.scale;
+  return KH_OK;
+}
+
+int kh_map_seeds(const kh_map_view * view, double seed_spacing, const double * center_xy, double radius, int32_t * cells, double * xy,
+  int32_t cap, int32_t * n_seeds)
+{
+  if (!n_seeds || cap < 0) {return KH_ERR_INVALID_ARG;}
+  *n_seeds = 0;
+  if (map_view_check(view) != KH_OK) {return KH_ERR_INVALID_ARG;}
+  if (!std::isfinite(radius) || (center_xy && (!std::isfinite(center_xy[0]) || !std::isfinite(center_xy[1])))) {
+    set_error("kh_map_seeds: the region must be finite");
+    return KH_ERR_INVALID_ARG;
+  }
+  const int32_t pitch = seed_pitch(seed_spacing, view->scale);
+  if (pitch == 0) {
+    set_error("kh_map_seeds: seed_spacing must be finite, > 0 and at most " + std::to_string(kMaxSeedPitch) + " cells");
+    return KH_ERR_INVALID_ARG;
+  }
+  if (require_device(view->device) != KH_OK) {return KH_ERR_NO_DEVICE;}
+  const SeedBlocks blocks = seed_blocks(view->ox, view->oy, view->width, view->height, pitch);
+  MapWork * w = map_work_create(view->device);
+  if (!w) {return KH_ERR_HIP;}
+  std::vector<int32_t> local(static_cast<size_t>(blocks.count()));
+  const int rc = map_seed_blocks(w, *view, pitch, blocks.bx0, blocks.by0, blocks.nx, blocks.ny, local.data(), nullptr);
+  map_work_destroy(w);
+  if (rc) {return rc;}
+  const std::vector<Seed> seeds = compact_seeds(blocks, pitch, local.data(), view->anchor[0], view->anchor[1], view->scale, center_xy, radius);
+  if (seeds.size() > static_cast<size_t>(INT32_MAX)) {set_error("kh_map_seeds: more than 2^31 seeds"); return KH_ERR_INVALID_ARG;}
+  for (size_t k = 0; k < seeds.size() && k < static_cast<size_t>(cap); ++k) {
+    if (cells) {cells[2 * k] = seeds[k].i; cells[2 * k + 1] = seeds[k].j;}
+    if (xy) {xy[2 * k] = seeds[k].x; xy[2 * k + 1] = seeds[k].y;}
+  }
+  *n_seeds = static_cast<int32_t>(seeds.size());
+  return KH_OK;
+}
+
+int kh_map_fit(const kh_map_view * view, const kh_laser * laser, const double * ranges, int32_t n_poses, const double * sensor_poses,
+  kh_merge_fit_t * out)
+{
+  if (!laser || !ranges || !sensor_poses || !out || n_poses < 1 || laser->n_beams < 1 || map_view_check(view) != KH_OK) {return KH_ERR_INVALID_ARG;}
+  if (!fit_laser_ok(laser->range_threshold, laser->minimum_range, laser->maximum_range, view->scale) || !std::isfinite(laser->minimum_angle) ||
+    !std::isfinite(laser->angular_resolution))
+  {
+    set_error("kh_map_fit: the laser's range_threshold * scale must stay below 2^20 cells, its other fields must be numbers");
+    return KH_ERR_INVALID_ARG;
+  }
+  for (int32_t k = 0; k < n_poses; ++k) {
+    if (!fit_pose_ok(sensor_poses + 3 * static_cast<size_t>(k), view->anchor[0], view->anchor[1], view->scale)) {
+      set_error("kh_map_fit: pose " + std::to_string(k) + " is not finite or lies more than 2^30 cells from the anchor");
+      return KH_ERR_INVALID_ARG;
+    }
+  }
+  if (require_device(view->device) != KH_OK) {return KH_ERR_NO_DEVICE;}
+  const size_t nb = static_cast<size_t>(laser->n_beams), np = static_cast<size_t>(n_poses);
+  std::vector<double> points(2 * nb * np), sensor_xy(2 * np);
+  std::vector<uint64_t> counts(np * kFitCounters);
+  host_parallel_for_wide(np, [&](size_t k) {
+    kh_scan_points(ranges, laser->n_beams, sensor_poses + 3 * k, laser->minimum_angle, laser->angular_resolution, &points[2 * nb * k]);
+    sensor_xy[2 * k] = sensor_poses[3 * k]; sensor_xy[2 * k + 1] = sensor_poses[3 * k + 1];
+  });
+  MapWork * w = map_work_create(view->device);
+  if (!w) {return KH_ERR_HIP;}
+  const int rc = map_fit_counts(w, *view, laser->n_beams, ranges, n_poses, points.data(), sensor_xy.data(), laser->range_threshold,
+      laser->minimum_range, laser->maximum_range, counts.data(), nullptr);
+  map_work_destroy(w);
+  if (rc) {return rc;}
+  for (size_t k = 0; k < np; ++k) {out[k] = fit_derive(&counts[k * kFitCounters]);}
   return KH_OK;
 }
 

@@ -89,6 +89,15 @@ struct LiveWindow
   uint8_t * cells;
 };
 
+// a kh_map_view as k_map_seeds and k_map_fit read it: lattice cells [ox, ox + width) x [oy, oy + height) of cell states, the lattice's
+// anchor and scale
+struct MapWindow
+{
+  const uint8_t * cells;
+  int32_t ox, oy, width, height, ws;
+  double ax, ay, scale;
+};
+
 // what the live map classifies a scan of its mapper by: the sensor pose; and the scan's box (the default anchor)
 struct SensorView
 {
@@ -165,6 +174,22 @@ void live_update_cells(void * stream, const LiveWindow & w, int32_t x0, int32_t 
 // k_nav_feed over the job's tiles on `stream`: every tile whose nav values differ from the published grid takes a slot, in no
 // particular order.  The caller has set *job.count to 0 and holds room for every tile of the job.
 void nav_feed(void * stream, const NavFeedJob & job);
+
+// ---- a map view's two kernels (kh_map_seeds, kh_map_fit, kh_map_localizer_*) ----
+// a stream, two events and one growing device buffer on a device: what the two launchers below work with.  nullptr = it could not be made.
+struct MapWork;
+MapWork * map_work_create(int32_t device);
+void map_work_destroy(MapWork * w);
+// KH_OK for a view the two kernels can read (kh_matcher_add_map's test without the device comparison), else KH_ERR_INVALID_ARG and its text
+int map_view_check(const kh_map_view * v);
+// k_map_seeds over n_blocks = nbx * nby blocks of `pitch` cells, block column bx0 / block row by0 first: local takes one int32 per
+// block, row-major -- the row-major index of the block's seed inside the block, or -1.  *kernel_ms: the kernel by events.
+int map_seed_blocks(MapWork * w, const kh_map_view & v, int32_t pitch, int64_t bx0, int64_t by0, int64_t nbx, int64_t nby, int32_t * local,
+  double * kernel_ms);
+// k_map_fit: n_beams ranges, per pose 2 * n_beams point readings and the sensor's (x, y); counts takes kFitCounters sums per pose.
+// The caller has checked the poses and the laser (fit_pose_ok, fit_laser_ok).
+int map_fit_counts(MapWork * w, const kh_map_view & v, int32_t n_beams, const double * ranges, int32_t n_poses, const double * points,
+  const double * sensor_xy, double range_threshold, double min_range, double max_range, uint64_t * counts, double * kernel_ms);
 
 #ifdef __HIP__
 // ---- what the module's host files do with the device the same way (absent from a build without HIP: tests/live_map_plan_check.cpp);
