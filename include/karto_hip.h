@@ -1386,6 +1386,72 @@ typedef struct kh_map_localizer_stats_t {
 } kh_map_localizer_stats_t;
 KH_API int kh_map_localizer_stats(const kh_map_localizer * loc, kh_map_localizer_stats_t * out);
 
+/* ---------------------------------------------------------------- where scans contradict a map, and the patched map
+ * A change layer on a map view: two uint32 grids `pass` and `hits` on the view's window, zero at creation.  The lattice is section
+ * 7k's.  Observing a scan at a sensor pose walks every beam that passes AddScan's gate with TraceLine, adds 1 to `pass` of every
+ * visited cell inside the window and, at a hit end cell inside it, 1 more to `pass` and 1 to `hits` -- what kh_occupancy_add_scans
+ * counts.  The map's cells are only read. */
+typedef struct kh_map_changes kh_map_changes;
+/* what a beam says about the map, with a tolerance of t cells around its end cell: `blocked` = the visited window cells of its line
+ * (the hit's second visit of the end cell apart) of map state 100 further than t from the end cell (Chebyshev); `near` = a window cell
+ * of map state 100 within t of the end cell */
+enum {
+  KH_BEAM_DROPPED = 0,      /* the gate dropped the beam */
+  KH_BEAM_EXPLAINED = 1,    /* hit, blocked == 0, near */
+  KH_BEAM_NOVEL = 2,        /* hit, blocked == 0, not near, the end cell is free */
+  KH_BEAM_UNKNOWN = 3,      /* hit, blocked == 0, not near, the end cell is unknown or outside the window */
+  KH_BEAM_THROUGH = 4,      /* blocked > 0, hit or not */
+  KH_BEAM_CLEAR = 5         /* not a hit, blocked == 0 */
+};
+/* what the observed state of a cell -- UpdateCell's rule on the layer: pass > min_pass_through ? (hits / pass > occupancy_threshold ?
+ * 100 : 255) : 0 -- makes of the map's state (a map state that is none of 0 / 100 / 255 counts as unknown) */
+enum {
+  KH_CELL_UNOBSERVED = 0,           /* observed state 0 */
+  KH_CELL_CONFIRMED = 1,            /* observed state = map state */
+  KH_CELL_APPEARED = 2,             /* map 255 -> observed 100 */
+  KH_CELL_VANISHED = 3,             /* map 100 -> observed 255 */
+  KH_CELL_DISCOVERED_OCCUPIED = 4,  /* map 0 -> observed 100 */
+  KH_CELL_DISCOVERED_FREE = 5       /* map 0 -> observed 255 */
+};
+/* copies the view STRUCT; the cells stay borrowed under kh_map_view's validity rule.  The window is fixed.  Allocates the layer, the
+ * codes and the patched cells on the view's device.  A NULL or malformed view or a NULL out: KH_ERR_INVALID_ARG before a device is
+ * looked for; then KH_ERR_NO_DEVICE. */
+KH_API int kh_map_changes_create(const kh_map_view * view, kh_map_changes ** out);
+KH_API void kh_map_changes_destroy(kh_map_changes * c);
+/* zeroes the layer and its counters of scans and beams; the last diff's codes and patched cells stay */
+KH_API int kh_map_changes_clear(kh_map_changes * c);
+/* pass >>= shift, hits >>= shift on every cell, 1 <= shift <= 31: the only forgetting */
+KH_API int kh_map_changes_decay(kh_map_changes * c, int32_t shift);
+/* Observes n_scans scans of the laser's n_beams beams: scan k has ranges[k * n_beams ..] and the sensor pose sensor_poses[3 k ..]
+ * (its points: kh_scan_points).  labels, where not NULL, takes 2 int32 per beam, scan-major: the KH_BEAM_ class and `blocked`, against
+ * the MAP's cell states (not the layer), with end_tolerance cells of tolerance.  KH_ERR_INVALID_ARG, with nothing changed: everything
+ * kh_map_fit refuses, n_scans < 1, end_tolerance outside 0 .. 4, and a call after which a cell could hold more than 2^32 - 1 (the
+ * layer keeps a bound: + 2 * n_beams per scan, shifted by a decay, 0 after a clear).  Arguments that need no handle are checked before
+ * a device is looked for; then KH_ERR_NO_DEVICE; then the handle and what depends on its view. */
+KH_API int kh_map_changes_observe(kh_map_changes * c, const kh_laser * laser, int32_t n_scans, const double * ranges /* n_scans * n_beams */,
+                                  const double * sensor_poses /* 3 n_scans */, int32_t end_tolerance, int32_t * labels /* 2 per beam, or NULL */);
+typedef struct kh_map_changes_summary_t {
+  int64_t n_unobserved, n_confirmed, n_appeared, n_vanished, n_discovered_occupied, n_discovered_free;   /* window cells by KH_CELL_ code */
+  int64_t n_changed;        /* cells of code >= 2: the length of the whole list */
+  int64_t n_listed;         /* min(n_changed, cap): the entries written */
+  int64_t scans_observed, beams_observed;      /* since the last clear */
+  double observe_kernel_ms; /* k_map_observe since the last clear, by events */
+  double diff_kernel_ms, list_kernel_ms, download_ms;      /* this call, by events: k_map_diff; count, prefix and fill; the copies to the host */
+} kh_map_changes_summary_t;
+/* Sets the layer against the map: the code and the patched state (the observed state where it is known, else the map's) of every
+ * window cell, the counts, and the cells of code >= 2 in row-major window order -- cells takes (lattice i, lattice j, code) for the
+ * first `cap` of them, out->n_changed is the total.  NULL out, cap < 0, cells NULL with cap > 0 or a NaN threshold:
+ * KH_ERR_INVALID_ARG before a device is looked for. */
+KH_API int kh_map_changes_diff(kh_map_changes * c, uint32_t min_pass_through, double occupancy_threshold, int32_t * cells /* 3 per entry */,
+                               int32_t cap, kh_map_changes_summary_t * out);
+/* the layer, and the codes and patched cells of the last diff (zeros before one), row stride width_step; any pointer may be NULL */
+KH_API int kh_map_changes_read(kh_map_changes * c, uint32_t * pass, uint32_t * hits, uint8_t * codes, uint8_t * patched);
+/* the patched cells of the last diff as a view on the source view's lattice, for kh_map_localizer_set_map and the matcher's map entry
+ * points: borrowed until the next diff or destroy.  KH_ERR_NOT_FOUND before a diff. */
+KH_API int kh_map_changes_view(kh_map_changes * c, kh_map_view * out);
+/* the patched cells of the last diff as width * height nav values, kh_occupancy_read_nav's mapping.  KH_ERR_NOT_FOUND before a diff. */
+KH_API int kh_map_changes_read_nav(kh_map_changes * c, int8_t * out);
+
 #ifdef __cplusplus
 }
 #endif

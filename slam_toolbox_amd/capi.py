@@ -170,6 +170,8 @@ SYMBOLS = [
     "kh_map_seeds", "kh_map_fit", "kh_map_localizer_create", "kh_map_localizer_destroy", "kh_map_localizer_set_map",
     "kh_map_relocalize_params_default", "kh_map_localizer_relocalize", "kh_map_localizer_set_pose", "kh_map_localizer_get_pose",
     "kh_map_localizer_process", "kh_map_localizer_stats",
+    "kh_map_changes_create", "kh_map_changes_destroy", "kh_map_changes_clear", "kh_map_changes_decay", "kh_map_changes_observe",
+    "kh_map_changes_diff", "kh_map_changes_read", "kh_map_changes_view", "kh_map_changes_read_nav",
 ]
 
 
@@ -305,6 +307,16 @@ class KhMapLocalizerStats(C.Structure):
                [(k, C.c_double) for k in ("relocalize_ms", "process_ms", "match_ms", "seed_kernel_ms", "fit_kernel_ms")]
 
 
+class KhMapChangesSummary(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_unobserved", "n_confirmed", "n_appeared", "n_vanished", "n_discovered_occupied", "n_discovered_free",
+                                           "n_changed", "n_listed", "scans_observed", "beams_observed")] + \
+               [(k, C.c_double) for k in ("observe_kernel_ms", "diff_kernel_ms", "list_kernel_ms", "download_ms")]
+
+
+KH_BEAM_DROPPED, KH_BEAM_EXPLAINED, KH_BEAM_NOVEL, KH_BEAM_UNKNOWN, KH_BEAM_THROUGH, KH_BEAM_CLEAR = range(6)
+KH_CELL_UNOBSERVED, KH_CELL_CONFIRMED, KH_CELL_APPEARED, KH_CELL_VANISHED, KH_CELL_DISCOVERED_OCCUPIED, KH_CELL_DISCOVERED_FREE = range(6)
+
+
 class KhMergeAlignParams(C.Structure):
     _fields_ = [("n_probes", C.c_int32), ("top_k", C.c_int32), ("min_known", C.c_uint64), ("min_pass_through", C.c_uint32), ("pad", C.c_uint32),
                 ("occupancy_threshold", C.c_double), ("relocalize", KhRelocalizeParams)]
@@ -406,6 +418,17 @@ def lib():
         L.kh_map_localizer_get_pose.argtypes = [vp, vp, vp]
         L.kh_map_localizer_process.argtypes = [vp, vp, vp, C.POINTER(KhMapTrack)]
         L.kh_map_localizer_stats.argtypes = [vp, C.POINTER(KhMapLocalizerStats)]
+    if hasattr(L, "kh_map_changes_create"):      # (KH_LIBRARY may name a build from before the change layer existed)
+        L.kh_map_changes_create.argtypes = [C.POINTER(KhMapView), C.POINTER(vp)]
+        L.kh_map_changes_destroy.argtypes = [vp]
+        L.kh_map_changes_destroy.restype = None
+        L.kh_map_changes_clear.argtypes = [vp]
+        L.kh_map_changes_decay.argtypes = [vp, i32]
+        L.kh_map_changes_observe.argtypes = [vp, C.POINTER(KhLaser), i32, vp, vp, i32, vp]
+        L.kh_map_changes_diff.argtypes = [vp, C.c_uint32, dbl, vp, i32, C.POINTER(KhMapChangesSummary)]
+        L.kh_map_changes_read.argtypes = [vp, vp, vp, vp, vp]
+        L.kh_map_changes_view.argtypes = [vp, C.POINTER(KhMapView)]
+        L.kh_map_changes_read_nav.argtypes = [vp, vp]
     if hasattr(L, "kh_spa_create"):
         L.kh_spa_options_default.argtypes = [C.POINTER(KhSpaOptions)]
         L.kh_spa_create.argtypes = [i32, C.POINTER(vp)]

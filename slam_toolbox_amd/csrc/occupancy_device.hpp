@@ -191,6 +191,34 @@ int map_seed_blocks(MapWork * w, const kh_map_view & v, int32_t pitch, int64_t b
 int map_fit_counts(MapWork * w, const kh_map_view & v, int32_t n_beams, const double * ranges, int32_t n_poses, const double * points,
   const double * sensor_xy, double range_threshold, double min_range, double max_range, uint64_t * counts, double * kernel_ms);
 
+// ---- a change layer's kernels (kh_map_changes_*; the handle and its buffers: map_changes.cpp) ----
+// the layer's two counter grids on the window of its view, row stride the view's width_step
+struct ChangeLayer
+{
+  uint32_t * pass;
+  uint32_t * hits;
+};
+enum : int32_t {kChangeCodes = 6};                    // KH_CELL_UNOBSERVED .. KH_CELL_DISCOVERED_FREE
+// the units of the changed-cell list: 64 consecutive cells of a row of the window
+inline int64_t change_units(int32_t width, int32_t height) {return (static_cast<int64_t>(width) + 63) / 64 * height;}
+// k_map_observe on `stream`: n_scans scans of n_beams beams -- d_ranges n_scans * n_beams, d_points 2 per beam (kh_scan_points at the
+// scan's pose), d_sensors 2 per scan -- add to the layer; d_labels takes 2 int32 per beam.  The caller has checked the poses and the
+// laser (fit_pose_ok, fit_laser_ok) and 0 <= tolerance <= kMaxEndTolerance.
+void map_observe(void * stream, const kh_map_view & v, const ChangeLayer & layer, const double * d_ranges, const double * d_points,
+  const double * d_sensors, int32_t n_scans, int32_t n_beams, double range_threshold, double min_range, double max_range, int32_t tolerance,
+  int32_t * d_labels);
+// k_map_decay on `stream`: both grids >>= shift
+void map_decay(void * stream, const kh_map_view & v, const ChangeLayer & layer, int32_t shift);
+// k_map_diff on `stream`: d_codes and d_patched take one byte per cell of the strided window (the padding 0), d_counts[kChangeCodes]
+// (zeroed by the caller) the window cells by code
+void map_diff(void * stream, const kh_map_view & v, const ChangeLayer & layer, uint32_t min_pass, double threshold, uint8_t * d_codes,
+  uint8_t * d_patched, unsigned long long * d_counts);
+// the cells of code >= 2 in row-major order on `stream`: d_unit holds change_units() + 1 int32 (it ends as the exclusive prefix of the
+// units' counts, the total last); d_list takes (lattice i, lattice j, code) of the first `cap` cells
+void map_changed_cells(void * stream, const kh_map_view & v, const uint8_t * d_codes, int32_t * d_unit, int32_t * d_list, int32_t cap);
+// k_occ_to_nav of any strided cells on `stream`: d_out takes width * height values, rounded up to a dword
+void cells_to_nav(void * stream, const uint8_t * d_cells, int32_t width, int32_t height, int32_t ws, uint32_t * d_out);
+
 #ifdef __HIP__
 // ---- what the module's host files do with the device the same way (absent from a build without HIP: tests/live_map_plan_check.cpp);
 // set_error and require_device: host_common.hpp ----

@@ -22,6 +22,7 @@ FIT_FIELDS = tuple(k for k, _ in capi.KhMergeFit._fields_)
 MapHypothesis = namedtuple("MapHypothesis", "index seed_cell heading coarse_mean coarse_cov coarse_response fine_mean fine_cov fine_response "
                                             "robot_pose fit")
 TrackStep = namedtuple("TrackStep", "predicted_pose robot_pose sensor_pose covariance response fit")
+TrackStepObserved = namedtuple("TrackStepObserved", TrackStep._fields + ("labels",))      # process(..., changes=layer)
 
 
 def _fit_dict(f):
@@ -134,14 +135,24 @@ class MapLocalizer:
         capi.check(capi.lib().kh_map_localizer_get_pose(self._h, robot.ctypes.data, odom.ctypes.data), "kh_map_localizer_get_pose")
         return robot, odom
 
-    def process(self, ranges, odometric_pose) -> TrackStep:
-        """kh_map_localizer_process: one tracking step; response and fit say how far to trust it"""
+    def process(self, ranges, odometric_pose, changes=None, min_fit_score: float = 0.0):
+        """kh_map_localizer_process: one tracking step; response and fit say how far to trust it.  -> TrackStep.
+        changes: a map_changes.MapChanges layer (on this localizer's map, as a rule).  The step's scan is observed into it at the
+        step's matched sensor pose when the fit has known > 0 and score >= min_fit_score -- a step that cannot be trusted teaches the
+        layer nothing -- and the answer is a TrackStepObserved whose `labels` are the beams' (class, blocked), None where the scan was
+        not observed."""
         ranges = self._ranges(ranges)
         odom = np.ascontiguousarray(odometric_pose, dtype=np.float64).copy()
         t = capi.KhMapTrack()
         capi.check(capi.lib().kh_map_localizer_process(self._h, ranges.ctypes.data, odom.ctypes.data, C.byref(t)), "kh_map_localizer_process")
-        return TrackStep(np.array(t.predicted_pose), np.array(t.robot_pose), np.array(t.sensor_pose), np.array(t.covariance).reshape(3, 3),
+        step = TrackStep(np.array(t.predicted_pose), np.array(t.robot_pose), np.array(t.sensor_pose), np.array(t.covariance).reshape(3, 3),
                          t.response, _fit_dict(t.fit))
+        if changes is None:
+            return step
+        labels = None
+        if step.fit["known"] > 0 and step.fit["score"] >= min_fit_score:
+            labels = changes.observe(self._laser, ranges, step.sensor_pose)
+        return TrackStepObserved(*step, labels)
 
     def stats(self) -> dict:
         st = capi.KhMapLocalizerStats()
