@@ -1452,6 +1452,71 @@ KH_API int kh_map_changes_view(kh_map_changes * c, kh_map_view * out);
 /* the patched cells of the last diff as width * height nav values, kh_occupancy_read_nav's mapping.  KH_ERR_NOT_FOUND before a diff. */
 KH_API int kh_map_changes_read_nav(kh_map_changes * c, int8_t * out);
 
+/* ---------------------------------------------------------------- the scan a map would produce; placing one map in another
+ * Ray casting on the lattice of section 7k.  Beam b of sensor pose k runs from the lattice cell c0 of the sensor's (x, y) to the
+ * lattice cell c1 of its far point: what kh_scan_points gives at that pose for a reading of range_threshold.  Its cells are exactly
+ * the cells TraceLine(c0, c1) visits, ordered outward by s = |long-axis coordinate - c0's|, s = 0 .. L.  A window cell of state 100 is
+ * occupied, of state 255 free; every other state, and a cell outside the window, is unknown.  In ascending s: an occupied cell ends
+ * the beam (HIT); an unknown cell counts, and ends the beam (UNKNOWN) when max_unknown >= 0 and more than max_unknown were counted;
+ * the end of the line is FREE, reported with c1 and s = L.  The sensor's own cell is treated like any other. */
+enum {
+  KH_RAY_FREE = 0,          /* the line ended: nothing within range_threshold */
+  KH_RAY_HIT = 1,           /* an occupied cell */
+  KH_RAY_UNKNOWN = 2        /* the budget of unknown cells ran out */
+};
+typedef struct kh_ray_t {
+  double range;             /* HIT: from the sensor to the hit cell's centre anchor + cell / scale, sqrt((dx * dx) + (dy * dy)); else no_return */
+  int32_t cell[2];          /* lattice cell the beam ended on */
+  int32_t steps;            /* its s */
+  int32_t code;             /* KH_RAY_ */
+} kh_ray_t;
+/* out takes n_poses * laser->n_beams answers, pose-major; *kernel_ms (may be NULL) the kernel's time by events.  no_return is any
+ * double, NaN included; a reading the caller's laser drops (> range_threshold and, to be dropped by AddScan's gate, >= maximum_range)
+ * keeps a cast scan from painting walls where the map ended.  The map is only read.  KH_ERR_INVALID_ARG before a device is looked
+ * for: everything kh_map_fit refuses of a view, a laser and poses, NULL sensor_poses / out, n_poses < 1, max_unknown < -1. */
+KH_API int kh_map_raycast(const kh_map_view * view, const kh_laser * laser, int32_t n_poses, const double * sensor_poses /* 3n */,
+                          int32_t max_unknown, double no_return, kh_ray_t * out /* n_poses * n_beams */, double * kernel_ms);
+
+/* ---- placing the map `moving` in the localizer's map, with no scan of either.  Seeds of the moving map (kh_map_seeds at
+ * probe_spacing) are robot poses of heading 0; the scans the moving map would produce there are cast in ONE kh_map_raycast launch
+ * (max_unknown; no_return = the next double above range_threshold where that is below maximum_range, else NaN).  The n_probes seeds
+ * with the most HIT beams are the probes (ties to the lower seed index; a seed without a HIT is none).  Each probe's cast ranges are
+ * relocalized in the localizer's map; a hypothesis implies the correction C = P . inverse(Q), P the hypothesis' robot pose, Q the
+ * probe's, `.` and inverse as kh_merge_move_submap composes.  Candidate 0 is `initial`, then the probes in pick order, each one's
+ * hypotheses in rank order; nothing is de-duplicated.  Every candidate is fitted with every probe -- kh_map_fit of the probe's cast
+ * ranges at the sensor pose C . S, S the probe's sensor pose, against the localizer's map -- the six counters summed over the probes
+ * and derived as kh_merge_fit_t; the ranking is kh_merge_align's: known >= min_known first, then score descending, agree
+ * descending, candidate index ascending. */
+typedef struct kh_map_align_params {
+  double probe_spacing;        /* > 0 (default: the localizer's default seed_spacing) */
+  int32_t n_probes;            /* >= 1 (default 3) */
+  int32_t top_k;               /* hypotheses kept per probe, >= 1 (default 4) */
+  int32_t max_unknown;         /* the cast's budget, >= -1 (default 20) */
+  int32_t pad;
+  uint64_t min_known;          /* candidates with fewer known visits rank last (default 0) */
+  double initial[3];           /* candidate 0 (default 0, 0, 0) */
+  kh_map_relocalize_params relocalize;   /* as for kh_map_localizer_relocalize; its top_k is overridden by top_k above */
+} kh_map_align_params;
+typedef struct kh_map_align_cand {
+  double correction[3];        /* moving map -> the localizer's map */
+  int32_t probe_seed;          /* seed index in the moving map; -1 for candidate 0 */
+  int32_t hypothesis;          /* rank of the hypothesis in the probe's relocalization; -1 for candidate 0 */
+  double fine_response;        /* 0 for candidate 0 */
+  int32_t index, enough;       /* candidate index before ranking; known >= min_known */
+  kh_merge_fit_t fit;
+} kh_map_align_cand;
+/* defaults; the relocalization parameters are those of the localizer's mapper parameters (loc NULL: of kh_mapper_params_default) */
+KH_API void kh_map_align_params_default(const kh_map_localizer * loc, kh_map_align_params * p);
+/* out takes the first min(cap, n) ranked candidates, *n_candidates takes n.  times_ms (may be NULL): [0] seeds and cast, [1] the
+ * relocalizations, [2] the fits, [3] the whole call.  The localizer (its map, its tracked pose) and both maps are left as they were.
+ * KH_ERR_INVALID_ARG before a device is looked for: NULL params / n_candidates, out NULL with cap > 0, cap < 0, a malformed moving
+ * view, probe_spacing not finite or <= 0, n_probes < 1, top_k < 1, max_unknown < -1, a non-finite initial, invalid relocalization
+ * parameters.  Then: no device KH_ERR_NO_DEVICE, a NULL localizer KH_ERR_INVALID_ARG, no map set KH_ERR_NOT_FOUND, a moving view on
+ * another device than the localizer or a probe pitch above 4096 cells KH_ERR_INVALID_ARG.  A moving map without a probe is KH_OK
+ * with candidate 0 alone. */
+KH_API int kh_map_align(kh_map_localizer * loc, const kh_map_view * moving, const kh_map_align_params * params,
+                        kh_map_align_cand * out, int32_t cap, int32_t * n_candidates, double times_ms[4]);
+
 #ifdef __cplusplus
 }
 #endif

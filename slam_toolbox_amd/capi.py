@@ -172,6 +172,7 @@ SYMBOLS = [
     "kh_map_localizer_process", "kh_map_localizer_stats",
     "kh_map_changes_create", "kh_map_changes_destroy", "kh_map_changes_clear", "kh_map_changes_decay", "kh_map_changes_observe",
     "kh_map_changes_diff", "kh_map_changes_read", "kh_map_changes_view", "kh_map_changes_read_nav",
+    "kh_map_raycast", "kh_map_align_params_default", "kh_map_align",
 ]
 
 
@@ -317,6 +318,26 @@ KH_BEAM_DROPPED, KH_BEAM_EXPLAINED, KH_BEAM_NOVEL, KH_BEAM_UNKNOWN, KH_BEAM_THRO
 KH_CELL_UNOBSERVED, KH_CELL_CONFIRMED, KH_CELL_APPEARED, KH_CELL_VANISHED, KH_CELL_DISCOVERED_OCCUPIED, KH_CELL_DISCOVERED_FREE = range(6)
 
 
+KH_RAY_FREE, KH_RAY_HIT, KH_RAY_UNKNOWN = range(3)
+
+
+class KhRay(C.Structure):
+    _fields_ = [("range", C.c_double), ("cell", C.c_int32 * 2), ("steps", C.c_int32), ("code", C.c_int32)]
+
+
+RAY_DTYPE = np.dtype([("range", np.float64), ("cell", np.int32, (2,)), ("steps", np.int32), ("code", np.int32)])
+
+
+class KhMapAlignParams(C.Structure):
+    _fields_ = [("probe_spacing", C.c_double), ("n_probes", C.c_int32), ("top_k", C.c_int32), ("max_unknown", C.c_int32), ("pad", C.c_int32),
+                ("min_known", C.c_uint64), ("initial", C.c_double * 3), ("relocalize", KhMapRelocalizeParams)]
+
+
+class KhMapAlignCand(C.Structure):
+    _fields_ = [("correction", C.c_double * 3), ("probe_seed", C.c_int32), ("hypothesis", C.c_int32), ("fine_response", C.c_double),
+                ("index", C.c_int32), ("enough", C.c_int32), ("fit", KhMergeFit)]
+
+
 class KhMergeAlignParams(C.Structure):
     _fields_ = [("n_probes", C.c_int32), ("top_k", C.c_int32), ("min_known", C.c_uint64), ("min_pass_through", C.c_uint32), ("pad", C.c_uint32),
                 ("occupancy_threshold", C.c_double), ("relocalize", KhRelocalizeParams)]
@@ -429,6 +450,11 @@ def lib():
         L.kh_map_changes_read.argtypes = [vp, vp, vp, vp, vp]
         L.kh_map_changes_view.argtypes = [vp, C.POINTER(KhMapView)]
         L.kh_map_changes_read_nav.argtypes = [vp, vp]
+    if hasattr(L, "kh_map_raycast"):      # (KH_LIBRARY may name a build from before the ray cast existed)
+        L.kh_map_raycast.argtypes = [C.POINTER(KhMapView), C.POINTER(KhLaser), i32, vp, i32, dbl, vp, C.POINTER(dbl)]
+        L.kh_map_align_params_default.argtypes = [vp, C.POINTER(KhMapAlignParams)]
+        L.kh_map_align_params_default.restype = None
+        L.kh_map_align.argtypes = [vp, C.POINTER(KhMapView), C.POINTER(KhMapAlignParams), C.POINTER(KhMapAlignCand), i32, C.POINTER(i32), vp]
     if hasattr(L, "kh_spa_create"):
         L.kh_spa_options_default.argtypes = [C.POINTER(KhSpaOptions)]
         L.kh_spa_create.argtypes = [i32, C.POINTER(vp)]

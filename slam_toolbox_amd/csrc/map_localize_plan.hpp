@@ -102,6 +102,15 @@ inline kh_merge_fit_t fit_derive(const uint64_t c[kFitCounters])
   return f;
 }
 
+// what kh_map_localizer_relocalize (and kh_map_align, which hands them on) takes of its parameters before a device is looked for
+inline bool relocalize_params_ok(const kh_map_relocalize_params & p)
+{
+  return p.seed_spacing > 0 && std::isfinite(p.seed_spacing) && p.n_headings >= 0 && p.n_headings <= 4096 && p.top_k >= 0 &&
+         std::isfinite(p.radius) && std::isfinite(p.center_xy[0]) && std::isfinite(p.center_xy[1]) && !std::isnan(p.minimum_response_coarse) &&
+         !std::isnan(p.maximum_variance_coarse) && !std::isnan(p.minimum_response_fine) && !std::isnan(p.min_fit_score) &&
+         !std::isnan(p.merge_distance) && !std::isnan(p.merge_heading);
+}
+
 // ---- the answer of a relocalization ----
 // what the ranking reads of an accepted hypothesis
 struct Ranked

@@ -11,25 +11,10 @@
 #include <string>
 #include <vector>
 
-#include "map_localize_plan.hpp"
-#include "mapper_private.hpp"
+#include "map_localizer_private.hpp"
 
 using namespace kh;
 using namespace kh::mapper;
-
-struct kh_map_localizer
-{
-  kh_mapper_params p;
-  Laser laser;
-  int32_t device = 0, max_batch = 1;
-  kh_matcher * loop = nullptr;         // MapperGraph's loop matcher (Mapper.cpp:1397-1400)
-  kh_matcher * seq = nullptr;          // Mapper::Initialize's sequential matcher (Mapper.cpp:2606-2631)
-  MapWork * work = nullptr;
-  kh_map_view view;
-  bool has_map = false, has_pose = false;
-  Pose robot, odometric;               // the pose the localizer holds, and the odometric pose it belongs to
-  kh_map_localizer_stats_t stats;
-};
 
 namespace
 {
@@ -68,6 +53,18 @@ int match_poses(kh_map_localizer * loc, kh_matcher * matcher, const double * ran
 // kh_map_fit of the readings at n sensor poses on the localizer's own work buffers
 int fit_poses(kh_map_localizer * loc, const double * ranges, size_t n, const double * poses, kh_merge_fit_t * out, double * kernel_ms)
 {
+  std::vector<uint64_t> counts(n * kFitCounters);
+  const int rc = localizer_fit_counts(loc, ranges, n, poses, counts.data(), kernel_ms);
+  if (rc) {return rc;}
+  for (size_t k = 0; k < n; ++k) {out[k] = fit_derive(&counts[k * kFitCounters]);}
+  return KH_OK;
+}
+}  // namespace
+
+namespace kh
+{
+int localizer_fit_counts(kh_map_localizer * loc, const double * ranges, size_t n, const double * poses, uint64_t * counts, double * kernel_ms)
+{
   double unused_ms = 0.0;
   if (!kernel_ms) {kernel_ms = &unused_ms;}
   *kernel_ms = 0.0;
@@ -88,15 +85,17 @@ int fit_poses(kh_map_localizer * loc, const double * ranges, size_t n, const dou
   host_parallel_for_wide(n, [&](size_t k) {
     kh_scan_points(ranges, loc->laser.n, poses + 3 * k, loc->laser.min_angle, loc->laser.ang_res, &points[2 * nb * k]);
   });
-  std::vector<uint64_t> counts(n * kFitCounters);
   const int rc = map_fit_counts(loc->work, loc->view, loc->laser.n, ranges, static_cast<int32_t>(n), points.data(), sensor_xy.data(),
-      loc->laser.range_threshold, loc->laser.min_range, loc->laser.max_range, counts.data(), kernel_ms);
+      loc->laser.range_threshold, loc->laser.min_range, loc->laser.max_range, counts, kernel_ms);
   if (rc) {return rc;}
-  for (size_t k = 0; k < n; ++k) {out[k] = fit_derive(&counts[k * kFitCounters]);}
   loc->stats.poses_fitted += static_cast<int64_t>(n);
   loc->stats.fit_kernel_ms += *kernel_ms;
   return KH_OK;
 }
+}  // namespace kh
+
+namespace
+{
 
 // (1) where to try
 int relocalize_seeds(kh_map_localizer * loc, const kh_map_relocalize_params * params, std::vector<Seed> & seeds, kh_map_relocalize_summary * summary)
@@ -267,11 +266,7 @@ int kh_map_localizer_relocalize(kh_map_localizer * loc, const double * ranges, c
 {
   if (!ranges || !params || !summary || cap < 0 || (cap > 0 && !out)) {return KH_ERR_INVALID_ARG;}
   std::memset(summary, 0, sizeof(*summary));
-  if (!(params->seed_spacing > 0) || !std::isfinite(params->seed_spacing) || params->n_headings < 0 || params->n_headings > 4096 ||
-    params->top_k < 0 || !std::isfinite(params->radius) || !std::isfinite(params->center_xy[0]) || !std::isfinite(params->center_xy[1]) ||
-    std::isnan(params->minimum_response_coarse) || std::isnan(params->maximum_variance_coarse) || std::isnan(params->minimum_response_fine) ||
-    std::isnan(params->min_fit_score) || std::isnan(params->merge_distance) || std::isnan(params->merge_heading))
-  {
+  if (!relocalize_params_ok(*params)) {
     set_error("kh_map_localizer_relocalize: seed_spacing > 0, 0 <= n_headings <= 4096, top_k >= 0, a finite region and no NaN are required");
     return KH_ERR_INVALID_ARG;
   }

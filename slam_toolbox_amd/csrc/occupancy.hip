@@ -302,6 +302,55 @@ __global__ __launch_bounds__(256) void k_map_fit(
   }
 }
 
+// The EXPECTED scan of a map view (kh_map_raycast): one lane per (pose, beam), k_map_fit's layout -- a wave holds
+// 64 consecutive beams of one pose, so neighbouring lanes read neighbouring cells near the sensor.  points: per pose the far point of
+// every beam (kh_scan_points of readings that are all range_threshold, on the host: libm stays there).  The lane visits the cells of
+// TraceLine(sensor cell, far cell) outward from the sensor (RayWalk) and leaves at the first decision: an occupied cell (HIT), or
+// the unknown cell that exceeds the budget (UNKNOWN; a cell outside the window and every state but 100 / 255 is unknown); the end of
+// the line is FREE at the far cell.  FitWindowCells' 64-bit index and bounds guard; k_map_fit's bound in front of the walk.  Once a
+// lane stands outside the window on a side its line leads away from, no later cell exists: with no budget to run out (max_unknown
+// < 0) the answer is FREE, and the lane says so at once.  No atomics, no LDS, one 16-byte store per lane.  A wave runs as long as its
+// longest lane.
+__global__ __launch_bounds__(256) void k_map_raycast(
+  MapWindow g, const double * __restrict__ points, const double * __restrict__ sensors, int32_t n_beams, int32_t blocks_per_pose,
+  int32_t max_unknown, RayCell * __restrict__ out)
+{
+  const int32_t pose = (int32_t)(blockIdx.x / (uint32_t)blocks_per_pose);
+  const int64_t i = ((int64_t)(blockIdx.x - (uint32_t)pose * (uint32_t)blocks_per_pose) * 4 + (threadIdx.x >> 6)) * 64 + (threadIdx.x & 63);
+  if (i >= n_beams) {return;}
+  const double sx = sensors[2 * (int64_t)pose], sy = sensors[2 * (int64_t)pose + 1];
+  const double * const p = points + 2 * ((int64_t)pose * n_beams + i);
+  const int32_t x0 = occ_cell(sx, g.ax, g.scale), y0 = occ_cell(sy, g.ay, g.scale);
+  const int32_t x1 = occ_cell(p[0], g.ax, g.scale), y1 = occ_cell(p[1], g.ay, g.scale);
+  const int64_t limit = (1ll << 30) + 2 * kMaxFitWalk;
+  const int64_t ex = (int64_t)x1 - x0, ey = (int64_t)y1 - y0;
+  const bool bounded = x0 >= -limit && x0 <= limit && y0 >= -limit && y0 <= limit && ex >= -kMaxFitWalk && ex <= kMaxFitWalk &&
+    ey >= -kMaxFitWalk && ey <= kMaxFitWalk;
+  RayCell r{x1, y1, 0, KH_RAY_FREE};
+  if (bounded) {
+    RayWalk walk(x0, y0, x1, y1);
+    const int32_t length = walk.length();
+    r.steps = length;
+    int32_t unknown = 0;
+    for (int32_t s = 0; s <= length; ++s, walk.next()) {
+      const int32_t cx = walk.x(), cy = walk.y();
+      const int64_t wx = (int64_t)cx - g.ox, wy = (int64_t)cy - g.oy;
+      uint32_t state = 0u;
+      if (wx >= 0 && wx < g.width && wy >= 0 && wy < g.height) {
+        state = g.cells[wx + wy * g.ws];
+      } else if (max_unknown < 0 && ((wx < 0 && ex <= 0) || (wx >= g.width && ex >= 0) || (wy < 0 && ey <= 0) || (wy >= g.height && ey >= 0))) {
+        break;
+      }
+      if (state == 100u) {r = RayCell{cx, cy, s, KH_RAY_HIT}; break;}
+      if (state != 255u) {
+        ++unknown;
+        if (max_unknown >= 0 && unknown > max_unknown) {r = RayCell{cx, cy, s, KH_RAY_UNKNOWN}; break;}
+      }
+    }
+  }
+  out[(int64_t)pose * n_beams + i] = r;
+}
+
 // Where a robot can stand (kh_map_seeds): one wave per block of pitch x pitch lattice cells; block `b` of the launch is block column
 // bx0 + b % nbx, block row by0 + b / nbx of the lattice.  The lanes stride over the block's cells inside the window, row-major, so a
 // wave reads runs of consecutive bytes of a row wherever the row segment is long enough.  Each lane keeps the minimum of a 64-bit
@@ -1008,6 +1057,89 @@ int map_fit_counts(MapWork * w, const kh_map_view & v, int32_t n_beams, const do
   return finish_timed(w, "kh_map_fit", kernel_ms);
 }
 
+int map_raycast_cells(MapWork * w, const kh_map_view & v, int32_t n_beams, int32_t n_poses, const double * points, const double * sensor_xy,
+  int32_t max_unknown, RayCell * out, double * kernel_ms)
+{
+  if (kernel_ms) {*kernel_ms = 0.0;}
+  if (!w || n_beams < 1 || n_poses < 1 || !points || !sensor_xy || !out || max_unknown < -1) {return KH_ERR_INVALID_ARG;}
+  const int64_t blocks_per_pose = ((static_cast<int64_t>(n_beams) + 63) / 64 + 3) / 4;
+  if (blocks_per_pose * n_poses > INT32_MAX) {set_error("kh_map_raycast: too many poses for one launch"); return KH_ERR_INVALID_ARG;}
+  if (hipSetDevice(w->device) != hipSuccess) {return KH_ERR_HIP;}
+  // the answers first, then the tables: every part a multiple of 16 bytes
+  const size_t out_bytes = static_cast<size_t>(n_poses) * static_cast<size_t>(n_beams) * sizeof(RayCell);
+  const size_t sensor_bytes = static_cast<size_t>(n_poses) * 2 * sizeof(double);
+  const size_t point_bytes = static_cast<size_t>(n_poses) * static_cast<size_t>(n_beams) * 2 * sizeof(double);
+  const size_t bytes = out_bytes + sensor_bytes + point_bytes;
+  if (!grow_device(w->stream, reinterpret_cast<void **>(&w->d), &w->cap, bytes, bytes + bytes / 2)) {
+    set_error("kh_map_raycast: table allocation failed");
+    return KH_ERR_HIP;
+  }
+  uint8_t * const d_sensors = w->d + out_bytes, * const d_points = d_sensors + sensor_bytes;
+  if (hipMemcpyAsync(d_sensors, sensor_xy, sensor_bytes, hipMemcpyHostToDevice, w->stream) != hipSuccess ||
+    hipMemcpyAsync(d_points, points, point_bytes, hipMemcpyHostToDevice, w->stream) != hipSuccess)
+  {
+    (void)hipStreamSynchronize(w->stream);
+    return KH_ERR_HIP;
+  }
+  (void)hipEventRecord(w->ev[0], w->stream);
+  hipLaunchKernelGGL(k_map_raycast, dim3(static_cast<unsigned>(blocks_per_pose * n_poses)), dim3(256), 0, w->stream, window_of(v),
+    reinterpret_cast<const double *>(d_points), reinterpret_cast<const double *>(d_sensors), n_beams, static_cast<int32_t>(blocks_per_pose),
+    max_unknown, reinterpret_cast<RayCell *>(w->d));
+  (void)hipEventRecord(w->ev[1], w->stream);
+  if (hipMemcpyAsync(out, w->d, out_bytes, hipMemcpyDeviceToHost, w->stream) != hipSuccess) {
+    (void)hipStreamSynchronize(w->stream);
+    return KH_ERR_HIP;
+  }
+  return finish_timed(w, "kh_map_raycast", kernel_ms);
+}
+
+int map_raycast_check(const kh_map_view * view, const kh_laser * laser, int32_t n_poses, const double * sensor_poses, int32_t max_unknown)
+{
+  if (!laser || !sensor_poses || n_poses < 1 || max_unknown < -1 || laser->n_beams < 1 || map_view_check(view) != KH_OK) {return KH_ERR_INVALID_ARG;}
+  if (!fit_laser_ok(laser->range_threshold, laser->minimum_range, laser->maximum_range, view->scale) || !std::isfinite(laser->minimum_angle) ||
+    !std::isfinite(laser->angular_resolution))
+  {
+    set_error("kh_map_raycast: the laser's range_threshold * scale must stay below 2^20 cells, its other fields must be numbers");
+    return KH_ERR_INVALID_ARG;
+  }
+  for (int32_t k = 0; k < n_poses; ++k) {
+    if (!fit_pose_ok(sensor_poses + 3 * static_cast<size_t>(k), view->anchor[0], view->anchor[1], view->scale)) {
+      set_error("kh_map_raycast: pose " + std::to_string(k) + " is not finite or lies more than 2^30 cells from the anchor");
+      return KH_ERR_INVALID_ARG;
+    }
+  }
+  return KH_OK;
+}
+
+int map_raycast(MapWork * w, const kh_map_view & v, const kh_laser & laser, int32_t n_poses, const double * sensor_poses, int32_t max_unknown,
+  double no_return, kh_ray_t * out, double * kernel_ms)
+{
+  const size_t nb = static_cast<size_t>(laser.n_beams), np = static_cast<size_t>(n_poses);
+  const std::vector<double> far(nb, laser.range_threshold);
+  std::vector<double> points(2 * nb * np), sensor_xy(2 * np);
+  host_parallel_for_wide(np, [&](size_t k) {
+    kh_scan_points(far.data(), laser.n_beams, sensor_poses + 3 * k, laser.minimum_angle, laser.angular_resolution, &points[2 * nb * k]);
+    sensor_xy[2 * k] = sensor_poses[3 * k]; sensor_xy[2 * k + 1] = sensor_poses[3 * k + 1];
+  });
+  std::vector<RayCell> cells(nb * np);
+  const int rc = map_raycast_cells(w, v, laser.n_beams, n_poses, points.data(), sensor_xy.data(), max_unknown, cells.data(), kernel_ms);
+  if (rc) {return rc;}
+  for (size_t k = 0; k < np; ++k) {
+    const double sx = sensor_xy[2 * k], sy = sensor_xy[2 * k + 1];
+    for (size_t b = 0; b < nb; ++b) {
+      const RayCell & c = cells[k * nb + b];
+      kh_ray_t & r = out[k * nb + b];
+      r.cell[0] = c.i; r.cell[1] = c.j; r.steps = c.steps; r.code = c.code;
+      r.range = no_return;
+      if (c.code == KH_RAY_HIT) {         // to the hit cell's centre
+        const double dx = (v.anchor[0] + static_cast<double>(c.i) / v.scale) - sx, dy = (v.anchor[1] + static_cast<double>(c.j) / v.scale) - sy;
+        r.range = std::sqrt((dx * dx) + (dy * dy));
+      }
+    }
+  }
+  return KH_OK;
+}
+
 void map_observe(void * stream, const kh_map_view & v, const ChangeLayer & layer, const double * d_ranges, const double * d_points,
   const double * d_sensors, int32_t n_scans, int32_t n_beams, double range_threshold, double min_range, double max_range, int32_t tolerance,
   int32_t * d_labels)
@@ -1307,6 +1439,19 @@ int kh_map_fit(const kh_map_view * view, const kh_laser * laser, const double * 
   if (rc) {return rc;}
   for (size_t k = 0; k < np; ++k) {out[k] = fit_derive(&counts[k * kFitCounters]);}
   return KH_OK;
+}
+
+int kh_map_raycast(const kh_map_view * view, const kh_laser * laser, int32_t n_poses, const double * sensor_poses, int32_t max_unknown,
+  double no_return, kh_ray_t * out, double * kernel_ms)
+{
+  if (kernel_ms) {*kernel_ms = 0.0;}
+  if (!out || map_raycast_check(view, laser, n_poses, sensor_poses, max_unknown) != KH_OK) {return KH_ERR_INVALID_ARG;}
+  if (require_device(view->device) != KH_OK) {return KH_ERR_NO_DEVICE;}
+  MapWork * w = map_work_create(view->device);
+  if (!w) {return KH_ERR_HIP;}
+  const int rc = map_raycast(w, *view, *laser, n_poses, sensor_poses, max_unknown, no_return, out, kernel_ms);
+  map_work_destroy(w);
+  return rc;
 }
 
 int kh_occupancy_write_nav(kh_occupancy * g, const int8_t * nav)

@@ -7,6 +7,9 @@
 #include <string>
 #ifdef __HIP__
 #include <hip/hip_runtime.h>
+#define KH_HOST_DEVICE __host__ __device__ __forceinline__
+#else
+#define KH_HOST_DEVICE inline
 #endif
 
 #include "../../include/karto_hip.h"
@@ -190,6 +193,55 @@ int map_seed_blocks(MapWork * w, const kh_map_view & v, int32_t pitch, int64_t b
 // The caller has checked the poses and the laser (fit_pose_ok, fit_laser_ok).
 int map_fit_counts(MapWork * w, const kh_map_view & v, int32_t n_beams, const double * ranges, int32_t n_poses, const double * points,
   const double * sensor_xy, double range_threshold, double min_range, double max_range, uint64_t * counts, double * kernel_ms);
+
+// ---- the expected scan of a map (kh_map_raycast) ----
+// The cells of TraceLine((x0, y0), (x1, y1)) OUTWARD from (x0, y0), one per step s = 0 .. length.  TraceLine walks its long axis
+// upward, so where (x0, y0) has the larger long coordinate it starts at the far end -- and a line traced from the other end is not the
+// mirror image: half-way between two rows the walk steps (2 error >= dx), the mirrored walk would step one cell later.  Its error
+// at the last cell is k dy - dx floor(k dy / dx + 1 / 2) at k = dx, which is 0: the walk can be run backwards from its own end with no
+// division.  With the sign of the error flipped the backward recurrence is the forward one with the comparison made strict, so one
+// recurrence serves both directions: error += dy; step when 2 error + bias > dx, bias 1 where TraceLine starts at (x0, y0), else 0.
+// (tests/map_align_plan_check.cpp walks every short line against TraceLine on the CPU.)
+struct RayWalk
+{
+  int32_t a, b;              // the current cell: long-axis and short-axis coordinate
+  int32_t step_a, step_b;    // +-1: towards (x1, y1)
+  int32_t dx, dy, bias, error;
+  bool steep;
+  KH_HOST_DEVICE RayWalk(int32_t x0, int32_t y0, int32_t x1, int32_t y1)
+  {
+    const int64_t ex = static_cast<int64_t>(x1) - x0, ey = static_cast<int64_t>(y1) - y0;
+    steep = (ey < 0 ? -ey : ey) > (ex < 0 ? -ex : ex);
+    a = steep ? y0 : x0; b = steep ? x0 : y0;
+    const int64_t ea = steep ? ey : ex, eb = steep ? ex : ey;
+    dx = static_cast<int32_t>(ea < 0 ? -ea : ea); dy = static_cast<int32_t>(eb < 0 ? -eb : eb);
+    step_a = ea < 0 ? -1 : 1; step_b = eb < 0 ? -1 : 1;
+    bias = ea < 0 ? 0 : 1;
+    error = 0;
+  }
+  KH_HOST_DEVICE int32_t length() const {return dx;}
+  KH_HOST_DEVICE int32_t x() const {return steep ? b : a;}
+  KH_HOST_DEVICE int32_t y() const {return steep ? a : b;}
+  KH_HOST_DEVICE void next()
+  {
+    error += dy;
+    if (2 * error + bias > dx) {b += step_b; error -= dx;}
+    a += step_a;
+  }
+};
+// one beam's answer of k_map_raycast: the cell the walk ended on, its step, and the KH_RAY_ code
+struct alignas(16) RayCell {int32_t i, j, steps, code;};
+static_assert(sizeof(RayCell) == 16, "one int4 per beam");
+// k_map_raycast: per pose the 2 * n_beams far points (kh_scan_points of a scan whose readings are all range_threshold) and the sensor's
+// (x, y); out takes n_poses * n_beams answers, pose-major.  The caller has checked the poses and the laser (fit_pose_ok, fit_laser_ok)
+// and max_unknown >= -1.
+int map_raycast_cells(MapWork * w, const kh_map_view & v, int32_t n_beams, int32_t n_poses, const double * points, const double * sensor_xy,
+  int32_t max_unknown, RayCell * out, double * kernel_ms);
+// kh_map_raycast's argument checks but `out` (KH_OK, or KH_ERR_INVALID_ARG and its text), and the call itself on a caller's work
+// buffers once they passed: the far points (n_beams libm sincos per pose, on the worker pool), the launch, the ranges
+int map_raycast_check(const kh_map_view * view, const kh_laser * laser, int32_t n_poses, const double * sensor_poses, int32_t max_unknown);
+int map_raycast(MapWork * w, const kh_map_view & v, const kh_laser & laser, int32_t n_poses, const double * sensor_poses, int32_t max_unknown,
+  double no_return, kh_ray_t * out, double * kernel_ms);
 
 // ---- a change layer's kernels (kh_map_changes_*; the handle and its buffers: map_changes.cpp) ----
 // the layer's two counter grids on the window of its view, row stride the view's width_step

@@ -7,6 +7,8 @@ LiveMap, or a hand-filled capi.KhMapView -- and nothing else: no scans, no pose 
     hyps, summary = loc.relocalize(ranges)                 # where was this scan taken?
     loc.set_pose(hyps[0].robot_pose, odometric_pose)
     step = loc.process(next_ranges, next_odometric_pose)   # ... and from there on, scan by scan
+    cast = loc.expected(step.sensor_pose)                  # what the map expects every beam to measure there (kh_map_raycast)
+    candidates, _ = loc.align(other_map)                   # where a second map lies in this one (kh_map_align; section 7m)
 
 Nothing here computes: every call lands in the library."""
 from __future__ import annotations
@@ -23,6 +25,8 @@ MapHypothesis = namedtuple("MapHypothesis", "index seed_cell heading coarse_mean
                                             "robot_pose fit")
 TrackStep = namedtuple("TrackStep", "predicted_pose robot_pose sensor_pose covariance response fit")
 TrackStepObserved = namedtuple("TrackStepObserved", TrackStep._fields + ("labels",))      # process(..., changes=layer)
+MapCast = namedtuple("MapCast", "ranges codes cells steps kernel_ms")
+AlignCandidate = namedtuple("AlignCandidate", "correction probe_seed hypothesis fine_response index enough fit")
 
 
 def _fit_dict(f):
@@ -65,6 +69,29 @@ def map_fit(view, laser, ranges, poses):
     L = _laser_of(laser)
     capi.check(capi.lib().kh_map_fit(C.byref(v), C.byref(L), ranges.ctypes.data, len(poses), poses.ctypes.data, out), "kh_map_fit")
     return [_fit_dict(out[k]) for k in range(len(poses))]
+
+
+def ray_no_return(laser):
+    """the reading of a beam that found nothing: the next double above range_threshold where the laser's maximum_range lies above that
+    (dropped from the point readings, still clearing the beam in AddScan), else NaN"""
+    L = laser if isinstance(laser, capi.KhLaser) else _laser_of(laser)
+    above = float(np.nextafter(np.float64(L.range_threshold), np.inf))
+    return above if above < L.maximum_range else float("nan")
+
+
+def map_raycast(view, laser, poses, max_unknown=-1, no_return=None):
+    """kh_map_raycast: the scan the map would produce at each of `poses` (n, 3) sensor poses -> MapCast of arrays with a leading pose
+    axis: ranges (n, n_beams) float64, codes (KH_RAY_FREE / HIT / UNKNOWN), cells (n, n_beams, 2) lattice i, j, steps; kernel_ms.
+    max_unknown: unknown cells a beam may pass (-1: any number).  no_return: the range of a beam without a hit (default ray_no_return)"""
+    v = _view_of(view)
+    L = laser if isinstance(laser, capi.KhLaser) else _laser_of(laser)
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    out = np.zeros((max(1, len(poses)), L.n_beams), dtype=capi.RAY_DTYPE)
+    ms = C.c_double()
+    capi.check(capi.lib().kh_map_raycast(C.byref(v), C.byref(L), len(poses), poses.ctypes.data, int(max_unknown),
+                                         ray_no_return(L) if no_return is None else float(no_return), out.ctypes.data, C.byref(ms)), "kh_map_raycast")
+    out = out[:len(poses)]
+    return MapCast(out["range"].copy(), out["code"].copy(), out["cell"].copy(), out["steps"].copy(), ms.value)
 
 
 class MapLocalizer:
@@ -153,6 +180,43 @@ class MapLocalizer:
         if step.fit["known"] > 0 and step.fit["score"] >= min_fit_score:
             labels = changes.observe(self._laser, ranges, step.sensor_pose)
         return TrackStepObserved(*step, labels)
+
+    def expected(self, sensor_pose, max_unknown=-1, no_return=None):
+        """kh_map_raycast against the localizer's map: the scan expected at `sensor_pose` (3,) or poses (n, 3) -> MapCast, to set
+        beside the measured ranges of a tracking step (TrackStep.sensor_pose)"""
+        if self._map is None:
+            raise capi.KartoHipError(capi.KH_ERR_NOT_FOUND, "MapLocalizer.expected: no map set")
+        return map_raycast(self._map, self._laser, sensor_pose, max_unknown, no_return)
+
+    def align(self, moving, cap: int = 64, **params):
+        """kh_map_align: places the map `moving` (a capi.KhMapView, an OccupancyGrid or a LiveMap) in the localizer's map, with no scan
+        of either.  params: fields of kh_map_align_params over the defaults of this localizer; `relocalize` a dict of fields of
+        kh_map_relocalize_params.  -> (candidates best first as AlignCandidate records: correction = moving map -> this map;
+        times_ms: seeds + cast, relocalizations, fits, the call)"""
+        v = _view_of(moving)
+        p = capi.KhMapAlignParams()
+        capi.lib().kh_map_align_params_default(self._h, C.byref(p))
+        for k, value in params.items():
+            if k == "initial":
+                p.initial[0], p.initial[1], p.initial[2] = (float(x) for x in value)
+            elif k == "relocalize":
+                for rk, rv in value.items():
+                    if rk == "center_xy":
+                        p.relocalize.center_xy[0], p.relocalize.center_xy[1] = float(rv[0]), float(rv[1])
+                    elif hasattr(p.relocalize, rk):
+                        setattr(p.relocalize, rk, rv)
+                    else:
+                        raise KeyError(rk)
+            elif hasattr(p, k):
+                setattr(p, k, value)
+            else:
+                raise KeyError(k)
+        out = (capi.KhMapAlignCand * max(1, int(cap)))()
+        n, times = C.c_int32(), np.zeros(4)
+        capi.check(capi.lib().kh_map_align(self._h, C.byref(v), C.byref(p), out, int(cap), C.byref(n), times.ctypes.data), "kh_map_align")
+        cands = [AlignCandidate(np.array(c.correction), c.probe_seed, c.hypothesis, c.fine_response, c.index, bool(c.enough), _fit_dict(c.fit))
+                 for c in out[:min(n.value, int(cap))]]
+        return cands, times
 
     def stats(self) -> dict:
         st = capi.KhMapLocalizerStats()
