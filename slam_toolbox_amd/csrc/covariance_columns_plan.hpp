@@ -2,7 +2,7 @@
 // sweep of A X = E_q visits, and which query columns each of them carries.  A query's right-hand side is non-zero in the pivot rows
 // of the front that eliminates it; a forward sweep hands non-zeros to ancestors only, so per query exactly the fronts on the path
 // from that front to its root are touched -- at most one per level, which is why every (row, column) of the right-hand sides has one
-// writer per launch.  Nothing here knows HIP: spa_host.cpp plans with this before it queues anything on the device, and
+// writer per launch.  Nothing here knows HIP: spa_covariance.cpp plans with this before it queues anything on the device, and
 // tests/covariance_columns_plan_check.cpp runs it on the CPU (tests/test_covariance_columns_plan.py).
 #pragma once
 #include <cstdint>

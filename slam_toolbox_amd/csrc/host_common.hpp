@@ -2,6 +2,7 @@
 // the HIP-free files make.  Needs no HIP header (spa_symbolic.cpp is also built alone on the CPU).  Not part of the public ABI
 // (include/karto_hip.h).
 #pragma once
+#include <chrono>
 #include <cstddef>
 #include <cstdint>
 #include <functional>
@@ -17,4 +18,10 @@ void host_parallel_for_wide(size_t n, const std::function<void(size_t)> & fn);
 void stream_synchronize(void * hip_stream);
 // comm.cpp: KH_OK when `device` can be used, otherwise KH_ERR_NO_DEVICE and its text; require_device(0) asks for any device at all
 int require_device(int32_t device);
+// wall time in milliseconds: from a to b, and from t to now
+inline double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b)
+{
+  return std::chrono::duration<double, std::milli>(b - a).count();
+}
+inline double ms_since(std::chrono::steady_clock::time_point t) {return ms_between(t, std::chrono::steady_clock::now());}
 }  // namespace kh

@@ -89,13 +89,7 @@ namespace kh
 {
 namespace mapper
 {
-// ---- small idioms, one copy each ----
-inline double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b)
-{
-  return std::chrono::duration<double, std::milli>(b - a).count();
-}
-inline double ms_since(std::chrono::steady_clock::time_point t) {return ms_between(t, std::chrono::steady_clock::now());}
-
+// ---- small idioms, one copy each (ms_between, ms_since: host_common.hpp) ----
 struct ProfScope
 {
   kh_mapper * m; Prof k; std::chrono::steady_clock::time_point t0;

@@ -1,4 +1,4 @@
-// One round of marginalizing node removal (kh_spa_marginalize_nodes): what spa_host.cpp packs and marginalize.hip reads.
+// One round of marginalizing node removal (kh_spa_marginalize_nodes): what spa_marginalize.cpp packs and marginalize.hip reads.
 #pragma once
 #include <cstdint>
 

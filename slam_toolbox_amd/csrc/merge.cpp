@@ -360,11 +360,6 @@ int build_grid(kh_merge * g, int32_t skip, const char * who, uint32_t min_pass_t
 
 bool finite3(const double * t) {return std::isfinite(t[0]) && std::isfinite(t[1]) && std::isfinite(t[2]);}
 
-double ms_since(std::chrono::steady_clock::time_point t)
-{
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-}
-
 // The fit of n candidate corrections of submap `moving` against the merge of all the others: the reference
 // grid once, then one launch of k_occ_fit_merged.  times_ms[0] = the reference grid (wall), [1] = the fit kernel (events).
 int fit_candidates(kh_merge * g, const Submap & moving, const char * who, int32_t n, const double * corrections, uint32_t min_pass_through,

@@ -1,4 +1,4 @@
-// Internal structures shared by spa_host.cpp and spa_kernels.hip (pose-graph SPA solver, hot path B).
+// Internal structures shared by the solver's host files (spa_private.hpp lists them) and spa_kernels.hip (pose-graph SPA solver, hot path B).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -182,7 +182,7 @@ void spa_launch_lin_check(const SpaDev & d, const double * scale, const double *
 // projected-gradient norms: out[0] = max |x - Plus(x, -g)|, out[1] = |x_free|^2
 void spa_launch_grad_norms(const SpaDev & d, const double * x, double * out2, void * stream);
 
-// ---- what spa_host.cpp shows the mapper of a solver handle besides the public kh_spa_* calls ----
+// ---- what the solver's host files show the mapper of a solver handle besides the public kh_spa_* calls ----
 // whether the resident covariances still belong to the graph (the mapper recomputes lazily), whether the block column of node
 // `id` is resident with them, and whether node `id` is in the problem of the last covariance pass
 bool spa_covariances_valid(const kh_spa * s);
