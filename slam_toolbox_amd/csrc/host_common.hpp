@@ -14,6 +14,11 @@ void set_error(const std::string & s);                                          
 // the persistent host pools (host_pool.hpp, instantiated by matcher_host.cpp): fn(i) for i in [0, n), back when all are done
 void host_parallel_for(size_t n, const std::function<void(size_t)> & fn);
 void host_parallel_for_wide(size_t n, const std::function<void(size_t)> & fn);
+// matcher_host.cpp: scan points at these poses -- kh_scan_points (n_beams libm sincos) per sensor pose, on the wide pool.  Pose k (3
+// doubles) places readings ranges + k * ranges_stride (0: the same readings at every pose) into points + 2 * n_beams * k; sensor_xy,
+// unless nullptr, takes the pose's (x, y).
+void scan_points_at(const double * ranges, size_t ranges_stride, int32_t n_beams, double min_angle, double angular_resolution, size_t n_poses,
+  const double * sensor_poses, double * points, double * sensor_xy);
 // comm.cpp: waits for everything queued on the HIP stream
 void stream_synchronize(void * hip_stream);
 // comm.cpp: KH_OK when `device` can be used, otherwise KH_ERR_NO_DEVICE and its text; require_device(0) asks for any device at all

@@ -11,7 +11,7 @@
 // touched rectangle, the feed's tile job -- are plain functions in live_map_plan.hpp, checked on the CPU by
 // tests/test_live_map_plan.py.  This file is what needs the device: kh_live_map_update plans with them and then runs its stages
 // (re-layout, log, records, launch, commit), kh_map_feed_poll likewise; each states its failure rule at its top.  The kernels are
-// in occupancy.hip (k_occ_trace_delta, k_occ_update_rect, k_nav_feed).
+// in occupancy_live.hip (k_occ_trace_delta, k_occ_update_rect, k_nav_feed).
 //
 // The map feed (kh_map_feed_*) is at the end: the published grid of one consumer, the pending region the
 // updates leave it, and the poll that hands out the 16 x 16 tiles whose nav values changed.

@@ -63,7 +63,7 @@ inline int64_t reach_of(double range_threshold, double scale)
   return reach < kCellLimit ? static_cast<int64_t>(reach) : static_cast<int64_t>(kCellLimit);
 }
 
-// the sensor's cell by the operations of occ_cell (occupancy.hip): o_to_int(o_round((x - anchor) * scale)); false = too far from the anchor
+// the sensor's cell by the operations of occ_cell (occupancy_walk.hpp): o_to_int(o_round((x - anchor) * scale)); false = too far from the anchor
 inline bool cell_of(const Lattice & l, const double sensor[3], int32_t * cx, int32_t * cy)
 {
   const double x = round_half_away((sensor[0] - l.ax) * l.scale), y = round_half_away((sensor[1] - l.ay) * l.scale);

@@ -1,7 +1,7 @@
 // The map change layer (kh_map_changes_*): what the scans of a robot that holds only a map say about that map
 // -- per beam (explained, novel, through something solid), per cell (confirmed, appeared, vanished, discovered) and as the patched
 // map, a kh_map_view of its own.  The handle owns the layer's two counter grids, the codes and patched cells of the last diff and the
-// staging of a call; the kernels and their launchers are occupancy.hip's, the rules that need no device map_changes_plan.hpp's.
+// staging of a call; the kernels and their launchers are occupancy_changes.hip's, the rules that need no device map_changes_plan.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,14 +17,13 @@ using namespace kh;
 struct kh_map_changes
 {
   kh_map_view view;                    // the map: a copy of the struct, the cells borrowed
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  DeviceWork work;                     // the stream, the events around a call's first kernel, a call's tables and answers
+  hipEvent_t ev[2] = {nullptr, nullptr};       // a diff's third and fourth event
   ChangeLayer layer = {nullptr, nullptr};
   uint8_t * d_codes = nullptr;         // the last diff's codes ...
   uint8_t * d_patched = nullptr;       // ... and patched cells, both on the strided window
   int32_t * d_unit = nullptr;          // the changed-cell list's units: change_units() + 1 words
   unsigned long long * d_counts = nullptr;     // kChangeCodes
-  uint8_t * d_work = nullptr; size_t cap_work = 0;     // a call's tables and answers (bytes)
   bool has_diff = false;
   uint64_t bound = 0;                  // no cell of the layer holds more (map_changes_plan.hpp)
   int64_t scans = 0, beams = 0;        // observed since the last clear
@@ -36,7 +35,7 @@ namespace
 {
 int failed(kh_map_changes * c, const char * who)
 {
-  (void)hipStreamSynchronize(c->stream);
+  (void)hipStreamSynchronize(c->work.stream);
   set_error(std::string(who) + ": " + hipGetErrorString(hipGetLastError()));
   return KH_ERR_HIP;
 }
@@ -58,8 +57,8 @@ int enter(kh_map_changes * c)
 
 int zero_layer(kh_map_changes * c)
 {
-  if (hipMemsetAsync(c->layer.pass, 0, c->size() * 4, c->stream) != hipSuccess || hipMemsetAsync(c->layer.hits, 0, c->size() * 4, c->stream) != hipSuccess ||
-    hipStreamSynchronize(c->stream) != hipSuccess)
+  if (hipMemsetAsync(c->layer.pass, 0, c->size() * 4, c->work.stream) != hipSuccess || hipMemsetAsync(c->layer.hits, 0, c->size() * 4, c->work.stream) != hipSuccess ||
+    hipStreamSynchronize(c->work.stream) != hipSuccess)
   {
     return failed(c, "kh_map_changes_clear");
   }
@@ -81,16 +80,14 @@ int kh_map_changes_create(const kh_map_view * view, kh_map_changes ** out)
   c->view = *view;
   const size_t size = c->size();
   const size_t unit_bytes = static_cast<size_t>(change_units(view->width, view->height) + 1) * sizeof(int32_t);
-  if (hipSetDevice(view->device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-    hipEventCreate(&c->ev[0]) != hipSuccess || hipEventCreate(&c->ev[1]) != hipSuccess || hipEventCreate(&c->ev[2]) != hipSuccess ||
-    hipEventCreate(&c->ev[3]) != hipSuccess ||
+  if (!work_open(c->work, view->device) || hipEventCreate(&c->ev[0]) != hipSuccess || hipEventCreate(&c->ev[1]) != hipSuccess ||
     hipMalloc(reinterpret_cast<void **>(&c->layer.pass), size * 4) != hipSuccess ||
     hipMalloc(reinterpret_cast<void **>(&c->layer.hits), size * 4) != hipSuccess ||
     hipMalloc(reinterpret_cast<void **>(&c->d_codes), size) != hipSuccess || hipMalloc(reinterpret_cast<void **>(&c->d_patched), size) != hipSuccess ||
     hipMalloc(reinterpret_cast<void **>(&c->d_unit), unit_bytes) != hipSuccess ||
     hipMalloc(reinterpret_cast<void **>(&c->d_counts), kChangeCodes * sizeof(unsigned long long)) != hipSuccess ||
-    hipMemsetAsync(c->d_codes, 0, size, c->stream) != hipSuccess || hipMemsetAsync(c->d_patched, 0, size, c->stream) != hipSuccess ||
-    hipMemsetAsync(c->d_unit, 0, unit_bytes, c->stream) != hipSuccess || zero_layer(c) != KH_OK)
+    hipMemsetAsync(c->d_codes, 0, size, c->work.stream) != hipSuccess || hipMemsetAsync(c->d_patched, 0, size, c->work.stream) != hipSuccess ||
+    hipMemsetAsync(c->d_unit, 0, unit_bytes, c->work.stream) != hipSuccess || zero_layer(c) != KH_OK)
   {
     (void)hipGetLastError();
     set_error("kh_map_changes_create: HIP allocation failed");
@@ -105,13 +102,13 @@ void kh_map_changes_destroy(kh_map_changes * c)
 {
   if (!c) {return;}
   (void)hipSetDevice(c->view.device);
-  if (c->stream) {(void)hipStreamSynchronize(c->stream);}
+  if (c->work.stream) {(void)hipStreamSynchronize(c->work.stream);}
   (void)hipFree(c->layer.pass); (void)hipFree(c->layer.hits); (void)hipFree(c->d_codes); (void)hipFree(c->d_patched);
-  (void)hipFree(c->d_unit); (void)hipFree(c->d_counts); (void)hipFree(c->d_work);
+  (void)hipFree(c->d_unit); (void)hipFree(c->d_counts);
   for (hipEvent_t e : c->ev) {
     if (e) {(void)hipEventDestroy(e);}
   }
-  if (c->stream) {(void)hipStreamDestroy(c->stream);}
+  work_close(c->work);
   delete c;
 }
 
@@ -126,8 +123,8 @@ int kh_map_changes_decay(kh_map_changes * c, int32_t shift)
   if (!changes_shift_ok(shift)) {set_error("kh_map_changes_decay: 1 <= shift <= 31 is required"); return KH_ERR_INVALID_ARG;}
   const int rc = enter(c);
   if (rc) {return rc;}
-  map_decay(c->stream, c->view, c->layer, shift);
-  if (hipStreamSynchronize(c->stream) != hipSuccess) {return failed(c, "kh_map_changes_decay");}
+  map_decay(c->work.stream, c->view, c->layer, shift);
+  if (hipStreamSynchronize(c->work.stream) != hipSuccess) {return failed(c, "kh_map_changes_decay");}
   c->bound = changes_bound_decayed(c->bound, shift);
   return KH_OK;
 }
@@ -139,55 +136,36 @@ int kh_map_changes_observe(kh_map_changes * c, const kh_laser * laser, int32_t n
     set_error("kh_map_changes_observe: a laser of numbers, ranges, finite poses, n_scans >= 1 and 0 <= end_tolerance <= 4 are required");
     return KH_ERR_INVALID_ARG;
   }
-  const int rc = enter(c);
+  int rc = enter(c);
   if (rc) {return rc;}
-  const int32_t walk = changes_observe_walk(*laser, n_scans, sensor_poses, c->view.anchor[0], c->view.anchor[1], c->view.scale);
-  if (walk != 0) {
-    set_error(walk == 1 ? "kh_map_changes_observe: the laser's range_threshold * scale must stay below 2^20 cells of this map" :
-      "kh_map_changes_observe: a pose lies more than 2^30 cells from the map's anchor");
+  const FitInputs walk = changes_observe_walk(*laser, n_scans, sensor_poses, c->view.anchor[0], c->view.anchor[1], c->view.scale);
+  if (walk.failed) {
+    set_error(fit_inputs_text(walk, "kh_map_changes_observe", "the laser's range_threshold * scale must stay below 2^20 cells of this map",
+      "a pose lies more than 2^30 cells from the map's anchor"));
     return KH_ERR_INVALID_ARG;
   }
   const size_t ns = static_cast<size_t>(n_scans), nb = static_cast<size_t>(laser->n_beams);
-  const int64_t blocks = ((static_cast<int64_t>(laser->n_beams) + 63) / 64 + 3) / 4 * n_scans;
   uint64_t bound_after = 0;
-  if (blocks > INT32_MAX || !changes_bound_after(c->bound, n_scans, laser->n_beams, &bound_after)) {
+  if (blocks_per_pose(laser->n_beams, n_scans) == 0 || !changes_bound_after(c->bound, n_scans, laser->n_beams, &bound_after)) {
     set_error("kh_map_changes_observe: a counter of the layer could pass 2^32 - 1 (decay or clear the layer first)");
     return KH_ERR_INVALID_ARG;
   }
-  // the sensors, the ranges, the points, then the labels: every part a multiple of 8 bytes
-  const size_t sensor_bytes = ns * 2 * sizeof(double), range_bytes = ns * nb * sizeof(double), point_bytes = 2 * range_bytes;
-  const size_t label_bytes = ns * nb * 2 * sizeof(int32_t);
-  const size_t bytes = sensor_bytes + range_bytes + point_bytes + label_bytes;
   std::vector<double> points(2 * nb * ns), sensor_xy(2 * ns);
-  host_parallel_for_wide(ns, [&](size_t k) {
-    kh_scan_points(ranges + nb * k, laser->n_beams, sensor_poses + 3 * k, laser->minimum_angle, laser->angular_resolution, &points[2 * nb * k]);
-    sensor_xy[2 * k] = sensor_poses[3 * k]; sensor_xy[2 * k + 1] = sensor_poses[3 * k + 1];
-  });
-  if (!grow_device(c->stream, reinterpret_cast<void **>(&c->d_work), &c->cap_work, bytes, bytes + bytes / 2)) {
-    set_error("kh_map_changes_observe: table allocation failed");
-    return KH_ERR_HIP;
-  }
-  uint8_t * const d_sensors = c->d_work, * const d_ranges = d_sensors + sensor_bytes, * const d_points = d_ranges + range_bytes;
-  uint8_t * const d_labels = d_points + point_bytes;
-  if (hipMemcpyAsync(d_sensors, sensor_xy.data(), sensor_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-    hipMemcpyAsync(d_ranges, ranges, range_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-    hipMemcpyAsync(d_points, points.data(), point_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-  {
-    return failed(c, "kh_map_changes_observe");
-  }
-  (void)hipEventRecord(c->ev[0], c->stream);
-  map_observe(c->stream, c->view, c->layer, reinterpret_cast<const double *>(d_ranges), reinterpret_cast<const double *>(d_points),
-    reinterpret_cast<const double *>(d_sensors), n_scans, laser->n_beams, laser->range_threshold, laser->minimum_range, laser->maximum_range,
-    end_tolerance, reinterpret_cast<int32_t *>(d_labels));
-  (void)hipEventRecord(c->ev[1], c->stream);
-  // (from here on the layer has changed: the bound moves whatever becomes of the download)
-  c->bound = bound_after; c->scans += n_scans; c->beams += static_cast<int64_t>(ns * nb);
-  if ((labels && hipMemcpyAsync(labels, d_labels, label_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-    hipStreamSynchronize(c->stream) != hipSuccess)
-  {
-    return failed(c, "kh_map_changes_observe");
-  }
-  c->observe_ms += between(c->ev[0], c->ev[1]);
+  scan_points_at(ranges, nb, laser->n_beams, laser->minimum_angle, laser->angular_resolution, ns, sensor_poses, points.data(), sensor_xy.data());
+  // the sensors, the ranges, the points, then the labels: every part a multiple of 8 bytes
+  Part parts[] = {{sensor_xy.data(), ns * 2 * sizeof(double)}, {ranges, ns * nb * sizeof(double)}, {points.data(), ns * nb * 2 * sizeof(double)},
+    {nullptr, ns * nb * 2 * sizeof(int32_t)}};
+  rc = work_stage(c->work, "kh_map_changes_observe", "table", true, parts);
+  if (rc) {return rc;}
+  double ms = 0.0;
+  rc = work_run(c->work, "kh_map_changes_observe", [&] {
+    map_observe(c->work.stream, c->view, c->layer, parts[1].as<const double>(), parts[2].as<const double>(), parts[0].as<const double>(), n_scans,
+      laser->n_beams, laser->range_threshold, laser->minimum_range, laser->maximum_range, end_tolerance, parts[3].as<int32_t>());
+    // (from here on the layer has changed: the bound moves whatever becomes of the download)
+    c->bound = bound_after; c->scans += n_scans; c->beams += static_cast<int64_t>(ns * nb);
+  }, labels ? &parts[3] : nullptr, labels, &ms);
+  if (rc) {return rc;}
+  c->observe_ms += ms;
   return KH_OK;
 }
 
@@ -202,41 +180,41 @@ int kh_map_changes_diff(kh_map_changes * c, uint32_t min_pass_through, double oc
   const int rc = enter(c);
   if (rc) {return rc;}
   const size_t list_bytes = static_cast<size_t>(cap) * 3 * sizeof(int32_t);
-  if (!grow_device(c->stream, reinterpret_cast<void **>(&c->d_work), &c->cap_work, list_bytes, list_bytes)) {
+  if (!grow_device(c->work.stream, reinterpret_cast<void **>(&c->work.d), &c->work.cap, list_bytes, list_bytes)) {
     set_error("kh_map_changes_diff: list allocation failed");
     return KH_ERR_HIP;
   }
-  int32_t * const d_list = reinterpret_cast<int32_t *>(c->d_work);
+  int32_t * const d_list = reinterpret_cast<int32_t *>(c->work.d);
   const int64_t n_units = change_units(c->view.width, c->view.height);
   unsigned long long counts[kChangeCodes] = {0, 0, 0, 0, 0, 0};
   int32_t total = 0;
-  if (hipMemsetAsync(c->d_counts, 0, sizeof(counts), c->stream) != hipSuccess) {return failed(c, "kh_map_changes_diff");}
-  (void)hipEventRecord(c->ev[0], c->stream);
-  map_diff(c->stream, c->view, c->layer, min_pass_through, occupancy_threshold, c->d_codes, c->d_patched, c->d_counts);
-  (void)hipEventRecord(c->ev[1], c->stream);
-  map_changed_cells(c->stream, c->view, c->d_codes, c->d_unit, d_list, cap);
-  (void)hipEventRecord(c->ev[2], c->stream);
+  if (hipMemsetAsync(c->d_counts, 0, sizeof(counts), c->work.stream) != hipSuccess) {return failed(c, "kh_map_changes_diff");}
+  (void)hipEventRecord(c->work.ev[0], c->work.stream);
+  map_diff(c->work.stream, c->view, c->layer, min_pass_through, occupancy_threshold, c->d_codes, c->d_patched, c->d_counts);
+  (void)hipEventRecord(c->work.ev[1], c->work.stream);
+  map_changed_cells(c->work.stream, c->view, c->d_codes, c->d_unit, d_list, cap);
+  (void)hipEventRecord(c->ev[0], c->work.stream);
   c->has_diff = true;
-  if (hipMemcpyAsync(counts, c->d_counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-    hipMemcpyAsync(&total, c->d_unit + n_units, sizeof(total), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-    hipStreamSynchronize(c->stream) != hipSuccess)
+  if (hipMemcpyAsync(counts, c->d_counts, sizeof(counts), hipMemcpyDeviceToHost, c->work.stream) != hipSuccess ||
+    hipMemcpyAsync(&total, c->d_unit + n_units, sizeof(total), hipMemcpyDeviceToHost, c->work.stream) != hipSuccess ||
+    hipStreamSynchronize(c->work.stream) != hipSuccess)
   {
     return failed(c, "kh_map_changes_diff");
   }
   // (the list's length is known only now: the second copy takes what was written and no more)
   const int32_t listed = std::min(total, cap);
-  if (listed > 0 && hipMemcpyAsync(cells, d_list, static_cast<size_t>(listed) * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
+  if (listed > 0 && hipMemcpyAsync(cells, d_list, static_cast<size_t>(listed) * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, c->work.stream) != hipSuccess) {
     return failed(c, "kh_map_changes_diff");
   }
-  (void)hipEventRecord(c->ev[3], c->stream);
-  if (hipStreamSynchronize(c->stream) != hipSuccess) {return failed(c, "kh_map_changes_diff");}
+  (void)hipEventRecord(c->ev[1], c->work.stream);
+  if (hipStreamSynchronize(c->work.stream) != hipSuccess) {return failed(c, "kh_map_changes_diff");}
   out->n_unobserved = static_cast<int64_t>(counts[KH_CELL_UNOBSERVED]); out->n_confirmed = static_cast<int64_t>(counts[KH_CELL_CONFIRMED]);
   out->n_appeared = static_cast<int64_t>(counts[KH_CELL_APPEARED]); out->n_vanished = static_cast<int64_t>(counts[KH_CELL_VANISHED]);
   out->n_discovered_occupied = static_cast<int64_t>(counts[KH_CELL_DISCOVERED_OCCUPIED]);
   out->n_discovered_free = static_cast<int64_t>(counts[KH_CELL_DISCOVERED_FREE]);
   out->n_changed = total; out->n_listed = listed;
   out->scans_observed = c->scans; out->beams_observed = c->beams; out->observe_kernel_ms = c->observe_ms;
-  out->diff_kernel_ms = between(c->ev[0], c->ev[1]); out->list_kernel_ms = between(c->ev[1], c->ev[2]); out->download_ms = between(c->ev[2], c->ev[3]);
+  out->diff_kernel_ms = between(c->work.ev[0], c->work.ev[1]); out->list_kernel_ms = between(c->work.ev[1], c->ev[0]); out->download_ms = between(c->ev[0], c->ev[1]);
   return KH_OK;
 }
 
@@ -245,11 +223,11 @@ int kh_map_changes_read(kh_map_changes * c, uint32_t * pass, uint32_t * hits, ui
   const int rc = enter(c);
   if (rc) {return rc;}
   const size_t size = c->size();
-  if ((pass && hipMemcpyAsync(pass, c->layer.pass, size * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-    (hits && hipMemcpyAsync(hits, c->layer.hits, size * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-    (codes && hipMemcpyAsync(codes, c->d_codes, size, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-    (patched && hipMemcpyAsync(patched, c->d_patched, size, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-    hipStreamSynchronize(c->stream) != hipSuccess)
+  if ((pass && hipMemcpyAsync(pass, c->layer.pass, size * 4, hipMemcpyDeviceToHost, c->work.stream) != hipSuccess) ||
+    (hits && hipMemcpyAsync(hits, c->layer.hits, size * 4, hipMemcpyDeviceToHost, c->work.stream) != hipSuccess) ||
+    (codes && hipMemcpyAsync(codes, c->d_codes, size, hipMemcpyDeviceToHost, c->work.stream) != hipSuccess) ||
+    (patched && hipMemcpyAsync(patched, c->d_patched, size, hipMemcpyDeviceToHost, c->work.stream) != hipSuccess) ||
+    hipStreamSynchronize(c->work.stream) != hipSuccess)
   {
     return failed(c, "kh_map_changes_read");
   }
@@ -270,19 +248,17 @@ int kh_map_changes_view(kh_map_changes * c, kh_map_view * out)
 int kh_map_changes_read_nav(kh_map_changes * c, int8_t * out)
 {
   if (!out) {return KH_ERR_INVALID_ARG;}
-  const int rc = enter(c);
+  int rc = enter(c);
   if (rc) {return rc;}
   if (!c->has_diff) {set_error("kh_map_changes_read_nav: no diff yet"); return KH_ERR_NOT_FOUND;}
-  const size_t total = static_cast<size_t>(c->view.width) * static_cast<size_t>(c->view.height), bytes = (total + 3) / 4 * 4;
-  if (!grow_device(c->stream, reinterpret_cast<void **>(&c->d_work), &c->cap_work, bytes, bytes)) {
-    set_error("kh_map_changes_read_nav: output allocation failed");
-    return KH_ERR_HIP;
-  }
-  cells_to_nav(c->stream, c->d_patched, c->view.width, c->view.height, c->view.width_step, reinterpret_cast<uint32_t *>(c->d_work));
-  if (hipMemcpyAsync(out, c->d_work, total, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
-    return failed(c, "kh_map_changes_read_nav");
-  }
-  return KH_OK;
+  const size_t total = static_cast<size_t>(c->view.width) * static_cast<size_t>(c->view.height);
+  Part parts[] = {{nullptr, (total + 3) / 4 * 4}};           // (whole dwords are written ...
+  rc = work_stage(c->work, "kh_map_changes_read_nav", "output", false, parts);
+  if (rc) {return rc;}
+  parts[0].bytes = total;                                     // ... and the values downloaded)
+  return work_run(c->work, "kh_map_changes_read_nav", [&] {
+    cells_to_nav(c->work.stream, c->d_patched, c->view.width, c->view.height, c->view.width_step, parts[0].as<uint32_t>());
+  }, &parts[0], out, nullptr);
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "map_localize_plan.hpp"  // fit_laser_ok, fit_pose_ok
+#include "map_localize_plan.hpp"  // fit_inputs_check
 
 namespace kh
 {
@@ -41,14 +41,11 @@ inline bool changes_observe_args_ok(const kh_laser * laser, int32_t n_scans, con
   return true;
 }
 
-// ... and what depends on the view: kh_map_fit's two tests of the walk length (0 = fine, 1 = the laser, 2 = a pose)
-inline int32_t changes_observe_walk(const kh_laser & laser, int32_t n_scans, const double * sensor_poses, double ax, double ay, double scale)
+// ... and what depends on the view: kh_map_fit's check of the walk length (fit_inputs_check)
+inline FitInputs changes_observe_walk(const kh_laser & laser, int32_t n_scans, const double * sensor_poses, double ax, double ay, double scale)
 {
-  if (!fit_laser_ok(laser.range_threshold, laser.minimum_range, laser.maximum_range, scale)) {return 1;}
-  for (int32_t k = 0; k < n_scans; ++k) {
-    if (!fit_pose_ok(sensor_poses + 3 * static_cast<int64_t>(k), ax, ay, scale)) {return 2;}
-  }
-  return 0;
+  return fit_inputs_check(laser.range_threshold, laser.minimum_range, laser.maximum_range, laser.minimum_angle, laser.angular_resolution,
+      static_cast<size_t>(n_scans), sensor_poses, ax, ay, scale);
 }
 
 inline bool changes_diff_args_ok(double occupancy_threshold, const int32_t * cells, int32_t cap, const void * out)

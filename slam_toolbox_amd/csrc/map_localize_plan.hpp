@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "live_map_plan.hpp"     // floor_div
@@ -86,6 +87,33 @@ inline bool fit_pose_ok(const double pose[3], double ax, double ay, double scale
   if (!std::isfinite(pose[0]) || !std::isfinite(pose[1]) || !std::isfinite(pose[2])) {return false;}
   const double cx = (pose[0] - ax) * scale, cy = (pose[1] - ay) * scale;
   return std::fabs(cx) <= kMaxFitCell && std::fabs(cy) <= kMaxFitCell;
+}
+
+// The laser and pose check of every call that walks beams on a map view: the laser (fit_laser_ok, and angles that are numbers), then
+// pose 0 .. n_poses - 1 of `poses` (3 doubles each; fit_pose_ok).  Which input failed and, for a pose, which one.
+enum : int32_t {kFitInputsOk = 0, kFitInputsLaser = 1, kFitInputsPose = 2};
+struct FitInputs {int32_t failed; int32_t pose;};
+inline FitInputs fit_inputs_check(double range_threshold, double min_range, double max_range, double min_angle, double angular_resolution,
+  size_t n_poses, const double * poses, double ax, double ay, double scale)
+{
+  if (!fit_laser_ok(range_threshold, min_range, max_range, scale) || !std::isfinite(min_angle) || !std::isfinite(angular_resolution)) {
+    return FitInputs{kFitInputsLaser, -1};
+  }
+  for (size_t k = 0; k < n_poses; ++k) {
+    if (!fit_pose_ok(poses + 3 * k, ax, ay, scale)) {return FitInputs{kFitInputsPose, static_cast<int32_t>(k)};}
+  }
+  return FitInputs{kFitInputsOk, -1};
+}
+// ... and the refusal as the caller's message: "`who`: `laser_words`", or "`who`: `pose_words`" with the pose's index in the place of
+// its '#', if it has one.  The words of the calls that take a view (a handle speaks of its own map in words of its own):
+constexpr const char * kViewLaserWords = "the laser's range_threshold * scale must stay below 2^20 cells, its other fields must be numbers";
+constexpr const char * kViewPoseWords = "pose # is not finite or lies more than 2^30 cells from the anchor";
+inline std::string fit_inputs_text(const FitInputs & f, const char * who, const char * laser_words, const char * pose_words)
+{
+  std::string words = f.failed == kFitInputsLaser ? laser_words : pose_words;
+  const size_t at = f.failed == kFitInputsPose ? words.find('#') : std::string::npos;
+  if (at != std::string::npos) {words.replace(at, 1, std::to_string(f.pose));}
+  return std::string(who) + ": " + words;
 }
 
 // the six counters -> kh_merge_fit_t

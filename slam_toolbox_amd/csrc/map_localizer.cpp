@@ -35,9 +35,7 @@ int match_poses(kh_map_localizer * loc, kh_matcher * matcher, const double * ran
   for (size_t at = 0; at < n; at += piece) {
     const size_t np = std::min(piece, n - at);
     points.resize(2 * nb * np); q.resize(np); status.assign(np, KH_OK);
-    host_parallel_for_wide(np, [&](size_t j) {
-      kh_scan_points(ranges, loc->laser.n, poses + 3 * (at + j), loc->laser.min_angle, loc->laser.ang_res, &points[2 * nb * j]);
-    });
+    scan_points_at(ranges, 0, loc->laser.n, loc->laser.min_angle, loc->laser.ang_res, np, poses + 3 * at, points.data(), nullptr);
     for (size_t j = 0; j < np; ++j) {
       q[j].n = loc->laser.n; q[j].ranges = ranges; q[j].points_xy = &points[2 * nb * j]; q[j].device_points_xy = nullptr;
       std::copy(poses + 3 * (at + j), poses + 3 * (at + j) + 3, q[j].sensor_pose);
@@ -69,22 +67,17 @@ int localizer_fit_counts(kh_map_localizer * loc, const double * ranges, size_t n
   if (!kernel_ms) {kernel_ms = &unused_ms;}
   *kernel_ms = 0.0;
   if (n == 0) {return KH_OK;}
-  if (!fit_laser_ok(loc->laser.range_threshold, loc->laser.min_range, loc->laser.max_range, loc->view.scale)) {
-    set_error("map localizer: the laser's range_threshold * scale must stay below 2^20 cells of this map");
+  // (the angles of a localizer's laser are judged nowhere, here neither: 0 stands for them)
+  const FitInputs inputs = fit_inputs_check(loc->laser.range_threshold, loc->laser.min_range, loc->laser.max_range, 0.0, 0.0, n, poses,
+      loc->view.anchor[0], loc->view.anchor[1], loc->view.scale);
+  if (inputs.failed) {
+    set_error(fit_inputs_text(inputs, "map localizer", "the laser's range_threshold * scale must stay below 2^20 cells of this map",
+      "a matched pose is not finite or lies more than 2^30 cells from the map's anchor"));
     return KH_ERR_INVALID_ARG;
   }
   const size_t nb = static_cast<size_t>(loc->laser.n);
   std::vector<double> points(2 * nb * n), sensor_xy(2 * n);
-  for (size_t k = 0; k < n; ++k) {
-    if (!fit_pose_ok(poses + 3 * k, loc->view.anchor[0], loc->view.anchor[1], loc->view.scale)) {
-      set_error("map localizer: a matched pose is not finite or lies more than 2^30 cells from the map's anchor");
-      return KH_ERR_INVALID_ARG;
-    }
-    sensor_xy[2 * k] = poses[3 * k]; sensor_xy[2 * k + 1] = poses[3 * k + 1];
-  }
-  host_parallel_for_wide(n, [&](size_t k) {
-    kh_scan_points(ranges, loc->laser.n, poses + 3 * k, loc->laser.min_angle, loc->laser.ang_res, &points[2 * nb * k]);
-  });
+  scan_points_at(ranges, 0, loc->laser.n, loc->laser.min_angle, loc->laser.ang_res, n, poses, points.data(), sensor_xy.data());
   const int rc = map_fit_counts(loc->work, loc->view, loc->laser.n, ranges, static_cast<int32_t>(n), points.data(), sensor_xy.data(),
       loc->laser.range_threshold, loc->laser.min_range, loc->laser.max_range, counts, kernel_ms);
   if (rc) {return rc;}

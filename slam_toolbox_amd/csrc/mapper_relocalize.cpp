@@ -8,6 +8,7 @@
 #include <thread>
 
 #include "graph_internal.hpp"
+#include "map_localize_plan.hpp"     // heading_of
 #include "mapper_private.hpp"
 
 namespace kh
@@ -18,12 +19,6 @@ namespace
 {
 // what the two matches of one hypothesis answered: coarse / fine mean, covariance, response, and whether the coarse gate was passed
 struct Result {double cm[3], cc[9], cr, fm[3], fc[9], fr; int32_t passed;};
-
-// hypothesis i = seed i / n_headings at heading i % n_headings
-double heading_of(size_t i, int32_t n_headings)
-{
-  return -kPi + static_cast<double>(i % static_cast<size_t>(n_headings)) * (k2Pi / static_cast<double>(n_headings));
-}
 
 // (1) where to try: seeds and their bases, as positions in the store's scan list
 int relocalize_candidates(kh_mapper * m, const kh_relocalize_params * params, std::chrono::steady_clock::time_point t_begin, int32_t n_headings,
@@ -63,9 +58,7 @@ int relocalize_batches(kh_mapper * m, const double * ranges, int32_t n_headings,
       Pose robot; robot.x = seed.corrected.x; robot.y = seed.corrected.y; robot.h = heading_of(i, n_headings);
       put_pose(sensor_at(m->laser, robot), &poses[3 * j]);
     }
-    host_parallel_for_wide(np, [&](size_t j) {
-      kh_scan_points(ranges, m->laser.n, &poses[3 * j], m->laser.min_angle, m->laser.ang_res, &points[2 * nb * j]);
-    });
+    scan_points_at(ranges, 0, m->laser.n, m->laser.min_angle, m->laser.ang_res, np, poses.data(), points.data(), nullptr);
     summary->scans_ms += ms_since(t_scans);
     const auto t_batch = std::chrono::steady_clock::now();
     struct Share

@@ -28,6 +28,15 @@ static int32_t half_kernel_size(double smear, double resolution)   // Mapper.h:1
 // ---- host worker pool: host_pool.hpp ----
 void host_parallel_for(size_t n, const std::function<void(size_t)> & fn) {HostPool::instance().run(n, fn);}
 void host_parallel_for_wide(size_t n, const std::function<void(size_t)> & fn) {HostPool::wide().run(n, fn);}
+void scan_points_at(const double * ranges, size_t ranges_stride, int32_t n_beams, double min_angle, double angular_resolution, size_t n_poses,
+  const double * sensor_poses, double * points, double * sensor_xy)
+{
+  const size_t nb = static_cast<size_t>(n_beams);
+  host_parallel_for_wide(n_poses, [&](size_t k) {
+    kh_scan_points(ranges + ranges_stride * k, n_beams, sensor_poses + 3 * k, min_angle, angular_resolution, points + 2 * nb * k);
+    if (sensor_xy) {sensor_xy[2 * k] = sensor_poses[3 * k]; sensor_xy[2 * k + 1] = sensor_poses[3 * k + 1];}
+  });
+}
 
 // the geometry and scratch pointers of one slot's rasterisation job (the scan list and the order-dependent rule's tables are the
 // caller's)

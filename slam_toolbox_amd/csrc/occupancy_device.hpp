@@ -1,6 +1,8 @@
-// What the occupancy module shares between occupancy.hip (the kernels and their launchers) and the host files that feed it:
-// mapper_views.cpp (kh_mapper_build_map), merge.cpp (kh_merge_build), live_map.cpp (kh_live_map_*).  Not part of the public ABI
-// (include/karto_hip.h).  The live map's lattice, window and log are stated in DESIGN.md section 7b, the map feed's tiles in 7c.
+// What the occupancy module shares between its kernel files (occupancy.hip, occupancy_live.hip, occupancy_map.hip,
+// occupancy_changes.hip: the kernels and their launchers) and the host files that feed them: mapper_views.cpp (kh_mapper_build_map),
+// merge.cpp (kh_merge_build), live_map.cpp (kh_live_map_*), map_localizer.cpp, map_changes.cpp, map_align.cpp.  Needs no HIP header:
+// the CPU programs of tests/ include it.  Not part of the public ABI (include/karto_hip.h).  The live map's lattice, window and log
+// are stated in DESIGN.md section 7b, the map feed's tiles in 7c.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -43,6 +45,16 @@ inline void grid_dimensions(const Box & box, double resolution, int32_t * width,
 
 // the size cap of an occupancy grid and of a live window: (width + 7) * height cells stay below 2^31 - 4096, stated without the product
 inline bool grid_too_large(int64_t width, int64_t height) {return height > 0 && width + 7 > ((1ll << 31) - 4096) / height;}
+
+// ---- the launch sizes of the kernels that give a wave a run of 64 beams, and a workgroup four waves ----
+inline unsigned blocks_of_runs(int32_t n_scans, int32_t runs_per_scan) {return static_cast<unsigned>((static_cast<int64_t>(n_scans) * runs_per_scan + 3) / 4);}
+// ... and of those whose workgroups hold waves of ONE pose (scan): the workgroups of a pose of n_beams >= 1 beams, or 0 where those of
+// n_poses poses are more than one launch takes
+inline int32_t blocks_per_pose(int32_t n_beams, int32_t n_poses)
+{
+  const int64_t blocks = ((static_cast<int64_t>(n_beams) + 63) / 64 + 3) / 4;
+  return blocks * n_poses > INT32_MAX ? 0 : static_cast<int32_t>(blocks);
+}
 
 // ---- the records of the trace kernels ----
 // one scan whose readings are resident on the grid's device (k_occ_trace_resident)
@@ -100,6 +112,10 @@ struct MapWindow
   int32_t ox, oy, width, height, ws;
   double ax, ay, scale;
 };
+inline MapWindow window_of(const kh_map_view & v)
+{
+  return MapWindow{static_cast<const uint8_t *>(v.device_cells), v.ox, v.oy, v.width, v.height, v.width_step, v.anchor[0], v.anchor[1], v.scale};
+}
 
 // what the live map classifies a scan of its mapper by: the sensor pose; and the scan's box (the default anchor)
 struct SensorView
@@ -150,7 +166,7 @@ struct NavFeedJob
   uint32_t * packed;         // kTileWords per slot: the tile's new nav values, row-major
 };
 
-// ---- the launchers (occupancy.hip) ----
+// ---- the launchers of a whole grid (occupancy.hip) ----
 // the stream the grid's kernels run on: uploads a caller queues there are in place before the next trace reads them
 void * occupancy_stream(kh_occupancy * g);
 // AddScan for n_scans scans of n_beams beams whose readings are resident on the grid's device.  Returns after the trace (and
@@ -167,6 +183,10 @@ int occupancy_add_merged(kh_occupancy * g, int32_t n_scans, const MergeScan * sc
 // kernel has finished and the sums are in `out`.
 int occupancy_fit_merged(kh_occupancy * g, int32_t n_candidates, const FitCandidate * candidates, const FitSensor * sensors, int32_t n_scans,
   const ResidentScan * scans, int32_t n_beams, double range_threshold, double min_range, double max_range, uint64_t * out, double * kernel_ms);
+// k_occ_to_nav of any strided cells on `stream`: d_out takes width * height values, rounded up to a dword
+void cells_to_nav(void * stream, const uint8_t * d_cells, int32_t width, int32_t height, int32_t ws, uint32_t * d_out);
+
+// ---- the launchers of a live map (occupancy_live.hip) ----
 // n_records records on `stream`; counters[0] += lines walked, counters[1] += kept beams of MOVE records that were left alone
 void live_trace_delta(void * stream, const LiveWindow & w, double anchor_x, double anchor_y, double scale, const DeltaRecord * d_records,
   int32_t n_records, int32_t n_beams, double range_threshold, double min_range, double max_range, int32_t * d_log,
@@ -178,8 +198,8 @@ void live_update_cells(void * stream, const LiveWindow & w, int32_t x0, int32_t 
 // particular order.  The caller has set *job.count to 0 and holds room for every tile of the job.
 void nav_feed(void * stream, const NavFeedJob & job);
 
-// ---- a map view's two kernels (kh_map_seeds, kh_map_fit, kh_map_localizer_*) ----
-// a stream, two events and one growing device buffer on a device: what the two launchers below work with.  nullptr = it could not be made.
+// ---- a map view's kernels (occupancy_map.hip; kh_map_seeds, kh_map_fit, kh_map_localizer_*) ----
+// a stream, two events and one growing device buffer on a device: what the launchers below work with.  nullptr = it could not be made.
 struct MapWork;
 MapWork * map_work_create(int32_t device);
 void map_work_destroy(MapWork * w);
@@ -190,11 +210,11 @@ int map_view_check(const kh_map_view * v);
 int map_seed_blocks(MapWork * w, const kh_map_view & v, int32_t pitch, int64_t bx0, int64_t by0, int64_t nbx, int64_t nby, int32_t * local,
   double * kernel_ms);
 // k_map_fit: n_beams ranges, per pose 2 * n_beams point readings and the sensor's (x, y); counts takes kFitCounters sums per pose.
-// The caller has checked the poses and the laser (fit_pose_ok, fit_laser_ok).
+// The caller has checked the laser and the poses (fit_inputs_check).
 int map_fit_counts(MapWork * w, const kh_map_view & v, int32_t n_beams, const double * ranges, int32_t n_poses, const double * points,
   const double * sensor_xy, double range_threshold, double min_range, double max_range, uint64_t * counts, double * kernel_ms);
 
-// ---- the expected scan of a map (kh_map_raycast) ----
+// ---- the expected scan of a map (occupancy_map.hip; kh_map_raycast) ----
 // The cells of TraceLine((x0, y0), (x1, y1)) OUTWARD from (x0, y0), one per step s = 0 .. length.  TraceLine walks its long axis
 // upward, so where (x0, y0) has the larger long coordinate it starts at the far end -- and a line traced from the other end is not the
 // mirror image: half-way between two rows the walk steps (2 error >= dx), the mirrored walk would step one cell later.  Its error
@@ -233,8 +253,8 @@ struct RayWalk
 struct alignas(16) RayCell {int32_t i, j, steps, code;};
 static_assert(sizeof(RayCell) == 16, "one int4 per beam");
 // k_map_raycast: per pose the 2 * n_beams far points (kh_scan_points of a scan whose readings are all range_threshold) and the sensor's
-// (x, y); out takes n_poses * n_beams answers, pose-major.  The caller has checked the poses and the laser (fit_pose_ok, fit_laser_ok)
-// and max_unknown >= -1.
+// (x, y); out takes n_poses * n_beams answers, pose-major.  The caller has checked the laser and the poses (fit_inputs_check) and
+// max_unknown >= -1.
 int map_raycast_cells(MapWork * w, const kh_map_view & v, int32_t n_beams, int32_t n_poses, const double * points, const double * sensor_xy,
   int32_t max_unknown, RayCell * out, double * kernel_ms);
 // kh_map_raycast's argument checks but `out` (KH_OK, or KH_ERR_INVALID_ARG and its text), and the call itself on a caller's work
@@ -243,7 +263,7 @@ int map_raycast_check(const kh_map_view * view, const kh_laser * laser, int32_t 
 int map_raycast(MapWork * w, const kh_map_view & v, const kh_laser & laser, int32_t n_poses, const double * sensor_poses, int32_t max_unknown,
   double no_return, kh_ray_t * out, double * kernel_ms);
 
-// ---- a change layer's kernels (kh_map_changes_*; the handle and its buffers: map_changes.cpp) ----
+// ---- a change layer's kernels (occupancy_changes.hip; kh_map_changes_*; the handle and its buffers: map_changes.cpp) ----
 // the layer's two counter grids on the window of its view, row stride the view's width_step
 struct ChangeLayer
 {
@@ -254,8 +274,8 @@ enum : int32_t {kChangeCodes = 6};                    // KH_CELL_UNOBSERVED .. K
 // the units of the changed-cell list: 64 consecutive cells of a row of the window
 inline int64_t change_units(int32_t width, int32_t height) {return (static_cast<int64_t>(width) + 63) / 64 * height;}
 // k_map_observe on `stream`: n_scans scans of n_beams beams -- d_ranges n_scans * n_beams, d_points 2 per beam (kh_scan_points at the
-// scan's pose), d_sensors 2 per scan -- add to the layer; d_labels takes 2 int32 per beam.  The caller has checked the poses and the
-// laser (fit_pose_ok, fit_laser_ok) and 0 <= tolerance <= kMaxEndTolerance.
+// scan's pose), d_sensors 2 per scan -- add to the layer; d_labels takes 2 int32 per beam.  The caller has checked the laser and the
+// poses (fit_inputs_check), blocks_per_pose(n_beams, n_scans) and 0 <= tolerance <= kMaxEndTolerance.
 void map_observe(void * stream, const kh_map_view & v, const ChangeLayer & layer, const double * d_ranges, const double * d_points,
   const double * d_sensors, int32_t n_scans, int32_t n_beams, double range_threshold, double min_range, double max_range, int32_t tolerance,
   int32_t * d_labels);
@@ -268,8 +288,6 @@ void map_diff(void * stream, const kh_map_view & v, const ChangeLayer & layer, u
 // the cells of code >= 2 in row-major order on `stream`: d_unit holds change_units() + 1 int32 (it ends as the exclusive prefix of the
 // units' counts, the total last); d_list takes (lattice i, lattice j, code) of the first `cap` cells
 void map_changed_cells(void * stream, const kh_map_view & v, const uint8_t * d_codes, int32_t * d_unit, int32_t * d_list, int32_t cap);
-// k_occ_to_nav of any strided cells on `stream`: d_out takes width * height values, rounded up to a dword
-void cells_to_nav(void * stream, const uint8_t * d_cells, int32_t width, int32_t height, int32_t ws, uint32_t * d_out);
 
 #ifdef __HIP__
 // ---- what the module's host files do with the device the same way (absent from a build without HIP: tests/live_map_plan_check.cpp);
@@ -299,6 +317,90 @@ inline hipError_t grow_device_keeping(void ** buf, size_t * have, size_t need, s
   (void)hipFree(*buf);
   *buf = d_new; *have = cap;
   return hipSuccess;
+}
+
+// ---- the launch sequence of the module's timed kernels, stated once (occupancy.hip, occupancy_map.hip, map_changes.cpp): a stream, two events and one
+// growing device buffer; the buffer carved into the parts of a launch and the parts uploaded; the kernel between the two events, the
+// download, the wait, the elapsed time, a failure reported under the caller's name ----
+struct DeviceWork
+{
+  int32_t device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  uint8_t * d = nullptr; size_t cap = 0;               // a launch's tables and answers (bytes)
+};
+
+// false = the stream or an event could not be made (work_close the rest)
+inline bool work_open(DeviceWork & w, int32_t device)
+{
+  w.device = device;
+  return hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking) == hipSuccess &&
+         hipEventCreate(&w.ev[0]) == hipSuccess && hipEventCreate(&w.ev[1]) == hipSuccess;
+}
+
+inline void work_close(DeviceWork & w)
+{
+  (void)hipSetDevice(w.device);
+  if (w.stream) {(void)hipStreamSynchronize(w.stream);}
+  (void)hipFree(w.d);
+  if (w.ev[0]) {(void)hipEventDestroy(w.ev[0]);}
+  if (w.ev[1]) {(void)hipEventDestroy(w.ev[1]);}
+  if (w.stream) {(void)hipStreamDestroy(w.stream);}
+}
+
+// One part of a launch's buffer: `bytes` bytes that begin as a copy of `host`, as zeros (kZeros), or as they are (nullptr: an answer).
+// work_stage fills in `d`.  The parts lie in the order given; every size a multiple of the strictest alignment among them.
+struct Part
+{
+  const void * host;
+  size_t bytes;
+  uint8_t * d = nullptr;
+  template <typename T> T * as() const {return reinterpret_cast<T *>(d);}
+};
+inline const void * const kZeros = &kZeros;
+
+// Grows the buffer to the parts' sum (to half as much again where `spare`: a caller whose launches creep upward), carves it and
+// queues the uploads.  KH_ERR_HIP with "`who`: `what` allocation failed" where the buffer could not be made, with HIP's text for an upload.
+template <size_t N>
+int work_stage(DeviceWork & w, const char * who, const char * what, bool spare, Part (&parts)[N])
+{
+  size_t bytes = 0;
+  for (const Part & p : parts) {bytes += p.bytes;}
+  if (!grow_device(w.stream, reinterpret_cast<void **>(&w.d), &w.cap, bytes, spare ? bytes + bytes / 2 : bytes)) {
+    set_error(std::string(who) + ": " + what + " allocation failed");
+    return KH_ERR_HIP;
+  }
+  uint8_t * at = w.d;
+  for (Part & p : parts) {
+    p.d = at; at += p.bytes;
+    const hipError_t err = p.host == kZeros ? hipMemsetAsync(p.d, 0, p.bytes, w.stream) :
+      p.host ? hipMemcpyAsync(p.d, p.host, p.bytes, hipMemcpyHostToDevice, w.stream) : hipSuccess;
+    if (err != hipSuccess) {
+      (void)hipStreamSynchronize(w.stream);
+      set_error(std::string(who) + ": " + hipGetErrorString(hipGetLastError()));
+      return KH_ERR_HIP;
+    }
+  }
+  return KH_OK;
+}
+
+// launch() between the two events, the download of `answer` (nullptr: none) into `out`, the wait for all of it; *kernel_ms = the
+// time between the events.  A failure is reported under `who`.
+template <typename Launch>
+int work_run(DeviceWork & w, const char * who, Launch launch, const Part * answer, void * out, double * kernel_ms)
+{
+  (void)hipEventRecord(w.ev[0], w.stream);
+  launch();
+  (void)hipEventRecord(w.ev[1], w.stream);
+  const bool copied = !answer || hipMemcpyAsync(out, answer->d, answer->bytes, hipMemcpyDeviceToHost, w.stream) == hipSuccess;
+  if (hipStreamSynchronize(w.stream) != hipSuccess || !copied) {
+    set_error(std::string(who) + ": " + hipGetErrorString(hipGetLastError()));
+    return KH_ERR_HIP;
+  }
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, w.ev[0], w.ev[1]);
+  if (kernel_ms) {*kernel_ms = ms;}
+  return KH_OK;
 }
 #endif
 }  // namespace kh

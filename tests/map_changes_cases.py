@@ -1,4 +1,4 @@
-"""Inputs of the map change layer's kernels (k_map_observe, k_map_diff, k_map_changed, k_map_decay in csrc/occupancy.hip) as plain numpy
+"""Inputs of the map change layer's kernels (k_map_observe, k_map_diff, k_map_changed, k_map_decay in csrc/occupancy_changes.hip) as plain numpy
 data, and the changed world of its end-to-end test.  tests/test_map_changes_gpu.py asks the library and tests/map_changes_rule.py for
 the same cases and compares exactly; tests/test_map_changes_rule_oracle.py checks the changed world's three geometric statements with
 the rule alone."""

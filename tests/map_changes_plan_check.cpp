@@ -74,7 +74,7 @@ int main()
       const double scale = real(in), ax = real(in), ay = real(in);
       const int32_t n_scans = (int32_t)whole(in);
       const std::vector<double> p = poses(in, n_scans);
-      std::printf("%d\n", changes_observe_walk(laser, n_scans, p.data(), ax, ay, scale));
+      std::printf("%d\n", changes_observe_walk(laser, n_scans, p.data(), ax, ay, scale).failed);
     } else if (what == "diffargs") {
       const double threshold = real(in);
       const int32_t cap = (int32_t)whole(in);

@@ -1,4 +1,4 @@
-"""Edge inputs of the map localizer's two kernels (k_map_seeds, k_map_fit in csrc/occupancy.hip) as plain numpy data, and the small
+"""Edge inputs of the map localizer's two kernels (k_map_seeds, k_map_fit in csrc/occupancy_map.hip) as plain numpy data, and the small
 map its end-to-end tests share.  tests/test_map_localize_rule_oracle.py checks on the CPU that every case sits on the edge its name
 says (Case.check, fed with tests/map_localize_rule.py's answer); tests/test_map_seeds_gpu.py and tests/test_map_fit_gpu.py ask the
 library for the same cases and compare exactly.  Scales are powers of two and anchors multiples of the cell where a case needs an

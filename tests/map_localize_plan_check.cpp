@@ -9,6 +9,8 @@
 //                                                      -> rank order | kept | rejected duplicates   (hypothesis indices)
 //   predict (last odometric) (last corrected) (odometric)   -> x y heading of the predicted pose
 //   fitok range_threshold min_range max_range scale ax ay x y heading   -> laser_ok pose_ok
+//   inputs range_threshold min_range max_range min_angle angular_resolution scale ax ay  n (x y heading) * n
+//                                                      -> failed pose | the refusal in the words of a call that takes a view
 //
 // Doubles are read with strtod and printed with %a, so they pass bit for bit.
 #include <cstdio>
@@ -82,6 +84,12 @@ int main()
       double p[3];
       p[0] = real(in); p[1] = real(in); p[2] = real(in);
       std::printf("%d %d\n", fit_laser_ok(rt, lo, hi, scale) ? 1 : 0, fit_pose_ok(p, ax, ay, scale) ? 1 : 0);
+    } else if (what == "inputs") {
+      const double rt = real(in), lo = real(in), hi = real(in), a0 = real(in), da = real(in), scale = real(in), ax = real(in), ay = real(in);
+      std::vector<double> p(3 * static_cast<size_t>(whole(in)));
+      for (double & v : p) {v = real(in);}
+      const FitInputs f = fit_inputs_check(rt, lo, hi, a0, da, p.size() / 3, p.data(), ax, ay, scale);
+      std::printf("%d %d | %s\n", f.failed, f.pose, f.failed ? fit_inputs_text(f, "who", kViewLaserWords, kViewPoseWords).c_str() : "");
     } else {
       std::printf("error: unknown case %s\n", what.c_str());
     }

@@ -1,4 +1,4 @@
-"""Edge inputs of k_map_raycast (csrc/occupancy.hip) as plain numpy data.  tests/test_map_raycast_rule_oracle.py checks on the CPU that
+"""Edge inputs of k_map_raycast (csrc/occupancy_map.hip) as plain numpy data.  tests/test_map_raycast_rule_oracle.py checks on the CPU that
 every case sits on the edge its name says (Case.check, fed with tests/map_raycast_rule.py's answer, arrays with a leading pose axis);
 tests/test_map_raycast_gpu.py asks the library for the same cases and compares exactly.  Views, lasers and the small map are
 tests/map_localize_cases.py's: 0.25 m cells, sensors on cell centres where a case needs an exact cell."""

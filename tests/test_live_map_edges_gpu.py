@@ -1,4 +1,4 @@
-"""GPU: edge inputs of the live map's kernels (k_occ_trace_delta, k_occ_update_rect; csrc/occupancy.hip) through small mappers
+"""GPU: edge inputs of the live map's kernels (k_occ_trace_delta, k_occ_update_rect; csrc/occupancy_live.hip) through small mappers
 that place their scans where the test says (use_scan_matching 0, as tests/test_occupancy_edges_gpu.py feeds kh_mapper_build_map
 through a mapper), compared with tests/live_map_rule.py: dropped and clipped readings, readings on every range gate, an anchor
 inside the map (negative cells, rounding ties), beam counts around the 64-beam run, a single scan added / moved / removed, and 300

@@ -1,4 +1,4 @@
-"""GPU: the map change layer (kh_map_changes_*; k_map_observe, k_map_diff, k_map_changed, k_map_decay in csrc/occupancy.hip) against
+"""GPU: the map change layer (kh_map_changes_*; k_map_observe, k_map_diff, k_map_changed, k_map_decay in csrc/occupancy_changes.hip) against
 tests/map_changes_rule.py, exactly: pass, hits, labels, codes, counts, patched cells, the changed-cell list and its order -- on the
 hand-made views of tests/map_localize_cases.py and tests/map_changes_cases.py, then end to end on the small map: an unchanged world, a
 changed one, and through the map localizer.  After every call the source view's cells are downloaded and must be unchanged."""

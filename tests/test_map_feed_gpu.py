@@ -1,4 +1,4 @@
-"""GPU: the map feed (kh_map_feed_*, slam_toolbox_amd.live_map.MapFeed; k_nav_feed in csrc/occupancy.hip) through small mappers
+"""GPU: the map feed (kh_map_feed_*, slam_toolbox_amd.live_map.MapFeed; k_nav_feed in csrc/occupancy_live.hip) through small mappers
 that place their scans where the test says (tests/test_live_map_edges_gpu.py), against tests/map_feed_rule.py and the occupancy
 oracle.  After EVERY poll (Consumer.poll):
 

@@ -1,4 +1,4 @@
-"""GPU: kh_map_fit (k_map_fit in csrc/occupancy.hip) against tests/map_localize_rule.py on the hand-made views of
+"""GPU: kh_map_fit (k_map_fit in csrc/occupancy_map.hip) against tests/map_localize_rule.py on the hand-made views of
 tests/map_localize_cases.py: the six counters, the derived values and the bits of the score."""
 import ctypes as C
 

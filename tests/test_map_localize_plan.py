@@ -215,3 +215,30 @@ def test_walk_length_guard(check):
         if math.isnan(lo) or math.isnan(hi):
             continue
         assert rule.fit_refused(dict(scale=k, anchor=(ax, ay)), L(rt, lo, hi), (x, y, h)) == (not (laser_ok and pose_ok))
+
+
+def test_laser_and_pose_check(check):
+    """fit_inputs_check and fit_inputs_text: which input a call that walks beams on a view refuses, and in which words."""
+    scale = 20.0
+    good, far = (1.0, 2.0, 0.3), (2.0 ** 30 / scale + 1.0, 2.0, 0.3)
+    laser = (12.0, 0.1, 30.0, -1.5, 0.01)
+    laser_words = "who: the laser's range_threshold * scale must stay below 2^20 cells, its other fields must be numbers"
+    pose_words = "who: pose %d is not finite or lies more than 2^30 cells from the anchor"
+    cases = [(((2 ** 20 - 1) / scale, 0.1, 30.0, -1.5, 0.01), [good, good], (1, -1, laser_words)),       # a bad laser: the walk
+             ((12.0, 0.1, 30.0, math.nan, 0.01), [good], (1, -1, laser_words)),                          # ... an angle that is no number
+             ((12.0, 0.1, 30.0, -1.5, math.inf), [far], (1, -1, laser_words)),                           # ... and the laser is judged first
+             (laser, [good, (1.0, math.nan, 0.3), far], (2, 1, pose_words % 1)),                         # a non-finite pose
+             (laser, [good, good, (1.0, 2.0, math.inf)], (2, 2, pose_words % 2)),
+             (laser, [far, good, good], (2, 0, pose_words % 0)),                                         # beyond 2^30 cells at index 0
+             (laser, [good, good, far], (2, 2, pose_words % 2)),                                         # ... and at the last index
+             (laser, [good] * 11 + [far], (2, 11, pose_words % 11)),                                     # (an index of two digits)
+             (laser, [good, (2.0 ** 30 / scale, -2.0 ** 30 / scale, -3.0)], (0, -1, "")),                # a good input: cells of +-2^30
+             (laser, [], (0, -1, ""))]
+    lines = []
+    for l, poses, _ in cases:
+        lines.append("inputs " + " ".join(hx(v) for v in l) + f" {hx(scale)} {hx(0.0)} {hx(0.0)} {len(poses)} " + " ".join(hx(v) for p in poses for v in p))
+    got = check(lines)
+    for g, (_, _, (failed, pose, text)) in zip(got, cases):
+        head, _, words = g.partition(" | ")
+        assert tuple(int(v) for v in head.split()) == (failed, pose), g
+        assert words.strip() == text, g

@@ -1,4 +1,4 @@
-"""GPU: kh_map_raycast (k_map_raycast in csrc/occupancy.hip) against tests/map_raycast_rule.py on the hand-made views of
+"""GPU: kh_map_raycast (k_map_raycast in csrc/occupancy_map.hip) against tests/map_raycast_rule.py on the hand-made views of
 tests/map_raycast_cases.py, uploaded through kh_device_upload, and on the small map: cells, steps, codes and the bits of the ranges."""
 import ctypes as C
 import math

@@ -1,4 +1,4 @@
-"""GPU: kh_map_seeds (k_map_seeds in csrc/occupancy.hip) against tests/map_localize_rule.py on the hand-made views of
+"""GPU: kh_map_seeds (k_map_seeds in csrc/occupancy_map.hip) against tests/map_localize_rule.py on the hand-made views of
 tests/map_localize_cases.py, uploaded through kh_device_upload, and on the views the library itself hands out (kh_occupancy_view,
 kh_live_map_view after a growth).  Cells and world points are compared exactly."""
 import ctypes as C
