@@ -14,6 +14,11 @@ nearest (index, dist_sq) and the hits per radius, all from tests/near_by_rule.py
 the library's documented rule between equal distances: the lower index).  Equal distances are the SUBJECT here, so the
 best_two_differ / hits_are_distinct guards of the random test are not applied.
 
+The capped launch: k_near_by_radius runs on min(ceil(n / 256), 256) workgroups of 256, so its strided loop takes a second trip from
+65 537 vertices on (NEAR_TRIP = 65 536); the size, tie and radius cases hold 1281 vertices at the most, near_trip_cases() holds
+stores on either side of one and two trips.  k_near_by_scan is one workgroup per query whose loop of 1024 vertices a round the size
+cases take into a second round at 1025 and 1281 vertices, and the trip cases through up to 129.
+
 Not tested: non-finite poses or queries (NaN, and infinities as coordinates): nanoflann's answer to a NaN depends on the shape
 of its tree, so there is no reference to hold the kernels to."""
 import math
@@ -296,6 +301,7 @@ def reuse_order(cases):
 
 # ==== near-by =================================================================================================================
 NEAR_SIZES = (1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 1281)
+NEAR_TRIP = 256 * 256                                       # vertices per trip of k_near_by_radius: at most 256 workgroups of 256
 INF = float("inf")
 
 
@@ -396,6 +402,62 @@ def near_radius_cases():
 CAP_CASE = "near radius: infinite over 257 vertices"      # the GPU side asks it with cap below the number of hits
 
 
+# ---- stores beyond one trip of k_near_by_radius ------------------------------------------------------------------------------
+def lattice(n, x0=0.0):
+    """n distinct points on a 1 / 8 m lattice, LATTICE_ROW to a row: vertex i at column i % 512 of row i // 512 (distinct for every n)"""
+    i = np.arange(n)
+    return np.stack([x0 + (i % LATTICE_ROW) / 8.0, (i // LATTICE_ROW) / 8.0], axis=1)
+
+
+LATTICE_ROW = 512
+TIE_QUERY, TIED = (-50.0, -50.0), (5, NEAR_TRIP + 5)
+NEAR_TRIP_SIZES = (NEAR_TRIP - 1, NEAR_TRIP, NEAR_TRIP + 1, NEAR_TRIP + 257, 2 * NEAR_TRIP + 1)
+# on which side of vertex 65 536 the hits of radius 0.05 lie (trip one, trip two): around the last vertex, around vertex (100, 128)
+# of the lattice, which is vertex 65 636 where the store holds it.  Around vertex (100, 10) they lie in trip one at every size.
+SIDES = {NEAR_TRIP - 1: ((True, False), (True, False)), NEAR_TRIP: ((True, False), (True, False)), NEAR_TRIP + 1: ((True, True), (True, False)),
+         NEAR_TRIP + 257: ((True, True), (True, True)), 2 * NEAR_TRIP + 1: ((False, True), (True, True))}
+ROWS_HELD = {NEAR_TRIP - 1: 1, NEAR_TRIP: 1, NEAR_TRIP + 1: 1, NEAR_TRIP + 257: 2, 2 * NEAR_TRIP + 1: 3}      # of rows 127 .. 129 at columns 99 .. 101
+
+
+def sides(hits):
+    hits = np.asarray(hits)
+    return bool((hits < NEAR_TRIP).any()), bool((hits >= NEAR_TRIP).any())
+
+
+def near_trip_cases():
+    """stores around one and two trips of k_near_by_radius' strided loop.  Radius 1 / 128 holds one lattice point, 0.05 the 3 x 3
+    points around one (d2 0, 1 / 64, 2 / 64; the next is 4 / 64); the rows of a 3 x 3 block lie 512 vertices apart, so a block on
+    rows 127 and 128 has hits on both sides of vertex 65 536."""
+    for n in NEAR_TRIP_SIZES:
+        poses = lattice(n)
+        tied = tuple(i for i in TIED if i < n)
+        for k, i in enumerate(tied):
+            poses[i] = (TIE_QUERY[0] + (3.0, 4.0)[k], TIE_QUERY[1] + (4.0, 3.0)[k])
+        last = poses[n - 1]
+        queries = [last + (1.0 / 64.0, 0.0), last, (100 / 8.0, 10 / 8.0), TIE_QUERY, (100 / 8.0, 128 / 8.0)]
+
+        def check(res, n=n, tied=tied):
+            # the nearest vertex is the LAST one (the clamped reads past the end return this very point at indices >= n)
+            assert res[0].nearest == (n - 1, 1.0 / 4096.0) and res[1].nearest == (n - 1, 0.0)
+            assert all(0 <= r.nearest[0] < n for r in res)
+            assert list(res[1].hits[0]) == [n - 1] and sides(res[1].hits[0]) == (n <= NEAR_TRIP, n > NEAR_TRIP)
+            assert sides(res[1].hits[1]) == SIDES[n][0] and sides(res[4].hits[1]) == SIDES[n][1] and sides(res[2].hits[1]) == (True, False)
+            assert len(res[2].hits[1]) == 9 and len(res[4].hits[1]) == 3 * ROWS_HELD[n]
+            # equal distances on either side of vertex 65 536: the lower index, in the nearest and in the list
+            assert (res[3].d2[list(tied)].view(np.uint64) == np.float64(25.0).view(np.uint64)).all() and (np.delete(res[3].d2, list(tied)) > 25.0).all()
+            assert res[3].nearest == (5, 25.0) and list(res[3].hits[2]) == list(tied) and list(res[3].hits[1]) == []
+            assert len(tied) == (2 if n > TIED[1] else 1)
+            for r in res:                                                             # every vertex, every slot of the hit list used
+                assert len(r.hits[3]) == n and np.array_equal(r.hits[3], np.lexsort((np.arange(n), r.d2)))
+                assert (np.sort(r.d2)[1:] == np.sort(r.d2)[:-1]).any()
+        yield NearCase(f"near trips: {n} vertices", poses, np.array(queries), [1.0 / 128.0, 0.05, up(25.0), INF], check)
+
+
+TRIP_CAP_CASE = f"near trips: {NEAR_TRIP + 257} vertices"   # ... and this one with caps on either side of the first trip
+
+
 def near_cases():
-    for gen in (near_size_cases, near_tie_cases, near_special_cases, near_radius_cases):
+    """the stores of more than one trip come last: every test on the shared handle after them, the short-output test on 257
+    vertices among them, runs in scratch that a store of 131 073 vertices left"""
+    for gen in (near_size_cases, near_tie_cases, near_special_cases, near_radius_cases, near_trip_cases):
         yield from gen()

@@ -1,7 +1,15 @@
 """Inputs of the map change layer's kernels (k_map_observe, k_map_diff, k_map_changed, k_map_decay in csrc/occupancy_changes.hip) as plain numpy
 data, and the changed world of its end-to-end test.  tests/test_map_changes_gpu.py asks the library and tests/map_changes_rule.py for
 the same cases and compares exactly; tests/test_map_changes_rule_oracle.py checks the changed world's three geometric statements with
-the rule alone."""
+the rule alone.
+
+The capped launches.  The changed-cell list is built by k_map_changed on min(ceil(n_units / 4), 1024) workgroups of four waves, a wave
+a unit of 64 cells of a row, so a wave's strided loop takes a second trip from 4097 units on; k_map_changed_scan is one workgroup of
+1024 threads with ceil(n_units / 1024) units each, more than one from 1025 units on.  unit_cases() holds views of 1023 .. 35 200 units
+around both thresholds (a 2000 x 2000 map has 64 000); test_unit_case_sits_on_its_edges asserts with the rule that each of them
+puts changes on the first and last unit of every trip and of three threads' ranges.  (The end-to-end tests' small map holds 4592
+units, so they reach a second trip too -- with whatever changed cells the world puts there, none at a threshold.)  k_map_diff and k_map_decay launch one thread per
+cell of the strided window without a cap."""
 from __future__ import annotations
 
 import math
@@ -54,6 +62,102 @@ def corner_view():
     cells[2, 2] = O
     cells[5, 9] = O
     return mlc.view_of(cells, (0.0, 0.0), 4.0, -6, -4, padding=O)
+
+
+# ---------------------------------------------------------------- unit counts around the capped launch of the list kernels
+# k_map_changed runs on min(ceil(n_units / 4), 1024) workgroups of four waves, a wave a unit: TRIP_UNITS units per trip of its strided
+# loop.  k_map_changed_scan is one workgroup of SCAN_THREADS threads, thread t summing the units [t per, (t + 1) per) clamped to n_units,
+# per = ceil(n_units / SCAN_THREADS).  The hand-made views above hold nine units at the most.
+TRIP_UNITS, SCAN_THREADS = 4096, 1024
+UnitCase = namedtuple("UnitCase", "name view laser ranges poses min_pass threshold caps n_units")
+UNIT_SHAPES = ((1, 1023), (1, 1024), (65, 512), (1, 1025), (65, 513), (1, 2048), (65, 1024), (1, 2049), (1, 4095), (1, 4096), (65, 2048),
+               (1, 4097), (65, 2049), (1, 8193), (2048, 1100))
+DECAY_CASE, ROOM_CASE = "4097 units (1 x 4097)", "4098 units (65 x 2049)"
+
+
+def units_of(width, height):
+    return -(-width // 64) * height
+
+
+def scan_range(t, n_units):
+    """[lo, hi): the units thread t of the scan sums"""
+    per = -(-n_units // SCAN_THREADS)
+    lo = min(t * per, n_units)
+    return lo, min(lo + per, n_units)
+
+
+def edge_units(n_units):
+    """the first and the last unit of every trip, and of the scan's first, middle and last non-empty thread"""
+    out = []
+    for first in range(0, n_units, TRIP_UNITS):
+        out += [first, min(first + TRIP_UNITS, n_units) - 1]
+    last_thread = (n_units - 1) // -(-n_units // SCAN_THREADS)
+    for t in (0, last_thread // 2, last_thread):
+        lo, hi = scan_range(t, n_units)
+        out += [lo, hi - 1]
+    return sorted(set(out))
+
+
+def unit_counts(view, changed):
+    """changed (height, width) bool -> the number of set cells per unit, row-major"""
+    h, w = view["height"], view["width"]
+    padded = np.zeros((h, -(-w // 64) * 64), dtype=np.int64)
+    padded[:, :w] = changed[:h, :w]
+    return padded.reshape(h, -1, 64).sum(axis=2).ravel()
+
+
+def unit_view(width, height, seed, ox=0, oy=0, padding=U):
+    """random states, half of them free; on a view of more than one column every seventh row all free and every seventh all occupied;
+    then an occupied cell into every edge unit that holds no other state than free"""
+    rng = np.random.default_rng(seed)
+    cells = mlc.random_cells(rng, height, width, p_free=0.5, p_occ=0.3)
+    if width > 1:
+        rows = np.arange(height)
+        cells[rows % 7 == 3] = F
+        cells[rows % 7 == 5] = O
+    per_row = -(-width // 64)
+    for u in edge_units(per_row * height):
+        row, x0 = u // per_row, 64 * (u % per_row)
+        span = min(64, width - x0)
+        if (cells[row, x0:x0 + span] == F).all():
+            cells[row, x0 + int(rng.integers(span))] = O
+    return mlc.view_of(cells, (-1.0, 0.5), 4.0, ox, oy, padding)
+
+
+def column_scans(view):
+    """one scan per column of the view: a single beam along +y from the centre of the column's first cell to the centre of its last.
+    Every cell is passed once, the end cell twice with one hit: at min_pass_through 0 and threshold 0.6 every cell is observed free, so
+    the changed cells are the cells of another state than free."""
+    h, k = view["height"], view["scale"]
+    laser = mlc.CaseLaser(1, math.pi / 2.0, 0.1, 0.1, (h + 20) / k, (h + 10) / k)
+    i = np.arange(view["width"])
+    poses = np.stack([view["anchor"][0] + (view["ox"] + i) / k, np.full(i.size, view["anchor"][1] + view["oy"] / k), np.zeros(i.size)], axis=1)
+    return laser, np.full((i.size, 1), (h - 1) / k), poses
+
+
+def unit_cases():
+    """caps: None, 0, then -- above one trip -- the prefix at unit 4096 exactly and a cap that ends inside the first unit of trip two
+    that holds two changes (on a view of one column: behind the first that holds one); else such a cap three quarters into the units"""
+    if "units" in _cache:
+        return _cache["units"]
+    out = []
+    for k, (w, h) in enumerate(UNIT_SHAPES):
+        ox, oy, padding = ((0, 0, U), (-7, -1000, O), (3, -5, O), (-40, 11, U))[k % 4]
+        view = unit_view(w, h, 100 + k, ox, oy, padding)
+        laser, ranges, poses = column_scans(view)
+        n_units = units_of(w, h)
+        counts = unit_counts(view, view["cells"] != F)
+        prefix = np.concatenate([[0], np.cumsum(counts)])
+        need = 2 if w > 1 else 1
+        if n_units > TRIP_UNITS:
+            u = TRIP_UNITS + int(np.argmax(counts[TRIP_UNITS:] >= need))
+            caps = (None, 0, int(prefix[TRIP_UNITS]), int(prefix[u]) + 1)
+        else:
+            u = 3 * n_units // 4 - int(np.argmax(counts[3 * n_units // 4::-1] >= need))
+            caps = (None, 0, int(prefix[u]) + 1)
+        out.append(UnitCase(f"{n_units} units ({w} x {h})", view, laser, ranges, poses, 0, 0.6, caps, n_units))
+    _cache["units"] = out
+    return out
 
 
 # ---------------------------------------------------------------- the changed world of the end-to-end test

@@ -71,6 +71,39 @@ def rule_grid(om, query_pose, points, stats=None):
     return data.reshape(-1)
 
 
+def _inside_span(anchor, scale, o, n, offset, grid_scale, roi_n):
+    """(first, last) of the map's cells 0 .. n - 1 along one axis whose centre WorldToGrid puts inside the region of interest; None
+    where there is none"""
+    v = anchor + (o + np.arange(n, dtype=np.int64)).astype(np.float64) / scale
+    g = _round((v - offset) * grid_scale)
+    k = np.nonzero((g >= 0) & (g < roi_n))[0]
+    return (int(k[0]), int(k[-1])) if k.size else None
+
+
+def _unit_bound(view, gi, grow):
+    cols = _inside_span(view["anchor"][0], view["scale"], view["ox"], view["width"], gi["offset_x"], gi["scale"], gi["roi_w"])
+    rows = _inside_span(view["anchor"][1], view["scale"], view["oy"], view["height"], gi["offset_y"], gi["scale"], gi["roi_h"])
+    if cols is None or rows is None:
+        return 0
+    cw = min(cols[1] + grow, view["width"] - 1) - max(cols[0] - grow, 0) + 1
+    ch = min(rows[1] + grow, view["height"] - 1) - max(rows[0] - grow, 0) + 1
+    return -(-cw // 64) * ch
+
+
+def units_lower_bound(view, grid_info):
+    """A lower bound of the units (64 cells of a row) of the map's clip to the region of interest, from the rule's own WorldToGrid: the
+    columns and rows whose cell centres fall inside the region span cw' and ch' cells, the clip keeps at least those, so
+    n_units >= ceil(cw' / 64) * ch'.  grid_info: the oracle's, centred on the query (rule_grid centres it)."""
+    return _unit_bound(view, grid_info, 0)
+
+
+def units_upper_bound(view, grid_info):
+    """... and an upper bound where a cell centre falls inside the region: the clip starts at floor(edge) - 1 and ends at ceil(edge) + 1
+    for the region's edges in map cells, which is at most two cells beyond the first and the last centre inside, and it ends with the map.
+    (A region that holds no cell centre gives 0, which bounds nothing.)"""
+    return _unit_bound(view, grid_info, 2)
+
+
 def install(om, grid):
     """writes `grid` into the oracle's own correlation grid (ko_grid_data is the live buffer; Matcher.grid() copies)"""
     n = om.grid_info()["data_size"]

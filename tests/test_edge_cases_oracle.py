@@ -285,6 +285,12 @@ def test_graph_table_holds_every_size_and_goes_large_small_large():
     assert len(sizes) == len(LOOPS) and sizes[0] == max(sizes) and sizes[1] == min(sizes) and sizes[2] > sizes[1] and sizes[2] > sizes[3]
     assert any(c.starts is None for c in LOOPS) and any(c.starts is not None and not c.starts.any() for c in LOOPS)
     assert any(c.name == gc.CAP_CASE for c in NEAR)
+    # k_near_by_radius: min(ceil(n / 256), 256) workgroups of 256, so a trip of its strided loop takes NEAR_TRIP vertices
+    assert gc.NEAR_TRIP == 256 * 256 and max(gc.NEAR_SIZES) <= gc.NEAR_TRIP, "the size cases stay within one trip"
+    trips = [c.poses.shape[0] for c in NEAR if c.name.startswith("near trips")]
+    assert trips == list(gc.NEAR_TRIP_SIZES) == [c.poses.shape[0] for c in NEAR][-len(trips):], "the large stores come last"
+    assert [-(-n // gc.NEAR_TRIP) for n in trips] == [1, 1, 2, 2, 3] and next(c for c in NEAR if c.name == gc.TRIP_CAP_CASE).poses.shape[0] > gc.NEAR_TRIP
+    assert all(np.unique(c.poses, axis=0).shape[0] == c.poses.shape[0] for c in NEAR if c.name.startswith("near trips")), "distinct points"
 
 
 # ---- tests/spa_cases.py: the pose-graph solver's table through oracle/spa.py alone (GPU side: tests/test_spa_edges_gpu.py) --------

@@ -207,16 +207,18 @@ def test_near_by_case_equals_the_rule(search, case):
 
 
 def test_near_by_vertices_with_a_short_output(search, kartohip_lib):
-    """cap below the number of hits: *n_found is the total, cap entries are written, the sentinel behind them is intact"""
-    case = next(c for c in NEAR if c.name == gc.CAP_CASE)
-    load_near(search, case)
-    n = case.poses.shape[0]
-    q = np.ascontiguousarray(case.queries[0], dtype=np.float64)
-    want = near_by_rule.find_near_by_vertices(case.poses, q, gc.INF)
-    assert want.size == n
-    for cap in (0, 1, 64, n - 1, n):
-        out = np.full(cap + 4, SENTINEL, dtype=np.int32)
-        found = C.c_int32(SENTINEL)
-        rc = kartohip_lib.kh_graph_find_near_by_vertices(search._h, q.ctypes.data, gc.INF, out.ctypes.data if cap else None, cap, C.byref(found))
-        assert rc == 0 and found.value == n, cap
-        assert np.array_equal(out[:cap], want[:cap]) and (out[cap:] == SENTINEL).all(), cap
+    """cap below the number of hits: *n_found is the total, cap entries are written, the sentinel behind them is intact -- on a store
+    of one trip of k_near_by_radius, and on one of two trips with caps on either side of the first trip's 65 536 vertices"""
+    for name, caps in ((gc.CAP_CASE, lambda n: (0, 1, 64, n - 1, n)), (gc.TRIP_CAP_CASE, lambda n: (0, 1, gc.NEAR_TRIP, n - 1))):
+        case = next(c for c in NEAR if c.name == name)
+        load_near(search, case)
+        n = case.poses.shape[0]
+        q = np.ascontiguousarray(case.queries[0], dtype=np.float64)
+        want = near_by_rule.find_near_by_vertices(case.poses, q, gc.INF)
+        assert want.size == n
+        for cap in caps(n):
+            out = np.full(cap + 4, SENTINEL, dtype=np.int32)
+            found = C.c_int32(SENTINEL)
+            rc = kartohip_lib.kh_graph_find_near_by_vertices(search._h, q.ctypes.data, gc.INF, out.ctypes.data if cap else None, cap, C.byref(found))
+            assert rc == 0 and found.value == n, (name, cap)
+            assert np.array_equal(out[:cap], want[:cap]) and (out[cap:] == SENTINEL).all(), (name, cap)

@@ -22,6 +22,7 @@ from test_map_seeds_gpu import DeviceView
 pytestmark = pytest.mark.gpu
 
 OBSERVE_CASES = cc.observe_cases()
+UNIT_CASES = cc.unit_cases()
 F, O, U = cc.F, cc.O, cc.U
 
 
@@ -134,6 +135,34 @@ def test_diff_lists_around_the_unit_boundaries(kartohip_lib, oracle_lib):
     capi.check(kartohip_lib.kh_map_changes_diff(p.lib._h, 0, 0.1, room.ctypes.data, 4, s), "kh_map_changes_diff")
     assert s.n_changed == 9 and s.n_listed == 4 and np.array_equal(room[:4], want["cells"][:4]) and (room[4:] == -77).all()
     assert s.diff_kernel_ms > 0 and s.list_kernel_ms > 0 and s.observe_kernel_ms > 0
+    p.close()
+
+
+@pytest.mark.parametrize("case", UNIT_CASES, ids=[c.name for c in UNIT_CASES])
+def test_unit_cases(kartohip_lib, oracle_lib, case):
+    """views of 1023 .. 35 200 units (tests/map_changes_cases.py): the second and later trips of k_map_changed's strided loop, and
+    k_map_changed_scan with more than one unit per thread; the whole list, no list, and lists cut at the caps of the case"""
+    p = Pair(case.view)
+    p.observe(case.laser, case.ranges, case.poses)
+    for cap in case.caps:
+        got, _ = p.diff(case.min_pass, case.threshold, cap)
+        assert got["n_changed"] > max(c or 0 for c in case.caps) or case.n_units == cc.TRIP_UNITS + 1
+    if case.name == cc.ROOM_CASE:
+        # no more than `cap` entries are written, by any trip: the caller's room past them stays as it was
+        want, cap = p.rule.diff(case.min_pass, case.threshold)["cells"], case.caps[-1]
+        room = np.full((len(want), 3), -77, dtype=np.int32)
+        s = capi.KhMapChangesSummary()
+        capi.check(kartohip_lib.kh_map_changes_diff(p.lib._h, case.min_pass, case.threshold, room.ctypes.data, cap, s), "kh_map_changes_diff")
+        assert s.n_changed == len(want) and s.n_listed == cap and np.array_equal(room[:cap], want[:cap]) and (room[cap:] == -77).all()
+    if case.name == cc.DECAY_CASE:
+        # a count phase over a unit buffer that holds the prefix of the diff before: after the decay only the end cell is observed
+        p.lib.decay(1)
+        p.rule.decay(1)
+        got, _ = p.diff(case.min_pass, case.threshold)
+        assert got["counts"][rule.UNOBSERVED] == case.view["height"] - 1 and got["n_changed"] == 1
+        p.observe(case.laser, case.ranges, case.poses)          # ... and the dense list again, over the buffer of the sparse one
+        got, _ = p.diff(case.min_pass, case.threshold, case.caps[-1])
+        assert got["n_listed"] == case.caps[-1]
     p.close()
 
 

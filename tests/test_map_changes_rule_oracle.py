@@ -11,6 +11,7 @@ import math
 import numpy as np
 import pytest
 
+import map_changes_cases as cc
 import map_changes_rule as rule
 import map_localize_cases as cases
 import map_match_rule as mr
@@ -140,6 +141,75 @@ def test_diff_codes_and_thresholds():
     assert d["codes"][0, 9:11].tolist() == [2, 2], "pass above min_pass_through; the ratio above the threshold"
     # an unobserved cell of state 7 stays 7 in the patched grid
     assert rule.Layer(layer.view).diff()["patched"][0, 7] == 7
+
+
+UNIT_CASES = cc.unit_cases()
+
+
+def test_unit_case_table_holds_every_count_and_both_shapes(oracle_lib):
+    counts = [c.n_units for c in UNIT_CASES]
+    assert set(counts) >= {1023, 1024, 1025, 2048, 2049, 4095, 4096, 4097, 8193} and max(counts) == 32 * 1100 == 35200
+    assert [cc.units_of(w, h) for w, h in cc.UNIT_SHAPES] == counts
+    one = {c.n_units for c in UNIT_CASES if c.view["width"] == 1}
+    assert one == {1023, 1024, 1025, 2048, 2049, 4095, 4096, 4097, 8193}, "every count by the narrowest view that reaches it"
+    assert {c.view["height"] for c in UNIT_CASES if c.view["width"] == 65} >= {512, 513, 1024, 2048, 2049}
+    assert sum(c.view["ox"] < 0 and c.view["oy"] < 0 for c in UNIT_CASES) >= 2
+    assert sum(c.view["cells"].shape[1] > c.view["width"] and (c.view["cells"][:, c.view["width"]:] == O).all() for c in UNIT_CASES) >= 2
+    assert {c.name for c in UNIT_CASES} >= {cc.DECAY_CASE, cc.ROOM_CASE} and len({c.name for c in UNIT_CASES}) == len(UNIT_CASES)
+    # the launches: ceil(n_units / 4) workgroups capped at 1024, per = ceil(n_units / 1024)
+    trips = lambda n: -(-n // (4 * min(-(-n // 4), 1024)))      # noqa: E731
+    assert cc.TRIP_UNITS == 4 * 1024 and [trips(n) for n in (4096, 4097, 8193, 35200)] == [1, 2, 3, 9]
+    assert [-(-n // cc.SCAN_THREADS) for n in (1024, 1025, 2048, 2049, 35200)] == [1, 2, 2, 3, 35]
+    assert cc.scan_range(512, 1025) == (1024, 1025) and cc.scan_range(513, 1025) == (1025, 1025), "per = 2: threads 513 and up are empty"
+    # the largest hand-made view before this table
+    assert cc.units_of(cc.wide_view()["width"], cc.wide_view()["height"]) == 9
+    # ... and the end-to-end tests' small map, which lies past one trip but puts nothing on a threshold
+    small = cases.small_map()[1]
+    assert cc.units_of(small.width, small.height) == 4592 > cc.TRIP_UNITS
+
+
+@pytest.mark.parametrize("case", UNIT_CASES, ids=[c.name for c in UNIT_CASES])
+def test_unit_case_sits_on_its_edges(oracle_lib, case):
+    """from the rule alone: the unit count of the name; a change in the first and in the last unit of every trip of k_map_changed and of
+    three threads' ranges of k_map_changed_scan, the last non-empty thread among them; a quarter of the units with a change; varied
+    counts; the caps where the case says they are"""
+    view = case.view
+    w, h, n_units = view["width"], view["height"], case.n_units
+    per_row = -(-w // 64)
+    assert case.name.startswith(f"{n_units} units") and n_units == per_row * h
+    layer = rule.Layer(view)
+    layer.observe(case.laser, case.ranges, case.poses)
+    assert (layer.passes[:, :w] >= 1).all() and layer.hits.sum() == w, "every cell passed, one hit per column"
+    d = layer.diff(case.min_pass, case.threshold)
+    cells = d["cells"]
+    unit = (cells[:, 1] - view["oy"]).astype(np.int64) * per_row + (cells[:, 0] - view["ox"]) // 64
+    assert (np.diff(unit) >= 0).all(), "row-major: ascending units"
+    counts = np.bincount(unit, minlength=n_units)
+    assert np.array_equal(counts, cc.unit_counts(view, view["cells"] != F)), "the changed cells are those of another state than free"
+    prefix = np.concatenate([[0], np.cumsum(counts)])
+    for first in range(0, n_units, cc.TRIP_UNITS):
+        assert counts[first] > 0 and counts[min(first + cc.TRIP_UNITS, n_units) - 1] > 0, f"trip {first // cc.TRIP_UNITS}"
+    per = -(-n_units // cc.SCAN_THREADS)
+    ranges = [cc.scan_range(t, n_units) for t in range(cc.SCAN_THREADS)]
+    full = [t for t, (lo, hi) in enumerate(ranges) if hi > lo and counts[lo] > 0 and counts[hi - 1] > 0]
+    last = max(t for t, (lo, hi) in enumerate(ranges) if hi > lo)
+    assert len(full) >= 3 and last in full and last == (n_units - 1) // per
+    assert (n_units > cc.SCAN_THREADS) == (per > 1) and (ranges[-1][0] == ranges[-1][1]) == (last < cc.SCAN_THREADS - 1)
+    assert 4 * np.count_nonzero(counts) >= n_units
+    values = set(counts.tolist())
+    if w == 1:
+        assert values == {0, 1}, "a unit of one cell"
+    else:
+        assert len(values) >= 3 and {0, 64} <= values and (1 in set(counts[1::per_row].tolist()) or w % 64 != 1)
+    # the caps
+    assert case.caps[:2] == (None, 0) and all(0 < c < len(cells) or n_units == cc.TRIP_UNITS + 1 for c in case.caps[2:])
+    inside = case.caps[-1]
+    u = int(np.searchsorted(prefix, inside, side="left")) - 1               # prefix[u] < inside <= prefix[u + 1]
+    if n_units > cc.TRIP_UNITS:
+        assert case.caps[2] == prefix[cc.TRIP_UNITS] and len(case.caps) == 4 and u >= cc.TRIP_UNITS
+    else:
+        assert len(case.caps) == 3
+    assert prefix[u] < inside and (inside < prefix[u + 1] if w > 1 else inside == prefix[u + 1])
 
 
 def test_changed_world_statements_hold_for_the_rule(oracle_lib):

@@ -1,24 +1,26 @@
 """GPU: the map-sourced correlation grid and the matches on it (kh_matcher_add_map / _match_map*, k_map_collect in
 csrc/matcher_kernels.hip; kh_occupancy_write_nav, k_nav_to_occ in csrc/occupancy.hip) against tests/map_match_rule.py: the grid
 bytes with np.array_equal, the matches bit for bit.  Small matchers, maps of at most about 200 x 200 cells filled through
-OccupancyGrid.from_nav; one test -- does a map localise as well as a chain of scans -- uses a built map of the synthetic world."""
+OccupancyGrid.from_nav, then the maps of tests/map_match_cases.py, whose clips take k_map_collect through more than one trip of its
+capped launch; one test -- does a map localise as well as a chain of scans -- uses a built map of the synthetic world."""
 import ctypes as C
 import math
 
 import numpy as np
 import pytest
 
+import map_match_cases as mc
 import map_match_rule as mr
 from common import LASER, OFFLINE_PARAMS, Scenario, bits
 from slam_toolbox_amd import capi, synth
 
 pytestmark = pytest.mark.gpu
 
-SMALL = (0.3, 0.01, 0.03, 4.0)              # 13 x 13 smear kernel, region of interest 831 cells
+SMALL = mc.SMALL                            # 13 x 13 smear kernel, region of interest 831 cells
 LOOP = (2.0, 0.05, 0.03, 4.0)               # loop-like: 3 x 3 kernel, region of interest 201 cells
-FOOT = (0.3, 0.01, 0.0999, 4.0)             # sigma / res = 9.99: the kernel holds 100 on the centre's four neighbours
+FOOT = mc.FOOT                              # sigma / res = 9.99: the kernel holds 100 on the centre's four neighbours
 DYADIC = (2.0, 0.25, 0.25, 8.0)             # every product below is exact: 5 x 5 kernel, region of interest 73 cells
-TO_CELL = {-1: 0, 100: 100, 0: 255}
+cells_of = mc.cells_of
 
 
 def pair(create, params=OFFLINE_PARAMS, max_batch=1):
@@ -33,13 +35,6 @@ def scans_at(pose, ranges=None):
     from slam_toolbox_amd.scan_matcher import LocalizedRangeScan
     ranges = np.full(8, 1.0) if ranges is None else ranges
     return LocalizedRangeScan(ranges, pose, LASER.min_angle, LASER.ang_res), karto.Scan(ranges, pose, LASER)
-
-
-def cells_of(nav):
-    out = np.zeros(nav.shape, dtype=np.uint8)
-    for k, v in TO_CELL.items():
-        out[nav == k] = v
-    return out
 
 
 def random_nav(rng, h, w, p_occ=0.3):
@@ -428,6 +423,51 @@ def test_empty_query(kartohip_lib, oracle_lib, match_case):
             assert np.array_equal(bits(a), bits(b))
     for a, b in zip(hm.MatchScanMap(he, g), w):
         assert np.array_equal(bits(a), bits(b))
+    hm.close(); g.close()
+
+
+# ---------------------------------------------------------------- clips beyond one trip of k_map_collect
+
+TRIP_CASES = mc.trip_cases()
+
+
+@pytest.mark.parametrize("case", TRIP_CASES, ids=[c.name for c in TRIP_CASES])
+def test_clips_of_more_units_than_one_trip(kartohip_lib, oracle_lib, case):
+    """maps of 1040 .. 8320 units inside the region of interest (tests/map_match_cases.py): k_map_collect's second and third trip,
+    k_map_collect_scan with up to nine units per thread; the point order decides the bytes where the kernel holds 100 off-centre and
+    the skips where several map cells share a grid cell"""
+    hm, om = pair(case.create)
+    stats = {}
+    check_grid(hm, om, case.pose, case.nav, case.offset, case.res, stats=stats)
+    assert stats["inside"] == (case.nav == 100).sum() and stats["stamped"] > 1000
+    assert stats["skipped"] > 1000 or (case.res == 0.01 and case.create == mc.SMALL)
+    hm.close()
+
+
+def test_match_map_batch_with_clips_of_every_size(kartohip_lib, oracle_lib):
+    """one batch whose jobs hold 8320 units, 3 units at the most and none: the launch is sized by the first, the waves of the second
+    leave the loop at once and the scan of the third writes a total of 0"""
+    from slam_toolbox_amd.occupancy_grid import OccupancyGrid
+    b = mc.batch_case()
+    sc = Scenario(seed=12, n_base=8, start=90)
+    g = OccupancyGrid.from_nav(b.nav, b.offset, b.res)
+    hm, om = pair(b.create, max_batch=len(b.poses))
+    queries = [scans_at(p, sc.query_ranges) for p in b.poses]
+    pts = mr.map_points(mr.view_dict(mc.cells_of(b.nav), b.offset, 1.0 / b.res))
+    resp, means, covs, status = hm.MatchScanMapBatch([q for q, _ in queries], g)
+    assert (status == capi.KH_OK).all()
+    occupied = []
+    for k, (_, oq) in enumerate(queries):
+        grid = mr.rule_grid(om, oq.sensor_pose, pts)
+        got = hm.GetCorrelationGrid(k)
+        assert np.array_equal(got, grid), f"job {k}: {int((got != grid).sum())} grid bytes differ"
+        occupied.append(int((grid == 100).sum()))
+        mr.install(om, grid)
+        w = mr.match(om, oq, OFFLINE_PARAMS)
+        assert np.array_equal(bits(resp[k]), bits(w[0])), (k, resp[k], w[0])
+        assert np.array_equal(bits(means[k]), bits(w[1])), (k, means[k], w[1])
+        assert np.array_equal(bits(covs[k]), bits(w[2])), k
+    assert occupied[0] > 10000 and occupied[1:] == [1, 0] and resp[2] == 0.0
     hm.close(); g.close()
 
 
