@@ -1517,6 +1517,72 @@ KH_API void kh_map_align_params_default(const kh_map_localizer * loc, kh_map_ali
 KH_API int kh_map_align(kh_map_localizer * loc, const kh_map_view * moving, const kh_map_align_params * params,
                         kh_map_align_cand * out, int32_t cap, int32_t * n_candidates, double times_ms[4]);
 
+/* ---------------------------------------------------------------- two finished maps merged into one
+ * The map `moving` is warped through a rigid correction onto the lattice of the map `target` and the two are composed cell by cell;
+ * the result is a kh_map_view on the target's own lattice (the same anchor, the same stored scale) that the localizer, the matcher's
+ * map entry points, the change layer, the ray cast and another merge take as it is.  `correction` carries moving-map coordinates
+ * into the target's frame: what kh_map_align_cand.correction holds.
+ *   warp     output cell (I, J) lies at w = anchor_t + (double)I / scale_t.  With footprint n it has n x n sample points (wx + d_a,
+ *            wy + d_b), d_k = ((2 k + 1 - n) / (2.0 n)) / scale_t (exactly 0 for n = 1).  Each goes through inverse(correction) -- (c * x -
+ *            s * y) + tx, (s * x + c * y) + ty, c and s the host's cos and sin of its yaw -- and is rounded to a cell of the moving
+ *            lattice (section 7k); a cell outside the moving window or beyond the int32 lattice reads unknown.  M = 100 if any
+ *            sample read 100, else 255 if any read 255, else unknown.  The default footprint min(4, max(1, ceil(scale_m / scale_t)))
+ *            is 1 unless the moving map is finer than the target: a footprint above the resolution ratio thickens walls.
+ *   compose  T = the target's state at (I, J): 100, 255, else (any other state, no such cell) unknown.  The code of the cell and
+ *            the merged state are KH_MERGED_'s below; a conflict is settled by the KH_MERGE_CONFLICT_ policy.
+ *   window   grow 0: the target's window.  grow 1: its union with the box of the moving map's cells of state != 0 -- the corner
+ *            points of their inclusive lattice box, pushed outward by half a moving cell, carried by the correction, rounded to
+ *            target-lattice cells, min / max over the four, one cell of padding on every side.  A moving map with no such cell adds
+ *            nothing.  Row stride (width + 7) & ~7, the padding columns 0.
+ * Neither input is written. */
+enum {
+  KH_MERGED_NEITHER = 0,           /* both unknown: 0 */
+  KH_MERGED_TARGET_ONLY = 1,       /* M unknown: T */
+  KH_MERGED_MOVING_ONLY = 2,       /* T unknown: M */
+  KH_MERGED_AGREE = 3,             /* equal and known: T */
+  KH_MERGED_MOVING_OCCUPIED = 4,   /* T free, M occupied: by policy */
+  KH_MERGED_MOVING_FREE = 5        /* T occupied, M free: by policy */
+};
+enum {
+  KH_MERGE_CONFLICT_TARGET = 0,    /* the target's state */
+  KH_MERGE_CONFLICT_MOVING = 1,    /* the moving map's state */
+  KH_MERGE_CONFLICT_OCCUPIED = 2,  /* 100 (the default: a planner must not lose a wall) */
+  KH_MERGE_CONFLICT_UNKNOWN = 3    /* 0 */
+};
+typedef struct kh_map_merge kh_map_merge;
+typedef struct kh_map_merge_params {
+  double correction[3];        /* moving map -> target map; finite */
+  int32_t footprint;           /* 1 .. 4, or 0 = the default */
+  int32_t conflict;            /* KH_MERGE_CONFLICT_ (default KH_MERGE_CONFLICT_OCCUPIED) */
+  int32_t grow;                /* 0 / 1 (default 1) */
+  int32_t pad;
+} kh_map_merge_params;
+typedef struct kh_map_merge_stats {
+  int32_t ox, oy, width, height, width_step, footprint;   /* the output window and the footprint used */
+  int32_t known_box[4];        /* i0, j0, i1, j1 of the moving map's cells of state != 0, lattice indices; i1 < i0: none */
+  uint64_t target_only, moving_only, agree_free, agree_occupied, conflict_moving_occupied, conflict_moving_free;   /* output cells */
+  uint64_t overlap;            /* the sum of the last four */
+  double agreement;            /* (agree_free + agree_occupied) / overlap; 0 without overlap */
+  double times_ms[3];          /* the known box and the merge kernel by events, the whole call */
+} kh_map_merge_stats;
+/* correction 0, footprint 0, KH_MERGE_CONFLICT_OCCUPIED, grow 1; a NULL output is ignored */
+KH_API void kh_map_merge_params_default(kh_map_merge_params * p);
+/* Merges and keeps the result on the device of the views.  KH_ERR_INVALID_ARG before a device is looked for: a NULL target, moving,
+ * params or out, a malformed view, a non-finite correction, a footprint outside 0 .. 4, a conflict outside 0 .. 3, a grow outside
+ * 0 .. 1.  Then: no device KH_ERR_NO_DEVICE; views on two different devices KH_ERR_INVALID_ARG; a carried corner of the moving map's
+ * box more than 2^30 cells from the target's anchor, an output side above 32768 cells or an output above 2^28 cells
+ * KH_ERR_INVALID_ARG.  A warp alone is a merge into an all-unknown target of the wanted lattice; a third map is merged with the
+ * first merge's view as its target. */
+KH_API int kh_map_merge_create(const kh_map_view * target, const kh_map_view * moving, const kh_map_merge_params * params, kh_map_merge ** out);
+KH_API void kh_map_merge_destroy(kh_map_merge * m);
+KH_API int kh_map_merge_stats_get(kh_map_merge * m, kh_map_merge_stats * out);
+/* the merged cells as a view on the target's lattice: owned by the handle, valid until kh_map_merge_destroy */
+KH_API int kh_map_merge_view(kh_map_merge * m, kh_map_view * out);
+/* the merged cells and the KH_MERGED_ codes, width_step * height bytes each; either may be NULL */
+KH_API int kh_map_merge_read(kh_map_merge * m, uint8_t * cells, uint8_t * codes);
+/* the merged cells as width * height nav values, kh_occupancy_read_nav's mapping, no row padding */
+KH_API int kh_map_merge_read_nav(kh_map_merge * m, int8_t * out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -173,6 +173,8 @@ SYMBOLS = [
     "kh_map_changes_create", "kh_map_changes_destroy", "kh_map_changes_clear", "kh_map_changes_decay", "kh_map_changes_observe",
     "kh_map_changes_diff", "kh_map_changes_read", "kh_map_changes_view", "kh_map_changes_read_nav",
     "kh_map_raycast", "kh_map_align_params_default", "kh_map_align",
+    "kh_map_merge_params_default", "kh_map_merge_create", "kh_map_merge_destroy", "kh_map_merge_stats_get", "kh_map_merge_view",
+    "kh_map_merge_read", "kh_map_merge_read_nav",
 ]
 
 
@@ -338,6 +340,21 @@ class KhMapAlignCand(C.Structure):
                 ("index", C.c_int32), ("enough", C.c_int32), ("fit", KhMergeFit)]
 
 
+KH_MERGED_NEITHER, KH_MERGED_TARGET_ONLY, KH_MERGED_MOVING_ONLY, KH_MERGED_AGREE, KH_MERGED_MOVING_OCCUPIED, KH_MERGED_MOVING_FREE = range(6)
+KH_MERGE_CONFLICT_TARGET, KH_MERGE_CONFLICT_MOVING, KH_MERGE_CONFLICT_OCCUPIED, KH_MERGE_CONFLICT_UNKNOWN = range(4)
+
+
+class KhMapMergeParams(C.Structure):
+    _fields_ = [("correction", C.c_double * 3), ("footprint", C.c_int32), ("conflict", C.c_int32), ("grow", C.c_int32), ("pad", C.c_int32)]
+
+
+class KhMapMergeStats(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("ox", "oy", "width", "height", "width_step", "footprint")] + [("known_box", C.c_int32 * 4)] + \
+               [(k, C.c_uint64) for k in ("target_only", "moving_only", "agree_free", "agree_occupied", "conflict_moving_occupied",
+                                           "conflict_moving_free", "overlap")] + \
+               [("agreement", C.c_double), ("times_ms", C.c_double * 3)]
+
+
 class KhMergeAlignParams(C.Structure):
     _fields_ = [("n_probes", C.c_int32), ("top_k", C.c_int32), ("min_known", C.c_uint64), ("min_pass_through", C.c_uint32), ("pad", C.c_uint32),
                 ("occupancy_threshold", C.c_double), ("relocalize", KhRelocalizeParams)]
@@ -455,6 +472,16 @@ def lib():
         L.kh_map_align_params_default.argtypes = [vp, C.POINTER(KhMapAlignParams)]
         L.kh_map_align_params_default.restype = None
         L.kh_map_align.argtypes = [vp, C.POINTER(KhMapView), C.POINTER(KhMapAlignParams), C.POINTER(KhMapAlignCand), i32, C.POINTER(i32), vp]
+    if hasattr(L, "kh_map_merge_create"):      # (KH_LIBRARY may name a build from before the map merge existed)
+        L.kh_map_merge_params_default.argtypes = [C.POINTER(KhMapMergeParams)]
+        L.kh_map_merge_params_default.restype = None
+        L.kh_map_merge_create.argtypes = [C.POINTER(KhMapView), C.POINTER(KhMapView), C.POINTER(KhMapMergeParams), C.POINTER(vp)]
+        L.kh_map_merge_destroy.argtypes = [vp]
+        L.kh_map_merge_destroy.restype = None
+        L.kh_map_merge_stats_get.argtypes = [vp, C.POINTER(KhMapMergeStats)]
+        L.kh_map_merge_view.argtypes = [vp, C.POINTER(KhMapView)]
+        L.kh_map_merge_read.argtypes = [vp, vp, vp]
+        L.kh_map_merge_read_nav.argtypes = [vp, vp]
     if hasattr(L, "kh_spa_create"):
         L.kh_spa_options_default.argtypes = [C.POINTER(KhSpaOptions)]
         L.kh_spa_create.argtypes = [i32, C.POINTER(vp)]

@@ -1,6 +1,6 @@
 // What the occupancy module shares between its kernel files (occupancy.hip, occupancy_live.hip, occupancy_map.hip,
 // occupancy_changes.hip: the kernels and their launchers) and the host files that feed them: mapper_views.cpp (kh_mapper_build_map),
-// merge.cpp (kh_merge_build), live_map.cpp (kh_live_map_*), map_localizer.cpp, map_changes.cpp, map_align.cpp.  Needs no HIP header:
+// merge.cpp (kh_merge_build), live_map.cpp (kh_live_map_*), map_localizer.cpp, map_changes.cpp, map_align.cpp, map_merge.cpp.  Needs no HIP header:
 // the CPU programs of tests/ include it.  Not part of the public ABI (include/karto_hip.h).  The live map's lattice, window and log
 // are stated in DESIGN.md section 7b, the map feed's tiles in 7c.
 #pragma once
@@ -262,6 +262,24 @@ int map_raycast_cells(MapWork * w, const kh_map_view & v, int32_t n_beams, int32
 int map_raycast_check(const kh_map_view * view, const kh_laser * laser, int32_t n_poses, const double * sensor_poses, int32_t max_unknown);
 int map_raycast(MapWork * w, const kh_map_view & v, const kh_laser & laser, int32_t n_poses, const double * sensor_poses, int32_t max_unknown,
   double no_return, kh_ray_t * out, double * kernel_ms);
+
+// ---- two maps merged into one (occupancy_map.hip; kh_map_merge_*; the handle and its buffers: map_merge.cpp) ----
+// one launch of k_map_merge: the output window on the target's lattice, the inverse correction, the samples of a cell
+constexpr int32_t kMergeTileWidth = 64, kMergeTileHeight = 16;     // cells of a workgroup's tile: 16 dwords x 16 rows = 256 threads
+struct MergeJob
+{
+  MapWindow target, moving;
+  int32_t ox, oy, width, height, ws;      // the output window; ws a multiple of 4
+  int32_t footprint, conflict;            // 1 .. 4; KH_MERGE_CONFLICT_
+  double c, s, tx, ty;                    // inverse(correction): cos / sin of its yaw (host libm), translation
+  double d[4];                            // the sample offsets of one axis (merge_sample_offsets)
+};
+// k_map_known_box on `stream`: d_box = (i0, j0, i1, j1), set by the caller to (INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN), takes the
+// inclusive lattice box of the window cells of state != 0
+void map_known_box(void * stream, const kh_map_view & v, int32_t * d_box);
+// k_map_merge on `stream`: d_cells and d_codes take one byte per cell of the strided output window (the padding 0), d_counts[6]
+// (zeroed by the caller) the window cells by counter (map_merge_plan.hpp's order).  Neither input is written.
+void map_merge_cells(void * stream, const MergeJob & job, uint8_t * d_cells, uint8_t * d_codes, unsigned long long * d_counts);
 
 // ---- a change layer's kernels (occupancy_changes.hip; kh_map_changes_*; the handle and its buffers: map_changes.cpp) ----
 // the layer's two counter grids on the window of its view, row stride the view's width_step

@@ -1,7 +1,8 @@
 // A map view as a localizer reads it (kh_map_seeds, kh_map_fit, kh_map_raycast; DESIGN.md sections 7k and 7m): the kernels that only
 // READ a kh_map_view -- where a robot can stand, how a scan at many poses fits, what a scan from a pose would be -- their launchers on
-// a caller's work buffers, and the three entry points that make such buffers for one call.  What the kernels share with the trace
-// kernels: occupancy_walk.hpp; the rules that need no device: map_localize_plan.hpp.
+// a caller's work buffers, and the three entry points that make such buffers for one call; and the two kernels of a merge of two
+// views (kh_map_merge_*, section 7n; the handle: map_merge.cpp), which read both and write a third.  What the kernels share with the
+// trace kernels: occupancy_walk.hpp; the rules that need no device: map_localize_plan.hpp, map_merge_plan.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,6 +13,7 @@
 
 #include "../../include/karto_hip.h"
 #include "occupancy_walk.hpp"
+#include "map_merge_plan.hpp"      // the order of a merge's six counters
 
 namespace kh
 {
@@ -127,6 +129,138 @@ __global__ __launch_bounds__(256) void k_map_seeds(MapWindow g, int32_t pitch, i
     key = other < key ? other : key;
   }
   if (lane == 0) {out[block] = key == ~0ull ? -1 : (int32_t)(key & 0xFFFFFFFFull);}
+}
+
+// The box of a map's known cells (kh_map_merge_create): one pass over the window, a workgroup per row in a
+// grid stride, its threads along the row, so a wave reads consecutive bytes and nothing of the padding.  Each lane keeps min / max of
+// the lattice i and j of its cells of state != 0; the wave reduces by shuffles, the four waves through LDS, then one atomicMin /
+// atomicMax on int32 per workgroup and bound that found a cell.  Integer extrema do not depend on the order.
+__global__ __launch_bounds__(256) void k_map_known_box(MapWindow g, int32_t * __restrict__ box)
+{
+  __shared__ int32_t part[4][4];
+  int32_t lo_i = INT32_MAX, lo_j = INT32_MAX, hi_i = INT32_MIN, hi_j = INT32_MIN;
+  for (int32_t y = blockIdx.x; y < g.height; y += gridDim.x) {
+    const uint8_t * const row = g.cells + (int64_t)y * g.ws;
+    for (int32_t x = threadIdx.x; x < g.width; x += 256) {
+      if (row[x] != 0u) {
+        const int32_t i = g.ox + x, j = g.oy + y;      // (inside the int32 lattice: map_view_check)
+        lo_i = i < lo_i ? i : lo_i; hi_i = i > hi_i ? i : hi_i;
+        lo_j = j < lo_j ? j : lo_j; hi_j = j > hi_j ? j : hi_j;
+      }
+    }
+  }
+#pragma unroll
+  for (int32_t d = 32; d >= 1; d >>= 1) {
+    const int32_t a = __shfl_xor(lo_i, d), b = __shfl_xor(lo_j, d), c = __shfl_xor(hi_i, d), e = __shfl_xor(hi_j, d);
+    lo_i = a < lo_i ? a : lo_i; lo_j = b < lo_j ? b : lo_j; hi_i = c > hi_i ? c : hi_i; hi_j = e > hi_j ? e : hi_j;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    int32_t * const mine = part[threadIdx.x >> 6];
+    mine[0] = lo_i; mine[1] = lo_j; mine[2] = hi_i; mine[3] = hi_j;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int32_t k = threadIdx.x;
+    const int32_t a = part[0][k], b = part[1][k], c = part[2][k], e = part[3][k];
+    if (k < 2) {
+      const int32_t ab = a < b ? a : b, ce = c < e ? c : e, v = ab < ce ? ab : ce;
+      if (v != INT32_MAX) {atomicMin(&box[k], v);}
+    } else {
+      const int32_t ab = a > b ? a : b, ce = c > e ? c : e, v = ab > ce ? ab : ce;
+      if (v != INT32_MIN) {atomicMax(&box[k], v);}
+    }
+  }
+}
+
+// the state of lattice cell (cx, cy) of a view as a merge reads it: 0 where the window has no such cell or the index is o_to_int's
+// "beyond the int32 lattice"
+__device__ __forceinline__ uint32_t merge_state(const MapWindow & g, int32_t cx, int32_t cy)
+{
+  const CellAt at = cell_at(g, cx, cy);
+  return (at.inside && cx != INT32_MIN && cy != INT32_MIN) ? g.cells[at.k] : 0u;
+}
+
+// Two maps merged (kh_map_merge_create): one thread per dword of the output, four horizontally adjacent cells;
+// a workgroup a tile of 64 x 16 cells (thread t: dword t % 16 of row t / 16), so the gathers of a rotated tile stay within a few
+// dozen rows of the moving map.  Every cell is evaluated by the rule as written, from its own lattice index -- nothing is stepped
+// along a row: the world point anchor + (double)I / scale, the footprint's sample points, each through the inverse correction and
+// occ_cell onto the moving lattice, one byte read there; the target's state at the same index; code and merged state by the table.
+// The thread writes one dword of cells and one of codes (the cells of the row padding 0).  The six counters travel as six 10-bit
+// fields of one 64-bit word (a wave holds 256 cells): lanes -> wave by shuffles, the four waves through LDS, one 64-bit atomicAdd per
+// non-zero counter and workgroup -- integer sums, no atomic decides a position or a value.  Neither input is written.
+__global__ __launch_bounds__(256) void k_map_merge(MergeJob q, uint8_t * __restrict__ cells, uint8_t * __restrict__ codes,
+  unsigned long long * __restrict__ counts)
+{
+  __shared__ unsigned long long part[4];
+  const int32_t col = 4 * (int32_t)(blockIdx.x * (kMergeTileWidth / 4) + (threadIdx.x & 15));
+  const int32_t row = (int32_t)(blockIdx.y * kMergeTileHeight + (threadIdx.x >> 4));
+  unsigned long long n = 0ull;
+  if (row < q.height && col < q.ws) {
+    const int32_t lj = q.oy + row;
+    const double wy = q.target.ay + (double)lj / q.target.scale;
+    uint32_t cell4 = 0u, code4 = 0u;
+#pragma unroll
+    for (int32_t e = 0; e < 4; ++e) {
+      if (col + e < q.width) {
+        const int32_t li = q.ox + col + e;
+        const double wx = q.target.ax + (double)li / q.target.scale;
+        bool occupied = false, is_free = false;
+        for (int32_t b = 0; b < q.footprint; ++b) {
+          const double sy = wy + q.d[b];
+          for (int32_t a = 0; a < q.footprint; ++a) {
+            const double sx = wx + q.d[a];
+            const double px = (q.c * sx - q.s * sy) + q.tx, py = (q.s * sx + q.c * sy) + q.ty;
+            const uint32_t state = merge_state(q.moving, occ_cell(px, q.moving.ax, q.moving.scale), occ_cell(py, q.moving.ay, q.moving.scale));
+            occupied = occupied || state == 100u;
+            is_free = is_free || state == 255u;
+          }
+        }
+        const uint32_t m = occupied ? 100u : is_free ? 255u : 0u;
+        const uint32_t raw = merge_state(q.target, li, lj);
+        const uint32_t t = (raw == 100u || raw == 255u) ? raw : 0u;
+        uint32_t code = KH_MERGED_NEITHER, cell = 0u;
+        int32_t counter = -1;
+        if (t == 0u) {
+          if (m != 0u) {code = KH_MERGED_MOVING_ONLY; cell = m; counter = kMergeMovingOnly;}
+        } else if (m == 0u) {
+          code = KH_MERGED_TARGET_ONLY; cell = t; counter = kMergeTargetOnly;
+        } else if (t == m) {
+          code = KH_MERGED_AGREE; cell = t; counter = t == 255u ? kMergeAgreeFree : kMergeAgreeOccupied;
+        } else {
+          code = m == 100u ? KH_MERGED_MOVING_OCCUPIED : KH_MERGED_MOVING_FREE;
+          counter = m == 100u ? kMergeMovingOccupied : kMergeMovingFree;
+          cell = q.conflict == KH_MERGE_CONFLICT_TARGET ? t : q.conflict == KH_MERGE_CONFLICT_MOVING ? m : q.conflict == KH_MERGE_CONFLICT_OCCUPIED ? 100u : 0u;
+        }
+        cell4 |= cell << (8 * e); code4 |= code << (8 * e);
+        if (counter >= 0) {n += 1ull << (10 * counter);}
+      }
+    }
+    const int64_t at = ((int64_t)row * q.ws + col) >> 2;
+    reinterpret_cast<uint32_t *>(cells)[at] = cell4;
+    reinterpret_cast<uint32_t *>(codes)[at] = code4;
+  }
+#pragma unroll
+  for (int32_t d = 32; d >= 1; d >>= 1) {n += __shfl_xor(n, d);}
+  if ((threadIdx.x & 63) == 0) {part[threadIdx.x >> 6] = n;}
+  __syncthreads();
+  if (threadIdx.x < kMergeCounters) {
+    const int32_t shift = 10 * (int32_t)threadIdx.x;
+    const unsigned long long v = ((part[0] >> shift) & 0x3FFull) + ((part[1] >> shift) & 0x3FFull) + ((part[2] >> shift) & 0x3FFull) +
+      ((part[3] >> shift) & 0x3FFull);
+    if (v) {atomicAdd(&counts[threadIdx.x], v);}
+  }
+}
+
+void map_known_box(void * stream, const kh_map_view & v, int32_t * d_box)
+{
+  hipLaunchKernelGGL(k_map_known_box, dim3(static_cast<unsigned>(std::min(v.height, 1024))), dim3(256), 0, static_cast<hipStream_t>(stream), window_of(v),
+    d_box);
+}
+
+void map_merge_cells(void * stream, const MergeJob & job, uint8_t * d_cells, uint8_t * d_codes, unsigned long long * d_counts)
+{
+  const dim3 blocks(static_cast<unsigned>((job.ws + kMergeTileWidth - 1) / kMergeTileWidth), static_cast<unsigned>((job.height + kMergeTileHeight - 1) / kMergeTileHeight));
+  hipLaunchKernelGGL(k_map_merge, blocks, dim3(256), 0, static_cast<hipStream_t>(stream), job, d_cells, d_codes, d_counts);
 }
 
 struct MapWork : DeviceWork {};

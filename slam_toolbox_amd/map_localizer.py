@@ -9,6 +9,7 @@ LiveMap, or a hand-filled capi.KhMapView -- and nothing else: no scans, no pose 
     step = loc.process(next_ranges, next_odometric_pose)   # ... and from there on, scan by scan
     cast = loc.expected(step.sensor_pose)                  # what the map expects every beam to measure there (kh_map_raycast)
     candidates, _ = loc.align(other_map)                   # where a second map lies in this one (kh_map_align; section 7m)
+    merged = loc.merge(other_map, candidates[0].correction)   # ... and the two as one map (kh_map_merge_*; section 7n)
 
 Nothing here computes: every call lands in the library."""
 from __future__ import annotations
@@ -34,8 +35,10 @@ def _fit_dict(f):
 
 
 def _view_of(source):
-    """a capi.KhMapView, or anything with .view() (OccupancyGrid, LiveMap)"""
-    return source if isinstance(source, capi.KhMapView) else source.view()
+    """a capi.KhMapView, or anything with .view() (OccupancyGrid, LiveMap, MapChanges) or a .view that is one (MapMerge)"""
+    if isinstance(source, capi.KhMapView):
+        return source
+    return source.view() if callable(source.view) else source.view
 
 
 def _laser_of(laser):
@@ -217,6 +220,14 @@ class MapLocalizer:
         cands = [AlignCandidate(np.array(c.correction), c.probe_seed, c.hypothesis, c.fine_response, c.index, bool(c.enough), _fit_dict(c.fit))
                  for c in out[:min(n.value, int(cap))]]
         return cands, times
+
+    def merge(self, moving, correction, **kw):
+        """kh_map_merge_create with the localizer's map as the target: `moving` laid into it under `correction` (an AlignCandidate's, as
+        `align` returns them).  kw: footprint, conflict, grow.  -> map_merge.MapMerge; its .view is the merged map on this map's lattice"""
+        from .map_merge import MapMerge
+        if self._map is None:
+            raise capi.KartoHipError(capi.KH_ERR_NOT_FOUND, "MapLocalizer.merge: no map set")
+        return MapMerge(self._map, moving, correction, **kw)
 
     def stats(self) -> dict:
         st = capi.KhMapLocalizerStats()
