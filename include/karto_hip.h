@@ -1583,6 +1583,119 @@ KH_API int kh_map_merge_read(kh_map_merge * m, uint8_t * cells, uint8_t * codes)
 /* the merged cells as width * height nav values, kh_occupancy_read_nav's mapping, no row padding */
 KH_API int kh_map_merge_read_nav(kh_map_merge * m, int8_t * out);
 
+/* ---------------------------------------------------------------- the distance field of a map
+ * How far every cell of a map lies from the nearest obstacle, and three readers of that: costmap values, clearance at world points,
+ * a dense endpoint score of a scan at many poses with the pose refinement built on it.  Every quantity a kernel produces is an
+ * INTEGER -- squared distances in cells, counts, sums of squared distances -- and every square root, division by scale and exp is
+ * taken on the host from those integers.
+ *   field    a SNAPSHOT of the view's window [ox, ox + width) x [oy, oy + height): the handle copies the cells, the view may go or
+ *            change once kh_map_field_create returns.  Cells outside the window do not exist (an obstacle there is not seen);
+ *            columns width .. width_step - 1 are never read.  An obstacle is a cell of state 100 (KH_FIELD_OBSTACLE_OCCUPIED) or of
+ *            any state other than 255 (KH_FIELD_OBSTACLE_NOT_FREE).  R = ceil(max_distance * scale) cells; max_distance 0 gives
+ *            R = 0: uncapped.  For window cell (i, j): d2 = min over obstacle cells (a, b) of (i - a)^2 + (j - b)^2; the stored value
+ *            is d2 when R == 0 or d2 <= R * R, else KH_FIELD_FAR; without any obstacle every value is KH_FIELD_FAR.  With sides of at
+ *            most 32768 cells d2 < 2^31: KH_FIELD_FAR is no value.  In metres: sqrt((double)d2) / scale, +inf for KH_FIELD_FAR. */
+#define KH_FIELD_FAR 0xFFFFFFFFu
+enum {
+  KH_FIELD_OBSTACLE_OCCUPIED = 0,  /* state 100 (the default) */
+  KH_FIELD_OBSTACLE_NOT_FREE = 1   /* every state other than 255: unknown space is an obstacle too */
+};
+typedef struct kh_map_field kh_map_field;
+typedef struct kh_map_field_params {
+  double max_distance;         /* metres, finite, >= 0; 0 = uncapped (default 2.0) */
+  int32_t obstacles;           /* KH_FIELD_OBSTACLE_ (default KH_FIELD_OBSTACLE_OCCUPIED) */
+  int32_t pad;
+} kh_map_field_params;
+typedef struct kh_map_field_stats {
+  int32_t ox, oy, width, height;   /* the window */
+  int32_t radius_cells;        /* R */
+  uint32_t max_d2;             /* the largest value that is not KH_FIELD_FAR; 0 when there is none */
+  uint64_t n_obstacles, n_far; /* cells of value 0, cells of value KH_FIELD_FAR */
+  double times_ms[3];          /* the column and the row kernel by events, the whole call */
+} kh_map_field_stats;
+/* max_distance 2.0, KH_FIELD_OBSTACLE_OCCUPIED; a NULL output is ignored */
+KH_API void kh_map_field_params_default(kh_map_field_params * p);
+/* KH_ERR_INVALID_ARG before a device is looked for: a NULL view, params or out, a malformed view, a max_distance that is not finite
+ * or < 0, R > 1024, obstacles outside 0 .. 1, a side above 32768 cells or more than 2^28 cells, R == 0 with a side above 4096 cells
+ * (the uncapped row pass costs width x (largest distance) per row: a bound the arguments alone give).  Then KH_ERR_NO_DEVICE. */
+KH_API int kh_map_field_create(const kh_map_view * view, const kh_map_field_params * params, kh_map_field ** out);
+KH_API void kh_map_field_destroy(kh_map_field * f);
+KH_API int kh_map_field_stats_get(kh_map_field * f, kh_map_field_stats * out);
+/* the values and the distances in metres, width * height each, row-major with no row padding; either may be NULL */
+KH_API int kh_map_field_read(kh_map_field * f, uint32_t * d2, double * metres);
+
+/* ---- costmap values: the field through an inflation curve.  Rt = ceil(inflation_radius * scale); the table has n = Rt * Rt + 1
+ * entries indexed by d2; with m = sqrt((double)d2) / scale: d2 == 0 -> 254; m <= inscribed_radius -> 253; m <= inflation_radius ->
+ * (uint8_t)(252.0 * exp(-cost_scaling_factor * (m - inscribed_radius))), truncated toward zero; else 0.  (nav2's
+ * InflationLayer::computeCost restated from its published source; nothing here is pinned to nav2.)  A cell: c = table[d2] when
+ * d2 <= Rt * Rt, else 0; a cell of state 100 or 255 gets c; any other state (unknown) gets c with track_unknown == 0, and with
+ * track_unknown == 1 it gets 255 -- unless c >= 253, or inflate_unknown is set and c > 0: then c. */
+typedef struct kh_inflation_params {
+  double inscribed_radius, inflation_radius, cost_scaling_factor;   /* metres, metres, 1 / metres: finite, >= 0, inscribed <= inflation */
+  int32_t track_unknown, inflate_unknown;                           /* 0 / 1 */
+} kh_inflation_params;
+/* 0.22, 0.55, 10.0, 1, 0; a NULL output is ignored */
+KH_API void kh_inflation_params_default(kh_inflation_params * p);
+/* the table on the host, no device: *n = Rt * Rt + 1 (also when cap is too small), table takes the entries when cap >= *n (table may
+ * be NULL with cap 0).  KH_ERR_INVALID_ARG: NULL params or n, parameters as above, a scale that is not finite or <= 0, Rt > 1024,
+ * cap < 0, a table that cap says is there and is NULL, cap > 0 and < *n. */
+KH_API int kh_inflation_table(const kh_inflation_params * p, double scale, uint8_t * table, int32_t cap, int32_t * n);
+/* out takes width * height costs, no row padding.  KH_ERR_INVALID_ARG before a device is looked for: NULL params or out, the
+ * parameters as above but Rt; then KH_ERR_NO_DEVICE, the handle, Rt > 1024 at the field's scale, and a field with 0 < R < Rt (it
+ * does not reach as far as the costs ask). */
+KH_API int kh_map_field_costs(kh_map_field * f, const kh_inflation_params * p, uint8_t * out);
+
+/* ---- clearance at n world points (x, y): the lattice cell of a point is section 7k's round_half_away((v - anchor) * scale); a cell
+ * outside the window, or a coordinate beyond +-2^30 cells, is KH_CLEAR_OUTSIDE and +inf; a KH_FIELD_FAR value KH_CLEAR_FAR and +inf;
+ * anything else KH_CLEAR_OK and sqrt((double)d2) / scale.  Any output may be NULL.  n < 1, NULL xy, a non-finite point:
+ * KH_ERR_INVALID_ARG before a device is looked for. */
+enum { KH_CLEAR_OK = 0, KH_CLEAR_FAR = 1, KH_CLEAR_OUTSIDE = 2 };
+KH_API int kh_map_field_clearance(kh_map_field * f, int32_t n, const double * xy /* 2n */, double * metres, int32_t * status, uint32_t * d2);
+
+/* ---- the endpoint score of ONE scan's readings at n_poses sensor poses.  The beams of pose k are kh_map_fit's: kh_scan_points at
+ * that pose through AddScan's gate; only beams with a valid end (r < range_threshold - 1e-6) are scored, at the reading itself: no
+ * line is walked.  T = truncate_cells, or the field's R when it is 0; T2 = T * T.  n_kept: beams that pass the gate; n_hit: those with
+ * a valid end; n_inside: hit beams whose end cell lies in the window; n_near: those of them with a value <= T2; sum_d2: the sum of
+ * their values; cost = sum_d2 + (n_hit - n_near) * T2 -- the sum of min(d2, T2), a missing cell counted as T2; score = 1 - cost /
+ * (n_hit * T2) in doubles, 0 without a hit beam.  KH_ERR_INVALID_ARG before a device is looked for: NULL laser / ranges / sensor_poses
+ * / out, n_poses < 1, n_beams < 1, truncate_cells < 0 or > 1024.  Then KH_ERR_NO_DEVICE, the handle, and on the handle's lattice
+ * what kh_map_fit refuses of a laser and of poses; truncate_cells and R both 0. */
+typedef struct kh_field_score {
+  int32_t n_kept, n_hit, n_inside, n_near;
+  uint64_t sum_d2, cost;
+  double score;
+} kh_field_score;
+KH_API int kh_map_field_score(kh_map_field * f, const kh_laser * laser, const double * ranges, int32_t n_poses,
+                              const double * sensor_poses /* 3n */, int32_t truncate_cells, kh_field_score * out /* n */);
+
+/* ---- pose refinement: a compass search on the integer cost, all n starts in lockstep.  Every start is scored once where it
+ * stands (cost_start, n_hit); then, per round, one launch scores the 27 candidates of every start that still runs.  Candidate
+ * c = 0 .. 26 of a start at (x, y, h) with steps (s, s, a) is (x + (c % 3 - 1) * s, y + (c / 3 % 3 - 1) * s, h + (c / 9 - 1) * a), in
+ * exactly these double operations; the heading is not normalised.  The start moves to the candidate of least cost -- on a tie the
+ * centre (c = 13) if it is among the least, else the smallest c.  n_hit is the same for all candidates of a start (the gate reads
+ * only the range), so comparing cost alone compares the scores.  When the centre wins: with halvings == n_halvings the start is
+ * KH_REFINE_CONVERGED, else both steps are multiplied by 0.5 and halvings goes up by one.  A start that has run max_rounds rounds
+ * stops there with KH_REFINE_MAX_ROUNDS; a start one of whose candidates kh_map_field_score would refuse stops where it is, before
+ * that round, with KH_REFINE_LEFT_LATTICE. */
+typedef struct kh_field_refine_params {
+  double step_xy, step_heading;    /* metres > 0, radians >= 0: finite */
+  int32_t n_halvings, max_rounds;  /* 0 .. 32, 1 .. 4096 */
+  int32_t truncate_cells, pad;     /* as kh_map_field_score's */
+} kh_field_refine_params;
+/* 2 / scale, 0.02 rad, 4, 64, 0; a NULL output is ignored */
+KH_API void kh_field_refine_params_default(kh_field_refine_params * p, double scale);
+typedef struct kh_field_refined {
+  double pose[3];
+  uint64_t cost_start, cost;   /* at the start, at `pose` */
+  int32_t n_hit, rounds, halvings, status;
+} kh_field_refined;
+enum { KH_REFINE_CONVERGED = 0, KH_REFINE_MAX_ROUNDS = 1, KH_REFINE_LEFT_LATTICE = 2 };
+/* times_ms (may be NULL): the kernels by events summed, the whole call.  KH_ERR_INVALID_ARG before a device is looked for: what
+ * kh_map_field_score refuses there (the starts are its poses), NULL params, steps and counts outside the ranges above; after the
+ * handle what kh_map_field_score refuses there. */
+KH_API int kh_map_field_refine(kh_map_field * f, const kh_laser * laser, const double * ranges, int32_t n, const double * sensor_poses /* 3n */,
+                               const kh_field_refine_params * params, kh_field_refined * out /* n */, double times_ms[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -175,6 +175,9 @@ SYMBOLS = [
     "kh_map_raycast", "kh_map_align_params_default", "kh_map_align",
     "kh_map_merge_params_default", "kh_map_merge_create", "kh_map_merge_destroy", "kh_map_merge_stats_get", "kh_map_merge_view",
     "kh_map_merge_read", "kh_map_merge_read_nav",
+    "kh_map_field_params_default", "kh_map_field_create", "kh_map_field_destroy", "kh_map_field_stats_get", "kh_map_field_read",
+    "kh_inflation_params_default", "kh_inflation_table", "kh_map_field_costs", "kh_map_field_clearance", "kh_map_field_score",
+    "kh_field_refine_params_default", "kh_map_field_refine",
 ]
 
 
@@ -355,6 +358,39 @@ class KhMapMergeStats(C.Structure):
                [("agreement", C.c_double), ("times_ms", C.c_double * 3)]
 
 
+KH_FIELD_FAR = 0xFFFFFFFF
+KH_FIELD_OBSTACLE_OCCUPIED, KH_FIELD_OBSTACLE_NOT_FREE = 0, 1
+KH_CLEAR_OK, KH_CLEAR_FAR, KH_CLEAR_OUTSIDE = range(3)
+KH_REFINE_CONVERGED, KH_REFINE_MAX_ROUNDS, KH_REFINE_LEFT_LATTICE = range(3)
+
+
+class KhMapFieldParams(C.Structure):
+    _fields_ = [("max_distance", C.c_double), ("obstacles", C.c_int32), ("pad", C.c_int32)]
+
+
+class KhMapFieldStats(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("ox", "oy", "width", "height", "radius_cells")] + [("max_d2", C.c_uint32)] + \
+               [("n_obstacles", C.c_uint64), ("n_far", C.c_uint64), ("times_ms", C.c_double * 3)]
+
+
+class KhInflationParams(C.Structure):
+    _fields_ = [("inscribed_radius", C.c_double), ("inflation_radius", C.c_double), ("cost_scaling_factor", C.c_double),
+                ("track_unknown", C.c_int32), ("inflate_unknown", C.c_int32)]
+
+
+class KhFieldScore(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_kept", "n_hit", "n_inside", "n_near")] + [("sum_d2", C.c_uint64), ("cost", C.c_uint64), ("score", C.c_double)]
+
+
+class KhFieldRefineParams(C.Structure):
+    _fields_ = [("step_xy", C.c_double), ("step_heading", C.c_double)] + [(k, C.c_int32) for k in ("n_halvings", "max_rounds", "truncate_cells", "pad")]
+
+
+class KhFieldRefined(C.Structure):
+    _fields_ = [("pose", C.c_double * 3), ("cost_start", C.c_uint64), ("cost", C.c_uint64)] + \
+               [(k, C.c_int32) for k in ("n_hit", "rounds", "halvings", "status")]
+
+
 class KhMergeAlignParams(C.Structure):
     _fields_ = [("n_probes", C.c_int32), ("top_k", C.c_int32), ("min_known", C.c_uint64), ("min_pass_through", C.c_uint32), ("pad", C.c_uint32),
                 ("occupancy_threshold", C.c_double), ("relocalize", KhRelocalizeParams)]
@@ -482,6 +518,23 @@ def lib():
         L.kh_map_merge_view.argtypes = [vp, C.POINTER(KhMapView)]
         L.kh_map_merge_read.argtypes = [vp, vp, vp]
         L.kh_map_merge_read_nav.argtypes = [vp, vp]
+    if hasattr(L, "kh_map_field_create"):      # (KH_LIBRARY may name a build from before the distance field existed)
+        L.kh_map_field_params_default.argtypes = [C.POINTER(KhMapFieldParams)]
+        L.kh_map_field_params_default.restype = None
+        L.kh_map_field_create.argtypes = [C.POINTER(KhMapView), C.POINTER(KhMapFieldParams), C.POINTER(vp)]
+        L.kh_map_field_destroy.argtypes = [vp]
+        L.kh_map_field_destroy.restype = None
+        L.kh_map_field_stats_get.argtypes = [vp, C.POINTER(KhMapFieldStats)]
+        L.kh_map_field_read.argtypes = [vp, vp, vp]
+        L.kh_inflation_params_default.argtypes = [C.POINTER(KhInflationParams)]
+        L.kh_inflation_params_default.restype = None
+        L.kh_inflation_table.argtypes = [C.POINTER(KhInflationParams), dbl, vp, i32, C.POINTER(i32)]
+        L.kh_map_field_costs.argtypes = [vp, C.POINTER(KhInflationParams), vp]
+        L.kh_map_field_clearance.argtypes = [vp, i32, vp, vp, vp, vp]
+        L.kh_map_field_score.argtypes = [vp, C.POINTER(KhLaser), vp, i32, vp, i32, C.POINTER(KhFieldScore)]
+        L.kh_field_refine_params_default.argtypes = [C.POINTER(KhFieldRefineParams), dbl]
+        L.kh_field_refine_params_default.restype = None
+        L.kh_map_field_refine.argtypes = [vp, C.POINTER(KhLaser), vp, i32, vp, C.POINTER(KhFieldRefineParams), C.POINTER(KhFieldRefined), vp]
     if hasattr(L, "kh_spa_create"):
         L.kh_spa_options_default.argtypes = [C.POINTER(KhSpaOptions)]
         L.kh_spa_create.argtypes = [i32, C.POINTER(vp)]

@@ -1,6 +1,6 @@
 // What the occupancy module shares between its kernel files (occupancy.hip, occupancy_live.hip, occupancy_map.hip,
-// occupancy_changes.hip: the kernels and their launchers) and the host files that feed them: mapper_views.cpp (kh_mapper_build_map),
-// merge.cpp (kh_merge_build), live_map.cpp (kh_live_map_*), map_localizer.cpp, map_changes.cpp, map_align.cpp, map_merge.cpp.  Needs no HIP header:
+// occupancy_changes.hip, occupancy_field.hip: the kernels and their launchers) and the host files that feed them: mapper_views.cpp (kh_mapper_build_map),
+// merge.cpp (kh_merge_build), live_map.cpp (kh_live_map_*), map_localizer.cpp, map_changes.cpp, map_align.cpp, map_merge.cpp, map_field.cpp.  Needs no HIP header:
 // the CPU programs of tests/ include it.  Not part of the public ABI (include/karto_hip.h).  The live map's lattice, window and log
 // are stated in DESIGN.md section 7b, the map feed's tiles in 7c.
 #pragma once
@@ -280,6 +280,34 @@ void map_known_box(void * stream, const kh_map_view & v, int32_t * d_box);
 // k_map_merge on `stream`: d_cells and d_codes take one byte per cell of the strided output window (the padding 0), d_counts[6]
 // (zeroed by the caller) the window cells by counter (map_merge_plan.hpp's order).  Neither input is written.
 void map_merge_cells(void * stream, const MergeJob & job, uint8_t * d_cells, uint8_t * d_codes, unsigned long long * d_counts);
+
+// ---- the distance field of a map (occupancy_field.hip; kh_map_field_*; the handle and its buffers: map_field.cpp) ----
+// The field's own arrays on its window, all of row stride ws = field_stride(width), a multiple of 4: the copied cell states (the
+// padding 0), the column distances, the values.  As a window of the lattice it is what cell_at() indexes.
+struct FieldWindow
+{
+  const uint8_t * cells;
+  uint16_t * g;                // the column pass' answer; only k_field_columns and k_field_rows touch it
+  uint32_t * d2;
+  int32_t ox, oy, width, height, ws;
+  double ax, ay, scale;
+  int32_t radius, obstacles;   // R; KH_FIELD_OBSTACLE_
+};
+// k_field_columns on `stream`: g[row][col] = the distance along the column to the nearest obstacle of that column, kFieldNoColumn where
+// there is none (within R, for R > 0).  One launch whatever the map holds.
+void field_columns(void * stream, const FieldWindow & f);
+// k_field_rows on `stream`: d2 from g; d_counts[kFieldCounters] (zeroed by the caller) takes the cells of value 0, those of
+// KH_FIELD_FAR, and the largest other value.  false = the launch could not be prepared (the row's LDS)
+bool field_rows(void * stream, const FieldWindow & f, unsigned long long * d_counts);
+// k_field_costs on `stream`: d_out (stride ws) from the values through d_table (rt2 + 1 entries) and the unknown policy
+void field_costs(void * stream, const FieldWindow & f, const uint8_t * d_table, uint32_t rt2, int32_t track_unknown, int32_t inflate_unknown,
+  uint8_t * d_out);
+// k_field_lookup on `stream`: n points (x, y) -> their value and KH_CLEAR_ status
+void field_lookup(void * stream, const FieldWindow & f, int32_t n, const double * d_xy, uint32_t * d_d2, int32_t * d_status);
+// k_field_score on `stream`: k_map_fit's tables and launch shape; d_sums[kScoreCounters] per pose, zeroed by the caller.  The caller
+// has checked the laser and the poses (fit_inputs_check) and blocks_per_pose(n_beams, n_poses).
+void field_score(void * stream, const FieldWindow & f, const double * d_ranges, const double * d_points, const double * d_sensors, int32_t n_beams,
+  int32_t n_poses, double range_threshold, double min_range, double max_range, uint32_t t2, unsigned long long * d_sums);
 
 // ---- a change layer's kernels (occupancy_changes.hip; kh_map_changes_*; the handle and its buffers: map_changes.cpp) ----
 // the layer's two counter grids on the window of its view, row stride the view's width_step

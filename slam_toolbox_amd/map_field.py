@@ -1,0 +1,131 @@
+"""The distance field of a map over the C ABI (kh_map_field_*; include/karto_hip.h): how far every cell lies
+from the nearest obstacle, and what reads that -- costmap values, clearance at world points, the endpoint score of a scan at many
+poses and the pose refinement built on it.
+
+    field = MapField(grid, max_distance=2.0)                # a snapshot: the grid may change or go afterwards
+    field.metres                                            # (height, width) float64, +inf beyond max_distance
+    costs = field.costs(inflation_radius=0.55)              # (height, width) uint8 costmap values
+    metres, status, d2 = field.clearance([[1.0, 2.0]])      # how much room is there at (x, y)?
+    refined = field.refine(ranges, [sensor_pose], laser)    # descend the endpoint cost from a candidate pose
+
+Nothing here computes: every call lands in the library."""
+from __future__ import annotations
+
+import ctypes as C
+from collections import namedtuple
+
+import numpy as np
+
+from . import capi
+from .map_localizer import _laser_of, _view_of
+
+OBSTACLES = dict(occupied=capi.KH_FIELD_OBSTACLE_OCCUPIED, not_free=capi.KH_FIELD_OBSTACLE_NOT_FREE)
+SCORE_FIELDS = tuple(k for k, _ in capi.KhFieldScore._fields_)
+Refined = namedtuple("Refined", "pose cost_start cost n_hit rounds halvings status")
+
+
+def inflation_table(scale, **params):
+    """kh_inflation_table: the costs by squared distance in cells, (Rt * Rt + 1,) uint8.  params: fields of kh_inflation_params"""
+    p = _inflation(params)
+    n = C.c_int32()
+    capi.check(capi.lib().kh_inflation_table(C.byref(p), float(scale), None, 0, C.byref(n)), "kh_inflation_table")
+    table = np.zeros(n.value, dtype=np.uint8)
+    capi.check(capi.lib().kh_inflation_table(C.byref(p), float(scale), table.ctypes.data, n.value, C.byref(n)), "kh_inflation_table")
+    return table
+
+
+def _inflation(params):
+    p = capi.KhInflationParams()
+    capi.lib().kh_inflation_params_default(C.byref(p))
+    for k, v in params.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+class MapField:
+    def __init__(self, view, max_distance: float = 2.0, obstacles=capi.KH_FIELD_OBSTACLE_OCCUPIED):
+        """kh_map_field_create.  view: a capi.KhMapView or anything that has one (an OccupancyGrid, a LiveMap, a MapChanges, a
+        MapMerge).  max_distance in metres, 0: uncapped; obstacles: a KH_FIELD_OBSTACLE_ value or "occupied" / "not_free".  The
+        field is a snapshot: no reference to the view's owner is kept once this returns."""
+        self._h = C.c_void_p()
+        v = _view_of(view)
+        p = capi.KhMapFieldParams()
+        capi.lib().kh_map_field_params_default(C.byref(p))
+        p.max_distance, p.obstacles = float(max_distance), int(OBSTACLES.get(obstacles, obstacles))
+        capi.check(capi.lib().kh_map_field_create(C.byref(v), C.byref(p), C.byref(self._h)), "kh_map_field_create")
+        st = capi.KhMapFieldStats()
+        capi.check(capi.lib().kh_map_field_stats_get(self._h, C.byref(st)), "kh_map_field_stats_get")
+        self.stats = {k: (list(getattr(st, k)) if k == "times_ms" else getattr(st, k)) for k, _ in capi.KhMapFieldStats._fields_}
+        self.width, self.height, self.scale = st.width, st.height, v.scale
+
+    @property
+    def d2(self):
+        """the squared distances in cells, (height, width) uint32, capi.KH_FIELD_FAR beyond the radius"""
+        out = np.zeros((self.height, self.width), dtype=np.uint32)
+        capi.check(capi.lib().kh_map_field_read(self._h, out.ctypes.data, None), "kh_map_field_read")
+        return out
+
+    @property
+    def metres(self):
+        """the distances in metres, (height, width) float64, +inf beyond the radius"""
+        out = np.zeros((self.height, self.width), dtype=np.float64)
+        capi.check(capi.lib().kh_map_field_read(self._h, None, out.ctypes.data), "kh_map_field_read")
+        return out
+
+    def costs(self, **params):
+        """kh_map_field_costs: (height, width) uint8 costmap values.  params: fields of kh_inflation_params over its defaults"""
+        p = _inflation(params)
+        out = np.zeros((self.height, self.width), dtype=np.uint8)
+        capi.check(capi.lib().kh_map_field_costs(self._h, C.byref(p), out.ctypes.data), "kh_map_field_costs")
+        return out
+
+    def clearance(self, xy):
+        """kh_map_field_clearance of (n, 2) world points -> (metres (n,) float64, status (n,) int32 KH_CLEAR_, d2 (n,) uint32)"""
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        n = len(xy)
+        metres, status, d2 = np.zeros(max(1, n)), np.zeros(max(1, n), dtype=np.int32), np.zeros(max(1, n), dtype=np.uint32)
+        capi.check(capi.lib().kh_map_field_clearance(self._h, n, xy.ctypes.data, metres.ctypes.data, status.ctypes.data, d2.ctypes.data),
+                   "kh_map_field_clearance")
+        return metres[:n], status[:n], d2[:n]
+
+    def score(self, ranges, poses, laser, truncate_cells: int = 0):
+        """kh_map_field_score: one scan's readings at each of `poses` (n, 3) sensor poses -> list of n dicts (kh_field_score's fields)"""
+        L = laser if isinstance(laser, capi.KhLaser) else _laser_of(laser)
+        ranges = np.ascontiguousarray(ranges, dtype=np.float64)
+        assert ranges.shape == (L.n_beams,)
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+        out = (capi.KhFieldScore * max(1, len(poses)))()
+        capi.check(capi.lib().kh_map_field_score(self._h, C.byref(L), ranges.ctypes.data, len(poses), poses.ctypes.data, int(truncate_cells), out),
+                   "kh_map_field_score")
+        return [{k: getattr(out[i], k) for k in SCORE_FIELDS} for i in range(len(poses))]
+
+    def refine(self, ranges, poses, laser, **params):
+        """kh_map_field_refine from each of `poses` (n, 3) sensor poses.  params: fields of kh_field_refine_params over its defaults
+        for this field's scale.  -> (list of n Refined records, times_ms: the kernels, the call)"""
+        L = laser if isinstance(laser, capi.KhLaser) else _laser_of(laser)
+        ranges = np.ascontiguousarray(ranges, dtype=np.float64)
+        assert ranges.shape == (L.n_beams,)
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+        p = capi.KhFieldRefineParams()
+        capi.lib().kh_field_refine_params_default(C.byref(p), self.scale)
+        for k, v in params.items():
+            if not hasattr(p, k):
+                raise KeyError(k)
+            setattr(p, k, v)
+        out, times = (capi.KhFieldRefined * max(1, len(poses)))(), np.zeros(2)
+        capi.check(capi.lib().kh_map_field_refine(self._h, C.byref(L), ranges.ctypes.data, len(poses), poses.ctypes.data, C.byref(p), out,
+                                                  times.ctypes.data), "kh_map_field_refine")
+        return [Refined(np.array(r.pose), r.cost_start, r.cost, r.n_hit, r.rounds, r.halvings, r.status) for r in out[:len(poses)]], times
+
+    def close(self):
+        if self._h:
+            capi.lib().kh_map_field_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

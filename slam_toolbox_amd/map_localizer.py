@@ -10,6 +10,7 @@ LiveMap, or a hand-filled capi.KhMapView -- and nothing else: no scans, no pose 
     cast = loc.expected(step.sensor_pose)                  # what the map expects every beam to measure there (kh_map_raycast)
     candidates, _ = loc.align(other_map)                   # where a second map lies in this one (kh_map_align; section 7m)
     merged = loc.merge(other_map, candidates[0].correction)   # ... and the two as one map (kh_map_merge_*; section 7n)
+    refined, _ = loc.refine(ranges, hyps[0].fine_mean, truncate_cells=6)   # a pose descended on the map's distance field (section 7o)
 
 Nothing here computes: every call lands in the library."""
 from __future__ import annotations
@@ -228,6 +229,26 @@ class MapLocalizer:
         if self._map is None:
             raise capi.KartoHipError(capi.KH_ERR_NOT_FOUND, "MapLocalizer.merge: no map set")
         return MapMerge(self._map, moving, correction, **kw)
+
+    def field(self, **params):
+        """kh_map_field_create on the localizer's map: its distance field (a snapshot).  params: max_distance, obstacles.
+        -> map_field.MapField"""
+        from .map_field import MapField
+        if self._map is None:
+            raise capi.KartoHipError(capi.KH_ERR_NOT_FOUND, "MapLocalizer.field: no map set")
+        return MapField(self._map, **params)
+
+    def refine(self, ranges, sensor_pose, field=None, max_distance: float = 2.0, **params):
+        """kh_map_field_refine of `sensor_pose` (3,) or poses (n, 3) -- a hypothesis' or a tracking step's -- with this localizer's
+        laser, on `field` (a MapField of the current map, as `field()` makes them) or on one made for this call.  params: fields of
+        kh_field_refine_params.  -> (list of map_field.Refined, times_ms)"""
+        own = field is None
+        f = self.field(max_distance=max_distance) if own else field
+        try:
+            return f.refine(self._ranges(ranges), sensor_pose, self._laser, **params)
+        finally:
+            if own:
+                f.close()
 
     def stats(self) -> dict:
         st = capi.KhMapLocalizerStats()
