@@ -1696,6 +1696,47 @@ enum { KH_REFINE_CONVERGED = 0, KH_REFINE_MAX_ROUNDS = 1, KH_REFINE_LEFT_LATTICE
 KH_API int kh_map_field_refine(kh_map_field * f, const kh_laser * laser, const double * ranges, int32_t n, const double * sensor_poses /* 3n */,
                                const kh_field_refine_params * params, kh_field_refined * out /* n */, double times_ms[2]);
 
+/* ---------------------------------------------------------------- a field that follows its map
+ * kh_map_field_update brings an existing field up to date with a view of the same lattice by the part of the map that changed, exact
+ * to the bit: afterwards every value, every reader and the statistics are what kh_map_field_create on the same view gives.  A field
+ * that has been updated keeps its column distances resident.  For a capped field (R > 0) a value can change only within R cells
+ * (Chebyshev) of a cell whose OBSTACLE-NESS changed: the call compares the view with the field's copy of the cells over `rect`,
+ * finds the box of those cells, and recomputes that box grown by R.  An uncapped field (R == 0) is always recomputed whole.
+ *   cells_box    the bounding box of the cells whose state changed at all (costs depend on the state)
+ *   values_box   the bounding box of the cells whose obstacle-ness changed, grown by R and clipped to the window: every value that
+ *                changed lies inside; after a rebuild both boxes are the whole window
+ * Boxes and rectangles are x, y, w, h in lattice cells (the units of ox, oy); all zero = none. */
+typedef struct kh_field_update {
+  int32_t cells_box[4], values_box[4];
+  int32_t rebuilt, relayout;              /* the whole window was recomputed / the window differs from the previous one */
+  int64_t cells_compared, cells_recomputed;  /* cells of `rect` compared with the copy (0 for a rebuild); the area of values_box */
+  double times_ms[4];                     /* compare, columns, rows by device events (0 where none ran); the call by wall time */
+} kh_field_update;
+/* The caller promises that cells outside `rect` (NULL: the whole window) equal the field's copy; rect is clipped to the window, an
+ * empty clip (w or h <= 0 among them) does nothing and is KH_OK.  `out` may be NULL.  KH_ERR_INVALID_ARG before a device is looked
+ * for: a NULL or malformed view; with a handle, a view off the field's lattice -- anchor x, anchor y, scale (each compared by its
+ * bits), device, in this order -- or a new window beyond kh_map_field_create's limits.  Then KH_ERR_NO_DEVICE and the handle.  A view
+ * whose window (ox, oy, width, height) differs reallocates and rebuilds (relayout = rebuilt = 1); so does the first update of a
+ * field made by kh_map_field_create (rebuilt = 1: it allocates the column distances), every update of an uncapped field, and the
+ * update after one that failed with KH_ERR_HIP (the field stays usable; what it holds until then is undefined inside `rect` grown
+ * by R). */
+KH_API int kh_map_field_update(kh_map_field * f, const kh_map_view * view, const int32_t rect[4], kh_field_update * out);
+/* debugging: the height in rows of the bands the column pass of an update is cut into; 0 = the library's choice (max(R, 8)).  The
+ * result does not depend on it.  rows < 0: KH_ERR_INVALID_ARG. */
+KH_API int kh_map_field_set_band_rows(kh_map_field * f, int32_t rows);
+/* the values / the costs of lattice cells [x, x + w) x [y, y + h), dense and row-major.  KH_ERR_INVALID_ARG before a device is
+ * looked for: a NULL output, w or h < 1, and for the costs what kh_map_field_costs refuses there; after the handle: a rectangle that
+ * does not lie inside the window, and what kh_map_field_costs refuses there. */
+KH_API int kh_map_field_read_rect(kh_map_field * f, int32_t x, int32_t y, int32_t w, int32_t h, uint32_t * d2);
+KH_API int kh_map_field_costs_rect(kh_map_field * f, const kh_inflation_params * p, int32_t x, int32_t y, int32_t w, int32_t h, uint8_t * out);
+/* A field of the live map's current window that follows it: kh_live_map_update adds the cells it handed to the cell-state kernel to
+ * the field's pending region (as it does for a kh_map_feed), kh_live_map_field_sync is kh_map_field_update with the live map's
+ * current view and that region, and clears it; with nothing pending it launches nothing and reports no box.  The field borrows the
+ * live map: kh_map_field_destroy detaches it; a live map destroyed first leaves the field readable and its sync KH_ERR_INVALID_ARG,
+ * as is the sync of a field that is not attached.  kh_live_map_field_create: KH_ERR_NOT_FOUND before the live map has a window. */
+KH_API int kh_live_map_field_create(kh_live_map * g, const kh_map_field_params * params, kh_map_field ** out);
+KH_API int kh_live_map_field_sync(kh_map_field * f, kh_field_update * out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,6 +178,8 @@ SYMBOLS = [
     "kh_map_field_params_default", "kh_map_field_create", "kh_map_field_destroy", "kh_map_field_stats_get", "kh_map_field_read",
     "kh_inflation_params_default", "kh_inflation_table", "kh_map_field_costs", "kh_map_field_clearance", "kh_map_field_score",
     "kh_field_refine_params_default", "kh_map_field_refine",
+    "kh_map_field_update", "kh_map_field_set_band_rows", "kh_map_field_read_rect", "kh_map_field_costs_rect",
+    "kh_live_map_field_create", "kh_live_map_field_sync",
 ]
 
 
@@ -391,6 +393,11 @@ class KhFieldRefined(C.Structure):
                [(k, C.c_int32) for k in ("n_hit", "rounds", "halvings", "status")]
 
 
+class KhFieldUpdate(C.Structure):
+    _fields_ = [("cells_box", C.c_int32 * 4), ("values_box", C.c_int32 * 4), ("rebuilt", C.c_int32), ("relayout", C.c_int32),
+                ("cells_compared", C.c_int64), ("cells_recomputed", C.c_int64), ("times_ms", C.c_double * 4)]
+
+
 class KhMergeAlignParams(C.Structure):
     _fields_ = [("n_probes", C.c_int32), ("top_k", C.c_int32), ("min_known", C.c_uint64), ("min_pass_through", C.c_uint32), ("pad", C.c_uint32),
                 ("occupancy_threshold", C.c_double), ("relocalize", KhRelocalizeParams)]
@@ -535,6 +542,13 @@ def lib():
         L.kh_field_refine_params_default.argtypes = [C.POINTER(KhFieldRefineParams), dbl]
         L.kh_field_refine_params_default.restype = None
         L.kh_map_field_refine.argtypes = [vp, C.POINTER(KhLaser), vp, i32, vp, C.POINTER(KhFieldRefineParams), C.POINTER(KhFieldRefined), vp]
+    if hasattr(L, "kh_map_field_update"):      # (KH_LIBRARY may name a build from before a field could follow its map)
+        L.kh_map_field_update.argtypes = [vp, C.POINTER(KhMapView), C.POINTER(i32 * 4), C.POINTER(KhFieldUpdate)]
+        L.kh_map_field_set_band_rows.argtypes = [vp, i32]
+        L.kh_map_field_read_rect.argtypes = [vp, i32, i32, i32, i32, vp]
+        L.kh_map_field_costs_rect.argtypes = [vp, C.POINTER(KhInflationParams), i32, i32, i32, i32, vp]
+        L.kh_live_map_field_create.argtypes = [vp, C.POINTER(KhMapFieldParams), C.POINTER(vp)]
+        L.kh_live_map_field_sync.argtypes = [vp, C.POINTER(KhFieldUpdate)]
     if hasattr(L, "kh_spa_create"):
         L.kh_spa_options_default.argtypes = [C.POINTER(KhSpaOptions)]
         L.kh_spa_create.argtypes = [i32, C.POINTER(vp)]

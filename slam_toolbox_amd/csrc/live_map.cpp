@@ -14,7 +14,8 @@
 // in occupancy_live.hip (k_occ_trace_delta, k_occ_update_rect, k_nav_feed).
 //
 // The map feed (kh_map_feed_*) is at the end: the published grid of one consumer, the pending region the
-// updates leave it, and the poll that hands out the 16 x 16 tiles whose nav values changed.
+// updates leave it, and the poll that hands out the 16 x 16 tiles whose nav values changed.  After it the distance fields that
+// follow the live map (kh_live_map_field_*): the same pending region, handed to kh_map_field_update.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -55,6 +56,9 @@ struct kh_live_map
   bool counters_suspect = false;             // an update failed half-way: the next one rebuilds
   kh_live_map_stats_t stats;
   std::vector<kh_map_feed *> feeds;          // the feeds attached (they borrow the live map); none: nothing below looks at them
+  // a distance field that follows the map, and its pending region in lattice cells (as a feed's)
+  struct Follower {kh_map_field * field; bool pending_whole; Rect pending;};
+  std::vector<Follower> fields;
 };
 
 struct kh_map_feed
@@ -262,13 +266,16 @@ int launch_stage(kh_live_map * g, const UpdatePlan & plan, uint32_t min_pass_thr
   return KH_OK;
 }
 
-// the cells an update handed to the cell-state kernel, for every feed attached: window columns / rows -> lattice cells
-void feeds_pending(kh_live_map * g, const Traced & t)
+// the cells an update handed to the cell-state kernel, for everything attached -- feeds and fields: window columns / rows ->
+// lattice cells
+void followers_pending(kh_live_map * g, const Traced & t)
 {
-  for (kh_map_feed * f : g->feeds) {
-    if (t.given_whole) {f->pending_whole = true; continue;}
-    f->pending = f->pending.join(t.given.moved_by(g->win.ox, g->win.oy));
-  }
+  auto add = [&](bool & whole, Rect & pending) {
+    if (t.given_whole) {whole = true; return;}
+    pending = pending.join(t.given.moved_by(g->win.ox, g->win.oy));
+  };
+  for (kh_map_feed * f : g->feeds) {add(f->pending_whole, f->pending);}
+  for (kh_live_map::Follower & f : g->fields) {add(f.pending_whole, f.pending);}
 }
 
 // the update has happened: the host's copy of the log, the parameters, the feeds and the stats follow
@@ -278,7 +285,7 @@ void commit_stage(kh_live_map * g, const std::vector<SensorView> & views, const 
   commit(g->log, views, plan);
   g->have_params = true; g->min_pass = min_pass_through; g->threshold = occupancy_threshold;
   g->all_cells_stale = false; g->counters_suspect = false;
-  if (t.cells_given > 0) {feeds_pending(g, t);}
+  if (t.cells_given > 0) {followers_pending(g, t);}
   kh_live_map_counts & last = g->stats.last;
   std::memset(&last, 0, sizeof(last));
   last.scans_added = plan.n_added; last.scans_removed = static_cast<int64_t>(plan.gone.size()); last.scans_moved = plan.n_moved;
@@ -348,6 +355,7 @@ void kh_live_map_destroy(kh_live_map * g)
   (void)hipSetDevice(g->device);
   if (g->stream) {(void)hipStreamSynchronize(g->stream);}
   for (kh_map_feed * f : g->feeds) {f->live = nullptr;}         // (feeds are to be destroyed first; one that was not must not follow us)
+  for (kh_live_map::Follower & f : g->fields) {map_field_set_live(f.field, nullptr);}      // (a field stays readable)
   free_window(g->win);
   (void)hipFree(g->d_log); (void)hipFree(g->d_records); (void)hipFree(g->d_counters);
   if (g->ev[0]) {(void)hipEventDestroy(g->ev[0]);}
@@ -634,4 +642,51 @@ int kh_map_feed_stats(const kh_map_feed * f, kh_map_feed_stats_t * out)
   return KH_OK;
 }
 
+// ---------------------------------------------------------------- the fields that follow the live map
+
+int kh_live_map_field_create(kh_live_map * g, const kh_map_field_params * params, kh_map_field ** out)
+{
+  if (!out) {return KH_ERR_INVALID_ARG;}
+  *out = nullptr;
+  if (!params) {return KH_ERR_INVALID_ARG;}
+  if (require_device(0) != KH_OK) {return KH_ERR_NO_DEVICE;}
+  if (!g) {return KH_ERR_INVALID_ARG;}
+  kh_map_view view;
+  int rc = kh_live_map_view(g, &view);
+  if (rc != KH_OK) {return rc;}
+  kh_map_field * f = nullptr;
+  if ((rc = map_field_create_empty(view, *params, "kh_live_map_field_create", &f)) != KH_OK) {return rc;}
+  if ((rc = kh_map_field_update(f, &view, nullptr, nullptr)) != KH_OK) {kh_map_field_destroy(f); return rc;}
+  map_field_set_live(f, g);
+  g->fields.push_back(kh_live_map::Follower{f, false, Rect{}});
+  *out = f;
+  return KH_OK;
+}
+
+// A sync that fails leaves the region pending; the field's own failure rule (kh_map_field_update) makes its next update a rebuild.
+int kh_live_map_field_sync(kh_map_field * f, kh_field_update * out)
+{
+  if (out) {std::memset(out, 0, sizeof(*out));}
+  if (require_device(0) != KH_OK) {return KH_ERR_NO_DEVICE;}
+  kh_live_map * const g = f ? map_field_live(f) : nullptr;
+  if (!g) {set_error("kh_live_map_field_sync: the field follows no live map (never attached, or the live map has been destroyed)"); return KH_ERR_INVALID_ARG;}
+  auto it = std::find_if(g->fields.begin(), g->fields.end(), [f](const kh_live_map::Follower & o) {return o.field == f;});
+  if (it == g->fields.end()) {return KH_ERR_INVALID_ARG;}
+  if (!it->pending_whole && it->pending.empty()) {return KH_OK;}
+  kh_map_view view;
+  int rc = kh_live_map_view(g, &view);
+  if (rc != KH_OK) {return rc;}
+  const int32_t rect[4] = {static_cast<int32_t>(it->pending.x0), static_cast<int32_t>(it->pending.y0), static_cast<int32_t>(it->pending.width()),
+    static_cast<int32_t>(it->pending.height())};
+  if ((rc = kh_map_field_update(f, &view, it->pending_whole ? nullptr : rect, out)) != KH_OK) {return rc;}
+  it->pending_whole = false; it->pending = Rect{};
+  return KH_OK;
+}
+
 }  // extern "C"
+
+void kh::live_map_forget_field(kh_live_map * g, kh_map_field * f)
+{
+  std::vector<kh_live_map::Follower> & fields = g->fields;
+  fields.erase(std::remove_if(fields.begin(), fields.end(), [f](const kh_live_map::Follower & o) {return o.field == f;}), fields.end());
+}

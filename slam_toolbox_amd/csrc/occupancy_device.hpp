@@ -1,5 +1,5 @@
 // What the occupancy module shares between its kernel files (occupancy.hip, occupancy_live.hip, occupancy_map.hip,
-// occupancy_changes.hip, occupancy_field.hip: the kernels and their launchers) and the host files that feed them: mapper_views.cpp (kh_mapper_build_map),
+// occupancy_changes.hip, occupancy_field.hip, occupancy_field_update.hip: the kernels and their launchers) and the host files that feed them: mapper_views.cpp (kh_mapper_build_map),
 // merge.cpp (kh_merge_build), live_map.cpp (kh_live_map_*), map_localizer.cpp, map_changes.cpp, map_align.cpp, map_merge.cpp, map_field.cpp.  Needs no HIP header:
 // the CPU programs of tests/ include it.  Not part of the public ABI (include/karto_hip.h).  The live map's lattice, window and log
 // are stated in DESIGN.md section 7b, the map feed's tiles in 7c.
@@ -308,6 +308,35 @@ void field_lookup(void * stream, const FieldWindow & f, int32_t n, const double 
 // has checked the laser and the poses (fit_inputs_check) and blocks_per_pose(n_beams, n_poses).
 void field_score(void * stream, const FieldWindow & f, const double * d_ranges, const double * d_points, const double * d_sensors, int32_t n_beams,
   int32_t n_poses, double range_threshold, double min_range, double max_range, uint32_t t2, unsigned long long * d_sums);
+
+// ---- a field that follows its map (occupancy_field_update.hip; kh_map_field_update; the rules: map_field_update_plan.hpp) ----
+// window columns [x0, x1) and rows [y0, y1)
+struct FieldRect {int32_t x0, y0, x1, y1;};
+// what k_field_changed leaves: two inclusive boxes (x0, y0, x1, y1) in window columns / rows -- the cells whose state changed, the
+// cells whose obstacle-ness changed; the caller sets both to (INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN) -- and, as one uint64 in
+// the last two words, the cells compared (set to 0)
+enum : int32_t {kChangedStates = 0, kChangedObstacles = 4, kChangedCount = 8, kChangedWords = 10};
+// k_field_changed on `stream`: the view's cells (row stride view_ws, first window cell first) against d_snapshot (the field's copy,
+// f.cells) over `r`; the copy takes the view's cells
+void field_changed(void * stream, const FieldWindow & f, uint8_t * d_snapshot, const uint8_t * d_view_cells, int32_t view_ws, const FieldRect & r,
+  int32_t * d_result);
+// k_field_columns_band on `stream`, capped fields only: k_field_columns' answer on the whole quads of columns that hold [x0, x1), rows
+// [y0, y1), cut into bands of band_rows >= 1 rows
+void field_columns_band(void * stream, const FieldWindow & f, const FieldRect & r, int32_t band_rows);
+// k_field_rows_region on `stream`, capped fields only: k_field_rows' values for the cells of `r`, no counters.  false = the launch
+// could not be prepared
+bool field_rows_region(void * stream, const FieldWindow & f, const FieldRect & r);
+// k_field_costs_rect on `stream`: k_field_costs' costs of the cells of `r`, row-major of row stride out_ws (a multiple of 4)
+void field_costs_rect(void * stream, const FieldWindow & f, const FieldRect & r, const uint8_t * d_table, uint32_t rt2, int32_t track_unknown,
+  int32_t inflate_unknown, uint8_t * d_out, int32_t out_ws);
+// k_field_count on `stream`: k_field_rows' three counters (zeroed by the caller) from the values as they stand
+void field_count(void * stream, const FieldWindow & f, unsigned long long * d_counts);
+// the live binding, between map_field.cpp and live_map.cpp: the live map a field follows (nullptr: none, or destroyed under it);
+// an empty field on the view's lattice that its first update builds; the live map forgets a field that is being destroyed
+kh_live_map * map_field_live(const kh_map_field * f);
+void map_field_set_live(kh_map_field * f, kh_live_map * g);
+int map_field_create_empty(const kh_map_view & view, const kh_map_field_params & params, const char * who, kh_map_field ** out);
+void live_map_forget_field(kh_live_map * g, kh_map_field * f);
 
 // ---- a change layer's kernels (occupancy_changes.hip; kh_map_changes_*; the handle and its buffers: map_changes.cpp) ----
 // the layer's two counter grids on the window of its view, row stride the view's width_step

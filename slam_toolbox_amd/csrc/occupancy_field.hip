@@ -1,5 +1,6 @@
 // The distance field of a map (kh_map_field_*): the two passes of the exact Euclidean distance transform
-// (k_field_columns, k_field_rows) and the field's three readers (k_field_costs, k_field_lookup, k_field_score), with their launchers.
+// (k_field_columns, k_field_rows) and the field's three readers (k_field_costs and its rectangle form, k_field_lookup, k_field_score),
+// with their launchers.  The kernels of an update (section 7p): occupancy_field_update.hip.
 // Every kernel works on the field's OWN arrays (FieldWindow: the copied cells, the column distances, the values, all of one row stride
 // that is a multiple of 4), so every dword and every 16-byte access is aligned whatever view the field was made from.  Everything a
 // kernel produces is an integer: no result depends on the order of an atomic, none is decided by one.  The handle: map_field.cpp;
@@ -144,6 +145,14 @@ __global__ __launch_bounds__(256) void k_field_rows(FieldWindow f, unsigned long
 // Costmap values: one thread per four cells -- a dword of states, 16 bytes of values, a dword of costs.  c = table[d2] where d2 <=
 // rt2, else 0 (KH_FIELD_FAR lies above every rt2); an unknown cell (neither 100 nor 255) under track_unknown is 255 unless c >= 253
 // or, with inflate_unknown, c > 0.  The cells of the row padding get 0.
+__device__ __forceinline__ uint32_t field_cost(uint32_t state, uint32_t v, const uint8_t * __restrict__ table, uint32_t rt2, int32_t track_unknown,
+  int32_t inflate_unknown)
+{
+  const uint32_t c = v <= rt2 ? table[v] : 0u;
+  const bool unknown = state != 100u && state != 255u;
+  return unknown && track_unknown && !(c >= 253u || (inflate_unknown && c > 0u)) ? 255u : c;
+}
+
 __global__ __launch_bounds__(256) void k_field_costs(FieldWindow f, const uint8_t * __restrict__ table, uint32_t rt2, int32_t track_unknown,
   int32_t inflate_unknown, uint32_t * __restrict__ out)
 {
@@ -158,12 +167,27 @@ __global__ __launch_bounds__(256) void k_field_costs(FieldWindow f, const uint8_
 #pragma unroll
   for (int32_t e = 0; e < 4; ++e) {
     if (col + e < f.width) {
-      const uint32_t state = (c4 >> (8 * e)) & 0xFFu;
-      uint32_t c = v[e] <= rt2 ? table[v[e]] : 0u;
-      const bool unknown = state != 100u && state != 255u;
-      if (unknown && track_unknown && !(c >= 253u || (inflate_unknown && c > 0u))) {c = 255u;}
-      cost4 |= c << (8 * e);
+      cost4 |= field_cost((c4 >> (8 * e)) & 0xFFu, v[e], table, rt2, track_unknown, inflate_unknown) << (8 * e);
     }
+  }
+  out[q] = cost4;
+}
+
+// The same costs for window columns [r.x0, r.x1) and rows [r.y0, r.y1) as a dense block of row stride out_ws (a multiple of 4): one
+// thread per dword of the block.  The rectangle begins at any column, so its states and values are read cell by cell; the four costs
+// leave as one dword.  The cells of the block's row padding get 0.
+__global__ __launch_bounds__(256) void k_field_costs_rect(FieldWindow f, FieldRect r, const uint8_t * __restrict__ table, uint32_t rt2,
+  int32_t track_unknown, int32_t inflate_unknown, uint32_t * __restrict__ out, int32_t out_ws)
+{
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int32_t quads = out_ws >> 2;
+  if (q >= (int64_t)quads * (r.y1 - r.y0)) {return;}
+  const int32_t col = r.x0 + 4 * (int32_t)(q % quads);
+  const int64_t at = (int64_t)(r.y0 + (int32_t)(q / quads)) * f.ws + col;
+  uint32_t cost4 = 0u;
+#pragma unroll
+  for (int32_t e = 0; e < 4; ++e) {
+    if (col + e < r.x1) {cost4 |= field_cost(f.cells[at + e], f.d2[at + e], table, rt2, track_unknown, inflate_unknown) << (8 * e);}
   }
   out[q] = cost4;
 }
@@ -252,6 +276,14 @@ void field_costs(void * stream, const FieldWindow & f, const uint8_t * d_table, 
   const int64_t quads = static_cast<int64_t>(f.ws >> 2) * f.height;
   hipLaunchKernelGGL(k_field_costs, dim3(static_cast<unsigned>((quads + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), f, d_table, rt2,
     track_unknown, inflate_unknown, reinterpret_cast<uint32_t *>(d_out));
+}
+
+void field_costs_rect(void * stream, const FieldWindow & f, const FieldRect & r, const uint8_t * d_table, uint32_t rt2, int32_t track_unknown,
+  int32_t inflate_unknown, uint8_t * d_out, int32_t out_ws)
+{
+  const int64_t quads = static_cast<int64_t>(out_ws >> 2) * (r.y1 - r.y0);
+  hipLaunchKernelGGL(k_field_costs_rect, dim3(static_cast<unsigned>((quads + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), f, r, d_table,
+    rt2, track_unknown, inflate_unknown, reinterpret_cast<uint32_t *>(d_out), out_ws);
 }
 
 void field_lookup(void * stream, const FieldWindow & f, int32_t n, const double * d_xy, uint32_t * d_d2, int32_t * d_status)

@@ -14,6 +14,11 @@ The way out for a consumer that wants nav_msgs/OccupancyGrid values and only wha
     full = feed.read(x, y, w, h)       # any lattice rectangle of what the consumer has been told, -1 outside
     feed.close()                       # before live.close()
 
+A distance field that follows the map (kh_live_map_field_*; slam_toolbox_amd.map_field.MapField):
+
+    field = live.field(max_distance=2.0)
+    u = field.sync()                   # after live.update(): what the updates changed since the last sync, recomputed exactly
+
 Nothing here computes: every call lands in the library."""
 from __future__ import annotations
 
@@ -78,6 +83,12 @@ class LiveMap:
     def feed(self) -> "MapFeed":
         """kh_map_feed_create: a feed of changed tiles for one consumer.  Close it before the live map."""
         return MapFeed(self)
+
+    def field(self, max_distance: float = 2.0, obstacles=capi.KH_FIELD_OBSTACLE_OCCUPIED):
+        """kh_live_map_field_create: a MapField of the current window that follows this map through its .sync().  Raises
+        (KH_ERR_NOT_FOUND) before the first scan."""
+        from .map_field import MapField
+        return MapField._following(self, max_distance, obstacles)
 
     def close(self):
         if self._h:

@@ -8,6 +8,12 @@ poses and the pose refinement built on it.
     metres, status, d2 = field.clearance([[1.0, 2.0]])      # how much room is there at (x, y)?
     refined = field.refine(ranges, [sensor_pose], laser)    # descend the endpoint cost from a candidate pose
 
+A field can follow its map: the part of the map that changed is compared and recomputed, exact to the bit.
+
+    u = field.update(grid, rect=(x, y, w, h))               # the caller knows where the map changed (None: compare everything)
+    field = live.field(max_distance=2.0); u = field.sync()  # or the live map does: after every live.update()
+    box = u["values_box"]; field.costs_rect(*box)           # the costs of what changed: a map_msgs/OccupancyGridUpdate
+
 Nothing here computes: every call lands in the library."""
 from __future__ import annotations
 
@@ -55,10 +61,69 @@ class MapField:
         capi.lib().kh_map_field_params_default(C.byref(p))
         p.max_distance, p.obstacles = float(max_distance), int(OBSTACLES.get(obstacles, obstacles))
         capi.check(capi.lib().kh_map_field_create(C.byref(v), C.byref(p), C.byref(self._h)), "kh_map_field_create")
+        self._live = None
+        self.scale = v.scale
+        self._read_stats()
+
+    @classmethod
+    def _following(cls, live, max_distance, obstacles):
+        """kh_live_map_field_create (LiveMap.field)"""
+        self = cls.__new__(cls)
+        self._h, self._live = C.c_void_p(), live     # the field borrows the live map: keep it alive
+        p = capi.KhMapFieldParams()
+        capi.lib().kh_map_field_params_default(C.byref(p))
+        p.max_distance, p.obstacles = float(max_distance), int(OBSTACLES.get(obstacles, obstacles))
+        capi.check(capi.lib().kh_live_map_field_create(live._h, C.byref(p), C.byref(self._h)), "kh_live_map_field_create")
+        self.scale = live.view().scale
+        self._read_stats()
+        return self
+
+    def _read_stats(self):
+        """kh_map_field_stats_get -> .stats, .width, .height (after an update the library recounts the three counters here)"""
         st = capi.KhMapFieldStats()
         capi.check(capi.lib().kh_map_field_stats_get(self._h, C.byref(st)), "kh_map_field_stats_get")
         self.stats = {k: (list(getattr(st, k)) if k == "times_ms" else getattr(st, k)) for k, _ in capi.KhMapFieldStats._fields_}
-        self.width, self.height, self.scale = st.width, st.height, v.scale
+        self.width, self.height = st.width, st.height
+
+    def _updated(self, u, stats):
+        if stats:
+            self._read_stats()
+        out = {k: getattr(u, k) for k, _ in capi.KhFieldUpdate._fields_}
+        out.update(cells_box=tuple(u.cells_box), values_box=tuple(u.values_box), times_ms=list(u.times_ms))
+        return out
+
+    def update(self, view, rect=None, stats=True) -> dict:
+        """kh_map_field_update: the field follows `view` (on the same lattice); rect = (x, y, w, h) in lattice cells is where the
+        map may have changed, None: anywhere.  -> kh_field_update's fields.  stats=False leaves .stats as it was (and the recount
+        to the next reader of the statistics)."""
+        v = _view_of(view)
+        r = None if rect is None else (C.c_int32 * 4)(*(int(k) for k in rect))
+        u = capi.KhFieldUpdate()
+        capi.check(capi.lib().kh_map_field_update(self._h, C.byref(v), r, C.byref(u)), "kh_map_field_update")
+        return self._updated(u, stats)
+
+    def sync(self, stats=True) -> dict:
+        """kh_live_map_field_sync: a field made by LiveMap.field() takes what the live map's updates changed since the last sync"""
+        u = capi.KhFieldUpdate()
+        capi.check(capi.lib().kh_live_map_field_sync(self._h, C.byref(u)), "kh_live_map_field_sync")
+        return self._updated(u, stats)
+
+    def set_band_rows(self, n: int):
+        """kh_map_field_set_band_rows (debugging): the band height of an update's column pass, 0: the library's choice"""
+        capi.check(capi.lib().kh_map_field_set_band_rows(self._h, int(n)), "kh_map_field_set_band_rows")
+
+    def read_rect(self, x: int, y: int, w: int, h: int):
+        """kh_map_field_read_rect: the values of lattice cells [x, x + w) x [y, y + h), (h, w) uint32"""
+        out = np.zeros((max(0, int(h)), max(0, int(w))), dtype=np.uint32)
+        capi.check(capi.lib().kh_map_field_read_rect(self._h, int(x), int(y), int(w), int(h), out.ctypes.data), "kh_map_field_read_rect")
+        return out
+
+    def costs_rect(self, x: int, y: int, w: int, h: int, **params):
+        """kh_map_field_costs_rect: the costs of lattice cells [x, x + w) x [y, y + h), (h, w) uint8"""
+        p = _inflation(params)
+        out = np.zeros((max(0, int(h)), max(0, int(w))), dtype=np.uint8)
+        capi.check(capi.lib().kh_map_field_costs_rect(self._h, C.byref(p), int(x), int(y), int(w), int(h), out.ctypes.data), "kh_map_field_costs_rect")
+        return out
 
     @property
     def d2(self):
@@ -123,6 +188,7 @@ class MapField:
         if self._h:
             capi.lib().kh_map_field_destroy(self._h)
             self._h = C.c_void_p()
+        self._live = None
 
     def __del__(self):
         try:
