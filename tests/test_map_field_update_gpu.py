@@ -21,11 +21,13 @@ REPORTED = ("rebuilt", "relayout", "cells_box", "values_box", "cells_recomputed"
 
 
 class Followed:
-    """a view in device memory of the caller's own and a field made from it; step() rewrites the cells and updates the field"""
+    """a view in device memory of the caller's own and a field made from it; step() rewrites the cells and updates the field.
+    d2_rule: the form of tests/map_field_rule.py the values are held against (d2_brute for windows too wide for the separable one);
+    place: what puts a view dict into device memory (DeviceView, or tests/embedded_view.py's EmbeddedView in one of its layouts)"""
 
-    def __init__(self, view, radius, obstacles=rule.OCCUPIED, first_update=True):
-        self.radius, self.obstacles, self.view = radius, obstacles, view
-        self.d = DeviceView(view)
+    def __init__(self, view, radius, obstacles=rule.OCCUPIED, first_update=True, d2_rule=rule.d2_separable, place=DeviceView):
+        self.radius, self.obstacles, self.view, self.d2_rule = radius, obstacles, view, d2_rule
+        self.d = place(view)
         self.field = MapField(self.d.v, max_distance=radius / view["scale"], obstacles=obstacles)
         if first_update:                                       # a field from kh_map_field_create: its first update allocates g and rebuilds
             got = self.field.update(self.d.v)
@@ -33,9 +35,7 @@ class Followed:
             self.check()
 
     def upload(self, view):
-        cells = np.ascontiguousarray(view["cells"])
-        assert cells.size == self.d.size
-        capi.check(capi.lib().kh_device_upload(self.d.buf, cells.ctypes.data, cells.size), "kh_device_upload")
+        self.d.upload(view)
         self.view = view
 
     def step(self, after, rect=None, want=None):
@@ -49,7 +49,7 @@ class Followed:
 
     def check(self):
         view, f = self.view, self.field
-        want = rule.d2_separable(view, self.radius, self.obstacles)
+        want = self.d2_rule(view, self.radius, self.obstacles)
         d2 = f.d2
         assert np.array_equal(d2, want), f"{int((d2 != want).sum())} values differ from the rule"
         fresh = MapField(self.d.v, max_distance=self.radius / view["scale"], obstacles=self.obstacles)

@@ -34,6 +34,12 @@ class DeviceView:
         v.ox, v.oy, v.anchor[0], v.anchor[1], v.scale = view["ox"], view["oy"], view["anchor"][0], view["anchor"][1], view["scale"]
         self.v = v
 
+    def upload(self, view):
+        """another view dict's cells into the same memory (the same window and stride)"""
+        cells = np.ascontiguousarray(view["cells"])
+        assert cells.size == self.size
+        capi.check(capi.lib().kh_device_upload(self.buf, cells.ctypes.data, cells.size), "kh_device_upload")
+
     def download(self):
         out = np.zeros(self.size, dtype=np.uint8)
         capi.check(capi.lib().kh_device_download(out.ctypes.data, self.buf, self.size), "kh_device_download")
