@@ -1065,12 +1065,14 @@ KH_API int kh_merge_remove_submap(kh_merge * g, int32_t submap_id);             
 KH_API int32_t kh_merge_num_submaps(const kh_merge * g);
 /* out[0] = scans still in the submap's map, out[1] = beams of its laser */
 KH_API int kh_merge_submap_info(const kh_merge * g, int32_t submap_id, int32_t out[2]);
-/* the correction of a submap (the identity (0, 0, 0) when it is added) */
+/* the correction of a submap (the identity (0, 0, 0) when it is added).  A correction that is not finite (NaN, +-inf in any of the
+ * three places) is KH_ERR_INVALID_ARG and leaves the correction as it was. */
 KH_API int kh_merge_set_transform(kh_merge * g, int32_t submap_id, const double t[3]);
 KH_API int kh_merge_get_transform(const kh_merge * g, int32_t submap_id, double t[3]);
 /* the release of the marker at marker_pose = (x, y, yaw): correction <- correction . inverse(translation(previous location)) .
  * marker_pose, then location <- (x, y, location yaw + yaw).  The location starts at the centre of the submap's own grid at the
- * merger's resolution, (offset + width * resolution / 2, offset + height * resolution / 2, 0) (addSubmapCallback :115-122). */
+ * merger's resolution, (offset + width * resolution / 2, offset + height * resolution / 2, 0) (addSubmapCallback :115-122).
+ * A marker pose that is not finite is KH_ERR_INVALID_ARG and leaves correction and location as they were. */
 KH_API int kh_merge_move_submap(kh_merge * g, int32_t submap_id, const double marker_pose[3]);
 KH_API int kh_merge_get_location(const kh_merge * g, int32_t submap_id, double location[3]);
 /* what transformScan leaves on scan `index` (0 .. info[0] - 1, scan-id order) of the submap under its current correction:
@@ -1112,6 +1114,12 @@ typedef struct kh_merge_fit_t {
  * is KH_ERR_INVALID_ARG (the handle is looked at after the device, as kh_mapper_relocalize looks at its mapper: a merger cannot
  * exist without one); an unknown id KH_ERR_NOT_FOUND; no other submap, or no scan in any other submap, KH_ERR_INVALID_ARG as for
  * kh_merge_build.  Every min_pass_through is valid (a cell is known when it was passed more often), as for kh_occupancy_update.
+ * A candidate may put the submap anywhere, and a beam is walked cell by cell from the sensor to its end: once the reference grid
+ * exists and before anything is launched, KH_ERR_INVALID_ARG (a) where the moving submap's laser has range_threshold / resolution +
+ * 2 > 2^20 cells, a range_threshold that is not finite and positive, or a minimum or maximum range that is NaN, and (b) where
+ * under some candidate the sensor of one of the submap's scans lies more than 2^30 cells from the reference grid's offset on either
+ * axis, |(sensor - offset) / resolution| > 2^30; kh_last_error() names the first such candidate by its index.  (Far outside the
+ * grid is no reason: such a candidate counts nothing.)  kh_merge_fit_stats is unchanged by a refusal.
  * A failure leaves the merger usable. */
 KH_API int kh_merge_fit(kh_merge * g, int32_t submap_id, int32_t n_candidates, const double * corrections /* 3n */,
                         uint32_t min_pass_through, double occupancy_threshold, kh_merge_fit_t * out /* n */);
@@ -1150,7 +1158,8 @@ KH_API void kh_merge_align_params_default(const kh_merge * g, int32_t target_sub
  * KH_ERR_INVALID_ARG before a device is looked for: NULL params / n_candidates, out NULL with cap > 0, cap < 0, n_probes < 1,
  * top_k < 1, a non-finite occupancy_threshold, invalid relocalization parameters, moving == target (every min_pass_through and
  * min_known is valid).  Then: no device KH_ERR_NO_DEVICE, a NULL merger KH_ERR_INVALID_ARG, an unknown id KH_ERR_NOT_FOUND, lasers that differ in any field of kh_laser KH_ERR_INVALID_ARG (the probe's ranges are read by the target's
- * laser; kh_merge_fit has no such restriction).  A failure leaves the merger usable. */
+ * laser; kh_merge_fit has no such restriction).  The candidates are fitted as kh_merge_fit fits them: its refusals (a) and (b)
+ * apply, under this call's name.  A failure leaves the merger usable. */
 KH_API int kh_merge_align(kh_merge * g, int32_t moving_submap, int32_t target_submap, const kh_merge_align_params * params,
                           kh_merge_align_cand * out, int32_t cap, int32_t * n_candidates, double times_ms[4]);
 

@@ -116,6 +116,27 @@ inline std::string fit_inputs_text(const FitInputs & f, const char * who, const 
   return std::string(who) + ": " + words;
 }
 
+// The same check for the fit of a session merge (kh_merge_fit, kh_merge_align): the moving submap's laser
+// (fit_laser_ok), then the sensor position of every scan under every candidate -- sensors_xy holds n_candidates * n_scans pairs
+// (x, y), candidate-major, as k_occ_fit_merged reads them -- by fit_pose_ok's arithmetic with the reference grid's offset as the
+// origin.  A refused position is reported with its CANDIDATE's index in FitInputs::pose.
+inline FitInputs merge_fit_check(double range_threshold, double min_range, double max_range, size_t n_candidates, size_t n_scans,
+  const double * sensors_xy, double off_x, double off_y, double scale)
+{
+  if (!fit_laser_ok(range_threshold, min_range, max_range, scale)) {return FitInputs{kFitInputsLaser, -1};}
+  for (size_t k = 0; k < n_candidates; ++k) {
+    for (size_t i = 0; i < n_scans; ++i) {
+      const double * xy = sensors_xy + 2 * (k * n_scans + i);
+      const double at[3] = {xy[0], xy[1], 0.0};
+      if (!fit_pose_ok(at, off_x, off_y, scale)) {return FitInputs{kFitInputsPose, static_cast<int32_t>(k)};}
+    }
+  }
+  return FitInputs{kFitInputsOk, -1};
+}
+constexpr const char * kMergeLaserWords =
+  "the moving submap's range_threshold * scale must stay below 2^20 cells, its minimum and maximum range must be numbers";
+constexpr const char * kMergePoseWords = "correction # puts a scan's sensor more than 2^30 cells from the offset of the reference grid";
+
 // the six counters -> kh_merge_fit_t
 inline kh_merge_fit_t fit_derive(const uint64_t c[kFitCounters])
 {

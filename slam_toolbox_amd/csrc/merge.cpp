@@ -22,6 +22,7 @@
 
 #include "../../include/karto_hip.h"
 #include "host_common.hpp"
+#include "map_localize_plan.hpp"     // merge_fit_check: the walk-length guard of the fit
 #include "mapper_internal.hpp"
 
 namespace kh
@@ -104,6 +105,8 @@ namespace kh
 {
 namespace
 {
+bool finite3(const double * t) {return std::isfinite(t[0]) && std::isfinite(t[1]) && std::isfinite(t[2]);}
+
 Submap * find_submap(kh_merge * g, int32_t id, const char * who)
 {
   for (Submap & s : g->submaps) {if (s.id == id) {return &s;}}
@@ -207,6 +210,7 @@ int kh_merge_set_transform(kh_merge * g, int32_t submap_id, const double t[3])
   if (!g || !t) {return KH_ERR_INVALID_ARG;}
   Submap * s = kh::find_submap(g, submap_id, "kh_merge_set_transform");
   if (!s) {return KH_ERR_NOT_FOUND;}
+  if (!kh::finite3(t)) {kh::set_error("kh_merge_set_transform: the correction is not finite"); return KH_ERR_INVALID_ARG;}
   s->correction = Rigid(t[0], t[1], t[2]);
   return KH_OK;
 }
@@ -225,6 +229,7 @@ int kh_merge_move_submap(kh_merge * g, int32_t submap_id, const double marker_po
   if (!g || !marker_pose) {return KH_ERR_INVALID_ARG;}
   Submap * s = kh::find_submap(g, submap_id, "kh_merge_move_submap");
   if (!s) {return KH_ERR_NOT_FOUND;}
+  if (!kh::finite3(marker_pose)) {kh::set_error("kh_merge_move_submap: the marker pose is not finite"); return KH_ERR_INVALID_ARG;}
   // processInteractiveFeedback :327-351: correction * previous_submap_correction.inverse() * new_submap_location, left to right
   const Rigid previous(s->location[0], s->location[1], 0.0);
   const Rigid marker(marker_pose[0], marker_pose[1], marker_pose[2]);
@@ -358,8 +363,6 @@ int build_grid(kh_merge * g, int32_t skip, const char * who, uint32_t min_pass_t
   return KH_OK;
 }
 
-bool finite3(const double * t) {return std::isfinite(t[0]) && std::isfinite(t[1]) && std::isfinite(t[2]);}
-
 // The fit of n candidate corrections of submap `moving` against the merge of all the others: the reference
 // grid once, then one launch of k_occ_fit_merged.  times_ms[0] = the reference grid (wall), [1] = the fit kernel (events).
 int fit_candidates(kh_merge * g, const Submap & moving, const char * who, int32_t n, const double * corrections, uint32_t min_pass_through,
@@ -394,6 +397,18 @@ int fit_candidates(kh_merge * g, const Submap & moving, const char * who, int32_
       laser_sensor_at(moving.laser, corrected, sensor);
       sensors[static_cast<size_t>(k) * n_scans + i] = FitSensor{sensor[0], sensor[1]};
     }
+  }
+  // The walk-length guard (merge_fit_check, map_localize_plan.hpp): a candidate may put the submap anywhere, a walk is as long as its
+  // end cells are apart, and the kernel's own bound only keeps a lane from spinning.  The scale is the grid's own (kh_occupancy_create).
+  static_assert(sizeof(FitSensor) == 2 * sizeof(double), "the sensors are checked as they lie: pairs (x, y)");
+  double offset[2] = {0.0, 0.0};
+  rc = kh_occupancy_geometry(grid, offset, nullptr);
+  if (rc) {return done(rc);}
+  const FitInputs inputs = merge_fit_check(moving.laser.range_threshold, moving.laser.minimum_range, moving.laser.maximum_range,
+      static_cast<size_t>(n), n_scans, sensors.empty() ? nullptr : &sensors[0].sx, offset[0], offset[1], 1.0 / g->resolution);
+  if (inputs.failed != kFitInputsOk) {
+    set_error(fit_inputs_text(inputs, who, kMergeLaserWords, kMergePoseWords));
+    return done(KH_ERR_INVALID_ARG);
   }
   std::vector<uint64_t> sums(static_cast<size_t>(n) * kFitCounters);
   rc = occupancy_fit_merged(grid, n, candidates.data(), sensors.data(), static_cast<int32_t>(n_scans), resident.data(), moving.laser.n_beams,

@@ -88,7 +88,8 @@ __global__ __launch_bounds__(256) void k_occ_trace_merged(
 // cell it would have incremented and counts, per state, visits and hits in six registers of the lane (FitCells).  The grid is only
 // read.  A workgroup holds waves of ONE candidate (blocks_per_candidate = ceil(n_scans * runs_per_scan / 4)), so its sums go to one
 // row of `out` (fit_reduce).  A wave past the last scan and a lane past the beam count take part in the reduction with zeros:
-// every wave reaches the barrier.
+// every wave reaches the barrier.  A candidate may put the submap anywhere, so the walk stands behind walk_bounded as on a map view
+// (the host has refused what it would stop: merge_fit_check, map_localize_plan.hpp); a beam it stops counts nothing.
 __global__ __launch_bounds__(256) void k_occ_fit_merged(
   OccDev g, const ResidentScan * __restrict__ scans, const FitCandidate * __restrict__ candidates, const FitSensor * __restrict__ sensors,
   int32_t n_scans, int32_t n_beams, int32_t runs_per_scan, int32_t blocks_per_candidate, double range_threshold, double min_range,
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(256) void k_occ_fit_merged(
     if (b.kept) {
       const int32_t x0 = occ_cell(sensor.sx, g.off_x, g.scale), y0 = occ_cell(sensor.sy, g.off_y, g.scale);
       const int32_t x1 = occ_cell(b.px, g.off_x, g.scale), y1 = occ_cell(b.py, g.off_y, g.scale);
-      occ_walk(FitCells<OccDev>{g, n}, x0, y0, x1, y1, b.hit);
+      if (walk_bounded(x0, y0, x1, y1)) {occ_walk(FitCells<OccDev>{g, n}, x0, y0, x1, y1, b.hit);}
     }
   }
   fit_reduce(n, out, candidate);

@@ -11,6 +11,8 @@
 //   fitok range_threshold min_range max_range scale ax ay x y heading   -> laser_ok pose_ok
 //   inputs range_threshold min_range max_range min_angle angular_resolution scale ax ay  n (x y heading) * n
 //                                                      -> failed pose | the refusal in the words of a call that takes a view
+//   mergefit range_threshold min_range max_range scale off_x off_y  n_candidates n_scans (sensor x y) * n_candidates * n_scans
+//                                                      -> failed candidate | the refusal in the words of kh_merge_fit
 //
 // Doubles are read with strtod and printed with %a, so they pass bit for bit.
 #include <cstdio>
@@ -90,6 +92,13 @@ int main()
       for (double & v : p) {v = real(in);}
       const FitInputs f = fit_inputs_check(rt, lo, hi, a0, da, p.size() / 3, p.data(), ax, ay, scale);
       std::printf("%d %d | %s\n", f.failed, f.pose, f.failed ? fit_inputs_text(f, "who", kViewLaserWords, kViewPoseWords).c_str() : "");
+    } else if (what == "mergefit") {
+      const double rt = real(in), lo = real(in), hi = real(in), scale = real(in), ox = real(in), oy = real(in);
+      const size_t n_candidates = static_cast<size_t>(whole(in)), n_scans = static_cast<size_t>(whole(in));
+      std::vector<double> xy(2 * n_candidates * n_scans);
+      for (double & v : xy) {v = real(in);}
+      const FitInputs f = merge_fit_check(rt, lo, hi, n_candidates, n_scans, xy.data(), ox, oy, scale);
+      std::printf("%d %d | %s\n", f.failed, f.pose, f.failed ? fit_inputs_text(f, "kh_merge_fit", kMergeLaserWords, kMergePoseWords).c_str() : "");
     } else {
       std::printf("error: unknown case %s\n", what.c_str());
     }

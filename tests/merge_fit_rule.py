@@ -12,6 +12,8 @@ of a probe, of tests/relocalize_rule.py.  It reads nothing of the library.
                      (pass - 2 hits: the visits that are not the end cell of a hit beam -- that cell is visited twice)
     ranking          known >= min_known first, then score descending, agree descending, candidate index ascending
     probes           M's alive scans in scan-id order; probe j is entry floor(j * n_alive / n_probes), n_probes clipped to n_alive
+    refused          fit_refused: a moving laser with range_threshold * scale + 2 > 2^20 cells, or a candidate under which a sensor
+                     lies more than 2^30 cells from the reference grid's offset (the library: KH_ERR_INVALID_ARG, nothing launched)
     candidates       0: M's current correction; then per probe, per hypothesis in rank order, (T_target . P) . inverse(Q) with P the
                      hypothesis' robot pose and Q the probe's corrected pose in M; no de-duplication
 """
@@ -63,6 +65,31 @@ def fit_on(moving, candidates, grid, resolution):
             p = h = np.zeros(grid["cells"].shape, dtype=np.uint32)
         out.append(derive(count(grid["cells"], p, h)))
     return out
+
+
+MAX_FIT_WALK, MAX_FIT_CELL = 2 ** 20, 2.0 ** 30
+
+
+def fit_refused(moving, candidates, grid, resolution):
+    """What kh_merge_fit / kh_merge_align refuse before anything is launched (KH_ERR_INVALID_ARG), so that no beam walks more than
+    2^20 cells and no cell index leaves the int32 lattice: None = accepted, ("laser", -1) = the moving submap's laser has
+    range_threshold * scale + 2 > 2^20 (or a range_threshold that is not finite and positive), ("pose", k) = candidate k, the first
+    such, puts the sensor of one of its scans more than 2^30 cells from the reference grid's offset on either axis --
+    |(sensor - offset) * scale| > 2^30 with scale = 1 / resolution, one subtraction and one product."""
+    laser, scale = moving["laser"], 1.0 / float(resolution)
+    rt = float(laser.range_threshold)
+    if not (np.isfinite(rt) and rt > 0.0 and rt * scale + 2.0 <= float(MAX_FIT_WALK)):
+        return ("laser", -1)
+    if np.isnan(float(laser.min_range)) or np.isnan(float(laser.max_range)):
+        return ("laser", -1)
+    ox, oy = float(grid["offset"][0]), float(grid["offset"][1])
+    for k, c in enumerate(np.asarray(candidates, dtype=np.float64).reshape(-1, 3)):
+        for s in moving["scans"]:
+            sensor = merge_rule.sensor_at(merge_rule.transform_pose(tuple(c), s["corrected"]), getattr(laser, "offset", (0.0, 0.0, 0.0)))
+            cx, cy = (float(sensor[0]) - ox) * scale, (float(sensor[1]) - oy) * scale
+            if not (np.isfinite(cx) and np.isfinite(cy) and abs(cx) <= MAX_FIT_CELL and abs(cy) <= MAX_FIT_CELL):
+                return ("pose", k)
+    return None
 
 
 def fit(moving, candidates, others, transforms, resolution, min_pass_through=2, occupancy_threshold=0.1):

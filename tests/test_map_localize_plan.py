@@ -242,3 +242,77 @@ def test_laser_and_pose_check(check):
         head, _, words = g.partition(" | ")
         assert tuple(int(v) for v in head.split()) == (failed, pose), g
         assert words.strip() == text, g
+
+
+def _merge_fit(check, laser, resolution, offset, sensors, n_scans=1):
+    """one `mergefit` line -> (failed, candidate, words); sensors: (n_candidates * n_scans, 2), candidate-major"""
+    sensors = np.asarray(sensors, dtype=np.float64).reshape(-1, 2)
+    n_candidates = len(sensors) // n_scans if n_scans else len(sensors)
+    line = (f"mergefit {hx(laser[0])} {hx(laser[1])} {hx(laser[2])} {hx(1.0 / resolution)} {hx(offset[0])} {hx(offset[1])} {n_candidates} {n_scans} "
+            + " ".join(hx(v) for v in (sensors.ravel() if n_scans else [])))
+    head, _, words = check([line])[0].partition(" | ")
+    failed, candidate = (int(v) for v in head.split())
+    return failed, candidate, words.strip()
+
+
+def test_merge_fit_guard(check):
+    """merge_fit_check: what kh_merge_fit and kh_merge_align refuse before k_occ_fit_merged is launched, next to
+    tests/merge_fit_rule.py's fit_refused.  One scan at the origin under a pure translation has its sensor at the translation itself,
+    bit for bit, which is how the rule is fed here."""
+    import merge_fit_rule as fr
+    from collections import namedtuple
+    L = namedtuple("L", "range_threshold min_range max_range")
+    origin = {"corrected": np.zeros(3)}
+    laser_words = ("kh_merge_fit: the moving submap's range_threshold * scale must stay below 2^20 cells, its minimum and maximum range "
+                   "must be numbers")
+    pose_words = "kh_merge_fit: correction %d puts a scan's sensor more than 2^30 cells from the offset of the reference grid"
+    ok = (5.0, 0.1, 7.5)
+
+    def both(laser, resolution, offset, candidates):
+        """the program and the rule on one scan at the origin"""
+        got = _merge_fit(check, laser, resolution, offset, [c[:2] for c in candidates])
+        want = fr.fit_refused({"laser": L(*laser), "scans": [origin]}, [(c[0], c[1], 0.0) for c in candidates], {"offset": offset}, resolution)
+        assert (got[0], got[1]) == {None: (0, -1)}.get(want, (1 if want and want[0] == "laser" else 2, want[1] if want else -1)), (got, want)
+        return got
+
+    # the example of the defect: scale 20, offset -3.2, a sensor at x = 6.5 under tx = 107374170
+    res, off = 0.05, (-3.2, -3.2)
+    x = 6.5 + 107374170.0
+    cell = math.floor((x - off[0]) * (1.0 / res) + 0.5)
+    end = ((x + 5.0) - off[0]) * (1.0 / res)
+    assert cell == 2147483594 and end >= 2147483648.0, "the sensor is an int32 cell, the end of a 5 m beam is past the last one"
+    assert both(ok, res, off, [(1.0, 2.0), (x, 0.0)]) == (2, 1, pose_words % 1)
+    # the bound itself, on both axes and both sides: exactly 2^30 cells is accepted, a metre outward is not (0.25 m cells, offset 0.5)
+    res, off = 0.25, (0.5, -1.5)
+    far = 2.0 ** 30 * res
+    for axis in (0, 1):
+        for sign in (1.0, -1.0):
+            at = [1.0, 2.0]
+            at[axis] = off[axis] + sign * far
+            assert (at[axis] - off[axis]) * 4.0 == sign * 2.0 ** 30
+            assert both(ok, res, off, [tuple(at)]) == (0, -1, "")
+            at[axis] = off[axis] + sign * (far + 1.0)
+            assert both(ok, res, off, [(1.0, 2.0), (0.0, 0.0), tuple(at)]) == (2, 2, pose_words % 2)
+    # the neighbours of the int32 ends, NaN and the infinities: all refused, the first bad candidate is named
+    for c in (2.0 ** 31 - 1.0, 2.0 ** 31, -2.0 ** 31, -2.0 ** 31 - 1.0, 2.0 ** 31 + 1.0, 1e300):
+        assert both(ok, 1.0, (0.0, 0.0), [(c, 0.0)])[:2] == (2, 0)
+        assert both(ok, 1.0, (0.0, 0.0), [(0.0, 0.0), (0.0, c), (c, c)])[:2] == (2, 1)
+    for c in (math.nan, math.inf, -math.inf):
+        assert _merge_fit(check, ok, 1.0, (0.0, 0.0), [(0.0, 0.0), (c, 0.0)])[:2] == (2, 1)
+        assert _merge_fit(check, ok, 1.0, (0.0, 0.0), [(0.0, c)])[:2] == (2, 0)
+    assert both(ok, 0.25, (-10.0, -8.0), [(1000.0, 1000.0), (0.0, 0.0)]) == (0, -1, ""), "far outside the grid is no reason"
+    # several scans per candidate: a candidate is refused for any one of its scans, and the index is the candidate's
+    near, bad = (1.0, 2.0), (2.0 ** 31, 0.0)
+    assert _merge_fit(check, ok, 1.0, (0.0, 0.0), [near, near, near, near, near, bad, near, near, near], n_scans=3)[:2] == (2, 1)
+    assert _merge_fit(check, ok, 1.0, (0.0, 0.0), [near, near, near, near, near, near, bad, near, near], n_scans=3)[:2] == (2, 2)
+    assert _merge_fit(check, ok, 1.0, (0.0, 0.0), [near] * 9, n_scans=3) == (0, -1, "")
+    assert _merge_fit(check, ok, 1.0, (0.0, 0.0), [], n_scans=0) == (0, -1, ""), "a submap without scans"
+    # the laser: range_threshold * scale + 2 <= 2^20, judged before any position
+    res = 0.25
+    assert both(((2 ** 20 - 2) * res, 0.1, math.inf), res, (0.0, 0.0), [near]) == (0, -1, "")
+    assert both(((2 ** 20 - 1) * res, 0.1, 30.0), res, (0.0, 0.0), [near]) == (1, -1, laser_words)
+    assert both((20.0, 0.1, 30.0), 1e-5, (0.0, 0.0), [near, bad]) == (1, -1, laser_words)
+    for rt in (math.inf, math.nan, 0.0, -1.0):
+        assert both((rt, 0.1, 30.0), res, (0.0, 0.0), [near]) == (1, -1, laser_words)
+    assert both((5.0, math.nan, 30.0), res, (0.0, 0.0), [near]) == (1, -1, laser_words)
+    assert both((5.0, 0.1, math.nan), res, (0.0, 0.0), [near]) == (1, -1, laser_words)
