@@ -1746,6 +1746,86 @@ KH_API int kh_map_field_costs_rect(kh_map_field * f, const kh_inflation_params *
 KH_API int kh_live_map_field_create(kh_live_map * g, const kh_map_field_params * params, kh_map_field ** out);
 KH_API int kh_live_map_field_sync(kh_map_field * f, kh_field_update * out);
 
+/* ---------------------------------------------------------------- map regions: connected free space by clearance, frontier clusters
+ * (DESIGN.md section 7q).  An analysis is made from a kh_map_field: it reads the field's own snapshot of the cell states and its
+ * d2 values over the field's window.  Cells outside the window do not exist; columns width .. width_step - 1 are never read and
+ * never connect anything.  The handle never borrows the field: the field may change or go once a call returns.
+ *   N            the 4 or the 8 neighbours of a cell (connectivity), for everything below
+ *   Rc           ceil(min_clearance * scale) cells, the field's own rule for R
+ *   traversable  a cell of state 255 with d2 >= Rc * Rc (KH_FIELD_FAR counts as beyond)
+ *   unknown      a cell of state neither 100 nor 255 (what kh_map_field_costs calls unknown)
+ *   frontier     a cell of state 255 with at least one unknown cell of N inside the window: on states alone, not on clearance
+ *   regions      the connected components of the traversable mask under N; frontier clusters: those of the frontier mask
+ *   label        the root of a component: the window index j * width + i of its smallest cell
+ *   kept         a component of at least min_region_cells (min_frontier_cells) cells that stands among the first max_regions
+ *                (max_frontiers) such components in root order.  Kept components are numbered 0, 1, ... in root order.
+ *   id grid      per cell the kept id, KH_REGION_NONE outside the mask, KH_REGION_DROPPED for a cell of a component that was too
+ *                small or past the cap
+ * Every quantity a kernel produces is an integer that does not depend on the order in which anything ran. */
+#define KH_REGION_NONE 0xFFFFFFFFu
+#define KH_REGION_DROPPED 0xFFFFFFFEu
+enum { KH_REGIONS = 0, KH_FRONTIERS = 1 };   /* `which`: the two sets */
+typedef struct kh_map_regions kh_map_regions;
+typedef struct kh_map_regions_params {
+  double min_clearance;                          /* metres, finite, >= 0 (default 0: every free cell) */
+  int32_t connectivity;                          /* 4 or 8 (default 8) */
+  int32_t min_region_cells, max_regions;         /* >= 1 (default 1), 1 .. 2^20 (default 4096) */
+  int32_t min_frontier_cells, max_frontiers;     /* >= 1 (default 1), 1 .. 2^20 (default 4096) */
+  int32_t pad;
+} kh_map_regions_params;
+/* One component of either set.  The doubles are taken on the host, in exactly these operations:
+ *   centroid[k]  = anchor[k] + ((double)o_k + (double)sum_k / (double)n_cells) / scale      (o_k: ox, oy; sum_k: sum_i, sum_j)
+ *   anchor_xy[k] = anchor[k] + (double)(o_k + a_k) / scale, (a_0, a_1) = (anchor_cell % width, anchor_cell / width): the world
+ *                  point of the anchor cell by the view's rule */
+typedef struct kh_region {
+  uint32_t root, n_cells;
+  int32_t box[4];              /* x, y, w, h in lattice cells (the units of ox, oy) */
+  uint64_t sum_i, sum_j;       /* window-relative sums of the members' columns and rows */
+  uint32_t max_d2;             /* the largest field value over the members; KH_FIELD_FAR if any member is FAR */
+  uint32_t n_other;            /* members that are set in the OTHER mask: a region's frontier cells (0: nothing is left to explore
+                                  from it), a cluster's traversable cells */
+  uint32_t link;               /* the smallest kept id of the other set among the members -- for a cluster the region it can be
+                                  reached from -- KH_REGION_NONE when there is none */
+  uint32_t anchor_cell;        /* the member nearest the centroid cell ((2 sum_i + n) / (2 n), (2 sum_j + n) / (2 n)), integer
+                                  divisions, by squared cell distance; ties go to the smallest window index */
+  double centroid[2], anchor_xy[2];
+} kh_region;
+typedef struct kh_map_regions_stats {
+  int32_t ox, oy, width, height;               /* the window */
+  int32_t clearance_cells, connectivity;       /* Rc, 4 or 8 */
+  uint64_t n_traversable, n_frontier_cells;
+  uint32_t n_total[2], n_kept[2];              /* by KH_REGIONS / KH_FRONTIERS: all components, the kept ones */
+  int32_t truncated[2];                        /* more components passed the minimum than the maximum takes */
+  double times_ms[7];          /* by device events: tiles, seams, flatten and count, compaction and ids, records, anchors; the call */
+} kh_map_regions_stats;
+/* 0.0, 8, 1, 4096, 1, 4096; a NULL output is ignored */
+KH_API void kh_map_regions_params_default(kh_map_regions_params * p);
+/* KH_ERR_INVALID_ARG before a device is looked for, in this order: a NULL field, params or out; a min_clearance that is not finite
+ * or < 0; Rc > 1024; a connectivity other than 4 or 8; a minimum < 1; a maximum outside 1 .. 2^20.  Then KH_ERR_NO_DEVICE; then a
+ * field with 0 < R < Rc (it does not reach as far as the threshold asks: kh_map_field_costs' refusal). */
+KH_API int kh_map_regions_create(kh_map_field * field, const kh_map_regions_params * params, kh_map_regions ** out);
+/* the whole analysis again, of `field` as it stands (after kh_map_field_update or kh_live_map_field_sync, or of another field of the
+ * same lattice): the allocations are reused, or made anew where the window changed.  KH_ERR_INVALID_ARG before a device is looked
+ * for: a NULL field; with a handle, a field on another device or lattice (anchor x, anchor y, scale by their bits, device).  After
+ * the handle: a field with 0 < R < Rc.  After a failure the handle holds no analysis until a recompute succeeds. */
+KH_API int kh_map_regions_recompute(kh_map_regions * r, kh_map_field * field);
+KH_API void kh_map_regions_destroy(kh_map_regions * r);
+KH_API int kh_map_regions_stats_get(kh_map_regions * r, kh_map_regions_stats * out);
+/* the id grid of set `which`: width * height values, row-major with no row padding.  NULL ids, which outside 0 .. 1:
+ * KH_ERR_INVALID_ARG before a device is looked for. */
+KH_API int kh_map_regions_read(kh_map_regions * r, int32_t which, uint32_t * ids);
+/* the records of the kept components of set `which` in id order: *n = n_kept (also when cap is smaller), records takes the first
+ * min(cap, n_kept).  KH_ERR_INVALID_ARG before a device is looked for: which outside 0 .. 1, NULL n, cap < 0, cap > 0 with NULL
+ * records. */
+KH_API int kh_map_regions_get(kh_map_regions * r, int32_t which, kh_region * records, int32_t cap, int32_t * n);
+/* the region at n world points (x, y), by kh_map_field_clearance's cell rule: KH_REGION_OUTSIDE off the window or beyond +-2^30
+ * cells (id KH_REGION_NONE), KH_REGION_AT_NONE where the cell is not traversable (KH_REGION_NONE), KH_REGION_AT_DROPPED where its
+ * region was dropped (KH_REGION_DROPPED), KH_REGION_AT_OK with the id.  Two points can reach each other iff both are
+ * KH_REGION_AT_OK with the same id.  Either output may be NULL.  n < 1, NULL xy, a non-finite point: KH_ERR_INVALID_ARG before a
+ * device is looked for. */
+enum { KH_REGION_AT_OK = 0, KH_REGION_AT_NONE = 1, KH_REGION_AT_DROPPED = 2, KH_REGION_OUTSIDE = 3 };
+KH_API int kh_map_regions_lookup(kh_map_regions * r, int32_t n, const double * xy /* 2n */, int32_t * status, uint32_t * id);
+
 #ifdef __cplusplus
 }
 #endif

@@ -180,6 +180,8 @@ SYMBOLS = [
     "kh_field_refine_params_default", "kh_map_field_refine",
     "kh_map_field_update", "kh_map_field_set_band_rows", "kh_map_field_read_rect", "kh_map_field_costs_rect",
     "kh_live_map_field_create", "kh_live_map_field_sync",
+    "kh_map_regions_params_default", "kh_map_regions_create", "kh_map_regions_recompute", "kh_map_regions_destroy", "kh_map_regions_stats_get",
+    "kh_map_regions_read", "kh_map_regions_get", "kh_map_regions_lookup",
 ]
 
 
@@ -398,6 +400,27 @@ class KhFieldUpdate(C.Structure):
                 ("cells_compared", C.c_int64), ("cells_recomputed", C.c_int64), ("times_ms", C.c_double * 4)]
 
 
+KH_REGION_NONE, KH_REGION_DROPPED = 0xFFFFFFFF, 0xFFFFFFFE
+KH_REGIONS, KH_FRONTIERS = 0, 1
+KH_REGION_AT_OK, KH_REGION_AT_NONE, KH_REGION_AT_DROPPED, KH_REGION_OUTSIDE = range(4)
+
+
+class KhMapRegionsParams(C.Structure):
+    _fields_ = [("min_clearance", C.c_double)] + \
+               [(k, C.c_int32) for k in ("connectivity", "min_region_cells", "max_regions", "min_frontier_cells", "max_frontiers", "pad")]
+
+
+class KhRegion(C.Structure):
+    _fields_ = [("root", C.c_uint32), ("n_cells", C.c_uint32), ("box", C.c_int32 * 4), ("sum_i", C.c_uint64), ("sum_j", C.c_uint64)] + \
+               [(k, C.c_uint32) for k in ("max_d2", "n_other", "link", "anchor_cell")] + [("centroid", C.c_double * 2), ("anchor_xy", C.c_double * 2)]
+
+
+class KhMapRegionsStats(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("ox", "oy", "width", "height", "clearance_cells", "connectivity")] + \
+               [("n_traversable", C.c_uint64), ("n_frontier_cells", C.c_uint64), ("n_total", C.c_uint32 * 2), ("n_kept", C.c_uint32 * 2),
+                ("truncated", C.c_int32 * 2), ("times_ms", C.c_double * 7)]
+
+
 class KhMergeAlignParams(C.Structure):
     _fields_ = [("n_probes", C.c_int32), ("top_k", C.c_int32), ("min_known", C.c_uint64), ("min_pass_through", C.c_uint32), ("pad", C.c_uint32),
                 ("occupancy_threshold", C.c_double), ("relocalize", KhRelocalizeParams)]
@@ -549,6 +572,17 @@ def lib():
         L.kh_map_field_costs_rect.argtypes = [vp, C.POINTER(KhInflationParams), i32, i32, i32, i32, vp]
         L.kh_live_map_field_create.argtypes = [vp, C.POINTER(KhMapFieldParams), C.POINTER(vp)]
         L.kh_live_map_field_sync.argtypes = [vp, C.POINTER(KhFieldUpdate)]
+    if hasattr(L, "kh_map_regions_create"):    # (KH_LIBRARY may name a build from before the region analysis existed)
+        L.kh_map_regions_params_default.argtypes = [C.POINTER(KhMapRegionsParams)]
+        L.kh_map_regions_params_default.restype = None
+        L.kh_map_regions_create.argtypes = [vp, C.POINTER(KhMapRegionsParams), C.POINTER(vp)]
+        L.kh_map_regions_recompute.argtypes = [vp, vp]
+        L.kh_map_regions_destroy.argtypes = [vp]
+        L.kh_map_regions_destroy.restype = None
+        L.kh_map_regions_stats_get.argtypes = [vp, C.POINTER(KhMapRegionsStats)]
+        L.kh_map_regions_read.argtypes = [vp, i32, vp]
+        L.kh_map_regions_get.argtypes = [vp, i32, C.POINTER(KhRegion), i32, C.POINTER(i32)]
+        L.kh_map_regions_lookup.argtypes = [vp, i32, vp, vp, vp]
     if hasattr(L, "kh_spa_create"):
         L.kh_spa_options_default.argtypes = [C.POINTER(KhSpaOptions)]
         L.kh_spa_create.argtypes = [i32, C.POINTER(vp)]

@@ -663,6 +663,8 @@ namespace kh
 {
 kh_live_map * map_field_live(const kh_map_field * f) {return f->live;}
 void map_field_set_live(kh_map_field * f, kh_live_map * g) {f->live = g;}
+FieldWindow map_field_window(const kh_map_field * f) {return f->window();}
+int32_t map_field_device(const kh_map_field * f) {return f->view.device;}
 
 // a handle on the view's lattice with no window and no arrays yet: kh_map_field_update on the same view lays it out and builds it
 int map_field_create_empty(const kh_map_view & view, const kh_map_field_params & params, const char * who, kh_map_field ** out)

@@ -206,6 +206,11 @@ void map_diff(void * stream, const kh_map_view & v, const ChangeLayer & layer, u
     min_pass, threshold, d_codes, d_patched, d_counts);
 }
 
+void unit_scan(void * stream, int32_t * d_unit, int64_t n_units)
+{
+  hipLaunchKernelGGL(k_map_changed_scan, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), d_unit, n_units);
+}
+
 void map_changed_cells(void * stream, const kh_map_view & v, const uint8_t * d_codes, int32_t * d_unit, int32_t * d_list, int32_t cap)
 {
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -213,7 +218,7 @@ void map_changed_cells(void * stream, const kh_map_view & v, const uint8_t * d_c
   const int64_t n_units = change_units(v.width, v.height);
   const dim3 blocks(static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>((n_units + 3) / 4, 1024))));
   hipLaunchKernelGGL(k_map_changed<false>, blocks, dim3(256), 0, s, window_of(v), d_codes, units_per_row, n_units, d_unit, d_list, cap);
-  hipLaunchKernelGGL(k_map_changed_scan, dim3(1), dim3(1024), 0, s, d_unit, n_units);
+  unit_scan(s, d_unit, n_units);
   if (cap > 0) {hipLaunchKernelGGL(k_map_changed<true>, blocks, dim3(256), 0, s, window_of(v), d_codes, units_per_row, n_units, d_unit, d_list, cap);}
 }
 

@@ -337,6 +337,56 @@ kh_live_map * map_field_live(const kh_map_field * f);
 void map_field_set_live(kh_map_field * f, kh_live_map * g);
 int map_field_create_empty(const kh_map_view & view, const kh_map_field_params & params, const char * who, kh_map_field ** out);
 void live_map_forget_field(kh_live_map * g, kh_map_field * f);
+// what a reader of another module takes of a field (map_regions.cpp): its arrays as they stand, its device
+FieldWindow map_field_window(const kh_map_field * f);
+int32_t map_field_device(const kh_map_field * f);
+
+// ---- map regions (occupancy_regions.hip; kh_map_regions_*; the handle and its buffers: map_regions.cpp; the
+// rules: map_regions_plan.hpp) ----
+// A component's record as the kernels keep it: integers only, the box as inclusive window columns / rows, the anchor as its key
+// dist2 << 32 | window index.  k_region_assign writes the first two fields and the neutral elements of the rest.
+struct RegionRecord
+{
+  uint32_t root, n_cells;
+  int32_t x0, y0, x1, y1;
+  unsigned long long sum_i, sum_j;
+  uint32_t max_d2, n_other, link, pad;
+  unsigned long long anchor_key;
+};
+// One of the two sets on the window, every array dense (row stride `width`): label -- a cell's parent, then its root, then its id
+// (KH_REGION_NONE off the mask throughout); count -- cells per root, then the root's id; the records of the kept components.
+struct RegionSet
+{
+  uint32_t * label;
+  uint32_t * count;
+  RegionRecord * records;
+  uint32_t minimum, maximum;
+};
+struct RegionJob
+{
+  FieldWindow f;               // the field's cells and values: read only
+  RegionSet set[2];            // KH_REGIONS, KH_FRONTIERS
+  uint32_t rc2;                // Rc * Rc
+  int32_t conn8;               // 1: eight neighbours
+  int32_t * unit;              // region_grid().units + 1 words: the compaction's counts, then their exclusive prefix
+  unsigned long long * counters;   // kRegionCounters words, zeroed by the caller; [kRegionError] != 0: a watchdog ended a walk
+};
+// k_region_tiles on `stream`: both masks, the labels of both sets inside every 64 x 16 tile, the two mask counters
+void region_tiles(void * stream, const RegionJob & job);
+// k_region_seams on `stream`, once per set: the unions across tile borders
+void region_seams(void * stream, const RegionJob & job);
+// k_region_flatten on `stream`, once per set: label = root, count[root] = cells (count zeroed by the caller)
+void region_flatten(void * stream, const RegionJob & job);
+// k_region_roots (count, fill), the unit scan, k_region_ids on `stream`, per set: the kept roots numbered in row-major order, their
+// records begun, label = id
+void region_compact(void * stream, const RegionJob & job);
+// k_region_records, then k_region_anchor on `stream`: both sets in one launch each
+void region_records(void * stream, const RegionJob & job);
+void region_anchors(void * stream, const RegionJob & job);
+// k_region_lookup on `stream`: n points (x, y) -> the id of their cell in `ids` (dense) and a KH_REGION_AT_ / _OUTSIDE status
+void region_lookup(void * stream, const FieldWindow & f, const uint32_t * d_ids, int32_t n, const double * d_xy, uint32_t * d_id, int32_t * d_status);
+// k_map_changed_scan on `stream` (occupancy_changes.hip): d_unit[0 .. n_units) -> its exclusive prefix in place, d_unit[n_units] the sum
+void unit_scan(void * stream, int32_t * d_unit, int64_t n_units);
 
 // ---- a change layer's kernels (occupancy_changes.hip; kh_map_changes_*; the handle and its buffers: map_changes.cpp) ----
 // the layer's two counter grids on the window of its view, row stride the view's width_step

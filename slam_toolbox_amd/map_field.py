@@ -184,6 +184,12 @@ class MapField:
                                                   times.ctypes.data), "kh_map_field_refine")
         return [Refined(np.array(r.pose), r.cost_start, r.cost, r.n_hit, r.rounds, r.halvings, r.status) for r in out[:len(poses)]], times
 
+    def regions(self, **params):
+        """kh_map_regions_create on this field: connected free space by clearance and frontier clusters.
+        params: fields of kh_map_regions_params.  -> map_regions.MapRegions, which does not borrow the field"""
+        from .map_regions import MapRegions
+        return MapRegions(self, **params)
+
     def close(self):
         if self._h:
             capi.lib().kh_map_field_destroy(self._h)

@@ -238,6 +238,15 @@ class MapLocalizer:
             raise capi.KartoHipError(capi.KH_ERR_NOT_FOUND, "MapLocalizer.field: no map set")
         return MapField(self._map, **params)
 
+    def regions(self, max_distance: float = 2.0, **params):
+        """kh_map_regions_create on the localizer's map, through a distance field made for this call that reaches at least
+        min_clearance.  params: fields of kh_map_regions_params.  -> map_regions.MapRegions (it does not borrow the field)"""
+        f = self.field(max_distance=max(float(max_distance), float(params.get("min_clearance", 0.0))))
+        try:
+            return f.regions(**params)
+        finally:
+            f.close()
+
     def refine(self, ranges, sensor_pose, field=None, max_distance: float = 2.0, **params):
         """kh_map_field_refine of `sensor_pose` (3,) or poses (n, 3) -- a hypothesis' or a tracking step's -- with this localizer's
         laser, on `field` (a MapField of the current map, as `field()` makes them) or on one made for this call.  params: fields of
