@@ -1826,6 +1826,94 @@ KH_API int kh_map_regions_get(kh_map_regions * r, int32_t which, kh_region * rec
 enum { KH_REGION_AT_OK = 0, KH_REGION_AT_NONE = 1, KH_REGION_AT_DROPPED = 2, KH_REGION_OUTSIDE = 3 };
 KH_API int kh_map_regions_lookup(kh_map_regions * r, int32_t n, const double * xy /* 2n */, int32_t * status, uint32_t * id);
 
+/* ---------------------------------------------------------------- travel costs on a map: cost-to-go field from goals, paths, lookups
+ * (DESIGN.md section 7r).  A travel analysis is made from a kh_map_field, as a region analysis is: it reads the field's snapshot of
+ * the cell states and its d2 values over the field's window and never borrows the field.  Cells outside the window do not exist;
+ * columns width .. width_step - 1 are never read.
+ *   Rc, Rt       ceil(min_clearance * scale), ceil(inflation.inflation_radius * scale) cells, the field's rule for R
+ *   traversable  a cell of state 255 with d2 >= Rc * Rc (KH_FIELD_FAR counts as beyond): section 7q's mask
+ *   weight       q(v) = neutral_cost + ((cost_weight * c(v)) >> 4) for a traversable cell, c(v) what kh_map_field_costs gives a cell of
+ *                state 255 (table[d2] for d2 <= Rt * Rt, else 0); q = 0 for every other cell.  With cost_weight == 0 the table is not
+ *                needed and Rt is not checked against the field.
+ *   steps        directions n = 0 .. 7: (+1,0), (0,+1), (-1,0), (0,-1), (+1,+1), (-1,+1), (-1,-1), (+1,-1); connectivity 4 has 0 .. 3
+ *                only.  L(n) = 5 for n < 4, else 7.  A step u -> v is allowed when v is a traversable window cell; a diagonal step
+ *                (di, dj) from (i, j) only when cut_corners is set or both (i + di, j) and (i, j + dj) are traversable.  Allowedness
+ *                is symmetric.  The step costs L(n) * q(u): a cell is paid for when it is left.
+ *   values       V = 0 at every goal cell; elsewhere V(u) = min over allowed steps u -> v of V(v) + L * q(u); KH_TRAVEL_FAR where no
+ *                goal is reached and at every cell that is not traversable.  Shortest-path costs over positive integer weights are
+ *                unique: no execution order shows in them.
+ *   goal         the lattice cell of a goal point is kh_map_field_clearance's; the goal cell is the traversable window cell within
+ *                Chebyshev distance goal_snap_cells of it with the smallest key dist2 << 32 | window index (dist2: the squared cell
+ *                distance to the point's cell).  KH_TRAVEL_GOAL_BLOCKED: no such cell; KH_TRAVEL_GOAL_OUTSIDE: the point's own cell
+ *                is off the window or beyond +-2^30 cells.  A solve without a usable goal is KH_OK with every value KH_TRAVEL_FAR.
+ *   lookup       among the window cells within Chebyshev distance snap_cells of the point's cell whose value is not KH_TRAVEL_FAR,
+ *                the one with the smallest key V << 32 | window index: KH_TRAVEL_AT_OK with its value and lattice cell;
+ *                KH_TRAVEL_AT_UNREACHED where there is none, KH_TRAVEL_AT_OUTSIDE by the goal's rule: value KH_TRAVEL_FAR, cell (0, 0)
+ *   path         the start cell is the lookup's; emit it; while V(cur) != 0 go to the allowed neighbour v of the smallest direction
+ *                index with V(v) + L * q(cur) == V(cur).  V strictly decreases, so the walk ends.  KH_TRAVEL_PATH_TRUNCATED: max_cells
+ *                cells were emitted and the last is no goal cell. */
+#define KH_TRAVEL_FAR 0xFFFFFFFFu
+enum { KH_TRAVEL_GOAL_OK = 0, KH_TRAVEL_GOAL_BLOCKED = 1, KH_TRAVEL_GOAL_OUTSIDE = 2 };
+enum { KH_TRAVEL_AT_OK = 0, KH_TRAVEL_AT_UNREACHED = 1, KH_TRAVEL_AT_OUTSIDE = 2 };
+enum { KH_TRAVEL_PATH_OK = 0, KH_TRAVEL_PATH_TRUNCATED = 1, KH_TRAVEL_PATH_UNREACHED = 2, KH_TRAVEL_PATH_OUTSIDE = 3 };
+typedef struct kh_map_travel kh_map_travel;
+typedef struct kh_map_travel_params {
+  double min_clearance;                          /* metres, finite, >= 0 (default 0: every free cell) */
+  kh_inflation_params inflation;                 /* c(v)'s curve (default kh_inflation_params_default); the unknown policy is not read */
+  int32_t connectivity, cut_corners;             /* 4 or 8 (default 8); 0 / 1 (default 0) */
+  int32_t neutral_cost, cost_weight;             /* 1 .. 255 (default 50); 0 .. 255 in sixteenths (default 13) */
+  int32_t goal_snap_cells, pad;                  /* 0 .. 16 (default 0) */
+} kh_map_travel_params;
+typedef struct kh_map_travel_stats {
+  int32_t ox, oy, width, height;                 /* the window */
+  int32_t clearance_cells, inflation_cells;      /* Rc, Rt */
+  int32_t connectivity, pad;
+  uint64_t n_traversable, n_reached;             /* cells of weight > 0; cells of a value other than KH_TRAVEL_FAR (0 before a solve) */
+  uint32_t max_value;                            /* the largest value that is not KH_TRAVEL_FAR; 0 when there is none */
+  uint32_t rounds, launches;                     /* of the last solve: launches in which a tile ran; launches of k_travel_relax */
+  uint32_t pad2;
+  uint64_t tile_runs;                            /* tiles relaxed over all rounds (depends on what a tile saw of its neighbours in flight) */
+  double times_ms[4];          /* by device events: the weights, the goals, the relaxation (summed); the last call by wall time */
+} kh_map_travel_stats;
+typedef struct kh_travel_path {
+  int32_t status, n_cells;     /* KH_TRAVEL_PATH_; cells emitted */
+  uint32_t cost, start_cell;   /* the value at the first cell; its window index (both KH_TRAVEL_FAR without a start cell) */
+} kh_travel_path;
+/* 0.0, kh_inflation_params_default, 8, 0, 50, 13, 0; a NULL output is ignored */
+KH_API void kh_map_travel_params_default(kh_map_travel_params * p);
+/* Snapshots the weights (uint16 per cell, dense) and the traversable count.  KH_ERR_INVALID_ARG before a device is looked for, in
+ * this order: a NULL field, params or out; a connectivity other than 4 or 8; cut_corners outside 0 .. 1; neutral_cost outside
+ * 1 .. 255; cost_weight outside 0 .. 255; goal_snap_cells outside 0 .. 16; a min_clearance that is not finite or < 0; Rc > 1024; what
+ * kh_inflation_table refuses of the inflation parameters at the field's scale.  Then KH_ERR_NO_DEVICE; then, in this order: a field
+ * with 0 < R < Rc; with cost_weight > 0 a field with 0 < R < Rt; a window with width * height * Lmax * q_max > 0xFFFFFFFE, Lmax = 7
+ * under connectivity 8, else 5, q_max = neutral_cost + ((cost_weight * 253) >> 4): a bound the arguments alone give. */
+KH_API int kh_map_travel_create(kh_map_field * field, const kh_map_travel_params * params, kh_map_travel ** out);
+/* the snapshot again, of `field` as it stands (after kh_map_field_update or kh_live_map_field_sync, or of another field of the same
+ * lattice); the solution is dropped.  Refusals and the reuse of allocations are kh_map_regions_recompute's, then the three above. */
+KH_API int kh_map_travel_recompute(kh_map_travel * t, kh_map_field * field);
+KH_API void kh_map_travel_destroy(kh_map_travel * t);
+/* n_goals 1 .. 4096 world points (x, y); goal_status (may be NULL) takes a KH_TRAVEL_GOAL_ code each.  n_goals out of range, NULL
+ * goals_xy, a non-finite point: KH_ERR_INVALID_ARG before a device is looked for.  A watchdog that ended the relaxation:
+ * KH_ERR_HIP, and the handle holds no solution. */
+KH_API int kh_map_travel_solve(kh_map_travel * t, int32_t n_goals, const double * goals_xy /* 2n */, int32_t * goal_status);
+KH_API int kh_map_travel_stats_get(kh_map_travel * t, kh_map_travel_stats * out);
+/* the values (uint32) and the weights (uint16), width * height each, row-major with no padding; either may be NULL.  This and the
+ * two readers below: KH_ERR_NOT_FOUND before the first successful solve and after a recompute. */
+KH_API int kh_map_travel_read(kh_map_travel * t, uint32_t * values, uint16_t * weights);
+/* any output may be NULL.  n < 1, NULL xy, a non-finite point, snap_cells outside 0 .. 16: KH_ERR_INVALID_ARG before a device is
+ * looked for. */
+KH_API int kh_map_travel_lookup(kh_map_travel * t, int32_t n, const double * xy /* 2n */, int32_t snap_cells, int32_t * status, uint32_t * value,
+                                int32_t * cell /* 2n: lattice x, y */);
+/* heads takes n records; cells (may be NULL) 2 * n * max_cells int32 -- lattice x, y of cell s of path k at 2 * (k * max_cells + s) --
+ * zeros past a path's n_cells.  KH_ERR_INVALID_ARG before a device is looked for: what kh_map_travel_lookup refuses, NULL heads,
+ * max_cells outside 1 .. 65536, n * max_cells > 2^24.  A walk that finds no neighbour to go to (it cannot happen in a solved field)
+ * ends there, and the call returns KH_ERR_HIP. */
+KH_API int kh_map_travel_paths(kh_map_travel * t, int32_t n, const double * starts_xy /* 2n */, int32_t snap_cells, int32_t max_cells,
+                               kh_travel_path * heads /* n */, int32_t * cells);
+/* debugging: the launches of k_travel_relax between two reads of the "anything flagged" word; 0 = the library's choice, at most 64.
+ * The result does not depend on it.  k < 0 or > 64: KH_ERR_INVALID_ARG. */
+KH_API int kh_map_travel_set_rounds_per_check(kh_map_travel * t, int32_t k);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,8 @@ SYMBOLS = [
     "kh_live_map_field_create", "kh_live_map_field_sync",
     "kh_map_regions_params_default", "kh_map_regions_create", "kh_map_regions_recompute", "kh_map_regions_destroy", "kh_map_regions_stats_get",
     "kh_map_regions_read", "kh_map_regions_get", "kh_map_regions_lookup",
+    "kh_map_travel_params_default", "kh_map_travel_create", "kh_map_travel_recompute", "kh_map_travel_destroy", "kh_map_travel_solve",
+    "kh_map_travel_stats_get", "kh_map_travel_read", "kh_map_travel_lookup", "kh_map_travel_paths", "kh_map_travel_set_rounds_per_check",
 ]
 
 
@@ -421,6 +423,27 @@ class KhMapRegionsStats(C.Structure):
                 ("truncated", C.c_int32 * 2), ("times_ms", C.c_double * 7)]
 
 
+KH_TRAVEL_FAR = 0xFFFFFFFF
+KH_TRAVEL_GOAL_OK, KH_TRAVEL_GOAL_BLOCKED, KH_TRAVEL_GOAL_OUTSIDE = range(3)
+KH_TRAVEL_AT_OK, KH_TRAVEL_AT_UNREACHED, KH_TRAVEL_AT_OUTSIDE = range(3)
+KH_TRAVEL_PATH_OK, KH_TRAVEL_PATH_TRUNCATED, KH_TRAVEL_PATH_UNREACHED, KH_TRAVEL_PATH_OUTSIDE = range(4)
+
+
+class KhMapTravelParams(C.Structure):
+    _fields_ = [("min_clearance", C.c_double), ("inflation", KhInflationParams)] + \
+               [(k, C.c_int32) for k in ("connectivity", "cut_corners", "neutral_cost", "cost_weight", "goal_snap_cells", "pad")]
+
+
+class KhMapTravelStats(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("ox", "oy", "width", "height", "clearance_cells", "inflation_cells", "connectivity", "pad")] + \
+               [("n_traversable", C.c_uint64), ("n_reached", C.c_uint64)] + \
+               [(k, C.c_uint32) for k in ("max_value", "rounds", "launches", "pad2")] + [("tile_runs", C.c_uint64), ("times_ms", C.c_double * 4)]
+
+
+class KhTravelPath(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_cells", C.c_int32), ("cost", C.c_uint32), ("start_cell", C.c_uint32)]
+
+
 class KhMergeAlignParams(C.Structure):
     _fields_ = [("n_probes", C.c_int32), ("top_k", C.c_int32), ("min_known", C.c_uint64), ("min_pass_through", C.c_uint32), ("pad", C.c_uint32),
                 ("occupancy_threshold", C.c_double), ("relocalize", KhRelocalizeParams)]
@@ -583,6 +606,19 @@ def lib():
         L.kh_map_regions_read.argtypes = [vp, i32, vp]
         L.kh_map_regions_get.argtypes = [vp, i32, C.POINTER(KhRegion), i32, C.POINTER(i32)]
         L.kh_map_regions_lookup.argtypes = [vp, i32, vp, vp, vp]
+    if hasattr(L, "kh_map_travel_create"):     # (KH_LIBRARY may name a build from before the travel costs existed)
+        L.kh_map_travel_params_default.argtypes = [C.POINTER(KhMapTravelParams)]
+        L.kh_map_travel_params_default.restype = None
+        L.kh_map_travel_create.argtypes = [vp, C.POINTER(KhMapTravelParams), C.POINTER(vp)]
+        L.kh_map_travel_recompute.argtypes = [vp, vp]
+        L.kh_map_travel_destroy.argtypes = [vp]
+        L.kh_map_travel_destroy.restype = None
+        L.kh_map_travel_solve.argtypes = [vp, i32, vp, vp]
+        L.kh_map_travel_stats_get.argtypes = [vp, C.POINTER(KhMapTravelStats)]
+        L.kh_map_travel_read.argtypes = [vp, vp, vp]
+        L.kh_map_travel_lookup.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+        L.kh_map_travel_paths.argtypes = [vp, i32, vp, i32, i32, C.POINTER(KhTravelPath), vp]
+        L.kh_map_travel_set_rounds_per_check.argtypes = [vp, i32]
     if hasattr(L, "kh_spa_create"):
         L.kh_spa_options_default.argtypes = [C.POINTER(KhSpaOptions)]
         L.kh_spa_create.argtypes = [i32, C.POINTER(vp)]

@@ -388,6 +388,40 @@ void region_lookup(void * stream, const FieldWindow & f, const uint32_t * d_ids,
 // k_map_changed_scan on `stream` (occupancy_changes.hip): d_unit[0 .. n_units) -> its exclusive prefix in place, d_unit[n_units] the sum
 void unit_scan(void * stream, int32_t * d_unit, int64_t n_units);
 
+// ---- travel costs (occupancy_travel.hip; kh_map_travel_*; the handle and its buffers: map_travel.cpp; the
+// rules: map_travel_plan.hpp) ----
+// The analysis on the window, both arrays dense (row stride `width`): q -- a cell's weight, 0 where it is not traversable; v -- its
+// value.  The lattice is the field's (f.cells, f.g, f.d2 are read by travel_weights only).
+struct TravelJob
+{
+  FieldWindow f;
+  uint16_t * q;
+  uint32_t * v;
+  int32_t conn8, cut_corners;
+  uint32_t * flags;            // 2 * tiles words: the tiles to run in launches of even / odd parity
+  unsigned long long * counters;   // kTravelCounters words; [kTravelError] != 0: a watchdog ended a loop, or a path found no way on
+};
+// one answer of k_travel_lookup, one head of k_travel_paths
+struct alignas(16) TravelAt {int32_t status; uint32_t value; int32_t x, y;};
+struct alignas(16) TravelHead {int32_t status, n_cells; uint32_t cost, start_cell;};
+static_assert(sizeof(TravelAt) == 16 && sizeof(TravelHead) == sizeof(kh_travel_path), "one int4 per answer; a head is the ABI's record");
+// k_travel_weights on `stream`: q from the field through d_table (rt2 + 1 entries; not read when cost_weight == 0);
+// counters[kTravelTraversable] (zeroed by the caller) takes the cells of weight > 0
+void travel_weights(void * stream, const TravelJob & job, uint32_t rc2, const uint8_t * d_table, uint32_t rt2, uint32_t neutral_cost, uint32_t cost_weight);
+// k_travel_goals on `stream`: n goals (x, y) -> their status and cell (window index, KH_TRAVEL_FAR without one); v = 0 at every goal
+// cell; the goal's tile and its neighbours are flagged for the first launch.  The caller has set v to KH_TRAVEL_FAR and the flags to 0.
+void travel_goals(void * stream, const TravelJob & job, int32_t n, const double * d_xy, int32_t snap, int32_t * d_status, uint32_t * d_cell);
+// k_travel_relax on `stream`: launch number `round` (its parity picks the flags it reads); *d_any (zeroed by the caller) becomes 1
+// where a tile flagged a neighbour for the next launch; counters[kTravelRuns] += the tiles that ran
+void travel_relax(void * stream, const TravelJob & job, uint32_t round, uint32_t * d_any);
+// k_travel_count on `stream`: counters[kTravelReached] and [kTravelMaxValue] (zeroed by the caller) from the values as they stand
+void travel_count(void * stream, const TravelJob & job);
+// k_travel_lookup on `stream`: n points (x, y) -> one TravelAt each
+void travel_lookup(void * stream, const TravelJob & job, int32_t n, const double * d_xy, int32_t snap, TravelAt * d_out);
+// k_travel_paths on `stream`: n starts -> one head each and, where d_cells is not null, the cells of path k from 2 * k * max_cells on
+void travel_paths(void * stream, const TravelJob & job, int32_t n, const double * d_xy, int32_t snap, int32_t max_cells, TravelHead * d_heads,
+  int32_t * d_cells);
+
 // ---- a change layer's kernels (occupancy_changes.hip; kh_map_changes_*; the handle and its buffers: map_changes.cpp) ----
 // the layer's two counter grids on the window of its view, row stride the view's width_step
 struct ChangeLayer

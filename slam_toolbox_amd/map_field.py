@@ -62,7 +62,7 @@ class MapField:
         p.max_distance, p.obstacles = float(max_distance), int(OBSTACLES.get(obstacles, obstacles))
         capi.check(capi.lib().kh_map_field_create(C.byref(v), C.byref(p), C.byref(self._h)), "kh_map_field_create")
         self._live = None
-        self.scale = v.scale
+        self.scale, self.anchor = v.scale, (v.anchor[0], v.anchor[1])
         self._read_stats()
 
     @classmethod
@@ -74,7 +74,8 @@ class MapField:
         capi.lib().kh_map_field_params_default(C.byref(p))
         p.max_distance, p.obstacles = float(max_distance), int(OBSTACLES.get(obstacles, obstacles))
         capi.check(capi.lib().kh_live_map_field_create(live._h, C.byref(p), C.byref(self._h)), "kh_live_map_field_create")
-        self.scale = live.view().scale
+        v = live.view()
+        self.scale, self.anchor = v.scale, (v.anchor[0], v.anchor[1])
         self._read_stats()
         return self
 
@@ -189,6 +190,12 @@ class MapField:
         params: fields of kh_map_regions_params.  -> map_regions.MapRegions, which does not borrow the field"""
         from .map_regions import MapRegions
         return MapRegions(self, **params)
+
+    def travel(self, **params):
+        """kh_map_travel_create on this field: travel costs to goal points, paths, lookups.  params: fields of
+        kh_map_travel_params and of its kh_inflation_params.  -> map_travel.MapTravel, which does not borrow the field"""
+        from .map_travel import MapTravel
+        return MapTravel(self, **params)
 
     def close(self):
         if self._h:

@@ -247,6 +247,17 @@ class MapLocalizer:
         finally:
             f.close()
 
+    def travel(self, max_distance: float = 2.0, **params):
+        """kh_map_travel_create on the localizer's map, through a distance field made for this call that reaches max(Rc, Rt): the
+        larger of min_clearance and -- with a cost_weight above 0 -- the inflation radius.  params: fields of kh_map_travel_params
+        and of its kh_inflation_params.  -> map_travel.MapTravel (it does not borrow the field)"""
+        from .map_travel import reach_of
+        f = self.field(max_distance=max(float(max_distance), reach_of(params)))
+        try:
+            return f.travel(**params)
+        finally:
+            f.close()
+
     def refine(self, ranges, sensor_pose, field=None, max_distance: float = 2.0, **params):
         """kh_map_field_refine of `sensor_pose` (3,) or poses (n, 3) -- a hypothesis' or a tracking step's -- with this localizer's
         laser, on `field` (a MapField of the current map, as `field()` makes them) or on one made for this call.  params: fields of
