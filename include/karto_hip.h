@@ -1914,6 +1914,73 @@ KH_API int kh_map_travel_paths(kh_map_travel * t, int32_t n, const double * star
  * The result does not depend on it.  k < 0 or > 64: KH_ERR_INVALID_ARG. */
 KH_API int kh_map_travel_set_rounds_per_check(kh_map_travel * t, int32_t k);
 
+/* ---------------------------------------------------------------- visibility on a map: the cells a pose would see, gain, greedy views
+ * (DESIGN.md section 7s).  The rays are kh_map_raycast's, with the same max_unknown; what is kept is every cell they visit.
+ *   beam cells   beam b of sensor pose p walks TraceLine(c0, c1) outward as kh_map_raycast does and leaves at step s_end (kh_ray_t.steps):
+ *                its visited cells are those of s = 0 .. s_end, the leaving cell included -- the HIT cell, the unknown cell that
+ *                exceeded the budget, or c1 on FREE
+ *   Seen(p)      the WINDOW cells among the visited cells of all beams of p, each once.  A cell outside the window is never counted;
+ *                a window cell of state 100 is occupied, of state 255 free, of any other state unknown.  The sensor's own cell is
+ *                treated like any other
+ *   covered      the handle's mask over the view's window, one bit per cell: cleared by create and _clear, _commit(poses) ORs Seen(p)
+ *                of every given pose into it
+ *   record       seen_*: the cells of Seen(p) by state; new_*: the same over Seen(p) minus the covered mask as it stands at the call;
+ *                gain = w_unknown * new_unknown + w_free * new_free + w_occupied * new_occupied; beams_*: the beams by KH_RAY_ code
+ *   reach        floor(range_threshold * scale) + 2 cells bounds the Chebyshev distance from c0 to any c1 (both cells are rounded);
+ *                a laser of reach > 511 is refused: the per-pose bitmap of side 2 * reach + 1 <= 1023 fits one workgroup's LDS, and
+ *                gain <= 1023^2 * 765 stays below 2^32
+ *   select       rounds r = 0 .. k - 1: among the candidates not yet picked, the largest gain against the mask as it stands, ties to
+ *                the smallest index; below min_gain the selection ends with r picks; else (index, gain) is recorded and the pose
+ *                committed.  The mask is not cleared first and is left holding the picks.
+ * Every result is an integer no execution order shows in. */
+typedef struct kh_map_visibility kh_map_visibility;
+typedef struct kh_visibility_params {
+  int32_t max_unknown;                           /* kh_map_raycast's budget, -1: none (default 20) */
+  int32_t w_unknown, w_free, w_occupied;         /* 0 .. 255 each, not all zero (default 1, 0, 0) */
+} kh_visibility_params;
+typedef struct kh_visibility_t {
+  uint32_t seen_free, seen_occupied, seen_unknown;
+  uint32_t new_free, new_occupied, new_unknown;
+  uint32_t gain;
+  uint32_t beams_free, beams_hit, beams_unknown;
+} kh_visibility_t;
+typedef struct kh_map_visibility_stats {
+  int32_t ox, oy, width, height;                 /* the window */
+  int32_t reach, bitmap_bytes;                   /* cells; the bytes of one pose's bitmap in LDS */
+  int32_t n_poses, pad;                          /* of the last gain, commit or select */
+  uint32_t rounds, launches;                     /* of the last call: a select's rounds that picked (else 0); its kernel launches */
+  double kernel_ms, call_ms;                     /* the last call's kernels by device events, the call by wall time */
+} kh_map_visibility_stats;
+/* 20, 1, 0, 0; a NULL output is ignored */
+KH_API void kh_map_visibility_params_default(kh_visibility_params * p);
+/* The handle copies the view struct; the cells stay borrowed under kh_map_view's validity rule.  KH_ERR_INVALID_ARG before a device
+ * is looked for, in this order: a NULL view, laser, params or out; what kh_map_raycast refuses of a view; laser->n_beams < 1 and what
+ * kh_map_raycast refuses of a laser; max_unknown < -1; a weight outside 0 .. 255, or all three zero; reach > 511. */
+KH_API int kh_map_visibility_create(const kh_map_view * view, const kh_laser * laser, const kh_visibility_params * params,
+                                    kh_map_visibility ** out);
+KH_API void kh_map_visibility_destroy(kh_map_visibility * v);
+/* another view of the same window (ox, oy, width, height), lattice (anchor, scale) and device: a map that changed in place or a
+ * patched copy.  Anything else, and what kh_map_raycast refuses of a view: KH_ERR_INVALID_ARG.  The mask is kept. */
+KH_API int kh_map_visibility_set_map(kh_map_visibility * v, const kh_map_view * view);
+KH_API int kh_map_visibility_clear(kh_map_visibility * v);
+/* The calls below take n sensor poses (x, y, heading).  KH_ERR_INVALID_ARG before a device is looked for, in this order: NULL
+ * sensor_poses or a NULL required output; n outside 1 .. 65536; a pose kh_map_raycast refuses; (select) k outside 1 .. min(n, 4096);
+ * (select) min_gain < 1; n * n_beams above 2^24 (the far points of a call are one table). */
+KH_API int kh_map_visibility_commit(kh_map_visibility * v, int32_t n, const double * sensor_poses /* 3n */);
+/* out takes n records; *kernel_ms (may be NULL) the kernel's time by events.  The mask is read, not written. */
+KH_API int kh_map_visibility_gain(kh_map_visibility * v, int32_t n, const double * sensor_poses /* 3n */, kh_visibility_t * out /* n */,
+                                  double * kernel_ms);
+/* picks and pick_gains take k entries each, the first *n_picked of them set and the rest 0.  The rounds run on the device with no
+ * host read between them. */
+KH_API int kh_map_visibility_select(kh_map_visibility * v, int32_t n, const double * sensor_poses /* 3n */, int32_t k, uint32_t min_gain,
+                                    int32_t * picks /* k */, uint32_t * pick_gains /* k */, int32_t * n_picked);
+/* the covered mask as width * height bytes of 0 / 1, row-major with no padding */
+KH_API int kh_map_visibility_read_mask(kh_map_visibility * v, uint8_t * out);
+KH_API int kh_map_visibility_stats_get(kh_map_visibility * v, kh_map_visibility_stats * out);
+/* debugging and measuring: 1 (the default) reads a bitmap word before the OR and leaves the OR out where the bit is set, 0 always ORs.
+ * The result does not depend on it.  Any other value: KH_ERR_INVALID_ARG. */
+KH_API int kh_map_visibility_set_skip(kh_map_visibility * v, int32_t skip);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,6 +184,9 @@ SYMBOLS = [
     "kh_map_regions_read", "kh_map_regions_get", "kh_map_regions_lookup",
     "kh_map_travel_params_default", "kh_map_travel_create", "kh_map_travel_recompute", "kh_map_travel_destroy", "kh_map_travel_solve",
     "kh_map_travel_stats_get", "kh_map_travel_read", "kh_map_travel_lookup", "kh_map_travel_paths", "kh_map_travel_set_rounds_per_check",
+    "kh_map_visibility_params_default", "kh_map_visibility_create", "kh_map_visibility_destroy", "kh_map_visibility_set_map", "kh_map_visibility_clear",
+    "kh_map_visibility_commit", "kh_map_visibility_gain", "kh_map_visibility_select", "kh_map_visibility_read_mask", "kh_map_visibility_stats_get",
+    "kh_map_visibility_set_skip",
 ]
 
 
@@ -444,6 +447,20 @@ class KhTravelPath(C.Structure):
     _fields_ = [("status", C.c_int32), ("n_cells", C.c_int32), ("cost", C.c_uint32), ("start_cell", C.c_uint32)]
 
 
+class KhVisibilityParams(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("max_unknown", "w_unknown", "w_free", "w_occupied")]
+
+
+class KhVisibility(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("seen_free", "seen_occupied", "seen_unknown", "new_free", "new_occupied", "new_unknown", "gain", "beams_free",
+                                          "beams_hit", "beams_unknown")]
+
+
+class KhMapVisibilityStats(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("ox", "oy", "width", "height", "reach", "bitmap_bytes", "n_poses", "pad")] + \
+               [("rounds", C.c_uint32), ("launches", C.c_uint32), ("kernel_ms", C.c_double), ("call_ms", C.c_double)]
+
+
 class KhMergeAlignParams(C.Structure):
     _fields_ = [("n_probes", C.c_int32), ("top_k", C.c_int32), ("min_known", C.c_uint64), ("min_pass_through", C.c_uint32), ("pad", C.c_uint32),
                 ("occupancy_threshold", C.c_double), ("relocalize", KhRelocalizeParams)]
@@ -619,6 +636,20 @@ def lib():
         L.kh_map_travel_lookup.argtypes = [vp, i32, vp, i32, vp, vp, vp]
         L.kh_map_travel_paths.argtypes = [vp, i32, vp, i32, i32, C.POINTER(KhTravelPath), vp]
         L.kh_map_travel_set_rounds_per_check.argtypes = [vp, i32]
+    if hasattr(L, "kh_map_visibility_create"):     # (KH_LIBRARY may name a build from before the visibility analysis existed)
+        L.kh_map_visibility_params_default.argtypes = [C.POINTER(KhVisibilityParams)]
+        L.kh_map_visibility_params_default.restype = None
+        L.kh_map_visibility_create.argtypes = [C.POINTER(KhMapView), C.POINTER(KhLaser), C.POINTER(KhVisibilityParams), C.POINTER(vp)]
+        L.kh_map_visibility_destroy.argtypes = [vp]
+        L.kh_map_visibility_destroy.restype = None
+        L.kh_map_visibility_set_map.argtypes = [vp, C.POINTER(KhMapView)]
+        L.kh_map_visibility_clear.argtypes = [vp]
+        L.kh_map_visibility_commit.argtypes = [vp, i32, vp]
+        L.kh_map_visibility_gain.argtypes = [vp, i32, vp, vp, C.POINTER(dbl)]
+        L.kh_map_visibility_select.argtypes = [vp, i32, vp, i32, C.c_uint32, vp, vp, C.POINTER(i32)]
+        L.kh_map_visibility_read_mask.argtypes = [vp, vp]
+        L.kh_map_visibility_stats_get.argtypes = [vp, C.POINTER(KhMapVisibilityStats)]
+        L.kh_map_visibility_set_skip.argtypes = [vp, i32]
     if hasattr(L, "kh_spa_create"):
         L.kh_spa_options_default.argtypes = [C.POINTER(KhSpaOptions)]
         L.kh_spa_create.argtypes = [i32, C.POINTER(vp)]

@@ -205,6 +205,16 @@ MapWork * map_work_create(int32_t device);
 void map_work_destroy(MapWork * w);
 // KH_OK for a view the two kernels can read (kh_matcher_add_map's test without the device comparison), else KH_ERR_INVALID_ARG and its text
 int map_view_check(const kh_map_view * v);
+// ... and the test itself, without the text: 0, or which of its three refusals (what a device-free check can state too)
+enum : int32_t {kViewOk = 0, kViewMalformed = 1, kViewTooLarge = 2, kViewLeavesLattice = 3};
+inline int32_t map_view_refusal(const kh_map_view * v)
+{
+  if (!v || !v->device_cells || v->width <= 0 || v->height <= 0 || v->width_step < v->width || !std::isfinite(v->scale) || !(v->scale > 0.0) ||
+    !std::isfinite(v->anchor[0]) || !std::isfinite(v->anchor[1])) {return kViewMalformed;}
+  if (static_cast<int64_t>(v->width_step) * v->height > (1ll << 31) - 4096) {return kViewTooLarge;}
+  if (static_cast<int64_t>(v->ox) + v->width > INT32_MAX || static_cast<int64_t>(v->oy) + v->height > INT32_MAX) {return kViewLeavesLattice;}
+  return kViewOk;
+}
 // k_map_seeds over n_blocks = nbx * nby blocks of `pitch` cells, block column bx0 / block row by0 first: local takes one int32 per
 // block, row-major -- the row-major index of the block's seed inside the block, or -1.  *kernel_ms: the kernel by events.
 int map_seed_blocks(MapWork * w, const kh_map_view & v, int32_t pitch, int64_t bx0, int64_t by0, int64_t nbx, int64_t nby, int32_t * local,
@@ -421,6 +431,36 @@ void travel_lookup(void * stream, const TravelJob & job, int32_t n, const double
 // k_travel_paths on `stream`: n starts -> one head each and, where d_cells is not null, the cells of path k from 2 * k * max_cells on
 void travel_paths(void * stream, const TravelJob & job, int32_t n, const double * d_xy, int32_t snap, int32_t max_cells, TravelHead * d_heads,
   int32_t * d_cells);
+
+// ---- visibility (occupancy_visibility.hip; kh_map_visibility_*; the handle and its buffers: map_visibility.cpp;
+// the rules: map_visibility_plan.hpp) ----
+// the words the kernels leave for the host, at the head of a call's buffer: a far cell beyond the reach; a select's state
+struct alignas(16) VisHead {uint32_t error, done, n_picked, current;};
+static_assert(sizeof(VisHead) == 16 && sizeof(kh_visibility_t) == 40, "one int4; a record is the ABI's");
+// One launch of k_vis_gain: workgroup p takes pose p of the tables (k_map_raycast's: 2 * n_beams far points and the sensor's (x, y)
+// per pose).  head: never null.  picked: null outside a select -- there a pose whose word is set, and every pose once head->done is
+// set, leaves at once.
+struct VisJob
+{
+  MapWindow g;
+  const double * points;
+  const double * sensors;
+  int32_t n_beams, max_unknown, reach;
+  uint32_t w_unknown, w_free, w_occupied;
+  uint32_t * mask;             // the covered mask: read by a gain, ORed into by a commit
+  VisHead * head;
+  const uint32_t * picked;
+};
+// k_vis_gain on `stream`, counting: one record per pose into d_out.  skip: read a bitmap word before the OR and leave the OR out where
+// the bit is set.  false = the launch could not be prepared (the bitmap's LDS)
+bool vis_gain(void * stream, const VisJob & job, int32_t n_poses, bool skip, kh_visibility_t * d_out);
+// k_vis_gain on `stream`, committing: Seen(p) of n_poses poses ORed into the mask; from_head: one workgroup, the pose head->current
+// (nothing where head->done is set)
+bool vis_commit(void * stream, const VisJob & job, int32_t n_poses, bool skip, bool from_head);
+// k_vis_best on `stream`: the unpicked candidate of the largest gain, ties to the smallest index -> d_picks / d_gains [head->n_picked],
+// its picked word, head->current; head->done where that gain is below min_gain
+void vis_best(void * stream, const kh_visibility_t * d_records, int32_t n, uint32_t min_gain, uint32_t * d_picked, VisHead * d_head, uint32_t * d_picks,
+  uint32_t * d_gains);
 
 // ---- a change layer's kernels (occupancy_changes.hip; kh_map_changes_*; the handle and its buffers: map_changes.cpp) ----
 // the layer's two counter grids on the window of its view, row stride the view's width_step

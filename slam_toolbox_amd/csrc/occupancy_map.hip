@@ -286,17 +286,9 @@ void map_work_destroy(MapWork * w)
 
 int map_view_check(const kh_map_view * v)
 {
-  if (!v || !v->device_cells || v->width <= 0 || v->height <= 0 || v->width_step < v->width || !std::isfinite(v->scale) || !(v->scale > 0.0) ||
-    !std::isfinite(v->anchor[0]) || !std::isfinite(v->anchor[1]))
-  {
-    set_error("malformed map view");
-    return KH_ERR_INVALID_ARG;
-  }
-  if (static_cast<int64_t>(v->width_step) * v->height > (1ll << 31) - 4096) {set_error("map view too large"); return KH_ERR_INVALID_ARG;}
-  if (static_cast<int64_t>(v->ox) + v->width > INT32_MAX || static_cast<int64_t>(v->oy) + v->height > INT32_MAX) {
-    set_error("map view: the window leaves the int32 lattice");
-    return KH_ERR_INVALID_ARG;
-  }
+  static const char * const kWhy[] = {"", "malformed map view", "map view too large", "map view: the window leaves the int32 lattice"};
+  const int32_t bad = map_view_refusal(v);
+  if (bad != kViewOk) {set_error(kWhy[bad]); return KH_ERR_INVALID_ARG;}
   return KH_OK;
 }
 

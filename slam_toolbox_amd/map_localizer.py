@@ -258,6 +258,14 @@ class MapLocalizer:
         finally:
             f.close()
 
+    def visibility(self, **params):
+        """kh_map_visibility_create on the localizer's map and laser: what a sensor pose would see of the map.  params: fields of
+        kh_visibility_params.  -> map_visibility.MapVisibility (it borrows the map's cells, as the localizer does)"""
+        from .map_visibility import MapVisibility
+        if self._map is None:
+            raise capi.KartoHipError(capi.KH_ERR_NOT_FOUND, "MapLocalizer.visibility: no map set")
+        return MapVisibility(self._map, self._laser, **params)
+
     def refine(self, ranges, sensor_pose, field=None, max_distance: float = 2.0, **params):
         """kh_map_field_refine of `sensor_pose` (3,) or poses (n, 3) -- a hypothesis' or a tracking step's -- with this localizer's
         laser, on `field` (a MapField of the current map, as `field()` makes them) or on one made for this call.  params: fields of
