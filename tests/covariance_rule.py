@@ -117,6 +117,23 @@ def ref_err(r):
     return worst
 
 
+def inverse_float64_reversed(H, jacobi=True):
+    """(a) on the same H with the free nodes eliminated in the reverse of the given order, handed back in the given order"""
+    n = H.shape[0] // 3
+    perm = (3 * np.arange(n - 1, -1, -1)[:, None] + np.arange(3)[None, :]).reshape(-1)
+    back = np.empty_like(perm)
+    back[perm] = np.arange(3 * n)
+    Z = inverse_float64(np.ascontiguousarray(H[np.ix_(perm, perm)]), jacobi)
+    return np.ascontiguousarray(Z[np.ix_(back, back)])
+
+
+def order_err(r, jacobi=True, reversed_sigma=None):
+    """what the elimination order alone changes in float64: rule (a) under the given node order against rule (a) under its
+    reverse (reversed_sigma: inverse_float64_reversed(r.H), where the caller has it already), block by block in the measure of
+    ref_err (diagonal blocks and the cross blocks of the edges)"""
+    return ref_err(r._replace(sigma_ref=inverse_float64_reversed(r.H, jacobi) if reversed_sigma is None else reversed_sigma))
+
+
 def tolerance(err):
     """a block of the library may be this far (relative Frobenius) from (a): the factor 8 covers another elimination order and the
     reciprocal-square-root pivots of the device"""

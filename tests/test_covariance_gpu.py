@@ -7,7 +7,9 @@ by the rule alone.  The graphs are the smallest that reach each branch of the ke
 root supernode of 177 pivots split into a chain by the 128-pivot limit, with fronts whose pivot count is no multiple of 16
 (complete graph on 60 nodes); many levels, fronts with more than three children and deferred update blocks (60 / 120 and
 200 / 500, as they are and with KH_SPA_LEAF=4); wide levels and the boundary where a level's small fronts leave for the fused
-update kernel (1000 / 3000)."""
+update kernel (1000 / 3000).  Which FRONT SHAPES the kernels see (pivot counts above 90, update blocks above 128 rows, chains of more
+than two fronts) is not decided here: the table in DESIGN.md, section 7e ("Front shapes"), is the authority, and its cases run in
+tests/test_covariance_shapes_gpu.py."""
 import ctypes as C
 
 import numpy as np
