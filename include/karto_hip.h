@@ -1981,6 +1981,65 @@ KH_API int kh_map_visibility_stats_get(kh_map_visibility * v, kh_map_visibility_
  * The result does not depend on it.  Any other value: KH_ERR_INVALID_ARG. */
 KH_API int kh_map_visibility_set_skip(kh_map_visibility * v, int32_t skip);
 
+/* ---------------------------------------------------------------- footprints on a map: an oriented convex polygon checked at poses and
+ * by heading.  A footprint analysis is made from a kh_map_field, as a travel analysis is: it snapshots the
+ * field's copy of the cell states and its d2 values over the field's window and never borrows the field.  A cell of state 100 is
+ * occupied, of state 255 free, of any other state unknown.  Cells outside the window do not exist; columns width .. width_step - 1
+ * are never read.
+ *   footprint    3 .. 16 vertices (vx, vy) in metres in the robot frame, finite and strictly convex in either winding: the cross
+ *                products of consecutive edges all have one sign, none is 0, and the polygon goes round once.  r_max = max_k
+ *                sqrt(vx^2 + vy^2); reach = ceil(r_max * scale) + 1 cells, at most 255
+ *   vertex cells of pose (x, y, theta), on the host: c = cos(theta), s = sin(theta); wx_k = x + (c vx_k - s vy_k), wy_k = y + (s vx_k +
+ *                c vy_k); V_k = (round_half_away((wx_k - anchor_x) * scale), round_half_away((wy_k - anchor_y) * scale)),
+ *                kh_map_field_clearance's cell of a point.  A coordinate of a vertex cell or of the pose's own cell beyond +-2^30
+ *                cells: KH_FOOTPRINT_LATTICE, the record all zeros but the status and min_d2 = KH_FIELD_FAR.  Every V_k lies within
+ *                Chebyshev distance reach of the pose's own cell
+ *   covered      edge k is the cells of the outward TraceLine walk (kh_map_raycast's) from V_k to V_(k + 1) mod n, in the order the
+ *                vertices were given; the outline is the union of the edges; for every row j from the smallest to the largest V_k.y,
+ *                lo_j and hi_j are the smallest and the largest column of an outline cell of that row; Covered(p) = {(i, j): lo_j <= i
+ *                <= hi_j}.  The outline is a closed 8-connected loop: no row of that range is empty
+ *   record       the counts over Covered(p) by state, n_outside the covered cells off the window, n_cells their sum; min_d2 the
+ *                smallest field value under the covered window cells, KH_FIELD_FAR without one; status the largest code that applies
+ *   layer        theta_h = (2.0 * pi * h) / H; O_hk = (round_half_away((c vx_k - s vy_k) * scale), round_half_away((s vx_k + c vy_k) *
+ *                scale)); for window cell (i, j) the vertex cells are (i, j) + O_hk, covered cells and status as above; bit h of the
+ *                cell's mask is set when that status is <= max_status.  Defined through the offsets: it is not promised to equal a
+ *                pose check at the cell's centre (a sum of roundings is not the rounding of a sum).  reach > 64 is refused: the
+ *                kernel's tile plus a halo of reach cells lies in LDS
+ * Every result is a set, a count, a minimum or an OR of integers: no execution order shows in it. */
+enum { KH_FOOTPRINT_FREE = 0, KH_FOOTPRINT_UNKNOWN = 1, KH_FOOTPRINT_OUTSIDE = 2, KH_FOOTPRINT_COLLISION = 3, KH_FOOTPRINT_LATTICE = 4 };
+#define KH_FOOTPRINT_LAYER_REACH 64
+typedef struct kh_map_footprint kh_map_footprint;
+typedef struct kh_footprint_t {
+  int32_t status;              /* KH_FOOTPRINT_: FREE, or the largest of UNKNOWN (n_unknown > 0), OUTSIDE (n_outside > 0), COLLISION
+                                * (n_occupied > 0), LATTICE */
+  uint32_t n_cells, n_free, n_occupied, n_unknown, n_outside;
+  uint32_t min_d2, pad;
+} kh_footprint_t;
+typedef struct kh_footprint_layer_t {
+  uint64_t n_fit[32];          /* cells whose bit h is set; 0 from n_headings on */
+  uint64_t n_any, n_all;       /* cells with a bit set; cells with all n_headings bits set */
+} kh_footprint_layer_t;
+typedef struct kh_map_footprint_stats {
+  int32_t ox, oy, width, height;                 /* the window */
+  int32_t n_vertices, reach;
+  int32_t layer_rows, pad;                       /* the rows of the last layer's stencils, all headings together (0 before one) */
+  double times_ms[3];          /* the last pose kernel and the last layer kernel by device events; the last call by wall time */
+} kh_map_footprint_stats;
+/* vertices_xy holds 2 * n_vertices doubles.  KH_ERR_INVALID_ARG before a device is looked for, in this order: a NULL argument;
+ * n_vertices outside 3 .. 16; a vertex that is not finite; a polygon that is not strictly convex; reach > 255 at the field's scale.
+ * Then KH_ERR_NO_DEVICE; then a field without a window. */
+KH_API int kh_map_footprint_create(kh_map_field * field, int32_t n_vertices, const double * vertices_xy, kh_map_footprint ** out);
+/* the snapshot again, of `field` as it stands; refusals and the reuse of allocations are kh_map_travel_recompute's */
+KH_API int kh_map_footprint_recompute(kh_map_footprint * fp, kh_map_field * field);
+KH_API void kh_map_footprint_destroy(kh_map_footprint * fp);
+KH_API int kh_map_footprint_stats_get(kh_map_footprint * fp, kh_map_footprint_stats * out);
+/* n poses (x, y, theta) -> n records.  KH_ERR_INVALID_ARG before a device is looked for, in this order: n outside 1 .. 65536; NULL
+ * poses or out; a pose that is not finite.  A vertex cell beyond the reach (it cannot happen) is KH_ERR_HIP. */
+KH_API int kh_map_footprint_check(kh_map_footprint * fp, int32_t n, const double * poses /* 3n */, kh_footprint_t * out /* n */);
+/* masks (may be NULL) takes width * height words, row-major with no padding; summary may be NULL.  KH_ERR_INVALID_ARG before a
+ * device is looked for, in this order: n_headings outside 1 .. 32; max_status outside 0 .. 2; reach > KH_FOOTPRINT_LAYER_REACH. */
+KH_API int kh_map_footprint_layer(kh_map_footprint * fp, int32_t n_headings, int32_t max_status, uint32_t * masks, kh_footprint_layer_t * summary);
+
 #ifdef __cplusplus
 }
 #endif

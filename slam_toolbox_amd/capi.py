@@ -187,6 +187,8 @@ SYMBOLS = [
     "kh_map_visibility_params_default", "kh_map_visibility_create", "kh_map_visibility_destroy", "kh_map_visibility_set_map", "kh_map_visibility_clear",
     "kh_map_visibility_commit", "kh_map_visibility_gain", "kh_map_visibility_select", "kh_map_visibility_read_mask", "kh_map_visibility_stats_get",
     "kh_map_visibility_set_skip",
+    "kh_map_footprint_create", "kh_map_footprint_recompute", "kh_map_footprint_destroy", "kh_map_footprint_stats_get", "kh_map_footprint_check",
+    "kh_map_footprint_layer",
 ]
 
 
@@ -461,6 +463,22 @@ class KhMapVisibilityStats(C.Structure):
                [("rounds", C.c_uint32), ("launches", C.c_uint32), ("kernel_ms", C.c_double), ("call_ms", C.c_double)]
 
 
+KH_FOOTPRINT_FREE, KH_FOOTPRINT_UNKNOWN, KH_FOOTPRINT_OUTSIDE, KH_FOOTPRINT_COLLISION, KH_FOOTPRINT_LATTICE = range(5)
+KH_FOOTPRINT_LAYER_REACH = 64
+
+
+class KhFootprint(C.Structure):
+    _fields_ = [("status", C.c_int32)] + [(k, C.c_uint32) for k in ("n_cells", "n_free", "n_occupied", "n_unknown", "n_outside", "min_d2", "pad")]
+
+
+class KhFootprintLayer(C.Structure):
+    _fields_ = [("n_fit", C.c_uint64 * 32), ("n_any", C.c_uint64), ("n_all", C.c_uint64)]
+
+
+class KhMapFootprintStats(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("ox", "oy", "width", "height", "n_vertices", "reach", "layer_rows", "pad")] + [("times_ms", C.c_double * 3)]
+
+
 class KhMergeAlignParams(C.Structure):
     _fields_ = [("n_probes", C.c_int32), ("top_k", C.c_int32), ("min_known", C.c_uint64), ("min_pass_through", C.c_uint32), ("pad", C.c_uint32),
                 ("occupancy_threshold", C.c_double), ("relocalize", KhRelocalizeParams)]
@@ -650,6 +668,14 @@ def lib():
         L.kh_map_visibility_read_mask.argtypes = [vp, vp]
         L.kh_map_visibility_stats_get.argtypes = [vp, C.POINTER(KhMapVisibilityStats)]
         L.kh_map_visibility_set_skip.argtypes = [vp, i32]
+    if hasattr(L, "kh_map_footprint_create"):     # (KH_LIBRARY may name a build from before the footprint analysis existed)
+        L.kh_map_footprint_create.argtypes = [vp, i32, vp, C.POINTER(vp)]
+        L.kh_map_footprint_recompute.argtypes = [vp, vp]
+        L.kh_map_footprint_destroy.argtypes = [vp]
+        L.kh_map_footprint_destroy.restype = None
+        L.kh_map_footprint_stats_get.argtypes = [vp, C.POINTER(KhMapFootprintStats)]
+        L.kh_map_footprint_check.argtypes = [vp, i32, vp, vp]
+        L.kh_map_footprint_layer.argtypes = [vp, i32, i32, vp, C.POINTER(KhFootprintLayer)]
     if hasattr(L, "kh_spa_create"):
         L.kh_spa_options_default.argtypes = [C.POINTER(KhSpaOptions)]
         L.kh_spa_create.argtypes = [i32, C.POINTER(vp)]

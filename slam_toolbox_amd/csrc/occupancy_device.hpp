@@ -462,6 +462,25 @@ bool vis_commit(void * stream, const VisJob & job, int32_t n_poses, bool skip, b
 void vis_best(void * stream, const kh_visibility_t * d_records, int32_t n, uint32_t min_gain, uint32_t * d_picked, VisHead * d_head, uint32_t * d_picks,
   uint32_t * d_gains);
 
+// ---- footprints (occupancy_footprint.hip; kh_map_footprint_*; the handle and its buffers: map_footprint.cpp;
+// the rules: map_footprint_plan.hpp) ----
+// one pose of k_footprint_poses as the host states it: whether a vertex left the lattice, the pose's own cell, the vertex cells
+struct alignas(16) FootPose {int32_t lattice, pad, cx, cy; int32_t v[32];};
+static_assert(sizeof(FootPose) == 144 && sizeof(kh_footprint_t) == 32, "nine int4 per pose; a record is the ABI's");
+// the handle's snapshot (f.cells and f.d2 are its own copies, f.g is null), the polygon's size, the call's error word
+struct FootJob
+{
+  FieldWindow f;
+  int32_t n_vertices, reach;
+  uint32_t * error;            // set where a vertex cell lies beyond the reach of its pose's cell
+};
+// k_footprint_poses on `stream`: one record per pose into d_out
+void footprint_poses(void * stream, const FootJob & job, int32_t n, const FootPose * d_poses, kh_footprint_t * d_out);
+// k_footprint_layer on `stream`: d_table is foot_layer_table's; d_masks (may be null) takes width * height words, dense; d_counts
+// (34 words, zeroed by the caller) the summary's counters in kh_footprint_layer_t's order
+void footprint_layer(void * stream, const FootJob & job, int32_t n_headings, int32_t max_status, const int32_t * d_table, uint32_t * d_masks,
+  unsigned long long * d_counts);
+
 // ---- a change layer's kernels (occupancy_changes.hip; kh_map_changes_*; the handle and its buffers: map_changes.cpp) ----
 // the layer's two counter grids on the window of its view, row stride the view's width_step
 struct ChangeLayer

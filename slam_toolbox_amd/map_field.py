@@ -197,6 +197,12 @@ class MapField:
         from .map_travel import MapTravel
         return MapTravel(self, **params)
 
+    def footprint(self, vertices):
+        """kh_map_footprint_create on this field: a convex polygon checked at poses and by heading.  vertices:
+        (n, 2) metres in the robot frame.  -> map_footprint.MapFootprint, which does not borrow the field"""
+        from .map_footprint import MapFootprint
+        return MapFootprint(self, vertices)
+
     def close(self):
         if self._h:
             capi.lib().kh_map_field_destroy(self._h)

@@ -266,6 +266,15 @@ class MapLocalizer:
             raise capi.KartoHipError(capi.KH_ERR_NOT_FOUND, "MapLocalizer.visibility: no map set")
         return MapVisibility(self._map, self._laser, **params)
 
+    def footprint(self, vertices, max_distance: float = 2.0, **params):
+        """kh_map_footprint_create on the localizer's map, through a distance field made for this call (max_distance, and `params`:
+        obstacles): its values are the records' min_d2.  -> map_footprint.MapFootprint (it does not borrow the field)"""
+        f = self.field(max_distance=max_distance, **params)
+        try:
+            return f.footprint(vertices)
+        finally:
+            f.close()
+
     def refine(self, ranges, sensor_pose, field=None, max_distance: float = 2.0, **params):
         """kh_map_field_refine of `sensor_pose` (3,) or poses (n, 3) -- a hypothesis' or a tracking step's -- with this localizer's
         laser, on `field` (a MapField of the current map, as `field()` makes them) or on one made for this call.  params: fields of
