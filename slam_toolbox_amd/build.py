@@ -8,7 +8,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libkartohip.so")
-SOURCES = ["matcher_host.cpp", "matcher_seq.cpp", "matcher_seq.hip", "matcher_group.cpp", "matcher_kernels.hip", "spa_host.cpp", "spa_graph_file.cpp", "spa_problem.cpp", "spa_compute.cpp", "spa_covariance.cpp", "spa_marginalize.cpp", "spa_symbolic.cpp", "spa_kernels.hip", "graph.hip", "occupancy.hip", "occupancy_live.hip", "occupancy_map.hip", "occupancy_changes.hip", "lifelong.hip", "comm.cpp", "mapper_host.cpp", "mapper_loop.cpp", "mapper_removal.cpp", "mapper_session.cpp", "mapper_relocalize.cpp", "mapper_views.cpp", "merge.cpp", "live_map.cpp", "marginalize.hip", "map_localizer.cpp", "map_changes.cpp", "map_align.cpp", "map_merge.cpp", "occupancy_field.hip", "occupancy_field_update.hip", "map_field.cpp", "occupancy_regions.hip", "map_regions.cpp", "occupancy_travel.hip", "map_travel.cpp", "occupancy_visibility.hip", "map_visibility.cpp", "occupancy_footprint.hip", "map_footprint.cpp"]
+SOURCES = ["matcher_host.cpp", "matcher_seq.cpp", "matcher_seq.hip", "matcher_group.cpp", "matcher_kernels.hip", "spa_host.cpp", "spa_graph_file.cpp", "spa_problem.cpp", "spa_compute.cpp", "spa_covariance.cpp", "spa_marginalize.cpp", "spa_symbolic.cpp", "spa_linearize.hip", "spa_factor_front.hip", "spa_potrf.hip", "spa_update.hip", "spa_selinv.hip", "spa_cov_columns.hip", "spa_audit.hip", "graph.hip", "occupancy.hip", "occupancy_live.hip", "occupancy_map.hip", "occupancy_changes.hip", "lifelong.hip", "comm.cpp", "mapper_host.cpp", "mapper_loop.cpp", "mapper_removal.cpp", "mapper_session.cpp", "mapper_relocalize.cpp", "mapper_views.cpp", "merge.cpp", "live_map.cpp", "marginalize.hip", "map_localizer.cpp", "map_changes.cpp", "map_align.cpp", "map_merge.cpp", "occupancy_field.hip", "occupancy_field_update.hip", "map_field.cpp", "occupancy_regions.hip", "map_regions.cpp", "occupancy_travel.hip", "map_travel.cpp", "occupancy_visibility.hip", "map_visibility.cpp", "occupancy_footprint.hip", "map_footprint.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
          "-fvisibility=hidden", "-Wno-unused-value", "-shared", "-ldl"]
 

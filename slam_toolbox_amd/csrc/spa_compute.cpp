@@ -1,5 +1,5 @@
 // Compute() of the pose-graph SPA solver (hot path B): the Levenberg-Marquardt control loop on the host, all numeric work on the
-// GPU (spa_kernels.hip), and the linear-algebra pieces it shares with the covariance pass (spa_covariance.cpp).
+// GPU (spa_linearize.hip, spa_potrf.hip + spa_update.hip, spa_factor_front.hip; spa_device.hpp lists the kernel files), and the linear-algebra pieces it shares with the covariance pass (spa_covariance.cpp).
 //
 // Reference: solvers/ceres_solver.cpp:214-269 (CeresSolver::Compute), solvers/ceres_utils.h (residual).  The minimiser restates
 // Ceres 2.0's trust-region LM (trust_region_minimizer.cc, levenberg_marquardt_strategy.cc, trust_region_step_evaluator.cc); Ceres

@@ -1,6 +1,6 @@
 // Covariances of the pose-graph SPA solver (hot path B): Sigma = (J^T J)^-1 on the pattern of H from the selected inverse of the
 // factor, block columns of Sigma for query nodes, their getters, and the constraint audit that reads them (DESIGN.md sections 7e, 7g and 7i).
-// All numeric work runs on the GPU (spa_kernels.hip); the columns' plan is covariance_columns_plan.hpp's.
+// All numeric work runs on the GPU (spa_selinv.hip, spa_cov_columns.hip, spa_audit.hip); the columns' plan is covariance_columns_plan.hpp's.
 #include <chrono>
 #include <cmath>
 #include <cstring>

@@ -1,5 +1,5 @@
 // Host side of the pose-graph SPA solver (hot path B): the plugin's handle and its graph store.  The other concerns have files of
-// their own (spa_private.hpp lists them); all numeric work runs on the GPU (spa_kernels.hip).
+// their own (spa_private.hpp lists them); all numeric work runs on the GPU (the spa_*.hip files, listed in spa_device.hpp).
 //
 // Reference: solvers/ceres_solver.cpp (state + options + gauge), lib/karto_sdk/include/karto_sdk/Mapper.h:954-1066
 // (karto::ScanSolver), :174-188 (LinkInfo::Update), Karto.h:2533-2577 (Matrix3::Inverse).

@@ -1,4 +1,4 @@
-// Internal structures shared by the solver's host files (spa_private.hpp lists them) and spa_kernels.hip (pose-graph SPA solver, hot path B).
+// Internal structures shared by the solver's host files (spa_private.hpp lists them) and its kernel files (spa_*.hip; spa_device.hpp lists them) -- pose-graph SPA solver, hot path B.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -113,7 +113,7 @@ void spa_launch_factor_level(const SpaDev & d, const int32_t * level_fronts, int
 void spa_launch_extend_add(const SpaDev & d, const int32_t * level_fronts, int32_t n, int32_t max_m, void * stream);
 // upd: per-front forward-solve contributions to the ancestors, 3 * front_rows_ptr[n_fronts] doubles
 void spa_launch_backward_level(const SpaDev & d, const int32_t * level_fronts, int32_t n, int32_t max_m, double * rhs, void * stream);
-// round-3 level pipeline (potrf -> trsm -> syrk, see spa_kernels.hip): the children's update matrices must already be summed
+// round-3 level pipeline (potrf -> trsm -> syrk, see spa_potrf.hip): the children's update matrices must already be summed
 // into the fronts (spa_launch_extend_add); also does the forward solve of the level like spa_launch_factor_level
 // (the level = fronts first_front .. first_front + n - 1)
 void spa_launch_potrf_level(const SpaDev & d, int32_t first_front, int32_t n, int32_t max_m, int32_t max_ns, int32_t * fail_flag,

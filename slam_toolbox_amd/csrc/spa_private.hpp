@@ -7,7 +7,7 @@
 //   spa_compute.cpp      the linear-algebra pieces Compute() and the covariance pass share, and kh_spa_compute
 //   spa_covariance.cpp   the covariance pass, its getters, the constraint audit
 //   spa_marginalize.cpp  the marginalizing removal
-// Not part of the ABI (include/karto_hip.h); spa_internal.hpp stays the contract with spa_kernels.hip and the mapper.  The shared
+// Not part of the ABI (include/karto_hip.h); spa_internal.hpp stays the contract with the kernel files (spa_*.hip, listed in spa_device.hpp) and the mapper.  The shared
 // names live in kh::spa; what one file alone uses stays in that file's anonymous namespace.
 //
 // Linear algebra design (MI355X): the normal matrix is factorised by a multifrontal block Cholesky.

@@ -1,4 +1,4 @@
-"""Front shapes of the covariance kernels (csrc/spa_kernels.hip: k_selinv_head / _z21 / _z11, k_cov_columns_forward / _backward and
+"""Front shapes of the covariance kernels (csrc/spa_selinv.hip: k_selinv_head / _z21 / _z11, csrc/spa_cov_columns.hip: k_cov_columns_forward / _backward and
 the gathers around them) as plain data: the graphs whose multifrontal analysis yields fronts at the edges of the kernels' tiles.
 tests/test_covariance_cases_oracle.py checks on the CPU (tools/sym_probe.cpp, the library's own analysis) that every case still
 has the shapes it claims and that the table covers every class; tests/test_covariance_shapes_gpu.py runs the table through the library

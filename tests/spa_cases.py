@@ -1,4 +1,4 @@
-"""Edge inputs of the pose-graph solver (csrc/spa_kernels.hip, csrc/spa_compute.cpp) as plain data: what tests/test_spa_oracle.py and
+"""Edge inputs of the pose-graph solver (csrc/spa_linearize.hip, csrc/spa_compute.cpp) as plain data: what tests/test_spa_oracle.py and
 tests/test_edge_cases_oracle.py run through oracle/spa.py alone (does every case still sit on the edge its name says?) and
 tests/test_spa_edges_gpu.py through the library next to it.
 

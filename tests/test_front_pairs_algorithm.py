@@ -1,4 +1,4 @@
-"""CPU: the panel-pair partial Cholesky of a front as k_factor2 runs it (csrc/spa_kernels.hip) -- pairs of 16-column panels
+"""CPU: the panel-pair partial Cholesky of a front as k_factor runs it (csrc/spa_factor_front.hip) -- pairs of 16-column panels
 kept in one 32-column panel P, thin update of the second panel inside P, ONE trailing update per pair, and the tail rules:
 a last pair whose second panel has fewer than 16 pivots, a last single panel with fewer than 16, non-pivot columns never
 loaded into P, the trailing update starting at the first 16-aligned row outside a FULL panel (R0) with the pivot columns

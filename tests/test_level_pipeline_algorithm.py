@@ -1,4 +1,4 @@
-"""CPU: the round-3 level pipeline of the solver (csrc/spa_kernels.hip: k_potrf / k_trsm / k_syrk / k_backward3) restated
+"""CPU: the round-3 level pipeline of the solver (csrc/spa_potrf.hip: k_potrf; csrc/spa_update.hip: k_trsm / k_syrk / k_backward3) restated
 in numpy with the kernels' own index rules, against plain dense linear algebra:
 
   * k_potrf factors the ns x ns pivot block in an nsp x nsp matrix (nsp = ns rounded up to 16, identity on the padding) and

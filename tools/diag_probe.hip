@@ -1,12 +1,15 @@
 // Microbenchmark of the 16 x 16 diagonal-block factorisations of k_potrf (one wave, LDS in and out):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off tools/diag_probe.hip -o /tmp/diag_probe && /tmp/diag_probe
-// prints clocks per call of the round-3 pivot chain (potrf_diag) and of the matrix-core form (potrf_diag_mfma), and the
-// error of both against a host Cholesky.
+// prints clocks per call of the round-3 pivot chain (potrf_diag, tools/diag_chain_round3.hpp) and of the matrix-core form the
+// solver runs (potrf_diag_mfma, csrc/spa_diag_block.hpp), and the error of both against a host Cholesky.  -DSTAMPS adds the
+// segment times inside the matrix-core form.
 #ifdef STAMPS
 #define KH_DIAG_STAMPS
 #endif
-#include "../slam_toolbox_amd/csrc/spa_kernels.hip"
+#include "diag_chain_round3.hpp"
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <vector>
 using namespace kh;
 
